@@ -15,6 +15,11 @@ One step = one pass of the hot path over the whole corpus, inputs already reside
   5. ke_cluster_labels : host union-find -> cluster membership (rank 0)
 PyTorch only provides device memory, the stream and the rendezvous (process group).
 Rank 0 prints ONE JSON line (contract in the task statement).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what is measured behind the timed
+region: the CPU baseline, the PCIe- and decode-inclusive legs, the per-phase timing pass, the pHash + dHash roofline and
+the pHash near-tie counts.  `--dump-outputs DIR` writes the last timed step's results (hash table, sorted edges, cluster
+labels, ...) as DIR/<name>.npy, so that two builds can be compared output for output on identical seeded inputs.
 """
 from __future__ import annotations
 
@@ -60,7 +65,42 @@ def parse_args():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launch check without a GPU: the ranks meet over gloo, count each other and rank 0 prints the line")
     ap.add_argument("--phase-steps", type=int, default=3, help="steps of the per-phase timing pass behind the timed region (0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline, behind the timed region: CPU baseline, PCIe- and decode-inclusive legs, "
+                         "per-phase timing pass, pHash + dHash roofline, pHash near-tie counts (a plain run only times the step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 60_000_000   # array data; the .npy headers stay well inside the 64 MB allowance
+
+
+def dump_outputs(dirname, arrays) -> None:
+    """Write `arrays` ({name: float32 / float64 array}) as DIR/<name>.npy.  Past the budget, every array keeps the same share
+    of its rows, chosen by a generator seeded with SEED (the same rows for arrays of the same length, run after run)."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        if total > DUMP_BUDGET_BYTES and len(a) > 1:
+            keep = max(1, int(len(a) * DUMP_BUDGET_BYTES / total))
+            a = a[np.sort(np.random.default_rng(SEED).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+    print(f"[bench] outputs of the last timed step written to {dirname}: {', '.join(sorted(arrays))}", file=sys.stderr, flush=True)
+
+
+def hash_words(h) -> np.ndarray:
+    """64-bit hashes as exact float64 pairs: column 0 = high 32 bits, column 1 = low 32 bits."""
+    h = np.ascontiguousarray(h).view(np.uint64)
+    return np.stack([h >> np.uint64(32), h & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)
+
+
+def edge_rows(edges) -> tuple[np.ndarray, np.ndarray]:
+    """Edge records as float64 rows (a, b, h, bands) in (a, b) order -- the scan emits them in no fixed order -- and that order."""
+    order = np.lexsort((edges["b"], edges["a"]))
+    rows = np.stack([edges[k].astype(np.float64) for k in ("a", "b", "h", "bands")], axis=1) if len(edges) else np.zeros((0, 4))
+    return rows[order], order
 
 
 def self_launch(args) -> int:
@@ -310,6 +350,7 @@ def main():
             state["ssim_kept"] = int((ssim >= args.ssim_threshold).sum())
             # decisions that a 1e-4 disagreement with skimage could flip (the SSIM value is unpinned against the real library)
             state["ssim_near_threshold"] = int((np.abs(ssim - args.ssim_threshold) < 1e-4).sum())
+            state["ssim_scores"], state["ssim_candidates"] = ssim, all_edges
             all_edges = all_edges[ssim >= args.ssim_threshold]
         # 5. cluster membership on the host: rank 0 (every rank holds the merged edges and could)
         labels = _native.cluster_labels(all_edges, n_total) if rank == 0 else None
@@ -347,21 +388,38 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
-    # what the batch-hasher seam launches per file is BOTH hashes (src/core/fastsig.py:31-34): the same kernel family with the
-    # dHash leg, timed behind the timed region on the same resident images
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from its last timed pass: the hash table, the merged edges (sorted), the cluster
+        # labels, the funnel's pair count; at one rank also the pHash tie margins, with --dhash the dHash table, with
+        # --ssim-threshold the candidate edges and their SSIM scores
+        rows, _ = edge_rows(state["edges"])
+        out_arrays = {"phash": hash_words(state["table"][:n_total].cpu().numpy()), "edges": rows,
+                      "labels": state["labels"].astype(np.float64), "scan_pairs": np.array([state["pairs"]], np.float64)}
+        if world == 1:
+            out_arrays["margin"] = local_margin[:n_local].cpu().numpy().astype(np.float32)
+            if args.dhash:
+                out_arrays["dhash"] = hash_words(local_dhash[:n_local].cpu().numpy())
+        if "ssim_scores" in state:
+            cand, order = edge_rows(state["ssim_candidates"])
+            out_arrays["ssim_candidates"], out_arrays["ssim"] = cand, np.asarray(state["ssim_scores"], np.float64)[order]
+        dump_outputs(args.dump_outputs, out_arrays)
+
     dual_ms = []
-    dual_hash = torch.zeros(per, dtype=torch.int64, device=dev)
-    dual_dhash = local_dhash if local_dhash is not None else torch.zeros(per, dtype=torch.int64, device=dev)
-    for k in range(2 + max(3, min(args.steps, 10))):
-        ctx.hash_uniform(pixels.data_ptr(), n_local, side, side, 3, phash_out=dual_hash.data_ptr(), dhash_out=dual_dhash.data_ptr(),
-                         want_dhash=True)
-        if k >= 2:
-            dual_ms.append(ctx.last_kernel_ms(0))
-    torch.cuda.synchronize()
-    assert torch.equal(dual_hash[:n_local], local_hash[:n_local]), "pHash of the dual-hash launch differs from the single-hash launch"
+    if args.full:
+        # what the batch-hasher seam launches per file is BOTH hashes (src/core/fastsig.py:31-34): the same kernel family with the
+        # dHash leg, timed behind the timed region on the same resident images
+        dual_hash = torch.zeros(per, dtype=torch.int64, device=dev)
+        dual_dhash = local_dhash if local_dhash is not None else torch.zeros(per, dtype=torch.int64, device=dev)
+        for k in range(2 + max(3, min(args.steps, 10))):
+            ctx.hash_uniform(pixels.data_ptr(), n_local, side, side, 3, phash_out=dual_hash.data_ptr(), dhash_out=dual_dhash.data_ptr(),
+                             want_dhash=True)
+            if k >= 2:
+                dual_ms.append(ctx.last_kernel_ms(0))
+        torch.cuda.synchronize()
+        assert torch.equal(dual_hash[:n_local], local_hash[:n_local]), "pHash of the dual-hash launch differs from the single-hash launch"
 
     phase_ms = None
-    if args.phase_timing or args.phase_steps > 0:
+    if args.phase_timing or (args.full and args.phase_steps > 0):
         # where a step's time goes: the same calls with a device sync (and, across ranks, the slowest rank) after each phase;
         # behind the timed region, so `value` is untouched
         acc = {}
@@ -408,7 +466,7 @@ def main():
             print("phase ms/step:", phase_ms, file=sys.stderr, flush=True)
 
     h2d = None
-    if rank == 0 and world == 1 and not args.no_h2d:
+    if args.full and rank == 0 and world == 1 and not args.no_h2d:
         # PCIe-inclusive rate of the hashing step (never `value`): the images start in the library's page-locked staging
         # buffers (where decoders put them, ke_stage_*), each batch is copied on the copy stream while the previous one is
         # hashed.  Two buffers of 512 images (403 MB each), 40 batches.
@@ -437,7 +495,7 @@ def main():
             ctx.stage_destroy()
 
     decode_leg = None
-    if rank == 0 and world == 1 and not args.no_decode:
+    if args.full and rank == 0 and world == 1 and not args.no_decode:
         # decode-inclusive rate (never `value`): the same corpus images as JPEG files in host memory (what a library scan starts
         # from) -> page-locked packing -> PCIe (compressed bytes) -> GPU JPEG decode -> the hash kernel on the decoded pixels.
         # 65 536 files in one call (one wave of the entropy kernel per SIMD); the hashes must be those of Pillow's decode of the
@@ -490,9 +548,18 @@ def main():
                 tj = json.load(fh)
             if tj.get("images_per_launch") == n_local and tj.get("side") == side:
                 traffic = tj.get("hbm_bytes_per_launch")
-        mg = local_margin[:n_local].cpu().numpy()                  # this rank's images (all of them at N=1)
-        near_ties = {"images": int(n_local), "lt_1e-3": int((mg < 1e-3).sum()), "lt_1e-4": int((mg < 1e-4).sum()),
-                     "exact_ties": int((mg == 0).sum()), "min_margin": float(mg.min())}
+        near_ties = None
+        if args.full:
+            mg = local_margin[:n_local].cpu().numpy()              # this rank's images (all of them at N=1)
+            near_ties = {"images": int(n_local), "lt_1e-3": int((mg < 1e-3).sum()), "lt_1e-4": int((mg < 1e-4).sum()),
+                         "exact_ties": int((mg == 0).sum()), "min_margin": float(mg.min())}
+        dual = None
+        if dual_ms:
+            # pHash + dHash in one launch: what kobato_eyes_amd.fastsig runs per batch (algorithmic bytes: 3*W*H read + 16 written)
+            dual = {"bound": "hbm", "kernel": "ke_phash_fused_mx (dHash leg on)", "ms": float(np.mean(dual_ms)),
+                    "achieved": n_local * (img_bytes + 16) / (float(np.mean(dual_ms)) * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": n_local * (img_bytes + 16) / (float(np.mean(dual_ms)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "images_per_s": n_local * world / (float(np.mean(dual_ms)) * 1e-3)}
         pairs_rank = state["pairs"]
         pairs_s = pairs_rank / (scan_avg * 1e-3) if scan_avg > 0 else 0.0
         n_clusters = int(len(np.unique(state["labels"][np.unique(np.concatenate([state["edges"]["a"], state["edges"]["b"]]))]))) \
@@ -529,18 +596,14 @@ def main():
                if "ssim_ms" in state else {}),
             # how exposed the corpus is to the one unpinnable step: images whose closest bit decision `coef > mean` sits
             # within 1e-3 / 1e-4 of a tie (another DCT implementation, e.g. OpenCV's float32 one, may flip such a bit)
-            "phash_near_ties": near_ties,
+            **({"phash_near_ties": near_ties} if near_ties else {}),
             **({"h2d_inclusive": h2d} if h2d else {}),
             **({"decode_inclusive": decode_leg} if decode_leg else {}),
             "roofline": {"bound": "hbm", "kernel": "ke_phash_fused_mx", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_source": "profiles/hash_kernel_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE pass of this kernel at this "
                                            "size, gfx950 corrections applied; counters cannot be read inside this process)" if traffic else None},
-            # pHash + dHash in one launch: what kobato_eyes_amd.fastsig runs per batch (algorithmic bytes: 3*W*H read + 16 written)
-            "roofline_dual": {"bound": "hbm", "kernel": "ke_phash_fused_mx (dHash leg on)", "ms": float(np.mean(dual_ms)),
-                              "achieved": n_local * (img_bytes + 16) / (float(np.mean(dual_ms)) * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                              "unit": "GB/s", "frac": n_local * (img_bytes + 16) / (float(np.mean(dual_ms)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              "images_per_s": n_local * world / (float(np.mean(dual_ms)) * 1e-3)},
+            **({"roofline_dual": dual} if dual else {}),
             # scan: one v_mfma_f32_16x16x128_f8f6f4 (fp4) = 256 pairs x 128 one-bit products -> 256 flop per pair
             # against the dense fp4 peak; the 16 B/pair HBM convention of SURVEY 8d is kept beside it (operands are
             # reused from registers/LDS, so that fraction exceeds 1)
@@ -548,7 +611,7 @@ def main():
                               "unit": "TFLOP/s", "frac": pairs_s * 256 / 1e12 / MFMA_FP4_PEAK_TFLOPS,
                               "hbm_convention_gbs": pairs_s * 16 / 1e9, "hbm_convention_frac": pairs_s * 16 / 1e9 / HBM_PEAK_GBS},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(ctx, args, state["table"].cpu().numpy().view(np.uint64))
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

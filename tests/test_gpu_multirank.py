@@ -105,7 +105,7 @@ def test_bench_self_launch_one_rank_over_rccl():
     import json
 
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--self-launch", "--steps", "2", "--warmup", "1",
-                          "--images", "6000", "--side", "256", "--no-cpu-baseline", "--no-h2d", "--no-decode"],
+                          "--images", "6000", "--side", "256", "--full", "--no-cpu-baseline", "--no-h2d", "--no-decode"],
                          capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
