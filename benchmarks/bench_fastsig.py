@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The batch-hasher seam end to end (`fast_fill_missing_signatures`, the drop-in for src/core/fastsig.py:102-126): N image files
 on disk -> signatures rows in SQLite.  Two runs of the same call: JPEG / PNG files decoded on the GPU (the default), and with
-`KE_GPU_JPEG=0 KE_GPU_PNG=0 KE_GPU_BMP=0` (Pillow on the thread pool, pixels through the pinned staging buffers -- the route every other
+`KE_GPU_JPEG=0 ... KE_GPU_WEBP=0` (Pillow on the thread pool, pixels through the pinned staging buffers -- the route every other
 format takes); both hash on the GPU.
     python benchmarks/bench_fastsig.py [--images 16384 --format jpeg|png|mixed --content corpus|drawing]
 One JSON line."""
@@ -27,7 +27,8 @@ def main():
     ap.add_argument("--images", type=int, default=16384)
     ap.add_argument("--side", type=int, default=512)
     ap.add_argument("--format", choices=["jpeg", "png", "mixed", "bmp", "gif", "webp", "tiff", "collection"], default="jpeg",
-                    help="webp / tiff: formats outside the GPU decoders -- the whole batch takes the Pillow route (decoder processes); "
+                    help="every format has a GPU decoder (lossy WebP, uncompressed TIFF); the second run takes the Pillow route "
+                         "(decoder processes); "
                          "collection: 70 %% JPEG, 20 %% PNG, 4 %% BMP, 3 %% WebP, 3 %% TIFF in one call (the Pillow share runs beside the GPU share)")
     ap.add_argument("--distinct", type=int, default=128, help="distinct images behind the files")
     ap.add_argument("--content", choices=["corpus", "drawing"], default="corpus")
@@ -83,7 +84,7 @@ def main():
         with sqlite3.connect(db) as conn:
             assert conn.execute("SELECT COUNT(*) FROM signatures").fetchone()[0] == args.images
         sample = items[: args.pillow_sample]
-        os.environ["KE_GPU_JPEG"] = os.environ["KE_GPU_PNG"] = os.environ["KE_GPU_BMP"] = os.environ["KE_GPU_GIF"] = os.environ["KE_GPU_TIFF"] = "0"
+        os.environ["KE_GPU_JPEG"] = os.environ["KE_GPU_PNG"] = os.environ["KE_GPU_BMP"] = os.environ["KE_GPU_GIF"] = os.environ["KE_GPU_TIFF"] = os.environ["KE_GPU_WEBP"] = "0"
         fastsig.fast_fill_missing_signatures(db, sample[:256], apply_to_db=False)
         t0 = time.perf_counter()
         rows_cpu = fastsig.fast_fill_missing_signatures(db, sample, apply_to_db=False)

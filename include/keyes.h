@@ -242,6 +242,27 @@ int ke_tiff_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, c
                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
 int ke_tiff_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
 
+/* ---- lossy WebP files decoded on the GPU: the same step (src/core/fastsig.py:31-34, src/utils/image_io.py:60-138) for WebP files
+ * of one VP8 key frame -- the simple format (RIFF / WEBP / "VP8 ") and VP8X files without alpha or animation, their ICCP / EXIF /
+ * "XMP " chunks skipped (Pillow applies none of them when it opens the file).  The pixels are libwebp's as Pillow drives it
+ * (WebPAnimDecoder, default options): RFC 6386 reconstruction and loop filter, "fancy" chroma upsampling and the 14-bit
+ * VP8YUVToR/G/B, bit for bit; channels = 3.  The container and the frame header are read on the host's threads; one thread per
+ * image walks the mode and token partitions, one wave per image reconstructs and filters the macroblocks in wavefront order,
+ * one thread per pixel upsamples and converts.  Lossless (VP8L), ALPH, ANIM / ANMF, unknown chunks, a VP8X canvas that differs
+ * from the frame, an inter frame, show_frame 0, a profile above 3, frames of more than 65 536 macroblocks (16.7 Mpx; the
+ * scratch is about 1.2 KB per macroblock) and blocks whose dequantised coefficients leave [-2048, 2048]: KE_JPEG_UNSUPPORTED_ (1)
+ * per file; a partition that runs past its end, RIFF or chunk sizes that do not fit the file: KE_JPEG_CORRUPT_ (2).  Arguments
+ * and conventions as ke_jpeg_probe / ke_jpeg_decode; ke_webp_probe reads the container and the frame tag only, so a file it
+ * reports as taken can still come back refused from ke_webp_decode (whose statuses are final).  ke_webp_caveats sets
+ * KE_CAVEAT_ORIENTATION for every file that carries an EXIF or an XMP chunk -- Pillow's getexif() takes an orientation from
+ * either -- without reading it: the loader decides.  Tuning knob (environment, read at every call): KE_WEBP_SCRATCH_BYTES caps
+ * the device scratch of one sub-batch (default: half the free device memory, 2-160 GB); results do not depend on it. */
+int ke_webp_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                  int32_t *heights, int32_t *channels, int32_t *status_out);
+int ke_webp_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                   uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+int ke_webp_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
+
 /* What `Image.open` alone does not tell about a file but the reference's defensive loader acts on (src/utils/image_io.py:60-138:
  * EXIF orientation applied, alpha composited over white): per file a set of KE_CAVEAT_* bits, so that a caller who wants that
  * loader's pixels sends flagged files through it and only the rest through ke_jpeg_decode / ke_png_decode.  ORIENTATION: the

@@ -115,9 +115,11 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
             gpu_kinds["bmp"] = (".bmp",)
         if os.environ.get("KE_GPU_TIFF", "1") != "0":
             gpu_kinds["tiff"] = (".tif", ".tiff")
+        if os.environ.get("KE_GPU_WEBP", "1") != "0":
+            gpu_kinds["webp"] = (".webp",)
 
     def decode_on_gpu(need: list, placed: dict, buffers: list) -> None:
-        """JPEG / PNG / BMP / TIFF files whose pixels the reference's loader would hand over exactly as Image.open yields them -- RGB, no
+        """JPEG / PNG / BMP / TIFF / WebP files whose pixels the reference's loader would hand over exactly as Image.open yields them -- RGB, no
         EXIF orientation to apply, nothing to shrink (src/utils/image_io.py:107-138 are all no-ops then) -- are decoded on the
         GPU and stay there: placed[path] = (device address, width, height).  Everything else is left for Pillow."""
         for kind, suffixes in gpu_kinds.items():
