@@ -9,17 +9,22 @@ from dataclasses import dataclass
 import numpy as np
 import pytest
 
+import _vp8_rewrite as R
 import _webp_cases as W
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def ctx():
+def _native():
     from kobato_eyes_amd import _native
 
-    return _native.get_context(0)
+    return _native
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    return _native().get_context(0)
 
 
 def test_webp_decode_matches_pillow_in_one_mixed_batch(ctx):
@@ -71,6 +76,10 @@ def test_batch_hasher_rows_with_the_route_on_and_off(tmp_path, monkeypatch):
 
     lossy = [c for c in W.taken_cases() if min(W.pillow_rgb(c[1]).shape[:2]) >= 8][:60]
     others = [(n, d) for n, d, _ in W.refused_cases()[:3]]                    # lossless, alpha, animated: Pillow's
+    up = [(n, d) for n, d, _ in R.quant_up_cases()]                           # over the coefficient limit: Pillow's
+    _, status = _native().get_context(0).webp_decode([d for _, d in up])
+    others += [c for c, st in zip(up, status) if st == W.UNSUPPORTED]
+    assert len(others) >= 3 + 10
     items = _write(tmp_path, lossy + others)
     seen = []
     original = K._Pipeline._decode_with_pillow
@@ -152,6 +161,67 @@ def test_large_frames_and_many_sub_batches(ctx, monkeypatch):
     for (name, _), px, st, ref in zip(cases, out, status, refs):
         assert st == W.OK and np.array_equal(px, ref), name
     monkeypatch.setenv("KE_WEBP_SCRATCH_BYTES", str(1 << 20))           # about one 512 x 512 frame per sub-batch
+    out, status = ctx.webp_decode([d for _, d in cases])
+    for (name, _), px, st, ref in zip(cases, out, status, refs):
+        assert st == W.OK and np.array_equal(px, ref), name
+
+
+# ---- rewritten key frames (tests/_vp8_rewrite.py): header fields and modes no encoder writes ----------------------------------
+@pytest.fixture(scope="module")
+def rewritten():
+    return {g: [(n, d) for n, d, _ in fn()] for g, fn in R.GROUPS.items()}
+
+
+def test_rewritten_files_match_pillow_in_one_mixed_batch(ctx, rewritten):
+    """All five groups with the taken and refused cases in one call.  modes / filter / header / quant_down: pixel-equal to
+    Pillow, no exemptions; quant_up: equal to Pillow or refused (the coefficient limit) where Pillow decodes, at least 10
+    of each; nothing Pillow refuses comes back OK."""
+    groups = [(g, n, d) for g, cases in rewritten.items() for n, d in cases]
+    taken, refused = W.taken_cases(), W.refused_cases()
+    blobs = [d for _, _, d in groups] + [d for _, d in taken] + [d for _, d, _ in refused]
+    out, status = ctx.webp_decode(blobs)
+    split = {W.OK: 0, W.UNSUPPORTED: 0}
+    for k, (group, name, data) in enumerate(groups):
+        ref = W.pillow_rgb(data)
+        if ref is None:
+            assert status[k] != W.OK, f"{name}: decoded where Pillow refuses"
+            continue
+        if group == "quant_up" and status[k] == W.UNSUPPORTED:
+            assert out[k] is None, name
+        else:
+            assert status[k] == W.OK, name
+            assert out[k].shape == ref.shape and np.array_equal(out[k], ref), name
+        if group == "quant_up":
+            split[int(status[k])] += 1
+    print(f"quant_up: {split[W.OK]} taken, {split[W.UNSUPPORTED]} refused")
+    assert split[W.OK] >= 10 and split[W.UNSUPPORTED] >= 10
+    for k, (name, data) in enumerate(taken, len(groups)):
+        assert status[k] == W.OK and np.array_equal(out[k], W.pillow_rgb(data)), name
+    for k, (name, _, expected) in enumerate(refused, len(groups) + len(taken)):
+        assert status[k] == expected and out[k] is None, name
+
+
+def test_rewritten_hashes_equal_the_oracle_of_pillow_pixels(ctx, rewritten):
+    cases = [(n, d) for g, cs in rewritten.items() for n, d in cs if min(W.pillow_rgb(d).shape[:2]) >= 8]
+    ph, dh, st = ctx.webp_hash([d for _, d in cases])
+    hashed = 0
+    for k, (name, data) in enumerate(cases):
+        if name.startswith("qup_") and st[k] == W.UNSUPPORTED:
+            continue
+        assert st[k] == 0 and (int(ph[k]), int(dh[k])) == O.hash_image(W.pillow_rgb(data)), name
+        hashed += 1
+    assert hashed >= 300
+
+
+def test_large_rewritten_frame_whole_and_in_sub_batches(ctx, rewritten, monkeypatch):
+    """2 176 x 1 088 with random modes and the strongest normal filter: 68 macroblocks in a wavefront step, beside the
+    rewritten files of the filter group; whole and cut into sub-batches by a 1 MiB scratch budget."""
+    cases = [R.big_frame_case()] + rewritten["filter"][:24]
+    refs = [W.pillow_rgb(d) for _, d in cases]
+    out, status = ctx.webp_decode([d for _, d in cases])
+    for (name, _), px, st, ref in zip(cases, out, status, refs):
+        assert st == W.OK and np.array_equal(px, ref), name
+    monkeypatch.setenv("KE_WEBP_SCRATCH_BYTES", str(1 << 20))
     out, status = ctx.webp_decode([d for _, d in cases])
     for (name, _), px, st, ref in zip(cases, out, status, refs):
         assert st == W.OK and np.array_equal(px, ref), name
