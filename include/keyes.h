@@ -263,6 +263,28 @@ int ke_webp_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, c
                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
 int ke_webp_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
 
+/* ---- lossless WebP files decoded on the GPU: the same step (src/core/fastsig.py:31-34, src/utils/image_io.py:60-138) for WebP
+ * files of one VP8L bitstream, which the reference ranks second among its keepers (src/dup/scanner.py:19) -- the simple format
+ * (RIFF / WEBP / "VP8L") and VP8X files without animation, their ICCP / EXIF / "XMP " chunks skipped.  The pixels are libwebp's
+ * as Pillow yields them, bit for bit: channels = 4 (RGBA) where Pillow opens the file as RGBA -- the VP8L header's alpha bit,
+ * whatever a VP8X chunk's alpha flag says --, 3 (RGB, the decoded alpha dropped) otherwise.  The container
+ * and the 5-byte header are read on the host's threads; one thread per image walks the stream (prefix codes, colour cache,
+ * LZ77), one workgroup per image undoes the transforms (the predictor as a skewed wavefront over rows), one thread per pixel
+ * writes the bytes.  Refused per file with KE_JPEG_UNSUPPORTED_ (1): "VP8 " (ke_webp_decode's), ALPH, ANIM / ANMF, unknown
+ * chunks, a canvas that differs from the image, a version other than 0, images of more than 16 777 216 pixels (the lossy
+ * decoder's cap: the scratch is about 9.2 bytes per pixel plus 96 KiB, 154 MB at the cap) and streams whose prefix codes need
+ * more than 64 KiB + 4 bytes per pixel; with KE_JPEG_CORRUPT_ (2): RIFF or chunk sizes that do not fit the file, a stream that
+ * ends early, an incomplete or over-subscribed prefix code, a distance that reaches before the first pixel, a transform given
+ * twice.  Arguments and conventions as ke_webp_probe / ke_webp_decode; ke_webpl_probe reads the container and the header only,
+ * ke_webpl_decode's statuses are final.  ke_webpl_caveats sets KE_CAVEAT_ORIENTATION for an EXIF or XMP chunk (unread: the
+ * loader decides) and KE_CAVEAT_TRANSPARENCY for a file of four channels.  KE_WEBP_SCRATCH_BYTES caps the device scratch of
+ * one sub-batch here too; results do not depend on it. */
+int ke_webpl_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                   int32_t *heights, int32_t *channels, int32_t *status_out);
+int ke_webpl_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+int ke_webpl_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
+
 /* What `Image.open` alone does not tell about a file but the reference's defensive loader acts on (src/utils/image_io.py:60-138:
  * EXIF orientation applied, alpha composited over white): per file a set of KE_CAVEAT_* bits, so that a caller who wants that
  * loader's pixels sends flagged files through it and only the rest through ke_jpeg_decode / ke_png_decode.  ORIENTATION: the

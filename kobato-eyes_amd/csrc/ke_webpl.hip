@@ -1,0 +1,235 @@
+// ke_webpl.hip -- lossless WebP files (one VP8L bitstream) decoded on the GPU: the decode step in front of the hash path (SURVEY
+// 8 f2) for the WebP files the reference ranks among its keepers (src/dup/scanner.py:16-28).  Replaces `Image.open(path)` + pixel
+// access of the reference's batch hasher (src/core/fastsig.py:31-34) for the files ke_webpl_parse.h takes; the arithmetic is
+// ke_webpl_core.h's (held against Pillow on the CPU).  The container and the 5-byte header are read on the host's threads.
+//
+//   ke_webpl_entropy    ONE THREAD PER IMAGE walks the stream: transforms' sub-images, colour cache, entropy image, the prefix
+//                       codes of every group, then the ARGB words of the image (literals, cache hits, LZ77 copies).  The
+//                       stream is serial, and the colour cache makes a later symbol depend on the values of copied pixels,
+//                       so the copies cannot be put off as ke_png_inflate puts them off; neighbours in a wave are sorted to
+//                       like stream lengths instead.
+//   ke_webpl_transform  ONE WORKGROUP PER IMAGE undoes the transforms, last to first.  Predictor: rows as a skewed wavefront,
+//                       (x, y) at step x + 2y -- after (x - 1, y) and (x + 1, y - 1) --, one lane per row of a step.
+//                       Cross-colour and subtract-green: a lane per pixel.  Colour indexing with packed pixels: row by row
+//                       towards the front of the buffer, the packed rows lying behind where their pixels go.
+//   ke_webpl_output     one thread per pixel: RGB or RGBA bytes at the caller's offsets.
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+#include "ke_internal.h"
+#include "ke_webpl_parse.h"
+
+namespace {
+
+struct KeWebplDev {
+    KeWebplHeader h;
+    uint64_t file_off;       // the file inside the uploaded bytes
+    uint64_t scratch_off;    // bytes into the scratch (16-aligned)
+    uint64_t scratch_words;  // ke_vp8l_scratch_words(width, height)
+    uint64_t out_off;        // bytes into the caller's pixel buffer
+};
+
+__global__ __launch_bounds__(64) void ke_webpl_entropy_k(const KeWebplDev *__restrict__ imgs, int64_t n, const uint8_t *__restrict__ files,
+                                                        uint8_t *__restrict__ scratch, KeVp8lPlan *__restrict__ plans,
+                                                        int32_t *__restrict__ status) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const KeWebplDev &d = imgs[i];
+    KeVp8lPlan plan;
+    status[i] = ke_vp8l_decode_stream(files + d.file_off + d.h.off, d.h.size, d.h.width, d.h.height, (uint32_t *)(scratch + d.scratch_off),
+                                      d.scratch_words, plan);
+    plans[i] = plan;
+}
+
+constexpr int kTransformThreads = 256;
+
+__global__ __launch_bounds__(kTransformThreads) void ke_webpl_transform_k(const KeWebplDev *__restrict__ imgs, uint8_t *__restrict__ scratch,
+                                                                         const KeVp8lPlan *__restrict__ plans,
+                                                                         const int32_t *__restrict__ status) {
+    const int64_t i = blockIdx.x;
+    if (status[i] != KE_WEBPL_OK) return;
+    const KeWebplDev &d = imgs[i];
+    uint32_t *mem = (uint32_t *)(scratch + d.scratch_off);
+    const KeVp8lPlan &plan = plans[i];
+    const int W = d.h.width, H = d.h.height, tid = threadIdx.x;
+    uint32_t *pix = mem + plan.pix;
+    for (int k = plan.ntrans - 1; k >= 0; --k) {
+        const KeVp8lXform t = plan.t[k];
+        const int w = t.xsize;
+        const uint32_t *data = mem + t.data;
+        const size_t count = (size_t)w * H;
+        if (t.type == KE_VP8L_PREDICTOR) {
+            const int steps = w + 2 * (H - 1);
+            for (int s = 0; s < steps; ++s) {
+                // pixels (s - 2y, y) of this step: y from max(0, ceil((s - w + 1) / 2)) to min(H - 1, s / 2)
+                const int ylo = s - w + 1 > 0 ? (s - w + 2) >> 1 : 0, yhi = min(H - 1, s >> 1);
+                for (int y = ylo + tid; y <= yhi; y += kTransformThreads) {
+                    const int x = s - 2 * y;
+                    uint32_t *p = pix + (size_t)y * w + x;
+                    *p = ke_vp8l_add(*p, ke_vp8l_predict(pix, w, x, y, data, t.bits));
+                }
+                __syncthreads();
+            }
+        } else if (t.type == KE_VP8L_CROSS_COLOUR) {
+            const int sw = ke_vp8l_subsample(w, t.bits);
+            for (size_t j = tid; j < count; j += kTransformThreads) {
+                const int y = (int)(j / w), x = (int)(j - (size_t)y * w);
+                pix[j] = ke_vp8l_cross_colour(pix[j], data[(size_t)(y >> t.bits) * sw + (x >> t.bits)]);
+            }
+        } else if (t.type == KE_VP8L_SUBTRACT_GREEN) {
+            for (size_t j = tid; j < count; j += kTransformThreads) pix[j] = ke_vp8l_add_green(pix[j]);
+        } else if (t.bits == 0) {
+            for (size_t j = tid; j < count; j += kTransformThreads) pix[j] = data[(pix[j] >> 8) & 255u];
+        } else {
+            // Pixel x of row y goes to y * w + x and comes from the packed word (W * H - sw * H) + y * sw + (x >> bits), which
+            // never lies in front of it: in ascending order, every chunk read before it is written, no word is lost.
+            const int sw = ke_vp8l_subsample(w, t.bits);
+            uint32_t *wide = mem + ((size_t)W * H - count);
+            for (int y = 0; y < H; ++y)
+                for (int x0 = 0; x0 < w; x0 += kTransformThreads) {
+                    const int x = x0 + tid;
+                    uint32_t v = 0;
+                    if (x < w) v = ke_vp8l_colour_index(pix + (size_t)y * sw, x, t.bits, data);
+                    __syncthreads();
+                    if (x < w) wide[(size_t)y * w + x] = v;
+                    __syncthreads();
+                }
+            pix = wide;
+        }
+        __syncthreads();
+    }
+}
+
+constexpr int kRowsPerBlock = 8;
+
+__global__ __launch_bounds__(256) void ke_webpl_output_k(const KeWebplDev *__restrict__ imgs, const uint8_t *__restrict__ scratch,
+                                                        const int32_t *__restrict__ status, uint8_t *__restrict__ out, int rows) {
+    const int64_t i = blockIdx.x;
+    const KeWebplDev &d = imgs[i];
+    const int y0 = blockIdx.y * rows;
+    if (status[i] != KE_WEBPL_OK || y0 >= d.h.height) return;
+    const int W = d.h.width, ch = d.h.channels;
+    const uint32_t *pix = (const uint32_t *)(scratch + d.scratch_off);     // the finished image lies at the front
+    const size_t lo = (size_t)y0 * W, hi = (size_t)min(y0 + rows, d.h.height) * W;
+    for (size_t j = lo + threadIdx.x; j < hi; j += 256) ke_vp8l_store(pix[j], out + d.out_off + j * ch, ch);
+}
+
+}  // namespace
+
+KE_API int ke_webpl_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                          int32_t *heights, int32_t *channels, int32_t *status_out) {
+    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
+    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
+        for (int64_t i = lo; i < hi; ++i) {
+            KeWebplHeader h;
+            ke_parse_webpl(files + offsets[i], (size_t)sizes[i], h);
+            widths[i] = h.width; heights[i] = h.height; channels[i] = h.channels;
+            status_out[i] = h.status;
+        }
+    });
+    return KE_OK;
+}
+
+KE_API int ke_webpl_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
+    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
+    // An EXIF chunk or an XMP packet may carry an orientation the reference's loader applies (flagged without reading it);
+    // an RGBA file is composited over white by it.
+    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
+        for (int64_t i = lo; i < hi; ++i) {
+            KeWebplHeader h;
+            ke_parse_webpl(files + offsets[i], (size_t)sizes[i], h);
+            flags_out[i] = (h.meta ? KE_CAVEAT_ORIENTATION : 0) | (h.channels == 4 ? KE_CAVEAT_TRANSPARENCY : 0);
+        }
+    });
+    return KE_OK;
+}
+
+KE_API int ke_webpl_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                           uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
+    if (!ctx) return KE_EINVAL;
+    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
+        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    if (n == 0) return KE_OK;
+    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "the files' headers are parsed on the host: pass host memory (pinned staging is fine)");
+    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
+    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
+        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
+    KE_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<KeWebplDev> items((size_t)n);
+    ke_parallel_ranges(n, [&](int64_t a, int64_t b, int) {
+        for (int64_t i = a; i < b; ++i) ke_parse_webpl(files + offsets[i], (size_t)sizes[i], items[(size_t)i].h);
+    });
+    std::vector<int64_t> which;
+    which.reserve((size_t)n);
+    uint64_t lo = ~0ull, hi = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        KeWebplDev &d = items[(size_t)i];
+        status_out[i] = d.h.status;
+        if (d.h.status != KE_WEBPL_OK) continue;
+        d.file_off = offsets[i];
+        d.out_off = out_offsets[i];
+        d.scratch_words = ke_vp8l_scratch_words(d.h.width, d.h.height);
+        lo = std::min(lo, offsets[i]);
+        hi = std::max(hi, offsets[i] + sizes[i]);
+        which.push_back(i);
+    }
+    if (which.empty()) return KE_OK;
+    // lanes of one wave finish together at best: neighbours in the batch should have streams of like length
+    std::stable_sort(which.begin(), which.end(), [&](int64_t a, int64_t b) { return sizes[a] > sizes[b]; });
+    void *d_files;
+    KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)(hi - lo) + 256, &d_files));
+    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
+    // sub-batches bounded by scratch: about 9.2 bytes per pixel and 96 KiB per image
+    size_t free_b = 0, total_b = 0;
+    KE_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    const uint64_t held = (uint64_t)ctx->buf[KE_BUF_SSIM_IN].bytes;
+    uint64_t budget = std::max<uint64_t>((uint64_t)2 << 30, std::min<uint64_t>((held + (uint64_t)free_b) / 2, (uint64_t)160 << 30));
+    if (const char *e = getenv("KE_WEBP_SCRATCH_BYTES")) {          // a smaller budget (tests: many sub-batches); results do not depend on it
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        if (v > 0) budget = std::min<uint64_t>(budget, v);
+    }
+    std::vector<KeWebplDev> devs;
+    std::vector<int32_t> st;
+    size_t first = 0;
+    ke_time_begin(ctx, KE_T_JPEG);
+    while (first < which.size()) {
+        uint64_t bytes = 0;
+        int max_height = 0;
+        size_t last = first;
+        devs.clear();
+        while (last < which.size()) {
+            KeWebplDev d = items[(size_t)which[last]];
+            const uint64_t need = (d.scratch_words * 4 + 15) & ~15ull;
+            if (last > first && bytes + need > budget) break;
+            d.file_off -= lo;
+            d.scratch_off = bytes;
+            bytes += need;
+            max_height = std::max(max_height, d.h.height);
+            devs.push_back(d);
+            ++last;
+        }
+        const int64_t m = (int64_t)devs.size();
+        void *d_imgs, *d_scratch, *d_status, *d_plans;
+        KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)m * sizeof(KeWebplDev), &d_imgs));
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)bytes + 64, &d_scratch));
+        KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)m * 4, &d_status));
+        KE_TRY(ke_reserve(ctx, KE_BUF_OUT1, (size_t)m * sizeof(KeVp8lPlan), &d_plans));
+        KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs.data(), (size_t)m * sizeof(KeWebplDev), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(ke_webpl_entropy_k, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (const KeWebplDev *)d_imgs, m,
+                           (const uint8_t *)d_files, (uint8_t *)d_scratch, (KeVp8lPlan *)d_plans, (int32_t *)d_status);
+        hipLaunchKernelGGL(ke_webpl_transform_k, dim3((unsigned)m), dim3(kTransformThreads), 0, ctx->stream, (const KeWebplDev *)d_imgs,
+                           (uint8_t *)d_scratch, (const KeVp8lPlan *)d_plans, (const int32_t *)d_status);
+        const int rows = std::max(kRowsPerBlock, (max_height + 65534) / 65535);
+        hipLaunchKernelGGL(ke_webpl_output_k, dim3((unsigned)m, (unsigned)((max_height + rows - 1) / rows)), dim3(256), 0, ctx->stream,
+                           (const KeWebplDev *)d_imgs, (const uint8_t *)d_scratch, (const int32_t *)d_status, pixels_out, rows);
+        KE_HIP(ctx, hipGetLastError());
+        st.resize((size_t)m);
+        KE_HIP(ctx, hipMemcpyAsync(st.data(), d_status, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // devs / st are host vectors; the scratch is reused
+        for (int64_t k = 0; k < m; ++k) status_out[which[first + (size_t)k]] = st[(size_t)k];
+        first = last;
+    }
+    ke_time_end(ctx, KE_T_JPEG);
+    return KE_OK;
+}

@@ -514,6 +514,8 @@ class _Pipeline:
                 except (RuntimeError, ValueError, MemoryError):      # e.g. no room on the device for this batch: Pillow decodes it
                     refused.extend(positions.tolist())
                     continue
+                if kind == "webp" and os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":
+                    p, d, st = self._offer_to_lossless(held, lo, first, positions, None if by_path or held is not None else blobs, p, d, st)
                 good = np.asarray(st) == 0
                 at = positions[good] - start
                 ph[at] = np.asarray(p, np.uint64).view(np.int64)[good]
@@ -525,6 +527,30 @@ class _Pipeline:
             if held is not None:
                 held.release()
         return refused
+
+    def _offer_to_lossless(self, held, lo: int, hi: int, positions, blobs, p, d, st):
+        """The .webp files the lossy decoder returned as UNSUPPORTED, offered to the lossless one (``KE_GPU_WEBP_LOSSLESS=1``)
+        over the same files -- the read-ahead range with the files already taken masked, their paths, or their bytes --
+        before they go to Pillow: (p, d, st) with its results filled in.  What it refuses keeps its status."""
+        p, d, st = np.array(p, np.uint64), np.array(d, np.uint64), np.array(st, np.int32)
+        again = st == 1
+        if not again.any():
+            return p, d, st
+        try:
+            if held is not None:
+                p2, d2, st2 = self.stage.hash_ahead(held, lo, hi, "webpl", skip=~again)
+                p2, d2, st2 = (np.asarray(a)[again] for a in (p2, d2, st2))
+            elif blobs is None:
+                p2, d2, st2 = self.stage.hash_files([self.paths[k] for k in positions[again].tolist()], "webpl")
+            else:
+                p2, d2, st2 = self.stage.jpeg_hash([b for b, a in zip(blobs, again.tolist()) if a], "webpl")
+        except (RuntimeError, ValueError, MemoryError):          # Pillow decodes them, as before
+            return p, d, st
+        took = np.nonzero(again)[0][np.asarray(st2) == 0]
+        p[took] = np.asarray(p2, np.uint64)[np.asarray(st2) == 0]
+        d[took] = np.asarray(d2, np.uint64)[np.asarray(st2) == 0]
+        st[took] = 0
+        return p, d, st
 
     # ---- the Pillow share: chunks through the two staging buffers
     def _start(self, positions: Sequence[int]):

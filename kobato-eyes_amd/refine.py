@@ -117,13 +117,15 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
             gpu_kinds["tiff"] = (".tif", ".tiff")
         if os.environ.get("KE_GPU_WEBP", "1") != "0":
             gpu_kinds["webp"] = (".webp",)
+            if os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":      # after the lossy decoder: what that one did not place
+                gpu_kinds["webpl"] = (".webp",)
 
     def decode_on_gpu(need: list, placed: dict, buffers: list) -> None:
         """JPEG / PNG / BMP / TIFF / WebP files whose pixels the reference's loader would hand over exactly as Image.open yields them -- RGB, no
         EXIF orientation to apply, nothing to shrink (src/utils/image_io.py:107-138 are all no-ops then) -- are decoded on the
         GPU and stay there: placed[path] = (device address, width, height).  Everything else is left for Pillow."""
         for kind, suffixes in gpu_kinds.items():
-            paths = [p for p in need if p.lower().endswith(suffixes)]
+            paths = [p for p in need if p.lower().endswith(suffixes) and p not in placed]
             if not paths:
                 continue
             dev, off, w, h, c, st, flags = ctx.decode_files_owned(paths, kind)

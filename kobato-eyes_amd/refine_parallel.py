@@ -84,11 +84,14 @@ def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) ->
         return out
     ctx = _native.get_context(device)
     not_laid = np.uint64(0xFFFFFFFFFFFFFFFF)
-    for kind, suffixes in _GPU_SUFFIXES.items():
+    kinds = list(_GPU_SUFFIXES.items())
+    if os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":           # after the lossy decoder: the files that one left out
+        kinds.append(("webpl", _GPU_SUFFIXES["webp"]))
+    for kind, suffixes in kinds:
         if os.environ.get({"jpeg": "KE_GPU_JPEG", "png": "KE_GPU_PNG", "bmp": "KE_GPU_BMP", "gif": "KE_GPU_GIF", "tiff": "KE_GPU_TIFF",
-                        "webp": "KE_GPU_WEBP"}[kind], "1") == "0":
+                        "webp": "KE_GPU_WEBP", "webpl": "KE_GPU_WEBP"}[kind], "1") == "0":
             continue
-        mine = [p for p in paths if str(p).lower().endswith(suffixes)]
+        mine = [p for p in paths if str(p).lower().endswith(suffixes) and p not in out]
         at = 0
         while at < len(mine):
             stop, estimate = at, 0                                   # a few GB of decoded pixels per call
@@ -116,7 +119,7 @@ def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) ->
                     ww, hh, cc = int(w[idx[0]]), int(h[idx[0]]), int(c[idx[0]])
                     thumbs = ctx.resize_luma_uniform(dev + int(off[idx[0]]), len(idx), ww, hh, cc, side, side, filter=1)
                     for k, i in enumerate(idx.tolist()):
-                        if st[i] == 0 and not flags[i] & 1:
+                        if st[i] == 0 and not flags[i] & (3 if kind == "webpl" else 1):     # an RGBA WebP file stays with the loader
                             out[part[i]] = thumbs[k]
                 # files to turn first (src/ui/dup_refine_parallel.py:67-70: ImageOps.exif_transpose before the resize -- every
                 # camera writes the tag): turned on the device into a buffer of their own, then shrunk group by group
