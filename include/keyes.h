@@ -285,6 +285,34 @@ int ke_webpl_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, 
                     uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
 int ke_webpl_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
 
+/* ---- lossy WebP files with an alpha plane decoded on the GPU: the same step (src/core/fastsig.py:31-34, src/utils/image_io.py:60-138)
+ * for what `cwebp` and `Image.save("x.webp")` write for a picture with transparency, among the WebP files the reference ranks
+ * with its keepers (src/dup/scanner.py:16-28): VP8X files without animation whose alpha flag is set and whose image is one "VP8 "
+ * key frame ke_webp_decode would take, with one ALPH chunk directly in front of the frame -- method 0 (the plane's bytes) or 1 (a
+ * VP8L stream without its header, the plane in its green channel), any of the four filters, pre-processing 0 or 1 -- or with no
+ * ALPH chunk at all (alpha 255); ICCP / EXIF / "XMP " chunks skipped.  The pixels are libwebp's as Pillow yields them
+ * (WebPAnimDecoder, non-premultiplied RGBA), bit for bit: channels = 4, the RGB that of the same frame without the plane.  The
+ * container, the frame header and the ALPH header byte are read on the host's threads; the frame goes through ke_webp_decode's
+ * token and reconstruction kernels, one thread per plane walks a method-1 stream, one workgroup per plane undoes its transforms
+ * and the plane's filter (horizontal / vertical: prefix sums mod 256; gradient: a wavefront over anti-diagonals), one thread per
+ * pixel converts and writes four bytes.  Refused per file with KE_JPEG_UNSUPPORTED_ (1): files without the alpha flag
+ * (ke_webp_decode's, an ALPH chunk without the flag included: Pillow's alpha is not the chunk's then), "VP8L" images
+ * (ke_webpl_decode's), ANIM / ANMF, unknown chunks, a chunk between the plane and the frame, everything ke_webp_decode refuses
+ * for the frame (its cap of 65 536 macroblocks included) and plane streams whose prefix codes need more than 64 KiB + 4 bytes
+ * per pixel; with KE_JPEG_CORRUPT_ (2), as Pillow fails them: two ALPH chunks, an ALPH chunk behind the frame, a chunk of fewer
+ * than two bytes, a raw plane shorter than width x height (more bytes are ignored), method 2 / 3, pre-processing 2 / 3, a
+ * reserved bit, a plane stream that ends early or is malformed as ke_webpl_decode has it, and what ke_webp_decode calls corrupt.
+ * Arguments and conventions as ke_webpl_probe / ke_webpl_decode; ke_webpa_probe reads the container, the frame tag and the ALPH
+ * header byte only, ke_webpa_decode's statuses are final.  ke_webpa_caveats sets KE_CAVEAT_ORIENTATION for an EXIF or XMP chunk
+ * (unread: the loader decides) and KE_CAVEAT_TRANSPARENCY for every file it takes.  Scratch: about 1.2 KB per macroblock, plus
+ * 9.2 bytes per pixel and 96 KiB for a method-1 plane or one byte per pixel for a raw one; KE_WEBP_SCRATCH_BYTES caps the device
+ * scratch of one sub-batch here too; results do not depend on it. */
+int ke_webpa_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                   int32_t *heights, int32_t *channels, int32_t *status_out);
+int ke_webpa_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+int ke_webpa_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
+
 /* What `Image.open` alone does not tell about a file but the reference's defensive loader acts on (src/utils/image_io.py:60-138:
  * EXIF orientation applied, alpha composited over white): per file a set of KE_CAVEAT_* bits, so that a caller who wants that
  * loader's pixels sends flagged files through it and only the rest through ke_jpeg_decode / ke_png_decode.  ORIENTATION: the

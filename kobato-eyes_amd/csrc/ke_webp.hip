@@ -15,16 +15,9 @@
 #include <vector>
 
 #include "ke_internal.h"
-#include "ke_webp_parse.h"
+#include "ke_webp_launch.h"
 
 namespace {
-
-struct KeWebpDev {
-    KeWebpHeader h;
-    uint64_t file_off;     // the file inside the uploaded bytes
-    uint64_t scratch_off;  // coefficients (768 B per macroblock) | planes (384 B) | mode records (20 B), inside the scratch
-    uint64_t out_off;      // bytes into the caller's pixel buffer
-};
 
 __device__ __forceinline__ void ke_webp_layout(const KeWebpDev &d, uint8_t *scratch, int16_t *&coeffs, uint8_t *&planes, KeWebpMb *&mbs) {
     const size_t nmb = (size_t)d.h.mb_w * d.h.mb_h;
@@ -96,6 +89,12 @@ __global__ __launch_bounds__(256) void ke_webp_colour_k(const KeWebpDev *__restr
 }
 
 }  // namespace
+
+int ke_webp_launch_frames(ke_ctx *ctx, const KeWebpDev *d_imgs, int64_t m, const uint8_t *d_files, uint8_t *d_scratch, int32_t *d_status) {
+    hipLaunchKernelGGL(ke_webp_tokens_k, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs, m, d_files, d_scratch, d_status);
+    hipLaunchKernelGGL(ke_webp_recon_k, dim3((unsigned)m), dim3(64), 0, ctx->stream, d_imgs, d_scratch, (const int32_t *)d_status);
+    return KE_OK;
+}
 
 KE_API int ke_webp_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                          int32_t *heights, int32_t *channels, int32_t *status_out) {
@@ -180,8 +179,7 @@ KE_API int ke_webp_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
         devs.clear();
         while (last < which.size()) {
             KeWebpDev d = items[(size_t)which[last]];
-            const uint64_t nmb = (uint64_t)d.h.mb_w * d.h.mb_h;
-            const uint64_t need = (nmb * (768 + 384 + sizeof(KeWebpMb)) + 15) & ~15ull;
+            const uint64_t need = ke_webp_frame_scratch(d.h);
             if (last > first && bytes + need > budget) break;
             d.file_off -= lo;
             d.scratch_off = bytes;
@@ -196,10 +194,7 @@ KE_API int ke_webp_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
         KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)bytes + 64, &d_scratch));
         KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)m * 4, &d_status));
         KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs.data(), (size_t)m * sizeof(KeWebpDev), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(ke_webp_tokens_k, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (const KeWebpDev *)d_imgs, m,
-                           (const uint8_t *)d_files, (uint8_t *)d_scratch, (int32_t *)d_status);
-        hipLaunchKernelGGL(ke_webp_recon_k, dim3((unsigned)m), dim3(64), 0, ctx->stream, (const KeWebpDev *)d_imgs, (uint8_t *)d_scratch,
-                           (const int32_t *)d_status);
+        KE_TRY(ke_webp_launch_frames(ctx, (const KeWebpDev *)d_imgs, m, (const uint8_t *)d_files, (uint8_t *)d_scratch, (int32_t *)d_status));
         const int rows = std::max(kRowsPerBlock, (max_height + 65534) / 65535);
         hipLaunchKernelGGL(ke_webp_colour_k, dim3((unsigned)m, (unsigned)((max_height + rows - 1) / rows)), dim3(256), 0, ctx->stream,
                            (const KeWebpDev *)d_imgs, (const uint8_t *)d_scratch, (const int32_t *)d_status, pixels_out, rows);

@@ -73,14 +73,10 @@ static inline int ke_webp_container(const uint8_t *p, size_t size, uint32_t &vp8
     return have_vp8 ? KE_WEBP_OK : KE_WEBP_UNSUPPORTED;
 }
 
-// The container and the frame tag (section 9.1, 9.2): status, size, macroblocks -- what ke_webp_probe reports, without the
-// boolean-coded part of the header.  A file that passes here can still be refused by ke_parse_webp.
-static inline void ke_webp_frame_tag(const uint8_t *p, size_t size, KeWebpHeader &h) {
+// The frame tag of the payload h.vp8_off / h.vp8_size name, whichever container walk found it (this file's, or
+// ke_webpa_parse.h's for files with an alpha plane); cw x ch: the canvas of a VP8X file, 0 for the simple format.
+static inline void ke_webp_frame_tag_at(const uint8_t *p, KeWebpHeader &h, int cw, int ch) {
     using namespace ke_webp_detail;
-    std::memset(&h, 0, sizeof h);
-    int cw, ch;
-    h.status = ke_webp_container(p, size, h.vp8_off, h.vp8_size, cw, ch, h.meta);
-    if (h.status != KE_WEBP_OK) return;
     h.status = KE_WEBP_CORRUPT;
     const uint8_t *f = p + h.vp8_off;
     const uint32_t n = h.vp8_size;
@@ -102,10 +98,19 @@ static inline void ke_webp_frame_tag(const uint8_t *p, size_t size, KeWebpHeader
     h.status = KE_WEBP_OK;
 }
 
-// The whole record: container, frame header (section 9) and the token partitions.
-static inline void ke_parse_webp(const uint8_t *p, size_t size, KeWebpHeader &h) {
+// The container and the frame tag (section 9.1, 9.2): status, size, macroblocks -- what ke_webp_probe reports, without the
+// boolean-coded part of the header.  A file that passes here can still be refused by ke_parse_webp.
+static inline void ke_webp_frame_tag(const uint8_t *p, size_t size, KeWebpHeader &h) {
+    std::memset(&h, 0, sizeof h);
+    int cw, ch;
+    h.status = ke_webp_container(p, size, h.vp8_off, h.vp8_size, cw, ch, h.meta);
+    if (h.status != KE_WEBP_OK) return;
+    ke_webp_frame_tag_at(p, h, cw, ch);
+}
+
+// The boolean-coded frame header (section 9) and the token partitions of a frame whose tag passed.
+static inline void ke_webp_frame_header(const uint8_t *p, KeWebpHeader &h) {
     using namespace ke_webp_detail;
-    ke_webp_frame_tag(p, size, h);
     if (h.status != KE_WEBP_OK) return;
     h.status = KE_WEBP_CORRUPT;
     const uint32_t n = h.vp8_size, part0 = le24(p + h.vp8_off) >> 5;
@@ -223,11 +228,19 @@ static inline void ke_parse_webp(const uint8_t *p, size_t size, KeWebpHeader &h)
     h.status = KE_WEBP_OK;
 }
 
+// The whole record: container, frame header (section 9) and the token partitions.
+static inline void ke_parse_webp(const uint8_t *p, size_t size, KeWebpHeader &h) {
+    ke_webp_frame_tag(p, size, h);
+    ke_webp_frame_header(p, h);
+}
+
 // The CPU decode the tests hold against Pillow: the same steps as the kernels, one after the other.  scratch: at least
-// ke_webp_scratch_bytes(h) bytes, 16-aligned; rgb: width * height * 3 bytes.  Returns the status.
+// ke_webp_scratch_bytes(h) bytes, 16-aligned; rgb: width * height * 3 bytes -- or, with stride 4, the first three of every
+// pixel's four bytes (ke_webpa_parse.h fills in the fourth).  Returns the status.
 static inline size_t ke_webp_scratch_bytes(const KeWebpHeader &h) { return (size_t)h.mb_w * h.mb_h * (sizeof(KeWebpMb) + 768 + 384) + 64; }
 
-static inline int ke_webp_decode_cpu(const uint8_t *file, const KeWebpHeader &h, uint8_t *scratch, uint8_t *rgb, uint8_t *yuv_out = nullptr) {
+static inline int ke_webp_decode_cpu(const uint8_t *file, const KeWebpHeader &h, uint8_t *scratch, uint8_t *rgb, uint8_t *yuv_out = nullptr,
+                                     int stride = 3) {
     if (h.status != KE_WEBP_OK) return h.status;
     const size_t nmb = (size_t)h.mb_w * h.mb_h;
     int16_t *coeffs = (int16_t *)scratch;
@@ -242,6 +255,6 @@ static inline int ke_webp_decode_cpu(const uint8_t *file, const KeWebpHeader &h,
         for (int x = 0; x < h.mb_w; ++x) ke_webp_filter_mb(h, mbs[y * h.mb_w + x], Y, U, V, x, y);
     if (yuv_out) std::memcpy(yuv_out, planes, nmb * 384);
     for (int y = 0; y < h.height; ++y)
-        for (int x = 0; x < h.width; ++x) ke_webp_rgb_at(Y, U, V, h.mb_w, h.width, h.height, x, y, rgb + ((size_t)y * h.width + x) * 3);
+        for (int x = 0; x < h.width; ++x) ke_webp_rgb_at(Y, U, V, h.mb_w, h.width, h.height, x, y, rgb + ((size_t)y * h.width + x) * stride);
     return KE_WEBP_OK;
 }

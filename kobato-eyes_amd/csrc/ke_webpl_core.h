@@ -330,15 +330,11 @@ KE_HD uint64_t ke_vp8l_scratch_words(int w, int h) {
     return px + 3 * sub + 256 + 2048 + 600 + 16384 + px + 16;
 }
 
-// mem: ke_vp8l_scratch_words(w, h) words; mem[0 .. w * h) will hold the pixels.  `p` is the VP8L chunk's payload.
-KE_HD int ke_vp8l_decode_stream(const uint8_t *p, uint32_t len, int w, int h, uint32_t *mem, uint64_t cap, KeVp8lPlan &plan) {
-    KeVp8lBits b;
-    ke_vp8l_bits_init(b, p, len);
+// What follows the 5-byte header: transforms, colour cache, entropy image, codes, pixels, read from `b` as it stands.  The
+// header is exactly 40 bits, so a stream without one -- the VP8L-coded plane of an ALPH chunk, whose size the container
+// supplies (libwebp's VP8LDecodeAlphaHeader) -- starts here with a fresh reader.  mem / cap / plan as ke_vp8l_decode_stream.
+KE_HD int ke_vp8l_decode_body(KeVp8lBits &b, int w, int h, uint32_t *mem, uint64_t cap, KeVp8lPlan &plan) {
     plan.ntrans = 0;
-    if (ke_vp8l_read(b, 8) != 0x2f) return KE_WEBPL_CORRUPT;
-    const int hw = (int)ke_vp8l_read(b, 14) + 1, hh = (int)ke_vp8l_read(b, 14) + 1;
-    ke_vp8l_read(b, 1);                                            // the alpha hint
-    if (ke_vp8l_read(b, 3) != 0 || hw != w || hh != h) return KE_WEBPL_UNSUPPORTED;
     KeVp8lArena ar;
     ar.mem = mem;
     ar.cap = (uint32_t)(cap > 0xffffffffull ? 0xffffffffull : cap);
@@ -405,6 +401,18 @@ KE_HD int ke_vp8l_decode_stream(const uint8_t *p, uint32_t len, int w, int h, ui
     plan.xsize = xs;
     plan.pix = (uint32_t)w * h - (uint32_t)xs * h;
     return ke_vp8l_decode_pixels(b, mem, e, mem + plan.pix, xs, h);
+}
+
+// mem: ke_vp8l_scratch_words(w, h) words; mem[0 .. w * h) will hold the pixels.  `p` is the VP8L chunk's payload.
+KE_HD int ke_vp8l_decode_stream(const uint8_t *p, uint32_t len, int w, int h, uint32_t *mem, uint64_t cap, KeVp8lPlan &plan) {
+    KeVp8lBits b;
+    ke_vp8l_bits_init(b, p, len);
+    plan.ntrans = 0;
+    if (ke_vp8l_read(b, 8) != 0x2f) return KE_WEBPL_CORRUPT;
+    const int hw = (int)ke_vp8l_read(b, 14) + 1, hh = (int)ke_vp8l_read(b, 14) + 1;
+    ke_vp8l_read(b, 1);                                            // the alpha hint
+    if (ke_vp8l_read(b, 3) != 0 || hw != w || hh != h) return KE_WEBPL_UNSUPPORTED;
+    return ke_vp8l_decode_body(b, w, h, mem, cap, plan);
 }
 
 // ---- inverse transforms, per pixel ------------------------------------------------------------------------------------------

@@ -91,14 +91,9 @@ KE_HD void ke_vp8l_store(uint32_t argb, uint8_t *o, int channels) {
     if (channels == 4) o[3] = (uint8_t)(argb >> 24);
 }
 
-// The CPU decode the tests hold against Pillow: the same steps as the kernels, one after the other.  mem:
-// ke_vp8l_scratch_words(width, height) words; out: width * height * channels bytes.  Returns the status.
-static inline int ke_webpl_decode_cpu(const uint8_t *file, const KeWebplHeader &h, uint32_t *mem, uint8_t *out) {
-    if (h.status != KE_WEBPL_OK) return h.status;
-    const int W = h.width, H = h.height;
-    KeVp8lPlan plan;
-    const int st = ke_vp8l_decode_stream(file + h.off, h.size, W, H, mem, ke_vp8l_scratch_words(W, H), plan);
-    if (st != KE_WEBPL_OK) return st;
+// The inverse transforms of a decoded stream on the CPU, last to first: the same steps as ke_webpl_transform_k, one after the
+// other.  Returns where the finished W x H image lies (the front of mem).
+static inline uint32_t *ke_vp8l_undo_transforms_cpu(uint32_t *mem, const KeVp8lPlan &plan, int W, int H) {
     uint32_t *pix = mem + plan.pix;
     for (int k = plan.ntrans - 1; k >= 0; --k) {
         const KeVp8lXform &t = plan.t[k];
@@ -121,6 +116,18 @@ static inline int ke_webpl_decode_cpu(const uint8_t *file, const KeWebplHeader &
             pix = wide;
         }
     }
+    return pix;
+}
+
+// The CPU decode the tests hold against Pillow: the same steps as the kernels, one after the other.  mem:
+// ke_vp8l_scratch_words(width, height) words; out: width * height * channels bytes.  Returns the status.
+static inline int ke_webpl_decode_cpu(const uint8_t *file, const KeWebplHeader &h, uint32_t *mem, uint8_t *out) {
+    if (h.status != KE_WEBPL_OK) return h.status;
+    const int W = h.width, H = h.height;
+    KeVp8lPlan plan;
+    const int st = ke_vp8l_decode_stream(file + h.off, h.size, W, H, mem, ke_vp8l_scratch_words(W, H), plan);
+    if (st != KE_WEBPL_OK) return st;
+    const uint32_t *pix = ke_vp8l_undo_transforms_cpu(mem, plan, W, H);
     for (size_t i = 0; i < (size_t)W * H; ++i) ke_vp8l_store(pix[i], out + i * h.channels, h.channels);
     return KE_WEBPL_OK;
 }

@@ -514,8 +514,10 @@ class _Pipeline:
                 except (RuntimeError, ValueError, MemoryError):      # e.g. no room on the device for this batch: Pillow decodes it
                     refused.extend(positions.tolist())
                     continue
-                if kind == "webp" and os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":
-                    p, d, st = self._offer_to_lossless(held, lo, first, positions, None if by_path or held is not None else blobs, p, d, st)
+                if kind == "webp":                         # what the lossy decoder refused: the opt-in decoders, one after the other
+                    for follow_up, variable in (("webpl", "KE_GPU_WEBP_LOSSLESS"), ("webpa", "KE_GPU_WEBP_ALPHA")):
+                        if os.environ.get(variable, "0") == "1":
+                            p, d, st = self._offer_to(follow_up, held, lo, first, positions, None if by_path or held is not None else blobs, p, d, st)
                 good = np.asarray(st) == 0
                 at = positions[good] - start
                 ph[at] = np.asarray(p, np.uint64).view(np.int64)[good]
@@ -528,8 +530,9 @@ class _Pipeline:
                 held.release()
         return refused
 
-    def _offer_to_lossless(self, held, lo: int, hi: int, positions, blobs, p, d, st):
-        """The .webp files the lossy decoder returned as UNSUPPORTED, offered to the lossless one (``KE_GPU_WEBP_LOSSLESS=1``)
+    def _offer_to(self, follow_up: str, held, lo: int, hi: int, positions, blobs, p, d, st):
+        """The .webp files still UNSUPPORTED after the decoders before it, offered to ``follow_up`` -- "webpl", the lossless
+        decoder (``KE_GPU_WEBP_LOSSLESS=1``), or "webpa", the one for lossy files with an alpha plane (``KE_GPU_WEBP_ALPHA=1``) --
         over the same files -- the read-ahead range with the files already taken masked, their paths, or their bytes --
         before they go to Pillow: (p, d, st) with its results filled in.  What it refuses keeps its status."""
         p, d, st = np.array(p, np.uint64), np.array(d, np.uint64), np.array(st, np.int32)
@@ -538,12 +541,12 @@ class _Pipeline:
             return p, d, st
         try:
             if held is not None:
-                p2, d2, st2 = self.stage.hash_ahead(held, lo, hi, "webpl", skip=~again)
+                p2, d2, st2 = self.stage.hash_ahead(held, lo, hi, follow_up, skip=~again)
                 p2, d2, st2 = (np.asarray(a)[again] for a in (p2, d2, st2))
             elif blobs is None:
-                p2, d2, st2 = self.stage.hash_files([self.paths[k] for k in positions[again].tolist()], "webpl")
+                p2, d2, st2 = self.stage.hash_files([self.paths[k] for k in positions[again].tolist()], follow_up)
             else:
-                p2, d2, st2 = self.stage.jpeg_hash([b for b, a in zip(blobs, again.tolist()) if a], "webpl")
+                p2, d2, st2 = self.stage.jpeg_hash([b for b, a in zip(blobs, again.tolist()) if a], follow_up)
         except (RuntimeError, ValueError, MemoryError):          # Pillow decodes them, as before
             return p, d, st
         took = np.nonzero(again)[0][np.asarray(st2) == 0]

@@ -119,6 +119,8 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
             gpu_kinds["webp"] = (".webp",)
             if os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":      # after the lossy decoder: what that one did not place
                 gpu_kinds["webpl"] = (".webp",)
+            if os.environ.get("KE_GPU_WEBP_ALPHA", "0") == "1":         # lossy files with an alpha plane: RGBA, composited below
+                gpu_kinds["webpa"] = (".webp",)
 
     def decode_on_gpu(need: list, placed: dict, buffers: list) -> None:
         """JPEG / PNG / BMP / TIFF / WebP files whose pixels the reference's loader would hand over exactly as Image.open yields them -- RGB, no
@@ -139,10 +141,13 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
                     placed[p] = (dev + int(o), ww, hh)
             count["gpu_decodes"] += int(ok.sum())
             # what the loader does to the rest (src/utils/image_io.py:116-131) happens on the device as well: the EXIF
-            # orientation of a JPEG file applied (every camera writes one), an RGBA PNG composited over white
+            # orientation of a JPEG file applied (every camera writes one), an RGBA PNG -- or a lossy WebP file with an alpha plane,
+            # KE_GPU_WEBP_ALPHA=1 -- composited over white
             orient = (flags >> 8) & 15
             turn = fits & (c == 3) & ((flags & 3) == 1) & (orient >= 2) & (orient <= 8) if kind == "jpeg" else np.zeros(len(paths), bool)
             over = fits & (c == 4) & ((flags & 3) == 0) if kind in ("png", "bmp", "tiff") else np.zeros(len(paths), bool)
+            if kind == "webpa":                                     # every file it takes carries the transparency bit: the orientation decides
+                over = fits & (c == 4) & ((flags & 1) == 0)
             fix = np.nonzero(turn | over)[0]
             if len(fix):
                 dev2, off2, w2, h2 = ctx.normalise_rgb(dev, off[fix], w[fix], h[fix], c[fix], np.where(turn[fix], orient[fix], 1))
