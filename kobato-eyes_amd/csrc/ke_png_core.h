@@ -145,7 +145,8 @@ struct KeNibWriter {
 };
 
 // Builds the decoding tables of one code from the lengths at nibbles [nib0, nib0 + n) (RFC 1951 3.2.2).
-// Returns 0 for a complete code (or one without any symbol, which decodes nothing), > 0 incomplete, < 0 over-subscribed;
+// Returns 0 for a complete code (or one without any symbol, which decodes nothing), > 0 incomplete: the code space left, out
+// of 2^15 (a lone 1-bit code, the one incomplete set zlib allows, leaves exactly 2^14), < 0 over-subscribed;
 // *unused = number of symbols without a code.
 template <typename Tab>
 KE_PNG_HD int ke_inflate_build(Tab &t, int which, int n, int nib0, int *unused) {
@@ -348,13 +349,15 @@ KE_PNG_HD int ke_inflate_zlib(KeBitsLsb<Src> &b, Sink &out, uint32_t zlen, uint3
             nw.flush();
             if (((t.nibword(256 >> 3) >> (4 * (256 & 7))) & 15u) == 0) return KE_PNG_CORRUPT;      // no end-of-block code
         }
-        // literal/length: an incomplete code is only allowed when it has a single code (zlib's rule); same for distances
-        // (the fixed distance code, 30 of 32 five-bit codes, is incomplete by definition)
+        // literal/length: an incomplete code is only allowed when it is a single code of ONE bit (zlib's rule, inftrees.c:
+        // incomplete only if the longest code is 1 bit long); same for distances.  Of the code space 2^15 such a code leaves
+        // exactly half, which two codes of 2 bits would too -- hence both conditions.  (The fixed distance code, 30 of 32
+        // five-bit codes, is incomplete by definition.)
         int unused;
         int err = ke_inflate_build(t, 0, nlen, 0, &unused);
-        if (type == 2 && (err < 0 || (err > 0 && nlen - unused != 1))) return KE_PNG_CORRUPT;
+        if (type == 2 && (err < 0 || (err > 0 && (nlen - unused != 1 || err != (1 << 14))))) return KE_PNG_CORRUPT;
         err = ke_inflate_build(t, 1, ndist, nlen, &unused);
-        if (type == 2 && (err < 0 || (err > 0 && ndist - unused != 1))) return KE_PNG_CORRUPT;
+        if (type == 2 && (err < 0 || (err > 0 && (ndist - unused != 1 || err != (1 << 14))))) return KE_PNG_CORRUPT;
         // the block's symbols.  Written for lock-step execution (on the GPU all 64 lanes of a wave pay for every path any of
         // them takes, every symbol): one way out of the loop, damage remembered instead of returned mid-way.
         KE_OCT_LOAD(l, KE_LIM0);
