@@ -242,6 +242,29 @@ int ke_tiff_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, c
                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
 int ke_tiff_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
 
+/* ---- LZW and PackBits TIFF files decoded on the GPU: the same step (src/core/fastsig.py:31-34; src/dup/scanner.py:16-28 ranks the
+ * format among the keepers) for the compressed files Pillow hands to libtiff: baseline 8-bit strip files whose Compression is 5
+ * (LZW) or 32773 (PackBits), Predictor absent, 1 or 2 (horizontal differencing), in the photometric layouts of ke_tiff_decode and
+ * with the same pixels -- gray (WhiteIsZero inverted), RGB, RGBA (unassociated alpha or no ExtraSamples), an unspecified fourth
+ * sample dropped, palette files as the luma `convert("L")` makes of them (src/sig/phash.py:25), channels = 1.  Every strip is a
+ * stream of its own: one thread per strip walks the LZW codes (MSB-first, 9 to 12 bits, "early" width change, as libtiff's
+ * LZWDecode) or the PackBits headers (literals to their place, strings and runs recorded as copies from earlier output), one
+ * wave per strip makes the copies, a last kernel undoes the predictor and maps the samples.  The whitelist is tighter than
+ * ke_tiff_decode's, because Pillow's parser decides mode and size but libtiff's directory reader decides what is decoded:
+ * entries in strictly ascending tag order (no tag twice) out of a fixed list of tags, layout tags SHORT or LONG with their
+ * exact counts, one StripOffsets / StripByteCounts value per strip of RowsPerStrip rows, LZW strips that open with the clear code
+ * (old-style LSB-first streams do not).  Deflate, JPEG-in-TIFF, CCITT, tiles, planar layout, 16-bit samples, predictor 3, BigTIFF
+ * and everything ke_tiff_decode refuses: KE_JPEG_UNSUPPORTED_ (1) per file; a strip that leaves the file or whose stream fails
+ * where libtiff's fails (a code not yet in the table, data that ends before the strip is full): KE_JPEG_CORRUPT_ (2).
+ * Uncompressed files are ke_tiff_decode's and are refused here (1).  Arguments and conventions as ke_jpeg_probe /
+ * ke_jpeg_decode; on an error after the upload has begun the stream is synchronised before the call returns.  ke_tiffc_caveats
+ * reports no flags (files with an orientation are refused). */
+int ke_tiffc_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                   int32_t *heights, int32_t *channels, int32_t *status_out);
+int ke_tiffc_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+int ke_tiffc_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
+
 /* ---- lossy WebP files decoded on the GPU: the same step (src/core/fastsig.py:31-34, src/utils/image_io.py:60-138) for WebP files
  * of one VP8 key frame -- the simple format (RIFF / WEBP / "VP8 ") and VP8X files without alpha or animation, their ICCP / EXIF /
  * "XMP " chunks skipped (Pillow applies none of them when it opens the file).  The pixels are libwebp's as Pillow drives it

@@ -31,18 +31,31 @@ struct KeTiffInfo {
     uint8_t lut[256];
 };
 
-// strips: the offsets of the image's strips are appended (nothing is appended unless the status is KE_TIFF_OK)
-static inline void ke_parse_tiff(const uint8_t *p, size_t size, std::vector<uint32_t> *strips, KeTiffInfo &info) {
+// A file's 16- and 32-bit fields in its byte order, and the size of a value per field type (0: not a type the readers know).
+struct KeTiffBytes {
+    const uint8_t *p;
+    bool le;
+    uint32_t rd16(size_t o) const { return le ? (uint32_t)p[o] | ((uint32_t)p[o + 1] << 8) : ((uint32_t)p[o] << 8) | p[o + 1]; }
+    uint32_t rd32(size_t o) const {
+        return le ? (uint32_t)p[o] | ((uint32_t)p[o + 1] << 8) | ((uint32_t)p[o + 2] << 16) | ((uint32_t)p[o + 3] << 24)
+                  : ((uint32_t)p[o] << 24) | ((uint32_t)p[o + 1] << 16) | ((uint32_t)p[o + 2] << 8) | p[o + 3];
+    }
+};
+static const int ke_tiff_unit[17] = {0, 1, 1, 2, 4, 8, 1, 1, 2, 4, 8, 4, 8, 4, 0, 0, 8};
+
+// The directory reading shared with the decoder for compressed files (ke_tiffc_parse.h).  compression == nullptr: the
+// uncompressed whitelist below, ke_parse_tiff's.  Otherwise the same reading for a file whose Compression is 5 (LZW) or 32773
+// (PackBits), written to *compression: a strip is a stream of its own there, so the raw decoder's strip rules (only the last
+// offset counts, every strip whole in the file) are the caller's to replace -- one offset per strip of RowsPerStrip rows.
+static inline void ke_parse_tiff_directory(const uint8_t *p, size_t size, std::vector<uint32_t> *strips, KeTiffInfo &info, uint32_t *compression) {
     std::memset(&info, 0, sizeof info);
     info.status = KE_TIFF_CORRUPT;
     if (size < 8) return;
     const bool le = p[0] == 'I' && p[1] == 'I', be = p[0] == 'M' && p[1] == 'M';
     if (!le && !be) return;
-    auto rd16 = [&](size_t o) { return le ? (uint32_t)p[o] | ((uint32_t)p[o + 1] << 8) : ((uint32_t)p[o] << 8) | p[o + 1]; };
-    auto rd32 = [&](size_t o) {
-        return le ? (uint32_t)p[o] | ((uint32_t)p[o + 1] << 8) | ((uint32_t)p[o + 2] << 16) | ((uint32_t)p[o + 3] << 24)
-                  : ((uint32_t)p[o] << 24) | ((uint32_t)p[o + 1] << 16) | ((uint32_t)p[o + 2] << 8) | p[o + 3];
-    };
+    const KeTiffBytes bytes_of{p, le};
+    auto rd16 = [&](size_t o) { return bytes_of.rd16(o); };
+    auto rd32 = [&](size_t o) { return bytes_of.rd32(o); };
     const uint32_t magic = rd16(2);
     if (magic != 42 && magic != 43) return;                        // Pillow: not identified
     info.status = KE_TIFF_UNSUPPORTED;
@@ -58,7 +71,7 @@ static inline void ke_parse_tiff(const uint8_t *p, size_t size, std::vector<uint
                                           34665, 34853, 40965, 0xBC01};
     Tag tags[T_COUNT];
     for (Tag &t : tags) t = Tag{0, 0, 0, false};
-    static const int unit[17] = {0, 1, 1, 2, 4, 8, 1, 1, 2, 4, 8, 4, 8, 4, 0, 0, 8};
+    const int *unit = ke_tiff_unit;
     for (size_t k = 0; k < n; ++k) {
         const size_t e = ifd + 2 + 12 * k;
         const uint32_t id = rd16(e), type = rd16(e + 2), count = rd32(e + 4);
@@ -90,7 +103,9 @@ static inline void ke_parse_tiff(const uint8_t *p, size_t size, std::vector<uint
     if (!scalar(T_COMP, 1, comp) || !scalar(T_PLANAR, 1, planar) || !scalar(T_PHOTO, 0, photo) || !scalar(T_FILL, 1, fill) ||
         !scalar(T_ORIENT, 1, orient) || !scalar(T_SPP, 1, spp))
         return;
-    if (comp != 1 || planar != 1 || fill != 1 || orient != 1 || photo > 3) return;
+    if (compression ? (comp != 5 && comp != 32773) : comp != 1) return;
+    if (compression) *compression = comp;
+    if (planar != 1 || fill != 1 || orient != 1 || photo > 3) return;
     if (!tags[T_WIDTH].have || !tags[T_LENGTH].have || !scalar(T_WIDTH, 0, W) || !scalar(T_LENGTH, 0, H)) return;
     if (W == 0 || H == 0 || W > 65535 || (uint64_t)W * H > (1ull << 28)) return;
     // resolution tags are read by _setup too: one value each (any numeric type), or absent
@@ -147,7 +162,7 @@ static inline void ke_parse_tiff(const uint8_t *p, size_t size, std::vector<uint
     if (!so.have || !is_int(so) || so.count == 0) return;
     if (!scalar(T_ROWS, H, rows) || rows == 0) return;
     uint32_t first = 0, count = so.count;
-    if (rows == H) {                                               // "every tile covers the image: only use the last offset"
+    if (rows == H && !compression) {                               // "every tile covers the image: only use the last offset"
         first = so.count - 1;
         count = 1;
     } else if ((uint64_t)count != ((uint64_t)H + rows - 1) / rows) {
@@ -155,7 +170,7 @@ static inline void ke_parse_tiff(const uint8_t *p, size_t size, std::vector<uint
     }
     if (count > (1u << 20)) return;                                // (a strip per row of a 1-pixel-wide giant: not worth a gigabyte of offsets)
     const uint64_t stride = (uint64_t)W * spp;
-    for (uint32_t s = 0; s < count; ++s) {
+    for (uint32_t s = 0; s < count && !compression; ++s) {
         const uint64_t off = value(so, first + s);
         const uint64_t y0 = (uint64_t)s * rows, nrows = (y0 + rows <= H ? rows : H - y0);
         if (off > size || stride * nrows > size - off) {           // the raw decoder wants every strip whole
@@ -170,4 +185,9 @@ static inline void ke_parse_tiff(const uint8_t *p, size_t size, std::vector<uint
     info.rows_per_strip = (int32_t)(rows > H ? H : rows);
     info.nstrips = (int32_t)count;
     info.status = KE_TIFF_OK;
+}
+
+// strips: the offsets of the image's strips are appended (nothing is appended unless the status is KE_TIFF_OK)
+static inline void ke_parse_tiff(const uint8_t *p, size_t size, std::vector<uint32_t> *strips, KeTiffInfo &info) {
+    ke_parse_tiff_directory(p, size, strips, info, nullptr);
 }

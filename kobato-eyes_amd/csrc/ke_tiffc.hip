@@ -1,0 +1,322 @@
+// ke_tiffc.hip -- LZW and PackBits TIFF files decoded on the GPU: the decode step in front of the hash path for the
+// compressed files of the fifth format the reference ranks as a keeper (src/dup/scanner.py:16-28).  Replaces `Image.open(path)` +
+// pixel access of the reference's batch hasher (src/core/fastsig.py:31-34) for the files ke_tiffc_parse.h takes -- those Pillow
+// hands to libtiff; the pixels that leave are ke_tiff_decode's for the same image stored uncompressed.  The arithmetic is
+// ke_tiffc_core.h's (held against Pillow on the CPU).  The scheme is ke_gif.hip's, with one difference that matters: every
+// strip of a TIFF file is a stream of its own (libtiff writes strips of at most 64 KB: a 512 x 512 RGB file has 13), so the
+// sequential walk is as long as a strip, not as a file, and there are strips-per-file times as many lanes.
+//
+//   ke_tiffc_codes   ONE LANE PER STRIP walks the LZW codes or the PackBits headers.  A literal goes to its place in the strip's
+//                    plane (its bytes before the predictor); a string or a run lies in the output already and is recorded as
+//                    a copy (ke_lz_copies.h), not made: a lane that waited for its own stores would stall the other 63.  The
+//                    strip's bytes come through a 16-byte register window refilled one step ahead.  The LZW dictionary (4 096
+//                    x {where, how long}) is a slice of HBM per RESIDENT lane, not per strip: the waves take groups of 64
+//                    strips off a list (one atomic per group) until it is empty.  The list is sorted by compression and
+//                    compressed length, longest first, so the lanes of a wave walk strips of like length and the long
+//                    groups start first.
+//   ke_tiffc_copies  ONE WAVE PER STRIP makes the recorded copies, 64 per round (ke_lz_copies.h, the PNG path's).
+//   ke_tiffc_rows    one wave per row: undoes predictor 2 (a prefix sum per sample modulo 256 over the lanes, 64 pixels a step,
+//                    the carry handed on), then ke_tiff_unpack's mapping -- WhiteIsZero and palette files through the table, an
+//                    unspecified fourth sample dropped -- into the caller's pixels.  Bytes in + bytes out, each once.
+#include <algorithm>
+#include <vector>
+
+#include "ke_internal.h"
+
+#include "ke_lz_copies.h"
+#include "ke_lz_window.h"
+#include "ke_tiffc_parse.h"
+
+namespace {
+
+struct KeTiffcImgDev {
+    uint64_t out_off;      // bytes into the caller's pixel buffer
+    uint64_t plane_off;    // the image's strip planes inside the scratch: strip s at plane_off + s * strip_stride
+    uint32_t strip_stride;
+    int32_t width, height, spp, channels, mapped, rows_per_strip, predictor;
+    uint8_t lut[256];
+};
+
+struct KeTiffcStripDev {
+    uint64_t file_off;     // the strip's bytes inside the uploaded bytes
+    uint64_t plane_off;    // its plane inside the scratch
+    uint64_t rec_off;      // its copy records (8 bytes each)
+    uint32_t bytes, want;  // compressed bytes; bytes the strip yields
+    uint32_t img, comp;
+};
+
+constexpr uint32_t kMaxCopy = 511 + 2;            // the record's length field
+constexpr uint32_t kMaxWaves = 2048;              // resident lanes: 131 072 dictionaries of 32 KB = 4 GB at most
+
+struct RecSink {
+    uint8_t *plane;
+    uint2 *rec;
+    uint32_t out, nrec;
+    __device__ __forceinline__ void literal(uint8_t b) { plane[out++] = b; }
+    __device__ __forceinline__ void copy(uint32_t from, uint32_t len) {
+        const uint32_t dist = out - from;
+        // A copy has at least 2 bytes; only a strip's last string can be cut to 1 -- it is recorded as 2, the second byte lands
+        // in the slack behind the strip's plane.  Pieces of at most 513, none of them a single byte.
+        if (len == 1) len = 2;
+        while (len) {
+            const uint32_t take = len > kMaxCopy ? (len - kMaxCopy == 1 ? kMaxCopy - 1 : kMaxCopy) : len;
+            rec[nrec++] = make_uint2(out, (dist << 9) | (take - 2));
+            out += take;
+            len -= take;
+        }
+    }
+};
+
+__global__ __launch_bounds__(64) void ke_tiffc_codes(const KeTiffcStripDev *__restrict__ strips, uint32_t n, const uint8_t *__restrict__ files,
+                                                   uint8_t *__restrict__ planes, uint2 *__restrict__ records, uint2 *__restrict__ dicts,
+                                                   int32_t *__restrict__ status, uint32_t *__restrict__ nrec, uint32_t *__restrict__ next_group) {
+    HbmDict dict{dicts + ((size_t)blockIdx.x * 64 + threadIdx.x) * 4096};
+    for (;;) {
+        uint32_t g = 0;
+        if (threadIdx.x == 0) g = atomicAdd(next_group, 1u);
+        g = (uint32_t)__shfl((int)g, 0);
+        if ((uint64_t)g * 64 >= n) break;
+        const uint32_t s = g * 64 + threadIdx.x;
+        if (s < n) {
+            const KeTiffcStripDev &d = strips[s];
+            WindowSrc src;
+            src.file = files + d.file_off;
+            src.limit = d.bytes;
+            src.start(0);
+            RecSink sink{planes + d.plane_off, records + d.rec_off, 0, 0};
+            const int st = d.comp == KE_TIFFC_LZW ? ke_tiffc_lzw(src, 0u, d.bytes, d.want, dict, sink) : ke_tiffc_packbits(src, 0u, d.bytes, d.want, sink);
+            if (st != KE_TIFFC_OK) status[d.img] = st;             // any strip's failure is the image's (the same value or another: not 0)
+            nrec[s] = sink.nrec;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void ke_tiffc_copies(const KeTiffcStripDev *__restrict__ strips, uint8_t *__restrict__ planes,
+                                                    const uint2 *__restrict__ records, const int32_t *__restrict__ status,
+                                                    const uint32_t *__restrict__ nrec) {
+    const KeTiffcStripDev &d = strips[blockIdx.x];
+    if (status[d.img] != KE_TIFFC_OK) return;
+    ke_lz_make_copies(planes + d.plane_off, records + d.rec_off, nrec[blockIdx.x], 2u);
+}
+
+constexpr int kRowsPerBlock = 8;      // at least; more for images taller than 65 535 bands of them
+
+__global__ __launch_bounds__(256) void ke_tiffc_rows(const KeTiffcImgDev *__restrict__ imgs, const uint8_t *__restrict__ planes,
+                                                   const int32_t *__restrict__ status, uint8_t *__restrict__ out, int rows) {
+    __shared__ uint8_t s_lut[256];
+    const KeTiffcImgDev &d = imgs[blockIdx.x];
+    const int y0 = blockIdx.y * rows;
+    if (status[blockIdx.x] != KE_TIFFC_OK || y0 >= d.height) return;
+    s_lut[threadIdx.x] = d.lut[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int W = d.width, spp = d.spp, ch = d.channels, y1 = min(y0 + rows, d.height);
+    const bool mapped = d.mapped != 0;
+    for (int y = y0 + wave; y < y1; y += 4) {
+        const uint8_t *row = planes + d.plane_off + (size_t)(y / d.rows_per_strip) * d.strip_stride + (size_t)(y % d.rows_per_strip) * W * spp;
+        uint8_t *dst = out + d.out_off + (size_t)y * W * ch;
+        if (d.predictor != 2) {
+            if (spp == ch) {
+                const int n = W * ch;
+                for (int k = lane; k < n; k += 64) dst[k] = mapped ? s_lut[row[k]] : row[k];
+            } else {                                           // four samples stored, three leave
+                for (int x = lane; x < W; x += 64) {
+                    uint32_t v;
+                    __builtin_memcpy(&v, row + 4 * (size_t)x, 4);
+                    uint8_t *w = dst + 3 * (size_t)x;
+                    w[0] = (uint8_t)v; w[1] = (uint8_t)(v >> 8); w[2] = (uint8_t)(v >> 16);
+                }
+            }
+            continue;
+        }
+        uint32_t carry = 0;                                    // the pixel in front of this step's first, its samples in the bytes
+        for (int x0 = 0; x0 < W; x0 += 64) {
+            const int x = x0 + lane;
+            uint32_t v = 0;
+            if (x < W) {
+                const uint8_t *r = row + (size_t)x * spp;
+                if (spp == 1) v = r[0];
+                else if (spp == 3) v = (uint32_t)r[0] | ((uint32_t)r[1] << 8) | ((uint32_t)r[2] << 16);
+                else __builtin_memcpy(&v, r, 4);
+            }
+#pragma unroll
+            for (int step = 1; step < 64; step <<= 1) {
+                const uint32_t t = (uint32_t)__shfl_up((int)v, step);
+                if (lane >= step) v = ke_tiffc_add4(v, t);
+            }
+            v = ke_tiffc_add4(v, carry);
+            carry = (uint32_t)__shfl((int)v, 63);
+            if (x < W) {
+                if (ch == 1) {
+                    dst[x] = mapped ? s_lut[v & 255u] : (uint8_t)v;
+                } else if (ch == 3) {
+                    uint8_t *w = dst + 3 * (size_t)x;
+                    w[0] = (uint8_t)v; w[1] = (uint8_t)(v >> 8); w[2] = (uint8_t)(v >> 16);
+                } else {
+                    __builtin_memcpy(dst + 4 * (size_t)x, &v, 4);
+                }
+            }
+        }
+    }
+}
+
+struct SyncOnExit {                               // keyes.h: the caller's buffers are free on return -- also on an error after the first async copy
+    hipStream_t stream;
+    bool armed;
+    ~SyncOnExit() {
+        if (armed) (void)hipStreamSynchronize(stream);
+    }
+};
+
+}  // namespace
+
+KE_API int ke_tiffc_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                          int32_t *heights, int32_t *channels, int32_t *status_out) {
+    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
+    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
+        for (int64_t i = lo; i < hi; ++i) {
+            KeTiffcInfo info;
+            ke_parse_tiffc(files + offsets[i], (size_t)sizes[i], nullptr, info);
+            widths[i] = info.t.width; heights[i] = info.t.height; channels[i] = info.t.channels;
+            status_out[i] = info.t.status;
+        }
+    });
+    return KE_OK;
+}
+
+KE_API int ke_tiffc_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
+    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
+    // files that carry an orientation (the tag, an EXIF directory, an XMP packet) are refused by the parser: Pillow turns them
+    for (int64_t i = 0; i < n; ++i) flags_out[i] = 0;
+    return KE_OK;
+}
+
+KE_API int ke_tiffc_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                           uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
+    if (!ctx) return KE_EINVAL;
+    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
+        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    if (n == 0) return KE_OK;
+    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "the files' directories are parsed on the host: pass host memory (pinned staging is fine)");
+    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
+    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
+        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
+    KE_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<KeTiffcInfo> infos((size_t)n);                   // the directories are read on the host's threads
+    std::vector<std::vector<KeTiffcStrip>> found((size_t)n);
+    ke_parallel_ranges(n, [&](int64_t a, int64_t b, int) {
+        for (int64_t i = a; i < b; ++i) ke_parse_tiffc(files + offsets[i], (size_t)sizes[i], &found[(size_t)i], infos[(size_t)i]);
+    });
+    std::vector<int64_t> which;
+    uint64_t lo = ~0ull, hi = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        status_out[i] = infos[(size_t)i].t.status;
+        if (status_out[i] != KE_TIFF_OK) continue;
+        which.push_back(i);
+        lo = std::min(lo, offsets[i]);
+        hi = std::max(hi, offsets[i] + sizes[i]);
+    }
+    if (which.empty()) return KE_OK;
+    void *d_files;
+    KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)(hi - lo) + 256, &d_files));
+    SyncOnExit guard{ctx->stream, true};
+    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
+    // sub-batches bounded by scratch: the strips' planes (1 B per sample) + their copy records (8 B each) + 32 KB of dictionary
+    // per resident lane when the sub-batch has LZW strips
+    size_t free_b = 0, total_b = 0;
+    KE_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    const uint64_t held = (uint64_t)ctx->buf[KE_BUF_TMP].bytes + ctx->buf[KE_BUF_SSIM_AUX].bytes + ctx->buf[KE_BUF_SSIM_IN].bytes;
+    uint64_t budget = std::max<uint64_t>((uint64_t)1 << 30, std::min<uint64_t>((held + (uint64_t)free_b) / 2, (uint64_t)32 << 30));
+    if (const char *e = std::getenv("KE_TIFFC_SCRATCH_BYTES")) budget = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+    std::vector<KeTiffcImgDev> imgs;
+    std::vector<KeTiffcStripDev> strips;
+    std::vector<int32_t> st;
+    auto dict_bytes = [](uint64_t strips_so_far, bool lzw) {
+        return lzw ? std::min<uint64_t>((strips_so_far + 63) / 64, kMaxWaves) * 64 * 32768 : (uint64_t)64;
+    };
+    size_t first = 0;
+    ke_time_begin(ctx, KE_T_JPEG);
+    while (first < which.size()) {
+        uint64_t plane_bytes = 0, nrecs = 0;
+        int max_height = 0;
+        bool any_lzw = false;
+        size_t last = first;
+        imgs.clear();
+        strips.clear();
+        while (last < which.size()) {
+            const int64_t i = which[last];
+            const KeTiffcInfo &info = infos[(size_t)i];
+            const KeTiffInfo &t = info.t;
+            const uint64_t row = (uint64_t)t.width * t.spp;
+            const uint64_t stride = (row * t.rows_per_strip + 2 + 15) & ~15ull;
+            uint64_t pb = stride * t.nstrips, rc = 0;
+            for (int s = 0; s < t.nstrips; ++s) {
+                const uint64_t want = row * std::min(t.rows_per_strip, t.height - s * t.rows_per_strip);
+                // a record per string or run -- at most one per compressed byte -- and per further 513 bytes of a long one;
+                // never more than one per 2 bytes the strip yields
+                rc += std::min<uint64_t>(want / 2 + 2, (uint64_t)found[(size_t)i][(size_t)s].bytes + want / 512 + 2);
+            }
+            const bool lzw = any_lzw || info.compression == KE_TIFFC_LZW;
+            if (last > first && plane_bytes + pb + (nrecs + rc) * 8 + dict_bytes(strips.size() + (size_t)t.nstrips, lzw) > budget) break;
+            KeTiffcImgDev d;
+            d.out_off = out_offsets[i];
+            d.plane_off = plane_bytes;
+            d.strip_stride = (uint32_t)stride;
+            d.width = t.width; d.height = t.height; d.spp = t.spp; d.channels = t.channels; d.mapped = t.mapped;
+            d.rows_per_strip = t.rows_per_strip; d.predictor = info.predictor;
+            std::memcpy(d.lut, t.lut, 256);
+            for (int s = 0; s < t.nstrips; ++s) {
+                const KeTiffcStrip &f = found[(size_t)i][(size_t)s];
+                KeTiffcStripDev sd;
+                sd.file_off = offsets[i] - lo + f.off;
+                sd.plane_off = plane_bytes + stride * (uint64_t)s;
+                sd.rec_off = nrecs;
+                sd.bytes = f.bytes;
+                sd.want = (uint32_t)(row * std::min(t.rows_per_strip, t.height - s * t.rows_per_strip));
+                sd.img = (uint32_t)imgs.size();
+                sd.comp = (uint32_t)info.compression;
+                nrecs += std::min<uint64_t>((uint64_t)sd.want / 2 + 2, (uint64_t)f.bytes + sd.want / 512 + 2);
+                strips.push_back(sd);
+            }
+            any_lzw = any_lzw || info.compression == KE_TIFFC_LZW;
+            plane_bytes += pb;
+            max_height = std::max(max_height, t.height);
+            imgs.push_back(d);
+            ++last;
+        }
+        // lanes of one wave finish together at best: neighbours in the list are strips of one compression and of like length,
+        // and the longest walks start first
+        std::stable_sort(strips.begin(), strips.end(), [](const KeTiffcStripDev &a, const KeTiffcStripDev &b) {
+            return a.comp != b.comp ? a.comp < b.comp : a.bytes > b.bytes;
+        });
+        const size_t m = imgs.size(), ns = strips.size();
+        const uint32_t waves = (uint32_t)std::min<uint64_t>((ns + 63) / 64, kMaxWaves);
+        void *d_imgs, *d_strips, *d_planes, *d_rec, *d_dict, *d_status, *d_nrec;
+        KE_TRY(ke_reserve(ctx, KE_BUF_META, m * sizeof(KeTiffcImgDev), &d_imgs));
+        KE_TRY(ke_reserve(ctx, KE_BUF_OUT1, ns * sizeof(KeTiffcStripDev), &d_strips));
+        KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)plane_bytes + 128, &d_planes));
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, (size_t)nrecs * 8 + 8, &d_rec));
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)dict_bytes(ns, any_lzw), &d_dict));
+        KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (m + 1) * 4, &d_status));                  // the statuses, then the list's counter
+        KE_TRY(ke_reserve(ctx, KE_BUF_TILE32, ns * 4, &d_nrec));
+        KE_HIP(ctx, hipMemcpyAsync(d_imgs, imgs.data(), m * sizeof(KeTiffcImgDev), hipMemcpyHostToDevice, ctx->stream));
+        KE_HIP(ctx, hipMemcpyAsync(d_strips, strips.data(), ns * sizeof(KeTiffcStripDev), hipMemcpyHostToDevice, ctx->stream));
+        KE_HIP(ctx, hipMemsetAsync(d_status, 0, (m + 1) * 4, ctx->stream));
+        hipLaunchKernelGGL(ke_tiffc_codes, dim3(waves), dim3(64), 0, ctx->stream, (const KeTiffcStripDev *)d_strips, (uint32_t)ns, (const uint8_t *)d_files,
+                           (uint8_t *)d_planes, (uint2 *)d_rec, (uint2 *)d_dict, (int32_t *)d_status, (uint32_t *)d_nrec, (uint32_t *)d_status + m);
+        hipLaunchKernelGGL(ke_tiffc_copies, dim3((unsigned)ns), dim3(64), 0, ctx->stream, (const KeTiffcStripDev *)d_strips, (uint8_t *)d_planes,
+                           (const uint2 *)d_rec, (const int32_t *)d_status, (const uint32_t *)d_nrec);
+        const int rows = std::max(kRowsPerBlock, (max_height + 65534) / 65535);
+        hipLaunchKernelGGL(ke_tiffc_rows, dim3((unsigned)m, (unsigned)((max_height + rows - 1) / rows)), dim3(256), 0, ctx->stream,
+                           (const KeTiffcImgDev *)d_imgs, (const uint8_t *)d_planes, (const int32_t *)d_status, pixels_out, rows);
+        KE_HIP(ctx, hipGetLastError());
+        st.resize(m);
+        KE_HIP(ctx, hipMemcpyAsync(st.data(), d_status, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // imgs / strips / st are host vectors; the scratch is reused
+        for (size_t k = 0; k < m; ++k) status_out[which[first + k]] = st[k];
+        first = last;
+    }
+    ke_time_end(ctx, KE_T_JPEG);
+    guard.armed = false;
+    return KE_OK;
+}

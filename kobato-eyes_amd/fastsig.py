@@ -122,6 +122,9 @@ GIF_SUFFIXES = (".gif",)
 TIFF_SUFFIXES = (".tif", ".tiff")
 WEBP_SUFFIXES = (".webp",)
 GPU_KINDS = ("jpeg", "png", "bmp", "gif", "tiff", "webp")           # the order in which a batch's files lie in the read-ahead buffer
+# kind -> the opt-in decoders that are offered what it left UNSUPPORTED, one after the other, each behind its variable
+FOLLOW_UPS = {"tiff": (("tiffc", "KE_GPU_TIFF_COMPRESSED"),),
+              "webp": (("webpl", "KE_GPU_WEBP_LOSSLESS"), ("webpa", "KE_GPU_WEBP_ALPHA"))}
 
 
 def _read_bytes(path_text: str):
@@ -514,10 +517,9 @@ class _Pipeline:
                 except (RuntimeError, ValueError, MemoryError):      # e.g. no room on the device for this batch: Pillow decodes it
                     refused.extend(positions.tolist())
                     continue
-                if kind == "webp":                         # what the lossy decoder refused: the opt-in decoders, one after the other
-                    for follow_up, variable in (("webpl", "KE_GPU_WEBP_LOSSLESS"), ("webpa", "KE_GPU_WEBP_ALPHA")):
-                        if os.environ.get(variable, "0") == "1":
-                            p, d, st = self._offer_to(follow_up, held, lo, first, positions, None if by_path or held is not None else blobs, p, d, st)
+                for follow_up, variable in FOLLOW_UPS.get(kind, ()):     # what the kind's decoder refused: the opt-in decoders
+                    if os.environ.get(variable, "0") == "1":
+                        p, d, st = self._offer_to(follow_up, held, lo, first, positions, None if by_path or held is not None else blobs, p, d, st)
                 good = np.asarray(st) == 0
                 at = positions[good] - start
                 ph[at] = np.asarray(p, np.uint64).view(np.int64)[good]
@@ -531,8 +533,9 @@ class _Pipeline:
         return refused
 
     def _offer_to(self, follow_up: str, held, lo: int, hi: int, positions, blobs, p, d, st):
-        """The .webp files still UNSUPPORTED after the decoders before it, offered to ``follow_up`` -- "webpl", the lossless
-        decoder (``KE_GPU_WEBP_LOSSLESS=1``), or "webpa", the one for lossy files with an alpha plane (``KE_GPU_WEBP_ALPHA=1``) --
+        """The files of a kind still UNSUPPORTED after the decoders before it, offered to ``follow_up`` (FOLLOW_UPS) -- "webpl", the
+        lossless WebP decoder (``KE_GPU_WEBP_LOSSLESS=1``), "webpa", the one for lossy files with an alpha plane
+        (``KE_GPU_WEBP_ALPHA=1``), or "tiffc", the one for LZW and PackBits TIFF files (``KE_GPU_TIFF_COMPRESSED=1``) --
         over the same files -- the read-ahead range with the files already taken masked, their paths, or their bytes --
         before they go to Pillow: (p, d, st) with its results filled in.  What it refuses keeps its status."""
         p, d, st = np.array(p, np.uint64), np.array(d, np.uint64), np.array(st, np.int32)

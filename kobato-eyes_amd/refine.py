@@ -115,6 +115,8 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
             gpu_kinds["bmp"] = (".bmp",)
         if os.environ.get("KE_GPU_TIFF", "1") != "0":
             gpu_kinds["tiff"] = (".tif", ".tiff")
+            if os.environ.get("KE_GPU_TIFF_COMPRESSED", "0") == "1":    # after the unpacker: the LZW and PackBits files it left out
+                gpu_kinds["tiffc"] = (".tif", ".tiff")
         if os.environ.get("KE_GPU_WEBP", "1") != "0":
             gpu_kinds["webp"] = (".webp",)
             if os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":      # after the lossy decoder: what that one did not place
@@ -126,11 +128,15 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
         """JPEG / PNG / BMP / TIFF / WebP files whose pixels the reference's loader would hand over exactly as Image.open yields them -- RGB, no
         EXIF orientation to apply, nothing to shrink (src/utils/image_io.py:107-138 are all no-ops then) -- are decoded on the
         GPU and stay there: placed[path] = (device address, width, height).  Everything else is left for Pillow."""
+        left = {}                                                    # kind -> the files its decoder returned as unsupported
         for kind, suffixes in gpu_kinds.items():
             paths = [p for p in need if p.lower().endswith(suffixes) and p not in placed]
+            if kind == "tiffc":                                      # only what the unpacker left out, not what it took and the loader keeps
+                paths = [p for p in paths if p in left.get("tiff", ())]
             if not paths:
                 continue
             dev, off, w, h, c, st, flags = ctx.decode_files_owned(paths, kind)
+            left[kind] = {p for p, s in zip(paths, st.tolist()) if s == 1}
             if not dev:
                 continue
             buffers.append(dev)
@@ -145,7 +151,7 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
             # KE_GPU_WEBP_ALPHA=1 -- composited over white
             orient = (flags >> 8) & 15
             turn = fits & (c == 3) & ((flags & 3) == 1) & (orient >= 2) & (orient <= 8) if kind == "jpeg" else np.zeros(len(paths), bool)
-            over = fits & (c == 4) & ((flags & 3) == 0) if kind in ("png", "bmp", "tiff") else np.zeros(len(paths), bool)
+            over = fits & (c == 4) & ((flags & 3) == 0) if kind in ("png", "bmp", "tiff", "tiffc") else np.zeros(len(paths), bool)
             if kind == "webpa":                                     # every file it takes carries the transparency bit: the orientation decides
                 over = fits & (c == 4) & ((flags & 1) == 0)
             fix = np.nonzero(turn | over)[0]

@@ -85,12 +85,14 @@ def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) ->
     ctx = _native.get_context(device)
     not_laid = np.uint64(0xFFFFFFFFFFFFFFFF)
     kinds = list(_GPU_SUFFIXES.items())
+    if os.environ.get("KE_GPU_TIFF_COMPRESSED", "0") == "1":         # after the unpacker: the LZW and PackBits files that one left out
+        kinds.append(("tiffc", _GPU_SUFFIXES["tiff"]))
     if os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":           # after the lossy decoder: the files that one left out
         kinds.append(("webpl", _GPU_SUFFIXES["webp"]))
     if os.environ.get("KE_GPU_WEBP_ALPHA", "0") == "1":              # lossy files with an alpha plane: convert("L") of RGBA ignores alpha
         kinds.append(("webpa", _GPU_SUFFIXES["webp"]))
     for kind, suffixes in kinds:
-        if os.environ.get({"jpeg": "KE_GPU_JPEG", "png": "KE_GPU_PNG", "bmp": "KE_GPU_BMP", "gif": "KE_GPU_GIF", "tiff": "KE_GPU_TIFF",
+        if os.environ.get({"jpeg": "KE_GPU_JPEG", "png": "KE_GPU_PNG", "bmp": "KE_GPU_BMP", "gif": "KE_GPU_GIF", "tiff": "KE_GPU_TIFF", "tiffc": "KE_GPU_TIFF",
                         "webp": "KE_GPU_WEBP", "webpl": "KE_GPU_WEBP", "webpa": "KE_GPU_WEBP"}[kind], "1") == "0":
             continue
         mine = [p for p in paths if str(p).lower().endswith(suffixes) and p not in out]
