@@ -170,7 +170,8 @@ int ke_stage_wait(ke_ctx *ctx, int32_t slot);
  *                  (heights[i] * widths[i] * channels[i] bytes) when status_out[i] == KE_JPEG_OK and left untouched
  *                  otherwise.  One thread per image decodes the entropy-coded segment, then one thread per 8x8 block runs the
  *                  IDCT and one per 4 pixels upsampling + colour: throughput comes from the batch (thousands of files per
- *                  call).  Blocks until the statuses are back. */
+ *                  call).  Blocks until the statuses are back; when it returns an error after the upload has begun the stream
+ *                  has been synchronised first, so the caller's host buffers are free again either way. */
 enum { KE_JPEG_OK_ = 0, KE_JPEG_UNSUPPORTED_ = 1, KE_JPEG_CORRUPT_ = 2 };   /* = KE_JPEG_OK / _UNSUPPORTED / _CORRUPT of the library */
 int ke_jpeg_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                   int32_t *heights, int32_t *channels, int32_t *status_out);
@@ -257,8 +258,7 @@ int ke_tiff_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_
  * and everything ke_tiff_decode refuses: KE_JPEG_UNSUPPORTED_ (1) per file; a strip that leaves the file or whose stream fails
  * where libtiff's fails (a code not yet in the table, data that ends before the strip is full): KE_JPEG_CORRUPT_ (2).
  * Uncompressed files are ke_tiff_decode's and are refused here (1).  Arguments and conventions as ke_jpeg_probe /
- * ke_jpeg_decode; on an error after the upload has begun the stream is synchronised before the call returns.  ke_tiffc_caveats
- * reports no flags (files with an orientation are refused). */
+ * ke_jpeg_decode.  ke_tiffc_caveats reports no flags (files with an orientation are refused). */
 int ke_tiffc_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                    int32_t *heights, int32_t *channels, int32_t *status_out);
 int ke_tiffc_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,

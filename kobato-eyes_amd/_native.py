@@ -13,6 +13,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from .formats import FORMATS, KINDS
+
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KE_LIBKEYES") or os.path.join(_PKG_DIR, "libkeyes_hip.so")   # KE_LIBKEYES: a build variant (benchmarks)
 
@@ -25,14 +27,15 @@ FILTER_LANCZOS, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2   # include/keyes.h KE
 EXPORTS = (
     "ke_abi_version", "ke_create", "ke_create_error", "ke_destroy", "ke_last_error", "ke_set_stream",
     "ke_get_stream", "ke_synchronize", "ke_device_info", "ke_malloc", "ke_free", "ke_memcpy",
-    "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan", "ke_band_pairs_after_size",
+    "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan",
     "ke_band_pairs_after_size",
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
-    "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files", "ke_jpeg_probe", "ke_jpeg_decode", "ke_png_probe", "ke_png_decode", "ke_jpeg_caveats", "ke_png_caveats", "ke_bmp_probe", "ke_bmp_decode", "ke_bmp_caveats", "ke_gif_probe", "ke_gif_decode", "ke_gif_caveats", "ke_tiff_probe", "ke_tiff_decode", "ke_tiff_caveats", "ke_tiffc_probe", "ke_tiffc_decode", "ke_tiffc_caveats", "ke_webp_probe", "ke_webp_decode", "ke_webp_caveats", "ke_webpl_probe", "ke_webpl_decode", "ke_webpl_caveats", "ke_webpa_probe", "ke_webpa_decode", "ke_webpa_caveats", "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode", "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash", "ke_sad_pairs", "ke_synth_rgb",
-    "ke_synth_rgb_indexed",
+    "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
+    "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode",
+    "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash", "ke_sad_pairs", "ke_synth_rgb", "ke_synth_rgb_indexed",
     "ke_synth_hashes", "ke_last_kernel_ms",
-)
+) + tuple(f"ke_{kind}_{call}" for kind in KINDS for call in ("probe", "decode", "caveats"))
 
 _lib: Optional[C.CDLL] = None
 _lib_lock = threading.Lock()
@@ -87,7 +90,8 @@ def load_library() -> C.CDLL:
         except OSError as exc:  # e.g. libamdhip64 not found
             raise NativeUnavailable(f"cannot load {LIB_PATH}: {exc}") from exc
         vp, i32, i64, u64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
-        lib.ke_abi_version.restype = C.c_int
+        for name in EXPORTS:                                 # all but the few below return a KE_* code
+            getattr(lib, name).restype = C.c_int
         lib.ke_create.argtypes = [C.c_int]
         lib.ke_create.restype = vp
         lib.ke_create_error.restype = C.c_char_p
@@ -125,33 +129,10 @@ def load_library() -> C.CDLL:
         lib.ke_host_free.argtypes = [vp, vp]
         lib.ke_host_pack.argtypes = [vp, vp, vp, vp, i64]
         lib.ke_host_read_files.argtypes = [vp, i64, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]
-        lib.ke_jpeg_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_jpeg_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_png_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_png_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_jpeg_caveats.argtypes = [vp, vp, vp, i64, vp]
-        lib.ke_png_caveats.argtypes = [vp, vp, vp, i64, vp]
-        lib.ke_bmp_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_bmp_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_bmp_caveats.argtypes = [vp, vp, vp, i64, vp]
-        lib.ke_gif_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_gif_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_gif_caveats.argtypes = [vp, vp, vp, i64, vp]
-        lib.ke_tiff_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_tiff_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_tiff_caveats.argtypes = [vp, vp, vp, i64, vp]
-        lib.ke_tiffc_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_tiffc_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_tiffc_caveats.argtypes = [vp, vp, vp, i64, vp]
-        lib.ke_webp_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_webp_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_webp_caveats.argtypes = [vp, vp, vp, i64, vp]
-        lib.ke_webpl_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_webpl_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_webpl_caveats.argtypes = [vp, vp, vp, i64, vp]
-        lib.ke_webpa_probe.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        lib.ke_webpa_decode.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
-        lib.ke_webpa_caveats.argtypes = [vp, vp, vp, i64, vp]
+        for kind in KINDS:
+            getattr(lib, f"ke_{kind}_probe").argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
+            getattr(lib, f"ke_{kind}_decode").argtypes = [vp, vp, vp, vp, i64, vp, vp, vp]
+            getattr(lib, f"ke_{kind}_caveats").argtypes = [vp, vp, vp, i64, vp]
         lib.ke_normalise_rgb.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
         lib.ke_thumbnail_rgb.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
         lib.ke_band_pairs_after_size.argtypes = [vp, vp, vp, i64, i32, i32, dbl, i64, vp]
@@ -170,13 +151,6 @@ def load_library() -> C.CDLL:
         lib.ke_synth_hashes.argtypes = [vp, u64, i64, vp]
         lib.ke_last_kernel_ms.argtypes = [vp, i32]
         lib.ke_last_kernel_ms.restype = dbl
-        for name in ("ke_set_stream", "ke_synchronize", "ke_device_info", "ke_malloc", "ke_free", "ke_memcpy",
-                     "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan", "ke_band_pairs_after_size",
-                     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
-                     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
-                     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files", "ke_jpeg_probe", "ke_jpeg_decode", "ke_png_probe", "ke_png_decode", "ke_jpeg_caveats", "ke_png_caveats", "ke_bmp_probe", "ke_bmp_decode", "ke_bmp_caveats", "ke_gif_probe", "ke_gif_decode", "ke_gif_caveats", "ke_tiff_probe", "ke_tiff_decode", "ke_tiff_caveats", "ke_tiffc_probe", "ke_tiffc_decode", "ke_tiffc_caveats", "ke_webp_probe", "ke_webp_decode", "ke_webp_caveats", "ke_webpl_probe", "ke_webpl_decode", "ke_webpl_caveats", "ke_webpa_probe", "ke_webpa_decode", "ke_webpa_caveats", "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode", "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash",
-                     "ke_sad_pairs", "ke_synth_rgb", "ke_synth_rgb_indexed", "ke_synth_hashes"):
-            getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib
 
@@ -210,6 +184,15 @@ def _leave_bombs_to_pillow(w, h, st, sizes) -> None:
         sizes[bombs] = 0
 
 
+def _lay_out16(nbytes):
+    """Byte offsets of items of ``nbytes`` (int64 array) laid back to back, each on a 16-byte boundary (see keyes.h), and the
+    bytes they take together."""
+    padded = (nbytes + 15) & ~np.int64(15)
+    offsets = np.zeros(len(nbytes), np.uint64)
+    offsets[1:] = np.cumsum(padded[:-1]).astype(np.uint64)
+    return offsets, int(padded.sum())
+
+
 class FilesAhead:
     """The files of a batch in one of a context's read-ahead buffers (Context.read_files_ahead): file i is
     ``flat[offsets[i]:offsets[i] + sizes[i]]`` (size 0 = unreadable).  ``release()`` hands the buffer back."""
@@ -238,7 +221,7 @@ class Context:
             raise NativeUnavailable(f"ke_create({device}) failed: {msg}")
         self.device = int(device)
         self._lock = threading.RLock()
-        self._pack_ptr, self._pack_cap = 0, 0
+        self._pack = [0, 0]                                  # the packing buffer: [page-locked ptr, capacity]
         self._decoded_ptr, self._decoded_cap = 0, 0
         self._ahead = [[0, 0, False], [0, 0, False]]         # read-ahead buffers: [page-locked ptr, capacity, taken]
         self._ahead_lock = threading.Lock()
@@ -250,13 +233,10 @@ class Context:
     # -- lifetime ---------------------------------------------------------------------------
     def close(self) -> None:
         if getattr(self, "_h", None):
-            if getattr(self, "_pack_ptr", 0):
-                self._lib.ke_host_free(self._h, self._pack_ptr)
-                self._pack_ptr, self._pack_cap = 0, 0
             if getattr(self, "_decoded_ptr", 0):
                 self._lib.ke_free(self._h, self._decoded_ptr)
                 self._decoded_ptr, self._decoded_cap = 0, 0
-            for buf in getattr(self, "_ahead", []):
+            for buf in [getattr(self, "_pack", [0, 0])] + getattr(self, "_ahead", []):
                 if buf[0]:
                     self._lib.ke_host_free(self._h, buf[0])
                     buf[0], buf[1] = 0, 0
@@ -439,7 +419,7 @@ class Context:
                 return merged[: total.value], counts
             cap = int(total.value)
 
-    # -- JPEG decode on the GPU ---------------------------------------------------------------
+    # -- file decode on the GPU (formats.FORMATS) ----------------------------------------------
     @staticmethod
     def _pack_blobs(blobs):
         sizes = np.fromiter((len(b) for b in blobs), np.uint64, len(blobs))
@@ -448,39 +428,45 @@ class Context:
         flat = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)     # one C-level copy; the decoder takes any alignment
         return flat, offsets, sizes
 
-    def _grow_pack(self, total: int) -> None:
-        if total > self._pack_cap:
-            if self._pack_ptr:
-                self._check(self._lib.ke_host_free(self._h, self._pack_ptr), "ke_host_free")
-                self._pack_ptr, self._pack_cap = 0, 0
+    def _grow_host(self, buf: list, total: int) -> None:
+        """A page-locked buffer ``[ptr, capacity, ...]`` made to hold ``total`` bytes (what it held is not kept)."""
+        if total > buf[1]:
+            if buf[0]:
+                self._check(self._lib.ke_host_free(self._h, buf[0]), "ke_host_free")
+                buf[0], buf[1] = 0, 0
             cap = max(total + total // 4, 1 << 24)
             p = C.c_void_p()
             self._check(self._lib.ke_host_alloc(self._h, cap, C.byref(p)), "ke_host_alloc")
-            self._pack_ptr, self._pack_cap = int(p.value), cap
+            buf[0], buf[1] = int(p.value), cap
 
-    def _read_files_pinned(self, paths, bounded: bool = True):
-        """The files themselves, read by the library's host threads straight into the page-locked buffer (no bytes objects, no
-        interpreter loop over the files); unreadable files get size 0.  Call with the lock held."""
+    def _read_files_into(self, buf: list, paths, bounded: bool = True):
+        """The files themselves, read by the library's host threads straight into the page-locked buffer ``buf`` (no bytes
+        objects, no interpreter loop over the files), which is grown when the batch needs it; unreadable files get size 0.
+        ``bounded``: a batch of more than ``pack_limit`` bytes is _BatchTooLarge.  Nothing but ``buf`` is touched: call with the
+        lock held when ``buf`` is the packing buffer (the read-ahead buffers have their own ``taken`` flag instead)."""
         n = len(paths)
         names = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
         offsets, sizes = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         needed = C.c_uint64(0)
-        rc = self._lib.ke_host_read_files(names, n, self._pack_ptr, self._pack_cap, _addr(offsets), _addr(sizes), C.byref(needed))
+
+        def read():
+            return self._lib.ke_host_read_files(names, n, buf[0], buf[1], _addr(offsets), _addr(sizes), C.byref(needed))
+
+        rc = read()
         if rc == -4:                                       # KE_ENOMEM: the buffer is too small for this batch
             if bounded and int(needed.value) > self.pack_limit and n > 1:
                 raise _BatchTooLarge
-            self._grow_pack(int(needed.value))
-            rc = self._lib.ke_host_read_files(names, n, self._pack_ptr, self._pack_cap, _addr(offsets), _addr(sizes), C.byref(needed))
+            self._grow_host(buf, int(needed.value))
+            rc = read()
         if rc != KE_OK:
             raise ValueError("ke_host_read_files: bad arguments")
-        total = int(needed.value)
-        flat = np.ctypeslib.as_array((C.c_uint8 * total).from_address(self._pack_ptr))
+        flat = np.ctypeslib.as_array((C.c_uint8 * int(needed.value)).from_address(buf[0]))
         return flat, offsets, sizes
 
     def read_files_ahead(self, paths, spans=()):
         """Read files into one of the context's two page-locked read-ahead buffers -- from any thread, while another call of the
         context is decoding the previous batch on the GPU (nothing here touches the stream or the context's lock).  Returns a
-        FilesAhead to pass to ``jpeg_hash(..., ahead=(it, lo, hi))`` and to ``release()`` afterwards, or None when both buffers
+        FilesAhead to pass to ``hash(..., ahead=(it, lo, hi))`` and to ``release()`` afterwards, or None when both buffers
         are taken or the files exceed ``pack_limit`` (the caller then lets the decode call read them itself).  ``spans`` =
         [(kind, lo, hi)]: the headers of files lo..hi are parsed here as well (``ke_<kind>_probe``), off the decoding thread."""
         paths = list(paths)
@@ -494,30 +480,13 @@ class Context:
             self._ahead[slot][2] = True
         buf = self._ahead[slot]
         try:
-            names = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
-            offsets, sizes = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
-            needed = C.c_uint64(0)
-            rc = self._lib.ke_host_read_files(names, n, buf[0], buf[1], _addr(offsets), _addr(sizes), C.byref(needed))
-            if rc == -4:                                   # KE_ENOMEM: the buffer is too small for this batch
-                if int(needed.value) > self.pack_limit and n > 1:
-                    raise _BatchTooLarge
-                if buf[0]:
-                    self._check(self._lib.ke_host_free(self._h, buf[0]), "ke_host_free")
-                    buf[0], buf[1] = 0, 0
-                cap = max(int(needed.value) + int(needed.value) // 4, 1 << 24)
-                p = C.c_void_p()
-                self._check(self._lib.ke_host_alloc(self._h, cap, C.byref(p)), "ke_host_alloc")
-                buf[0], buf[1] = int(p.value), cap
-                rc = self._lib.ke_host_read_files(names, n, buf[0], buf[1], _addr(offsets), _addr(sizes), C.byref(needed))
-            if rc != KE_OK:
-                raise ValueError("ke_host_read_files: bad arguments")
+            flat, offsets, sizes = self._read_files_into(buf, paths)
         except _BatchTooLarge:
             buf[2] = False
             return None
         except BaseException:
             buf[2] = False
             raise
-        flat = np.ctypeslib.as_array((C.c_uint8 * int(needed.value)).from_address(buf[0]))
         held = FilesAhead(self, slot, flat, offsets, sizes)
         for kind, lo, hi in spans:
             if hi > lo:
@@ -536,8 +505,8 @@ class Context:
         total = int(sizes.sum()) + 64
         if total > self.pack_limit and len(blobs) > 1:
             raise _BatchTooLarge
-        self._grow_pack(total)
-        base = self._pack_ptr
+        self._grow_host(self._pack, total)
+        base = self._pack[0]
         flat = np.ctypeslib.as_array((C.c_uint8 * total).from_address(base))
         n = len(blobs)
         srcs = (C.c_char_p * n)(*blobs)                    # the buffers of the bytes objects themselves, no copies
@@ -546,8 +515,8 @@ class Context:
         C.memset(base + total - 64, 0, 64)
         return flat, offsets, sizes
 
-    def jpeg_probe(self, blobs, kind: str = "jpeg"):
-        """(widths, heights, channels, status) of JPEG (or, kind="png", PNG) files given as bytes; status 0 = the GPU
+    def probe(self, blobs, kind: str):
+        """(widths, heights, channels, status) of files of a ``kind`` of formats.FORMATS given as bytes; status 0 = the GPU
         decoder takes the file."""
         flat, offsets, sizes = self._pack_blobs(blobs)
         n = len(blobs)
@@ -557,94 +526,7 @@ class Context:
             raise ValueError(f"ke_{kind}_probe: bad arguments")
         return w, h, c, st
 
-    def png_probe(self, blobs):
-        return self.jpeg_probe(blobs, "png")
-
-    def png_decode(self, blobs):
-        """Pixels of PNG files decoded on the GPU (HxW, HxWx3 or HxWx4), None where the decoder refused the file."""
-        return self.jpeg_decode(blobs, "png")
-
-    def png_hash(self, blobs, *, want_dhash=True):
-        return self.jpeg_hash(blobs, want_dhash=want_dhash, kind="png")
-
-    def bmp_probe(self, blobs):
-        return self.jpeg_probe(blobs, "bmp")
-
-    def bmp_decode(self, blobs):
-        """Pixels of uncompressed BMP files unpacked on the GPU (HxW luma of a palette file, HxWx3 or HxWx4), None where the
-        unpacker refused the file."""
-        return self.jpeg_decode(blobs, "bmp")
-
-    def bmp_hash(self, blobs, *, want_dhash=True):
-        return self.jpeg_hash(blobs, want_dhash=want_dhash, kind="bmp")
-
-    def gif_probe(self, blobs):
-        return self.jpeg_probe(blobs, "gif")
-
-    def gif_decode(self, blobs):
-        """Luma (HxW) of the first frame of GIF files decoded on the GPU -- what ``Image.open(f).convert("L")`` yields --, None
-        where the decoder refused the file."""
-        return self.jpeg_decode(blobs, "gif")
-
-    def gif_hash(self, blobs, *, want_dhash=True):
-        return self.jpeg_hash(blobs, want_dhash=want_dhash, kind="gif")
-
-    def tiff_probe(self, blobs):
-        return self.jpeg_probe(blobs, "tiff")
-
-    def tiff_decode(self, blobs):
-        """Pixels of uncompressed 8-bit TIFF files unpacked on the GPU (HxW gray or luma of a palette file, HxWx3, HxWx4), None
-        where the unpacker refused the file."""
-        return self.jpeg_decode(blobs, "tiff")
-
-    def tiff_hash(self, blobs, *, want_dhash=True):
-        return self.jpeg_hash(blobs, want_dhash=want_dhash, kind="tiff")
-
-    def tiffc_probe(self, blobs):
-        return self.jpeg_probe(blobs, "tiffc")
-
-    def tiffc_decode(self, blobs):
-        """Pixels of LZW and PackBits 8-bit TIFF files decoded on the GPU (the shapes of ``tiff_decode``), None where the file is
-        left to Pillow, and the statuses."""
-        return self.jpeg_decode(blobs, "tiffc")
-
-    def tiffc_hash(self, blobs, *, want_dhash=True):
-        return self.jpeg_hash(blobs, want_dhash=want_dhash, kind="tiffc")
-
-    def webp_probe(self, blobs):
-        return self.jpeg_probe(blobs, "webp")
-
-    def webp_decode(self, blobs):
-        """RGB pixels (HxWx3) of lossy WebP files decoded on the GPU -- what ``Image.open(f).convert("RGB")`` yields --, None
-        where the decoder refused the file."""
-        return self.jpeg_decode(blobs, "webp")
-
-    def webp_hash(self, blobs, *, want_dhash=True):
-        return self.jpeg_hash(blobs, want_dhash=want_dhash, kind="webp")
-
-    def webpl_probe(self, blobs):
-        return self.jpeg_probe(blobs, "webpl")
-
-    def webpl_decode(self, blobs):
-        """Pixels of lossless WebP files (one VP8L bitstream) decoded on the GPU, as ``Image.open(f)`` yields them -- HxWx3 RGB,
-        or HxWx4 RGBA where Pillow opens the file as RGBA --, None where the decoder refused; and the per-file status."""
-        return self.jpeg_decode(blobs, "webpl")
-
-    def webpl_hash(self, blobs, *, want_dhash=True):
-        return self.jpeg_hash(blobs, want_dhash=want_dhash, kind="webpl")
-
-    def webpa_probe(self, blobs):
-        return self.jpeg_probe(blobs, "webpa")
-
-    def webpa_decode(self, blobs):
-        """RGBA pixels (HxWx4) of lossy WebP files with an alpha plane (one VP8 key frame + an ALPH chunk, or the VP8X alpha flag
-        alone) decoded on the GPU, as ``Image.open(f)`` yields them, None where the decoder refused; and the per-file status."""
-        return self.jpeg_decode(blobs, "webpa")
-
-    def webpa_hash(self, blobs, *, want_dhash=True):
-        return self.jpeg_hash(blobs, want_dhash=want_dhash, kind="webpa")
-
-    def _jpeg_to_device(self, blobs, kind: str = "jpeg", *, paths=None, ahead=None, skip=None):
+    def _to_device(self, blobs, kind: str, *, paths=None, ahead=None, skip=None):
         """Decode what the GPU decoder takes into the context's decode buffer (device memory, grown on demand and kept:
         allocating tens of GB per call costs up to a second): (device ptr or 0, byte offsets, widths, heights, channels,
         status).  Call with the lock held and keep it until the pixels have been used."""
@@ -655,7 +537,7 @@ class Context:
                 held, lo, hi = ahead
                 flat, offsets, sizes = held.flat, np.ascontiguousarray(held.offsets[lo:hi]), np.array(held.sizes[lo:hi], np.uint64)
             else:
-                flat, offsets, sizes = self._pack_blobs_pinned(blobs) if paths is None else self._read_files_pinned(paths)
+                flat, offsets, sizes = self._pack_blobs_pinned(blobs) if paths is None else self._read_files_into(self._pack, paths)
             known = ahead[0].probed.get((kind, ahead[1], ahead[2])) if ahead is not None else None
             if known is not None:
                 w, h, c, st = (a.copy() for a in known)
@@ -668,11 +550,7 @@ class Context:
                 skip = np.asarray(skip, bool)
                 st[skip & (st == 0)] = 1
                 sizes[skip] = 0
-            nbytes = np.where(st == 0, w.astype(np.int64) * h * c, 0)
-            padded = (nbytes + 15) & ~np.int64(15)
-            out_off = np.zeros(n, np.uint64)
-            out_off[1:] = np.cumsum(padded[:-1]).astype(np.uint64)
-            total = int(padded.sum())
+            out_off, total = _lay_out16(np.where(st == 0, w.astype(np.int64) * h * c, 0))
             if total == 0:
                 return 0, out_off, w, h, c, st
             if total > self.decode_limit and n > 1:
@@ -702,7 +580,7 @@ class Context:
         if n == 0:
             return 0, out_off, w, h, c, st, flags
         with self._lock:
-            flat, offsets, sizes = self._read_files_pinned(paths, bounded=False)     # the caller paces its batches
+            flat, offsets, sizes = self._read_files_into(self._pack, paths, bounded=False)     # the caller paces its batches
             probe = getattr(self._lib, f"ke_{kind}_probe")
             if probe(_addr(flat), _addr(offsets), _addr(sizes), n, _addr(w), _addr(h), _addr(c), _addr(st)) != KE_OK:
                 raise ValueError(f"ke_{kind}_probe: bad arguments")
@@ -727,9 +605,7 @@ class Context:
                 out_off[nbytes == 0] = np.uint64(0xFFFFFFFFFFFFFFFF)   # not laid out (refused by the probe)
                 total = at
             else:
-                padded = (nbytes + 15) & ~np.int64(15)
-                out_off[1:] = np.cumsum(padded[:-1]).astype(np.uint64)
-                total = int(padded.sum())
+                out_off, total = _lay_out16(nbytes)
             if total == 0:
                 return 0, out_off, w, h, c, st, flags
             dev = self.malloc(total + 64)
@@ -766,9 +642,7 @@ class Context:
                 at += int(nbytes[k])
             total = at
         else:
-            padded = (nbytes + 15) & ~np.int64(15)
-            do[1:] = np.cumsum(padded[:-1]).astype(np.uint64)
-            total = int(padded.sum())
+            do, total = _lay_out16(nbytes)
         dev = self.malloc(total + 64)
         try:
             with self._lock:
@@ -806,9 +680,9 @@ class Context:
     def release_decode_buffers(self) -> None:
         """Give back the page-locked packing buffer and the device decode buffer (they are kept between calls otherwise)."""
         with self._lock:
-            if self._pack_ptr:
-                self._check(self._lib.ke_host_free(self._h, self._pack_ptr), "ke_host_free")
-                self._pack_ptr, self._pack_cap = 0, 0
+            if self._pack[0]:
+                self._check(self._lib.ke_host_free(self._h, self._pack[0]), "ke_host_free")
+                self._pack[0], self._pack[1] = 0, 0
             if self._decoded_ptr:
                 self.free(self._decoded_ptr)
                 self._decoded_ptr, self._decoded_cap = 0, 0
@@ -818,17 +692,17 @@ class Context:
                         self._check(self._lib.ke_host_free(self._h, buf[0]), "ke_host_free")
                         buf[0], buf[1] = 0, 0
 
-    def jpeg_decode(self, blobs, kind: str = "jpeg"):
-        """Pixels of JPEG files decoded on the GPU: list of ndarrays (HxW or HxWx3, what np.asarray(Image.open(f)) gives) with
-        None where the decoder refused the file (status != 0); also returns the statuses."""
+    def decode(self, blobs, kind: str):
+        """Pixels of files of a ``kind`` of formats.FORMATS decoded on the GPU: list of ndarrays (HxW or HxWxC, see the kind's
+        row) with None where the decoder refused the file (status != 0); also returns the statuses."""
         out = [None] * len(blobs)
         with self._lock:
             try:
-                dev, out_off, w, h, c, st = self._jpeg_to_device(blobs, kind)
+                dev, out_off, w, h, c, st = self._to_device(blobs, kind)
             except _BatchTooLarge:
                 half = len(blobs) // 2
-                a, sa = self.jpeg_decode(blobs[:half], kind)
-                b, sb = self.jpeg_decode(blobs[half:], kind)
+                a, sa = self.decode(blobs[:half], kind)
+                b, sb = self.decode(blobs[half:], kind)
                 return a + b, np.concatenate([sa, sb])
             for i in range(len(blobs)):
                 if st[i] == 0:
@@ -838,14 +712,14 @@ class Context:
         return out, st
 
     def hash_files(self, paths, *, want_dhash=True, kind: str = "jpeg"):
-        """jpeg_hash for files on disk: read (host threads, page-locked buffer), decoded and hashed on the GPU."""
-        return self.jpeg_hash(None, want_dhash=want_dhash, kind=kind, paths=list(paths))
+        """``hash`` for files on disk: read (host threads, page-locked buffer), decoded and hashed on the GPU."""
+        return self.hash(None, want_dhash=want_dhash, kind=kind, paths=list(paths))
 
-    def jpeg_hash(self, blobs, *, want_dhash=True, kind: str = "jpeg", paths=None, ahead=None, skip=None):
-        """pHash / dHash of JPEG files, decoded and hashed without the pixels leaving the GPU.  Returns (phash u64[n],
-        dhash u64[n] | None, status int32[n]); status != 0 = not handled here (decode the file with Pillow).  The files come
-        as bytes (``blobs``), as ``paths`` the library reads, or as ``ahead = (FilesAhead, lo, hi)``: files lo..hi of a batch
-        read beforehand."""
+    def hash(self, blobs, *, want_dhash=True, kind: str = "jpeg", paths=None, ahead=None, skip=None):
+        """pHash / dHash of files of a ``kind`` of formats.FORMATS, decoded and hashed without the pixels leaving the GPU.
+        Returns (phash u64[n], dhash u64[n] | None, status int32[n]); status != 0 = not handled here (decode the file with
+        Pillow).  The files come as bytes (``blobs``), as ``paths`` the library reads, or as ``ahead = (FilesAhead, lo, hi)``:
+        files lo..hi of a batch read beforehand."""
         n = ahead[2] - ahead[1] if ahead is not None else len(blobs) if paths is None else len(paths)
         ph = np.zeros(n, np.uint64)
         dh = np.zeros(n, np.uint64) if want_dhash else None
@@ -853,10 +727,10 @@ class Context:
             return ph, dh, np.zeros(0, np.int32)
         with self._lock:
             try:
-                dev, out_off, w, h, c, st = self._jpeg_to_device(blobs, kind, paths=paths, ahead=ahead, skip=skip)
+                dev, out_off, w, h, c, st = self._to_device(blobs, kind, paths=paths, ahead=ahead, skip=skip)
             except _BatchTooLarge:
                 half = n // 2
-                parts = [self.jpeg_hash(None if blobs is None else blobs[lo:hi], want_dhash=want_dhash, kind=kind,
+                parts = [self.hash(None if blobs is None else blobs[lo:hi], want_dhash=want_dhash, kind=kind,
                                         paths=None if paths is None else paths[lo:hi],
                                         ahead=None if ahead is None else (ahead[0], ahead[1] + lo, ahead[1] + hi),
                                         skip=None if skip is None else np.asarray(skip, bool)[lo:hi])
@@ -1049,6 +923,31 @@ class Context:
         with self._lock:
             self._check(self._lib.ke_synth_hashes(self._h, seed, n, _addr(out)), "ke_synth_hashes")
         return out
+
+
+def _name_per_kind(fmt) -> None:
+    """``Context.<kind>_probe`` / ``_decode`` / ``_hash``: the generic calls under the names tests, benchmarks and
+    INTEGRATION.md use (``kind=`` still overrides, as ``jpeg_hash(kind="png")`` always did)."""
+    def probe(self, blobs, kind: str = fmt.kind):
+        return self.probe(blobs, kind)
+
+    def decode(self, blobs, kind: str = fmt.kind):
+        return self.decode(blobs, kind)
+
+    def hash_(self, blobs, *, want_dhash=True, kind: str = fmt.kind, paths=None, ahead=None, skip=None):
+        return self.hash(blobs, want_dhash=want_dhash, kind=kind, paths=paths, ahead=ahead, skip=skip)
+
+    probe.__doc__ = f"``probe`` of {fmt.kind} files: (widths, heights, channels, status); status 0 = the GPU decoder takes the file."
+    decode.__doc__ = f"{fmt.decodes}, None where the decoder refused the file; and the per-file status."
+    hash_.__doc__ = f"``hash`` of {fmt.kind} files: (phash, dhash | None, status); status != 0 = decode the file with Pillow."
+    for call, fn in (("probe", probe), ("decode", decode), ("hash", hash_)):
+        fn.__name__ = f"{fmt.kind}_{call}"
+        fn.__qualname__ = f"Context.{fn.__name__}"
+        setattr(Context, fn.__name__, fn)
+
+
+for _fmt in FORMATS:
+    _name_per_kind(_fmt)
 
 
 _default: dict = {}

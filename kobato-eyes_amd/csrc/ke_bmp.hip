@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "ke_bmp_parse.h"
-#include "ke_internal.h"
+#include "ke_decode_batch.h"
 
 namespace {
 
@@ -98,36 +98,23 @@ __global__ __launch_bounds__(256) void ke_bmp_unpack(const KeBmpDev *__restrict_
 
 KE_API int ke_bmp_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                         int32_t *heights, int32_t *channels, int32_t *status_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            KeBmpInfo info;
-            ke_parse_bmp(files + offsets[i], (size_t)sizes[i], info);
-            widths[i] = info.width; heights[i] = info.height; channels[i] = info.channels;
-            status_out[i] = info.status;
-        }
-    });
-    return KE_OK;
+    return ke_probe_each(files, offsets, sizes, n, widths, heights, channels, status_out,
+                         [](const uint8_t *file, size_t size, int32_t &w, int32_t &h, int32_t &c, int32_t &st) {
+                             KeBmpInfo info;
+                             ke_parse_bmp(file, size, info);
+                             w = info.width; h = info.height; c = info.channels; st = info.status;
+                         });
 }
 
 KE_API int ke_bmp_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
     // the format carries no orientation tag; an alpha channel shows in ke_bmp_probe's channel count
-    for (int64_t i = 0; i < n; ++i) flags_out[i] = 0;
-    return KE_OK;
+    return ke_caveats_none(files, offsets, sizes, n, flags_out);
 }
 
 KE_API int ke_bmp_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                          uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
-        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "the files' headers are parsed"));
     if (n == 0) return KE_OK;
-    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "the files' headers are parsed on the host: pass host memory (pinned staging is fine)");
-    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
-    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
-        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
-    KE_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<KeBmpDev> devs;
     devs.reserve((size_t)n);
     uint64_t lo = ~0ull, hi = 0;
@@ -154,23 +141,24 @@ KE_API int ke_bmp_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offs
     }
     if (devs.empty()) return KE_OK;
     for (KeBmpDev &d : devs) d.src -= lo;
-    // the pixel data (one contiguous range of the caller's buffer) -> device; a 32-bit row may be read up to its last dword only
     void *d_files, *d_imgs;
-    KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)(hi - lo) + 16, &d_files));
     KE_TRY(ke_reserve(ctx, KE_BUF_META, devs.size() * sizeof(KeBmpDev), &d_imgs));
+    KeStreamGuard guard;                                           // after the host vectors it waits for
+    // the pixel data (one contiguous range of the caller's buffer) -> device; a 32-bit row may be read up to its last dword only
+    KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)(hi - lo) + 16, &d_files));   // outside the timed bracket: the upload finds it in place
     ke_time_begin(ctx, KE_T_JPEG);
-    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
+    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_SSIM_IN, 16, &d_files));
     KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs.data(), devs.size() * sizeof(KeBmpDev), hipMemcpyHostToDevice, ctx->stream));
-    // blockIdx.y covers the tallest image; the blocks beyond a shorter one's rows return at once
     const size_t kMaxX = 1u << 30;
-    const int rows = std::max(kRowsPerBlock, (max_height + 65534) / 65535);
+    const KeRowTiles tiles = ke_row_tiles(max_height, kRowsPerBlock);
     for (size_t first = 0; first < devs.size(); first += kMaxX) {
         const size_t m = std::min(kMaxX, devs.size() - first);
-        hipLaunchKernelGGL(ke_bmp_unpack, dim3((unsigned)m, (unsigned)((max_height + rows - 1) / rows)), dim3(256), 0, ctx->stream,
-                           (const KeBmpDev *)d_imgs + first, (const uint8_t *)d_files, pixels_out, rows);
+        hipLaunchKernelGGL(ke_bmp_unpack, dim3((unsigned)m, tiles.grid_y), dim3(256), 0, ctx->stream,
+                           (const KeBmpDev *)d_imgs + first, (const uint8_t *)d_files, pixels_out, tiles.rows);
     }
     KE_HIP(ctx, hipGetLastError());
     ke_time_end(ctx, KE_T_JPEG);
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // devs is a host vector; the scratch is reused
+    guard.disarm();
     return KE_OK;
 }

@@ -13,7 +13,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ke_internal.h"
+#include "ke_decode_batch.h"
 
 #include "ke_gif_core.h"
 #include "ke_lz_copies.h"
@@ -101,35 +101,22 @@ __global__ __launch_bounds__(256) void ke_gif_rows(const KeGifDev *__restrict__ 
 
 KE_API int ke_gif_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                         int32_t *heights, int32_t *channels, int32_t *status_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            KeGifInfo info;
-            ke_parse_gif(files + offsets[i], (size_t)sizes[i], info);
-            widths[i] = info.width; heights[i] = info.height; channels[i] = info.channels;
-            status_out[i] = info.status;
-        }
-    });
-    return KE_OK;
+    return ke_probe_each(files, offsets, sizes, n, widths, heights, channels, status_out,
+                         [](const uint8_t *file, size_t size, int32_t &w, int32_t &h, int32_t &c, int32_t &st) {
+                             KeGifInfo info;
+                             ke_parse_gif(file, size, info);
+                             w = info.width; h = info.height; c = info.channels; st = info.status;
+                         });
 }
 
 KE_API int ke_gif_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
-    for (int64_t i = 0; i < n; ++i) flags_out[i] = 0;               // (the decoder yields luma: only the hashing seams take it)
-    return KE_OK;
+    return ke_caveats_none(files, offsets, sizes, n, flags_out);       // (the decoder yields luma: only the hashing seams take it)
 }
 
 KE_API int ke_gif_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                          uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
-        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "the files' containers are walked"));
     if (n == 0) return KE_OK;
-    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "the files' containers are walked on the host: pass host memory (pinned staging is fine)");
-    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
-    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
-        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
-    KE_HIP(ctx, hipSetDevice(ctx->device));
     struct Item { KeGifDev d; int64_t which; };
     std::vector<Item> items;
     items.reserve((size_t)n);
@@ -157,60 +144,57 @@ KE_API int ke_gif_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offs
     if (items.empty()) return KE_OK;
     // lanes of one wave finish together at best: neighbours in the batch should have streams of like length
     std::stable_sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.d.file_size > b.d.file_size; });
-    void *d_files;
-    KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)(hi - lo) + 256, &d_files));
-    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
-    // sub-batches bounded by scratch: indices (1 B per pixel) + copy records (8 B per 2 pixels at worst) + 32 KB of dictionary
-    size_t free_b = 0, total_b = 0;
-    KE_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t held = (uint64_t)ctx->buf[KE_BUF_SSIM_IN].bytes + ctx->buf[KE_BUF_TMP].bytes + ctx->buf[KE_BUF_SSIM_AUX].bytes;
-    const uint64_t budget = std::max<uint64_t>((uint64_t)2 << 30, std::min<uint64_t>((held + (uint64_t)free_b) / 2, (uint64_t)160 << 30));
     std::vector<KeGifDev> devs;
-    std::vector<int32_t> st;
-    size_t first = 0;
-    ke_time_begin(ctx, KE_T_JPEG);
-    while (first < items.size()) {
-        uint64_t idx_bytes = 0, nrecs = 0;
-        int max_height = 0;
-        size_t last = first;
-        devs.clear();
-        while (last < items.size()) {
-            Item &it = items[last];
-            const uint64_t px = (uint64_t)it.d.width * it.d.height;
-            const uint64_t ib = (px + 64 + 15) & ~15ull, rc = px / 2 + 2;
-            if (last > first && idx_bytes + ib + (nrecs + rc) * 8 + (uint64_t)(last - first + 1) * 32768 > budget) break;
-            it.d.file_off -= lo;
-            it.d.idx_off = idx_bytes;
-            it.d.rec_off = nrecs;
-            idx_bytes += ib;
-            nrecs += rc;
-            max_height = std::max(max_height, it.d.height);
-            devs.push_back(it.d);
-            ++last;
+    KeStreamGuard guard;                                           // after the host vectors it waits for
+    void *d_files;
+    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));
+    // sub-batches bounded by scratch: indices (1 B per pixel) + copy records (8 B per 2 pixels at worst) + 32 KB of dictionary
+    uint64_t budget;
+    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_SSIM_IN, KE_BUF_TMP, KE_BUF_SSIM_AUX}, (uint64_t)2 << 30, (uint64_t)160 << 30, nullptr,
+                             KE_BUDGET_ENV_LOWERS, &budget));
+    uint64_t idx_bytes = 0, nrecs = 0;
+    int max_height = 0;
+    auto take = [&](size_t k, bool fresh) {
+        if (fresh) {
+            idx_bytes = nrecs = 0;
+            max_height = 0;
+            devs.clear();
         }
-        const int64_t m = (int64_t)devs.size();
+        Item &it = items[k];
+        const uint64_t px = (uint64_t)it.d.width * it.d.height;
+        const uint64_t ib = (px + 64 + 15) & ~15ull, rc = px / 2 + 2;
+        if (!fresh && idx_bytes + ib + (nrecs + rc) * 8 + (uint64_t)(devs.size() + 1) * 32768 > budget) return false;
+        it.d.file_off -= lo;
+        it.d.idx_off = idx_bytes;
+        it.d.rec_off = nrecs;
+        idx_bytes += ib;
+        nrecs += rc;
+        max_height = std::max(max_height, it.d.height);
+        devs.push_back(it.d);
+        return true;
+    };
+    auto launch = [&](size_t m, const int32_t **status, size_t *words) {
         void *d_imgs, *d_idx, *d_rec, *d_dict, *d_status, *d_nrec;
-        KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)m * sizeof(KeGifDev), &d_imgs));
+        KE_TRY(ke_reserve(ctx, KE_BUF_META, m * sizeof(KeGifDev), &d_imgs));
         KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)idx_bytes + 128, &d_idx));
         KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, (size_t)nrecs * 8, &d_rec));
-        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)m * 32768, &d_dict));
-        KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)m * 4, &d_status));
-        KE_TRY(ke_reserve(ctx, KE_BUF_TILE32, (size_t)m * 4, &d_nrec));
-        KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs.data(), (size_t)m * sizeof(KeGifDev), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(ke_gif_codes, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (const KeGifDev *)d_imgs, m, (const uint8_t *)d_files,
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, m * 32768, &d_dict));
+        KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, m * 4, &d_status));
+        KE_TRY(ke_reserve(ctx, KE_BUF_TILE32, m * 4, &d_nrec));
+        KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs.data(), m * sizeof(KeGifDev), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(ke_gif_codes, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (const KeGifDev *)d_imgs, (int64_t)m, (const uint8_t *)d_files,
                            (uint8_t *)d_idx, (uint2 *)d_rec, (uint2 *)d_dict, (int32_t *)d_status, (uint32_t *)d_nrec);
         hipLaunchKernelGGL(ke_gif_copies, dim3((unsigned)m), dim3(64), 0, ctx->stream, (const KeGifDev *)d_imgs, (uint8_t *)d_idx,
                            (const uint2 *)d_rec, (const int32_t *)d_status, (const uint32_t *)d_nrec);
-        const int rows = std::max(kRowsPerBlock, (max_height + 65534) / 65535);
-        hipLaunchKernelGGL(ke_gif_rows, dim3((unsigned)m, (unsigned)((max_height + rows - 1) / rows)), dim3(256), 0, ctx->stream,
-                           (const KeGifDev *)d_imgs, (const uint8_t *)d_idx, (const int32_t *)d_status, pixels_out, rows);
-        KE_HIP(ctx, hipGetLastError());
-        st.resize((size_t)m);
-        KE_HIP(ctx, hipMemcpyAsync(st.data(), d_status, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // devs / st are host vectors; the scratch is reused
-        for (int64_t k = 0; k < m; ++k) status_out[items[first + (size_t)k].which] = st[(size_t)k];
-        first = last;
-    }
-    ke_time_end(ctx, KE_T_JPEG);
+        const KeRowTiles tiles = ke_row_tiles(max_height, kRowsPerBlock);
+        hipLaunchKernelGGL(ke_gif_rows, dim3((unsigned)m, tiles.grid_y), dim3(256), 0, ctx->stream,
+                           (const KeGifDev *)d_imgs, (const uint8_t *)d_idx, (const int32_t *)d_status, pixels_out, tiles.rows);
+        *status = (const int32_t *)d_status;
+        *words = m;
+        return (int)KE_OK;
+    };
+    KE_TRY(ke_decode_sub_batches(ctx, items.size(), take, launch,
+                                 [&](size_t at, size_t k, size_t, const int32_t *st) { status_out[items[at].which] = st[k]; }));
+    guard.disarm();
     return KE_OK;
 }

@@ -20,7 +20,7 @@
 #include <memory>
 #include <cstdio>
 
-#include "ke_internal.h"
+#include "ke_decode_batch.h"
 #include "ke_jpeg_parse.h"
 
 namespace {
@@ -731,6 +731,7 @@ __global__ __launch_bounds__(256) void ke_jpeg_colour(const KeJpegDev *__restric
 
 }  // namespace
 
+// (not ke_probe_each: the parser interns Huffman tables, and a pool lives as long as one thread's range of one call)
 KE_API int ke_jpeg_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                          int32_t *heights, int32_t *channels, int32_t *status_out) {
     if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
@@ -787,28 +788,17 @@ static int jpeg_orientation(const uint8_t *p, size_t size) {
 }
 
 KE_API int ke_jpeg_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            const int o = sizes[i] >= 4 ? jpeg_orientation(files + offsets[i], (size_t)sizes[i]) : 1;
-            // bits 8..11: the orientation itself where the tag could be followed (1..8), for callers that apply it on the device
-            flags_out[i] = ((o < 0 || (o >= 2 && o <= 8)) ? KE_CAVEAT_ORIENTATION : 0) | (o >= 1 && o <= 8 ? o << 8 : 0);
-        }
+    return ke_caveats_each(files, offsets, sizes, n, flags_out, [](const uint8_t *file, size_t size) {
+        const int o = size >= 4 ? jpeg_orientation(file, size) : 1;
+        // bits 8..11: the orientation itself where the tag could be followed (1..8), for callers that apply it on the device
+        return ((o < 0 || (o >= 2 && o <= 8)) ? KE_CAVEAT_ORIENTATION : 0) | (o >= 1 && o <= 8 ? o << 8 : 0);
     });
-    return KE_OK;
 }
 
 KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                           uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
-        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "compressed files are parsed"));
     if (n == 0) return KE_OK;
-    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "compressed files are parsed on the host: pass host memory (pinned staging is fine)");
-    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
-    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
-        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
-    KE_HIP(ctx, hipSetDevice(ctx->device));
     const bool trace = std::getenv("KE_TRACE") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -837,9 +827,12 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
         for (int64_t i = 0; i < n; ++i) status_out[i] = KE_JPEG_CORRUPT;
         return KE_OK;
     }
+    KeJpegTables tables;                              // one pool for the batch: every part's tables interned again
+    std::vector<KeJpegScan> scans;                    // of the progressive files, image after image
+    std::vector<int32_t> prog_list;
+    KeStreamGuard guard;                                           // after the host vectors it waits for
     void *d_files;
-    KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)(hi - lo) + 256, &d_files));   // the stream windows read up to 64 bytes past a file
-    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
+    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));   // the stream windows read up to 64 bytes past a file
     std::unique_ptr<KeJpegDev[]> all(new KeJpegDev[(size_t)n]);           // record i <-> file i; status != OK = not decodable
     std::vector<Part> parts(16);
     const bool on_device_end = !std::getenv("KE_JPEG_HOST_END");      // 1: walk every file's entropy data on the host, as before
@@ -860,8 +853,6 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
         }
     });
     lap("parse (threads)");
-    KeJpegTables tables;                              // one pool for the batch: every part's tables interned again
-    std::vector<KeJpegScan> scans;                    // of the progressive files, image after image
     std::vector<std::vector<int>> remaps((size_t)nparts);
     std::vector<uint32_t> scan_base((size_t)nparts);
     for (int t = 0; t < nparts; ++t) {
@@ -889,10 +880,7 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
         const uint64_t work = (uint64_t)in.mcus_x * in.mcus_y * in.ncomp, bytes = (d.end_on_device ? d.file_size : in.scan_end) - in.scan_offset;
         order.push_back(keep_order ? Key{0, 0, (uint32_t)i} : Key{((uint64_t)(in.progressive ? 1 : 0) << 63) | (~work & 0x7FFFFFFFFFFFFFFFull), ~bytes, (uint32_t)i});
     }
-    if (order.empty()) {
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));        // the caller's buffer is still being read
-        return KE_OK;
-    }
+    if (order.empty()) return KE_OK;                           // (the guard waits: the caller's buffer is still being read)
     if (!keep_order)
         std::sort(order.begin(), order.end(), [](const Key &x, const Key &y) { return x.a != y.a ? x.a < y.a : x.b != y.b ? x.b < y.b : x.i < y.i; });
     lap("merge tables + order");
@@ -934,15 +922,12 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
         KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, scans.size() * sizeof(KeJpegScan), &d_scans));
         KE_HIP(ctx, hipMemcpyAsync(d_scans, scans.data(), scans.size() * sizeof(KeJpegScan), hipMemcpyHostToDevice, ctx->stream));
     }
-    std::vector<int32_t> prog_list;
     // sub-batches bounded by scratch: coefficients (2 B per sample) + planes (1 B per sample)
     // one thread per image: the larger the sub-batch the better the chip is filled (65 536 images are one wave per SIMD) -- the
     // half of what this context's scratch and the free HBM come to together (a sum that does not move when the scratch is
     // regrown, so that consecutive calls cut their batches alike and keep their buffers), up to 160 GB
-    size_t free_b = 0, total_b = 0;
-    KE_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t held = (uint64_t)ctx->buf[KE_BUF_TMP].bytes + ctx->buf[KE_BUF_SSIM_IN].bytes;
-    const uint64_t budget = std::max<uint64_t>((uint64_t)2 << 30, std::min<uint64_t>((held + (uint64_t)free_b) / 2, (uint64_t)160 << 30));
+    uint64_t budget;
+    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_TMP, KE_BUF_SSIM_IN}, (uint64_t)2 << 30, (uint64_t)160 << 30, nullptr, KE_BUDGET_ENV_LOWERS, &budget));
     int64_t first = 0;
     ke_time_begin(ctx, KE_T_JPEG);
     while (first < total) {
@@ -1041,5 +1026,6 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
         first = last;
     }
     ke_time_end(ctx, KE_T_JPEG);
+    guard.disarm();
     return KE_OK;
 }

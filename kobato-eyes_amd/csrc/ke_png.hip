@@ -17,7 +17,7 @@
 //                    the stream (ke_adam7_pass); the same loop runs once per pass and scatters the pixels (ADAM7 instances).
 #include <algorithm>
 
-#include "ke_internal.h"
+#include "ke_decode_batch.h"
 #include "ke_lz_copies.h"
 #include "ke_png_parse.h"
 
@@ -512,55 +512,38 @@ __global__ __launch_bounds__(64) void ke_png_unfilter(const KePngDev *__restrict
 
 KE_API int ke_png_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                         int32_t *heights, int32_t *channels, int32_t *status_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            KePngInfo info;
-            ke_parse_png(files + offsets[i], (size_t)sizes[i], nullptr, info);
-            widths[i] = info.width; heights[i] = info.height; channels[i] = info.channels;
-            status_out[i] = info.status;
-        }
-    });
-    return KE_OK;
+    return ke_probe_each(files, offsets, sizes, n, widths, heights, channels, status_out,
+                         [](const uint8_t *file, size_t size, int32_t &w, int32_t &h, int32_t &c, int32_t &st) {
+                             KePngInfo info;
+                             ke_parse_png(file, size, nullptr, info);
+                             w = info.width; h = info.height; c = info.channels; st = info.status;
+                         });
 }
 
 KE_API int ke_png_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            const uint8_t *p = files + offsets[i];
-            const size_t size = (size_t)sizes[i];
-            int32_t flags = 0;
-            size_t pos = 8;
-            while (pos + 12 <= size) {
-                const size_t len = ((size_t)p[pos] << 24) | ((size_t)p[pos + 1] << 16) | ((size_t)p[pos + 2] << 8) | p[pos + 3];
-                const uint8_t *type = p + pos + 4, *data = p + pos + 8;
-                if (len > 0x7fffffffu || pos + 12 + len > size || std::memcmp(type, "IEND", 4) == 0) break;
-                if (std::memcmp(type, "tRNS", 4) == 0) flags |= KE_CAVEAT_TRANSPARENCY;
-                if (std::memcmp(type, "eXIf", 4) == 0) flags |= KE_CAVEAT_ORIENTATION;
-                // EXIF blocks that ImageMagick-style writers put into text chunks ("Raw profile type exif" / "... APP1"): Pillow reads them
-                if ((std::memcmp(type, "tEXt", 4) == 0 || std::memcmp(type, "zTXt", 4) == 0 || std::memcmp(type, "iTXt", 4) == 0) && len >= 16 &&
-                    std::memcmp(data, "Raw profile type", 16) == 0)
-                    flags |= KE_CAVEAT_ORIENTATION;
-                pos += 12 + len;
-            }
-            flags_out[i] = flags;
+    return ke_caveats_each(files, offsets, sizes, n, flags_out, [](const uint8_t *p, size_t size) {
+        int32_t flags = 0;
+        size_t pos = 8;
+        while (pos + 12 <= size) {
+            const size_t len = ((size_t)p[pos] << 24) | ((size_t)p[pos + 1] << 16) | ((size_t)p[pos + 2] << 8) | p[pos + 3];
+            const uint8_t *type = p + pos + 4, *data = p + pos + 8;
+            if (len > 0x7fffffffu || pos + 12 + len > size || std::memcmp(type, "IEND", 4) == 0) break;
+            if (std::memcmp(type, "tRNS", 4) == 0) flags |= KE_CAVEAT_TRANSPARENCY;
+            if (std::memcmp(type, "eXIf", 4) == 0) flags |= KE_CAVEAT_ORIENTATION;
+            // EXIF blocks that ImageMagick-style writers put into text chunks ("Raw profile type exif" / "... APP1"): Pillow reads them
+            if ((std::memcmp(type, "tEXt", 4) == 0 || std::memcmp(type, "zTXt", 4) == 0 || std::memcmp(type, "iTXt", 4) == 0) && len >= 16 &&
+                std::memcmp(data, "Raw profile type", 16) == 0)
+                flags |= KE_CAVEAT_ORIENTATION;
+            pos += 12 + len;
         }
+        return flags;
     });
-    return KE_OK;
 }
 
 KE_API int ke_png_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                          uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
-        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "compressed files are parsed"));
     if (n == 0) return KE_OK;
-    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "compressed files are parsed on the host: pass host memory (pinned staging is fine)");
-    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
-    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
-        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
-    KE_HIP(ctx, hipSetDevice(ctx->device));
     // ---- host: containers (chunk walk, CRCs of the header chunks), where each image's IDAT payloads lie
     // (on the host's threads, as for JPEG)
     struct Item { KePngDev d; size_t seg0, seg1; int64_t which; };
@@ -602,17 +585,16 @@ KE_API int ke_png_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offs
     // lanes of one wave finish together at best: neighbours in the batch should have streams of like length
     std::stable_sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.d.info.zlen > b.d.info.zlen; });
     // the compressed files (one contiguous range of the caller's buffer) -> device
-    void *d_files;
-    KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)(hi - lo) + 256, &d_files));
-    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
-    // sub-batches bounded by scratch (streams + filtered scanlines + copy records)
-    size_t free_b = 0, total_b = 0;
-    KE_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t held = (uint64_t)ctx->buf[KE_BUF_SSIM_IN].bytes + ctx->buf[KE_BUF_TMP].bytes + ctx->buf[KE_BUF_SSIM_AUX].bytes;
-    const uint64_t budget = std::max<uint64_t>((uint64_t)2 << 30, std::min<uint64_t>((held + (uint64_t)free_b) / 2, (uint64_t)160 << 30));
     std::vector<KePngDev> devs;
     std::vector<KePngPiece> pieces;
     std::vector<int32_t> st;
+    KeStreamGuard guard;                                           // after the host vectors it waits for
+    void *d_files;
+    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));
+    // sub-batches bounded by scratch (streams + filtered scanlines + copy records)
+    uint64_t budget;
+    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_SSIM_IN, KE_BUF_TMP, KE_BUF_SSIM_AUX}, (uint64_t)2 << 30, (uint64_t)160 << 30, nullptr,
+                             KE_BUDGET_ENV_LOWERS, &budget));
     size_t first = 0;
     ke_time_begin(ctx, KE_T_JPEG);
     while (first < items.size()) {
@@ -701,5 +683,6 @@ KE_API int ke_png_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offs
         first = last;
     }
     ke_time_end(ctx, KE_T_JPEG);
+    guard.disarm();
     return KE_OK;
 }

@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "ke_internal.h"
+#include "ke_decode_batch.h"
 
 #include "ke_lz_copies.h"
 #include "ke_lz_window.h"
@@ -160,48 +160,27 @@ __global__ __launch_bounds__(256) void ke_tiffc_rows(const KeTiffcImgDev *__rest
     }
 }
 
-struct SyncOnExit {                               // keyes.h: the caller's buffers are free on return -- also on an error after the first async copy
-    hipStream_t stream;
-    bool armed;
-    ~SyncOnExit() {
-        if (armed) (void)hipStreamSynchronize(stream);
-    }
-};
-
 }  // namespace
 
 KE_API int ke_tiffc_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                           int32_t *heights, int32_t *channels, int32_t *status_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            KeTiffcInfo info;
-            ke_parse_tiffc(files + offsets[i], (size_t)sizes[i], nullptr, info);
-            widths[i] = info.t.width; heights[i] = info.t.height; channels[i] = info.t.channels;
-            status_out[i] = info.t.status;
-        }
-    });
-    return KE_OK;
+    return ke_probe_each(files, offsets, sizes, n, widths, heights, channels, status_out,
+                         [](const uint8_t *file, size_t size, int32_t &w, int32_t &h, int32_t &c, int32_t &st) {
+                             KeTiffcInfo info;
+                             ke_parse_tiffc(file, size, nullptr, info);
+                             w = info.t.width; h = info.t.height; c = info.t.channels; st = info.t.status;
+                         });
 }
 
 KE_API int ke_tiffc_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
     // files that carry an orientation (the tag, an EXIF directory, an XMP packet) are refused by the parser: Pillow turns them
-    for (int64_t i = 0; i < n; ++i) flags_out[i] = 0;
-    return KE_OK;
+    return ke_caveats_none(files, offsets, sizes, n, flags_out);
 }
 
 KE_API int ke_tiffc_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                            uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
-        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "the files' directories are parsed"));
     if (n == 0) return KE_OK;
-    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "the files' directories are parsed on the host: pass host memory (pinned staging is fine)");
-    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
-    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
-        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
-    KE_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<KeTiffcInfo> infos((size_t)n);                   // the directories are read on the host's threads
     std::vector<std::vector<KeTiffcStrip>> found((size_t)n);
     ke_parallel_ranges(n, [&](int64_t a, int64_t b, int) {
@@ -217,79 +196,77 @@ KE_API int ke_tiffc_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *of
         hi = std::max(hi, offsets[i] + sizes[i]);
     }
     if (which.empty()) return KE_OK;
-    void *d_files;
-    KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)(hi - lo) + 256, &d_files));
-    SyncOnExit guard{ctx->stream, true};
-    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
-    // sub-batches bounded by scratch: the strips' planes (1 B per sample) + their copy records (8 B each) + 32 KB of dictionary
-    // per resident lane when the sub-batch has LZW strips
-    size_t free_b = 0, total_b = 0;
-    KE_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t held = (uint64_t)ctx->buf[KE_BUF_TMP].bytes + ctx->buf[KE_BUF_SSIM_AUX].bytes + ctx->buf[KE_BUF_SSIM_IN].bytes;
-    uint64_t budget = std::max<uint64_t>((uint64_t)1 << 30, std::min<uint64_t>((held + (uint64_t)free_b) / 2, (uint64_t)32 << 30));
-    if (const char *e = std::getenv("KE_TIFFC_SCRATCH_BYTES")) budget = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
     std::vector<KeTiffcImgDev> imgs;
     std::vector<KeTiffcStripDev> strips;
-    std::vector<int32_t> st;
+    KeStreamGuard guard;                                           // after the host vectors it waits for
+    void *d_files;
+    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));
+    // sub-batches bounded by scratch: the strips' planes (1 B per sample) + their copy records (8 B each) + 32 KB of dictionary
+    // per resident lane when the sub-batch has LZW strips
+    uint64_t budget;
+    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_TMP, KE_BUF_SSIM_AUX, KE_BUF_SSIM_IN}, (uint64_t)1 << 30, (uint64_t)32 << 30, "KE_TIFFC_SCRATCH_BYTES",
+                             KE_BUDGET_ENV_REPLACES, &budget));
     auto dict_bytes = [](uint64_t strips_so_far, bool lzw) {
         return lzw ? std::min<uint64_t>((strips_so_far + 63) / 64, kMaxWaves) * 64 * 32768 : (uint64_t)64;
     };
-    size_t first = 0;
-    ke_time_begin(ctx, KE_T_JPEG);
-    while (first < which.size()) {
-        uint64_t plane_bytes = 0, nrecs = 0;
-        int max_height = 0;
-        bool any_lzw = false;
-        size_t last = first;
-        imgs.clear();
-        strips.clear();
-        while (last < which.size()) {
-            const int64_t i = which[last];
-            const KeTiffcInfo &info = infos[(size_t)i];
-            const KeTiffInfo &t = info.t;
-            const uint64_t row = (uint64_t)t.width * t.spp;
-            const uint64_t stride = (row * t.rows_per_strip + 2 + 15) & ~15ull;
-            uint64_t pb = stride * t.nstrips, rc = 0;
-            for (int s = 0; s < t.nstrips; ++s) {
-                const uint64_t want = row * std::min(t.rows_per_strip, t.height - s * t.rows_per_strip);
-                // a record per string or run -- at most one per compressed byte -- and per further 513 bytes of a long one;
-                // never more than one per 2 bytes the strip yields
-                rc += std::min<uint64_t>(want / 2 + 2, (uint64_t)found[(size_t)i][(size_t)s].bytes + want / 512 + 2);
-            }
-            const bool lzw = any_lzw || info.compression == KE_TIFFC_LZW;
-            if (last > first && plane_bytes + pb + (nrecs + rc) * 8 + dict_bytes(strips.size() + (size_t)t.nstrips, lzw) > budget) break;
-            KeTiffcImgDev d;
-            d.out_off = out_offsets[i];
-            d.plane_off = plane_bytes;
-            d.strip_stride = (uint32_t)stride;
-            d.width = t.width; d.height = t.height; d.spp = t.spp; d.channels = t.channels; d.mapped = t.mapped;
-            d.rows_per_strip = t.rows_per_strip; d.predictor = info.predictor;
-            std::memcpy(d.lut, t.lut, 256);
-            for (int s = 0; s < t.nstrips; ++s) {
-                const KeTiffcStrip &f = found[(size_t)i][(size_t)s];
-                KeTiffcStripDev sd;
-                sd.file_off = offsets[i] - lo + f.off;
-                sd.plane_off = plane_bytes + stride * (uint64_t)s;
-                sd.rec_off = nrecs;
-                sd.bytes = f.bytes;
-                sd.want = (uint32_t)(row * std::min(t.rows_per_strip, t.height - s * t.rows_per_strip));
-                sd.img = (uint32_t)imgs.size();
-                sd.comp = (uint32_t)info.compression;
-                nrecs += std::min<uint64_t>((uint64_t)sd.want / 2 + 2, (uint64_t)f.bytes + sd.want / 512 + 2);
-                strips.push_back(sd);
-            }
-            any_lzw = any_lzw || info.compression == KE_TIFFC_LZW;
-            plane_bytes += pb;
-            max_height = std::max(max_height, t.height);
-            imgs.push_back(d);
-            ++last;
+    uint64_t plane_bytes = 0, nrecs = 0;
+    int max_height = 0;
+    bool any_lzw = false;
+    auto take = [&](size_t k, bool fresh) {
+        if (fresh) {
+            plane_bytes = nrecs = 0;
+            max_height = 0;
+            any_lzw = false;
+            imgs.clear();
+            strips.clear();
         }
+        const int64_t i = which[k];
+        const KeTiffcInfo &info = infos[(size_t)i];
+        const KeTiffInfo &t = info.t;
+        const uint64_t row = (uint64_t)t.width * t.spp;
+        const uint64_t stride = (row * t.rows_per_strip + 2 + 15) & ~15ull;
+        uint64_t pb = stride * t.nstrips, rc = 0;
+        for (int s = 0; s < t.nstrips; ++s) {
+            const uint64_t want = row * std::min(t.rows_per_strip, t.height - s * t.rows_per_strip);
+            // a record per string or run -- at most one per compressed byte -- and per further 513 bytes of a long one;
+            // never more than one per 2 bytes the strip yields
+            rc += std::min<uint64_t>(want / 2 + 2, (uint64_t)found[(size_t)i][(size_t)s].bytes + want / 512 + 2);
+        }
+        const bool lzw = any_lzw || info.compression == KE_TIFFC_LZW;
+        if (!fresh && plane_bytes + pb + (nrecs + rc) * 8 + dict_bytes(strips.size() + (size_t)t.nstrips, lzw) > budget) return false;
+        KeTiffcImgDev d;
+        d.out_off = out_offsets[i];
+        d.plane_off = plane_bytes;
+        d.strip_stride = (uint32_t)stride;
+        d.width = t.width; d.height = t.height; d.spp = t.spp; d.channels = t.channels; d.mapped = t.mapped;
+        d.rows_per_strip = t.rows_per_strip; d.predictor = info.predictor;
+        std::memcpy(d.lut, t.lut, 256);
+        for (int s = 0; s < t.nstrips; ++s) {
+            const KeTiffcStrip &f = found[(size_t)i][(size_t)s];
+            KeTiffcStripDev sd;
+            sd.file_off = offsets[i] - lo + f.off;
+            sd.plane_off = plane_bytes + stride * (uint64_t)s;
+            sd.rec_off = nrecs;
+            sd.bytes = f.bytes;
+            sd.want = (uint32_t)(row * std::min(t.rows_per_strip, t.height - s * t.rows_per_strip));
+            sd.img = (uint32_t)imgs.size();
+            sd.comp = (uint32_t)info.compression;
+            nrecs += std::min<uint64_t>((uint64_t)sd.want / 2 + 2, (uint64_t)f.bytes + sd.want / 512 + 2);
+            strips.push_back(sd);
+        }
+        any_lzw = lzw;
+        plane_bytes += pb;
+        max_height = std::max(max_height, t.height);
+        imgs.push_back(d);
+        return true;
+    };
+    auto launch = [&](size_t m, const int32_t **status, size_t *words) {
         // lanes of one wave finish together at best: neighbours in the list are strips of one compression and of like length,
         // and the longest walks start first
         std::stable_sort(strips.begin(), strips.end(), [](const KeTiffcStripDev &a, const KeTiffcStripDev &b) {
             return a.comp != b.comp ? a.comp < b.comp : a.bytes > b.bytes;
         });
-        const size_t m = imgs.size(), ns = strips.size();
+        const size_t ns = strips.size();
         const uint32_t waves = (uint32_t)std::min<uint64_t>((ns + 63) / 64, kMaxWaves);
         void *d_imgs, *d_strips, *d_planes, *d_rec, *d_dict, *d_status, *d_nrec;
         KE_TRY(ke_reserve(ctx, KE_BUF_META, m * sizeof(KeTiffcImgDev), &d_imgs));
@@ -306,17 +283,15 @@ KE_API int ke_tiffc_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *of
                            (uint8_t *)d_planes, (uint2 *)d_rec, (uint2 *)d_dict, (int32_t *)d_status, (uint32_t *)d_nrec, (uint32_t *)d_status + m);
         hipLaunchKernelGGL(ke_tiffc_copies, dim3((unsigned)ns), dim3(64), 0, ctx->stream, (const KeTiffcStripDev *)d_strips, (uint8_t *)d_planes,
                            (const uint2 *)d_rec, (const int32_t *)d_status, (const uint32_t *)d_nrec);
-        const int rows = std::max(kRowsPerBlock, (max_height + 65534) / 65535);
-        hipLaunchKernelGGL(ke_tiffc_rows, dim3((unsigned)m, (unsigned)((max_height + rows - 1) / rows)), dim3(256), 0, ctx->stream,
-                           (const KeTiffcImgDev *)d_imgs, (const uint8_t *)d_planes, (const int32_t *)d_status, pixels_out, rows);
-        KE_HIP(ctx, hipGetLastError());
-        st.resize(m);
-        KE_HIP(ctx, hipMemcpyAsync(st.data(), d_status, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // imgs / strips / st are host vectors; the scratch is reused
-        for (size_t k = 0; k < m; ++k) status_out[which[first + k]] = st[k];
-        first = last;
-    }
-    ke_time_end(ctx, KE_T_JPEG);
-    guard.armed = false;
+        const KeRowTiles tiles = ke_row_tiles(max_height, kRowsPerBlock);
+        hipLaunchKernelGGL(ke_tiffc_rows, dim3((unsigned)m, tiles.grid_y), dim3(256), 0, ctx->stream,
+                           (const KeTiffcImgDev *)d_imgs, (const uint8_t *)d_planes, (const int32_t *)d_status, pixels_out, tiles.rows);
+        *status = (const int32_t *)d_status;
+        *words = m;
+        return (int)KE_OK;
+    };
+    KE_TRY(ke_decode_sub_batches(ctx, which.size(), take, launch,
+                                 [&](size_t at, size_t k, size_t, const int32_t *st) { status_out[which[at]] = st[k]; }));
+    guard.disarm();
     return KE_OK;
 }

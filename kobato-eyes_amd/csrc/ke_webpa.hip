@@ -21,10 +21,9 @@
 // A method-1 plane stays where the stream decoder left it, in the green bytes of its ARGB words (stride 4); a raw plane is read
 // from the file's bytes and, when filtered, written to W x H bytes of scratch.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
-#include "ke_internal.h"
+#include "ke_decode_batch.h"
 #include "ke_webp_launch.h"
 #include "ke_webpa_parse.h"
 #include "ke_webpl_transform.h"
@@ -194,43 +193,28 @@ __global__ __launch_bounds__(256) void ke_webpa_colour_k(const KeWebpDev *__rest
 
 KE_API int ke_webpa_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                           int32_t *heights, int32_t *channels, int32_t *status_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            KeWebpaHeader h;                                        // container, frame tag, ALPH header byte: the decode call parses the rest
-            ke_webpa_tag(files + offsets[i], (size_t)sizes[i], h);
-            widths[i] = h.f.width; heights[i] = h.f.height; channels[i] = 4;
-            status_out[i] = h.f.status;
-        }
-    });
-    return KE_OK;
+    return ke_probe_each(files, offsets, sizes, n, widths, heights, channels, status_out,
+                         [](const uint8_t *file, size_t size, int32_t &w, int32_t &h, int32_t &c, int32_t &st) {
+                             KeWebpaHeader hd;                       // container, frame tag, ALPH header byte: the decode call parses the rest
+                             ke_webpa_tag(file, size, hd);
+                             w = hd.f.width; h = hd.f.height; c = 4; st = hd.f.status;
+                         });
 }
 
 KE_API int ke_webpa_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
     // An EXIF chunk or an XMP packet may carry an orientation the reference's loader applies (flagged without reading it); every
     // file taken here is RGBA, which that loader composites over white.
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            KeWebpaHeader h;
-            ke_webpa_tag(files + offsets[i], (size_t)sizes[i], h);
-            flags_out[i] = (h.f.meta ? KE_CAVEAT_ORIENTATION : 0) | (h.f.status == KE_WEBPA_OK ? KE_CAVEAT_TRANSPARENCY : 0);
-        }
+    return ke_caveats_each(files, offsets, sizes, n, flags_out, [](const uint8_t *file, size_t size) {
+        KeWebpaHeader h;
+        ke_webpa_tag(file, size, h);
+        return (h.f.meta ? KE_CAVEAT_ORIENTATION : 0) | (h.f.status == KE_WEBPA_OK ? KE_CAVEAT_TRANSPARENCY : 0);
     });
-    return KE_OK;
 }
 
 KE_API int ke_webpa_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                            uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
-        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "the files' headers are parsed"));
     if (n == 0) return KE_OK;
-    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "the files' headers are parsed on the host: pass host memory (pinned staging is fine)");
-    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
-    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
-        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
-    KE_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<KeWebpaHeader> items((size_t)n);                    // the headers are parsed on the host's threads
     ke_parallel_ranges(n, [&](int64_t a, int64_t b, int) {
         for (int64_t i = a; i < b; ++i) ke_parse_webpa(files + offsets[i], (size_t)sizes[i], items[(size_t)i]);
@@ -248,58 +232,53 @@ KE_API int ke_webpa_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *of
     if (which.empty()) return KE_OK;
     // lanes of one wave finish together at best: neighbours in the batch should have streams of like length
     std::stable_sort(which.begin(), which.end(), [&](int64_t a, int64_t b) { return items[(size_t)a].f.vp8_size > items[(size_t)b].f.vp8_size; });
-    void *d_files;
-    KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)(hi - lo) + 256, &d_files));
-    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
-    // sub-batches bounded by scratch: 1 172 B per macroblock, and the plane's -- about 9.2 bytes per pixel and 96 KiB for a stream,
-    // a byte per pixel for raw bytes
-    size_t free_b = 0, total_b = 0;
-    KE_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t held = (uint64_t)ctx->buf[KE_BUF_SSIM_IN].bytes;
-    uint64_t budget = std::max<uint64_t>((uint64_t)2 << 30, std::min<uint64_t>((held + (uint64_t)free_b) / 2, (uint64_t)160 << 30));
-    if (const char *e = getenv("KE_WEBP_SCRATCH_BYTES")) {          // a smaller budget (tests: many sub-batches); results do not depend on it
-        const unsigned long long v = strtoull(e, nullptr, 10);
-        if (v > 0) budget = std::min<uint64_t>(budget, v);
-    }
     std::vector<KeWebpDev> devs;
     std::vector<KeWebpaDev> planes;
-    std::vector<int32_t> order, st;
-    size_t first = 0;
-    ke_time_begin(ctx, KE_T_JPEG);
-    while (first < which.size()) {
-        uint64_t bytes = 0;
-        int max_height = 0, max_filtered = 0;
-        size_t last = first;
-        devs.clear();
-        planes.clear();
-        order.clear();
-        while (last < which.size()) {
-            const int64_t i = which[last];
-            const KeWebpaHeader &h = items[(size_t)i];
-            const uint64_t frame = ke_webp_frame_scratch(h.f), plane = (ke_webpa_plane_words(h) * 4 + 15) & ~15ull;
-            if (last > first && bytes + frame + plane > budget) break;
-            KeWebpDev d;
-            d.h = h.f;
-            d.file_off = offsets[i] - lo;
-            d.scratch_off = bytes;
-            d.out_off = out_offsets[i];
-            KeWebpaDev a;
-            a.alph_off = d.file_off + h.alph_off;
-            a.plane_off = bytes + frame;
-            a.plane_words = ke_webpa_plane_words(h);
-            a.out_off = out_offsets[i];
-            a.alph_size = h.alph_size;
-            a.method = h.method; a.filter = h.filter;
-            a.width = h.f.width; a.height = h.f.height;
-            bytes += frame + plane;
-            max_height = std::max(max_height, h.f.height);
-            if (h.method != KE_ALPH_OPAQUE && h.filter == KE_ALPH_FILTER_GRADIENT) max_filtered = std::max(max_filtered, h.f.height);
-            if (h.method == KE_ALPH_VP8L) order.push_back((int32_t)devs.size());
-            devs.push_back(d);
-            planes.push_back(a);
-            ++last;
+    std::vector<int32_t> order;
+    KeStreamGuard guard;                                           // after the host vectors it waits for
+    void *d_files;
+    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));
+    // sub-batches bounded by scratch: 1 172 B per macroblock, and the plane's -- about 9.2 bytes per pixel and 96 KiB for a stream,
+    // a byte per pixel for raw bytes
+    uint64_t budget;                                                // KE_WEBP_SCRATCH_BYTES: a smaller one (tests: many sub-batches)
+    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_SSIM_IN}, (uint64_t)2 << 30, (uint64_t)160 << 30, "KE_WEBP_SCRATCH_BYTES", KE_BUDGET_ENV_LOWERS, &budget));
+    uint64_t bytes = 0;
+    int max_height = 0, max_filtered = 0;
+    auto take = [&](size_t k, bool fresh) {
+        if (fresh) {
+            bytes = 0;
+            max_height = max_filtered = 0;
+            devs.clear();
+            planes.clear();
+            order.clear();
         }
-        const int64_t m = (int64_t)devs.size(), m1 = (int64_t)order.size();
+        const int64_t i = which[k];
+        const KeWebpaHeader &h = items[(size_t)i];
+        const uint64_t frame = ke_webp_frame_scratch(h.f), plane = (ke_webpa_plane_words(h) * 4 + 15) & ~15ull;
+        if (!fresh && bytes + frame + plane > budget) return false;
+        KeWebpDev d;
+        d.h = h.f;
+        d.file_off = offsets[i] - lo;
+        d.scratch_off = bytes;
+        d.out_off = out_offsets[i];
+        KeWebpaDev a;
+        a.alph_off = d.file_off + h.alph_off;
+        a.plane_off = bytes + frame;
+        a.plane_words = ke_webpa_plane_words(h);
+        a.out_off = out_offsets[i];
+        a.alph_size = h.alph_size;
+        a.method = h.method; a.filter = h.filter;
+        a.width = h.f.width; a.height = h.f.height;
+        bytes += frame + plane;
+        max_height = std::max(max_height, h.f.height);
+        if (h.method != KE_ALPH_OPAQUE && h.filter == KE_ALPH_FILTER_GRADIENT) max_filtered = std::max(max_filtered, h.f.height);
+        if (h.method == KE_ALPH_VP8L) order.push_back((int32_t)devs.size());
+        devs.push_back(d);
+        planes.push_back(a);
+        return true;
+    };
+    auto launch = [&](size_t um, const int32_t **status, size_t *words) {
+        const int64_t m = (int64_t)um, m1 = (int64_t)order.size();
         std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return planes[(size_t)a].alph_size > planes[(size_t)b].alph_size; });
         // one record buffer: [frames | planes | order]; one status buffer: [frames | planes]
         const size_t at_planes = ((size_t)m * sizeof(KeWebpDev) + 15) & ~(size_t)15, at_order = at_planes + (((size_t)m * sizeof(KeWebpaDev) + 15) & ~(size_t)15);
@@ -325,17 +304,18 @@ KE_API int ke_webpa_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *of
         }
         hipLaunchKernelGGL(ke_webpa_filter_k, dim3((unsigned)m), dim3(kPlaneThreads), (size_t)3 * max_filtered, ctx->stream, d_planes,
                            (const uint8_t *)d_files, (uint8_t *)d_scratch, (const int32_t *)d_status_f, (const int32_t *)d_status_a);
-        const int rows = std::max(kRowsPerBlock, (max_height + 65534) / 65535);
-        hipLaunchKernelGGL(ke_webpa_colour_k, dim3((unsigned)m, (unsigned)((max_height + rows - 1) / rows)), dim3(256), 0, ctx->stream, d_imgs,
+        const KeRowTiles tiles = ke_row_tiles(max_height, kRowsPerBlock);
+        hipLaunchKernelGGL(ke_webpa_colour_k, dim3((unsigned)m, tiles.grid_y), dim3(256), 0, ctx->stream, d_imgs,
                            d_planes, (const uint8_t *)d_files, (const uint8_t *)d_scratch, (const int32_t *)d_status_f,
-                           (const int32_t *)d_status_a, pixels_out, rows);
-        KE_HIP(ctx, hipGetLastError());
-        st.resize((size_t)m * 2);
-        KE_HIP(ctx, hipMemcpyAsync(st.data(), d_status, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // the records / st are host vectors; the scratch is reused
-        for (int64_t k = 0; k < m; ++k) status_out[which[first + (size_t)k]] = st[(size_t)k] != KE_WEBP_OK ? st[(size_t)k] : st[(size_t)(m + k)];
-        first = last;
-    }
-    ke_time_end(ctx, KE_T_JPEG);
+                           (const int32_t *)d_status_a, pixels_out, tiles.rows);
+        *status = d_status_f;
+        *words = (size_t)m * 2;
+        return (int)KE_OK;
+    };
+    // a frame that failed keeps its status; otherwise the plane's decides
+    KE_TRY(ke_decode_sub_batches(ctx, which.size(), take, launch, [&](size_t at, size_t k, size_t m, const int32_t *st) {
+        status_out[which[at]] = st[k] != KE_WEBP_OK ? st[k] : st[m + k];
+    }));
+    guard.disarm();
     return KE_OK;
 }

@@ -14,10 +14,9 @@
 //                       towards the front of the buffer, the packed rows lying behind where their pixels go.
 //   ke_webpl_output     one thread per pixel: RGB or RGBA bytes at the caller's offsets.
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
-#include "ke_internal.h"
+#include "ke_decode_batch.h"
 #include "ke_webpl_parse.h"
 #include "ke_webpl_transform.h"
 
@@ -72,43 +71,28 @@ __global__ __launch_bounds__(256) void ke_webpl_output_k(const KeWebplDev *__res
 
 KE_API int ke_webpl_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                           int32_t *heights, int32_t *channels, int32_t *status_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !widths || !heights || !channels || !status_out))) return KE_EINVAL;
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            KeWebplHeader h;
-            ke_parse_webpl(files + offsets[i], (size_t)sizes[i], h);
-            widths[i] = h.width; heights[i] = h.height; channels[i] = h.channels;
-            status_out[i] = h.status;
-        }
-    });
-    return KE_OK;
+    return ke_probe_each(files, offsets, sizes, n, widths, heights, channels, status_out,
+                         [](const uint8_t *file, size_t size, int32_t &w, int32_t &h, int32_t &c, int32_t &st) {
+                             KeWebplHeader hd;
+                             ke_parse_webpl(file, size, hd);
+                             w = hd.width; h = hd.height; c = hd.channels; st = hd.status;
+                         });
 }
 
 KE_API int ke_webpl_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out) {
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !flags_out))) return KE_EINVAL;
     // An EXIF chunk or an XMP packet may carry an orientation the reference's loader applies (flagged without reading it);
     // an RGBA file is composited over white by it.
-    ke_parallel_ranges(n, [=](int64_t lo, int64_t hi, int) {
-        for (int64_t i = lo; i < hi; ++i) {
-            KeWebplHeader h;
-            ke_parse_webpl(files + offsets[i], (size_t)sizes[i], h);
-            flags_out[i] = (h.meta ? KE_CAVEAT_ORIENTATION : 0) | (h.channels == 4 ? KE_CAVEAT_TRANSPARENCY : 0);
-        }
+    return ke_caveats_each(files, offsets, sizes, n, flags_out, [](const uint8_t *file, size_t size) {
+        KeWebplHeader h;
+        ke_parse_webpl(file, size, h);
+        return (h.meta ? KE_CAVEAT_ORIENTATION : 0) | (h.channels == 4 ? KE_CAVEAT_TRANSPARENCY : 0);
     });
-    return KE_OK;
 }
 
 KE_API int ke_webpl_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                            uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    if (n < 0 || (n > 0 && (!files || !offsets || !sizes || !pixels_out || !out_offsets || !status_out)))
-        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "the files' headers are parsed"));
     if (n == 0) return KE_OK;
-    if (ke_is_device_ptr(files)) return ke_fail(ctx, KE_EINVAL, "the files' headers are parsed on the host: pass host memory (pinned staging is fine)");
-    if (!ke_is_device_ptr(pixels_out)) return ke_fail(ctx, KE_EINVAL, "pixels_out must be device memory");
-    for (const void *p : {(const void *)offsets, (const void *)sizes, (const void *)out_offsets, (const void *)status_out})
-        if (ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/sizes/status are host arrays");
-    KE_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<KeWebplDev> items((size_t)n);
     ke_parallel_ranges(n, [&](int64_t a, int64_t b, int) {
         for (int64_t i = a; i < b; ++i) ke_parse_webpl(files + offsets[i], (size_t)sizes[i], items[(size_t)i].h);
@@ -130,59 +114,51 @@ KE_API int ke_webpl_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *of
     if (which.empty()) return KE_OK;
     // lanes of one wave finish together at best: neighbours in the batch should have streams of like length
     std::stable_sort(which.begin(), which.end(), [&](int64_t a, int64_t b) { return sizes[a] > sizes[b]; });
-    void *d_files;
-    KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)(hi - lo) + 256, &d_files));
-    KE_HIP(ctx, hipMemcpyAsync(d_files, files + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, ctx->stream));
-    // sub-batches bounded by scratch: about 9.2 bytes per pixel and 96 KiB per image
-    size_t free_b = 0, total_b = 0;
-    KE_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t held = (uint64_t)ctx->buf[KE_BUF_SSIM_IN].bytes;
-    uint64_t budget = std::max<uint64_t>((uint64_t)2 << 30, std::min<uint64_t>((held + (uint64_t)free_b) / 2, (uint64_t)160 << 30));
-    if (const char *e = getenv("KE_WEBP_SCRATCH_BYTES")) {          // a smaller budget (tests: many sub-batches); results do not depend on it
-        const unsigned long long v = strtoull(e, nullptr, 10);
-        if (v > 0) budget = std::min<uint64_t>(budget, v);
-    }
     std::vector<KeWebplDev> devs;
-    std::vector<int32_t> st;
-    size_t first = 0;
-    ke_time_begin(ctx, KE_T_JPEG);
-    while (first < which.size()) {
-        uint64_t bytes = 0;
-        int max_height = 0;
-        size_t last = first;
-        devs.clear();
-        while (last < which.size()) {
-            KeWebplDev d = items[(size_t)which[last]];
-            const uint64_t need = (d.scratch_words * 4 + 15) & ~15ull;
-            if (last > first && bytes + need > budget) break;
-            d.file_off -= lo;
-            d.scratch_off = bytes;
-            bytes += need;
-            max_height = std::max(max_height, d.h.height);
-            devs.push_back(d);
-            ++last;
+    KeStreamGuard guard;                                           // after the host vectors it waits for
+    void *d_files;
+    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));
+    // sub-batches bounded by scratch: about 9.2 bytes per pixel and 96 KiB per image
+    uint64_t budget;                                                // KE_WEBP_SCRATCH_BYTES: a smaller one (tests: many sub-batches)
+    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_SSIM_IN}, (uint64_t)2 << 30, (uint64_t)160 << 30, "KE_WEBP_SCRATCH_BYTES", KE_BUDGET_ENV_LOWERS, &budget));
+    uint64_t bytes = 0;
+    int max_height = 0;
+    auto take = [&](size_t k, bool fresh) {
+        if (fresh) {
+            bytes = 0;
+            max_height = 0;
+            devs.clear();
         }
-        const int64_t m = (int64_t)devs.size();
+        KeWebplDev d = items[(size_t)which[k]];
+        const uint64_t need = (d.scratch_words * 4 + 15) & ~15ull;
+        if (!fresh && bytes + need > budget) return false;
+        d.file_off -= lo;
+        d.scratch_off = bytes;
+        bytes += need;
+        max_height = std::max(max_height, d.h.height);
+        devs.push_back(d);
+        return true;
+    };
+    auto launch = [&](size_t m, const int32_t **status, size_t *words) {
         void *d_imgs, *d_scratch, *d_status, *d_plans;
-        KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)m * sizeof(KeWebplDev), &d_imgs));
+        KE_TRY(ke_reserve(ctx, KE_BUF_META, m * sizeof(KeWebplDev), &d_imgs));
         KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)bytes + 64, &d_scratch));
-        KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)m * 4, &d_status));
-        KE_TRY(ke_reserve(ctx, KE_BUF_OUT1, (size_t)m * sizeof(KeVp8lPlan), &d_plans));
-        KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs.data(), (size_t)m * sizeof(KeWebplDev), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(ke_webpl_entropy_k, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (const KeWebplDev *)d_imgs, m,
+        KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, m * 4, &d_status));
+        KE_TRY(ke_reserve(ctx, KE_BUF_OUT1, m * sizeof(KeVp8lPlan), &d_plans));
+        KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs.data(), m * sizeof(KeWebplDev), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(ke_webpl_entropy_k, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (const KeWebplDev *)d_imgs, (int64_t)m,
                            (const uint8_t *)d_files, (uint8_t *)d_scratch, (KeVp8lPlan *)d_plans, (int32_t *)d_status);
         hipLaunchKernelGGL(ke_webpl_transform_k, dim3((unsigned)m), dim3(kTransformThreads), 0, ctx->stream, (const KeWebplDev *)d_imgs,
                            (uint8_t *)d_scratch, (const KeVp8lPlan *)d_plans, (const int32_t *)d_status);
-        const int rows = std::max(kRowsPerBlock, (max_height + 65534) / 65535);
-        hipLaunchKernelGGL(ke_webpl_output_k, dim3((unsigned)m, (unsigned)((max_height + rows - 1) / rows)), dim3(256), 0, ctx->stream,
-                           (const KeWebplDev *)d_imgs, (const uint8_t *)d_scratch, (const int32_t *)d_status, pixels_out, rows);
-        KE_HIP(ctx, hipGetLastError());
-        st.resize((size_t)m);
-        KE_HIP(ctx, hipMemcpyAsync(st.data(), d_status, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // devs / st are host vectors; the scratch is reused
-        for (int64_t k = 0; k < m; ++k) status_out[which[first + (size_t)k]] = st[(size_t)k];
-        first = last;
-    }
-    ke_time_end(ctx, KE_T_JPEG);
+        const KeRowTiles tiles = ke_row_tiles(max_height, kRowsPerBlock);
+        hipLaunchKernelGGL(ke_webpl_output_k, dim3((unsigned)m, tiles.grid_y), dim3(256), 0, ctx->stream,
+                           (const KeWebplDev *)d_imgs, (const uint8_t *)d_scratch, (const int32_t *)d_status, pixels_out, tiles.rows);
+        *status = (const int32_t *)d_status;
+        *words = m;
+        return (int)KE_OK;
+    };
+    KE_TRY(ke_decode_sub_batches(ctx, which.size(), take, launch,
+                                 [&](size_t at, size_t k, size_t, const int32_t *st) { status_out[which[at]] = st[k]; }));
+    guard.disarm();
     return KE_OK;
 }

@@ -28,6 +28,7 @@ from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native
+from .formats import BASE_KINDS, FORMATS, enabled_kinds, follow_ups
 
 _phash = importlib.import_module(".phash", __package__)   # the package also exports a function named phash
 
@@ -115,16 +116,8 @@ def _read_pixels(path_text: str, room: Optional[int] = None):
         return None
 
 
-JPEG_SUFFIXES = (".jpg", ".jpeg", ".jpe", ".jfif")
-PNG_SUFFIXES = (".png", ".apng")
-BMP_SUFFIXES = (".bmp",)
-GIF_SUFFIXES = (".gif",)
-TIFF_SUFFIXES = (".tif", ".tiff")
-WEBP_SUFFIXES = (".webp",)
-GPU_KINDS = ("jpeg", "png", "bmp", "gif", "tiff", "webp")           # the order in which a batch's files lie in the read-ahead buffer
-# kind -> the opt-in decoders that are offered what it left UNSUPPORTED, one after the other, each behind its variable
-FOLLOW_UPS = {"tiff": (("tiffc", "KE_GPU_TIFF_COMPRESSED"),),
-              "webp": (("webpl", "KE_GPU_WEBP_LOSSLESS"), ("webpa", "KE_GPU_WEBP_ALPHA"))}
+# suffix -> 1 + its place in BASE_KINDS (0: not a GPU decoder's file).  Every suffix is one dot and up to four letters.
+_KIND_CODE = {suffix: 1 + BASE_KINDS.index(f.kind) for f in FORMATS if f.follows is None for suffix in f.suffixes}
 
 
 def _read_bytes(path_text: str):
@@ -317,7 +310,7 @@ class _GpuStage:
     def jpeg_hash(self, blobs, kind: str = "jpeg"):
         """(phash, dhash, status) of JPEG / PNG files decoded on the GPU (``ke_jpeg_decode`` / ``ke_png_decode`` ->
         ``ke_hash_images``); status != 0: the decoder leaves the file to Pillow."""
-        return self.ctx.jpeg_hash(blobs, want_dhash=True, kind=kind)
+        return self.ctx.hash(blobs, want_dhash=True, kind=kind)
 
     def hash_files(self, paths, kind: str = "jpeg"):
         """jpeg_hash for files on disk: the library reads them (host threads, page-locked memory), no bytes objects."""
@@ -329,7 +322,7 @@ class _GpuStage:
 
     def hash_ahead(self, held, lo: int, hi: int, kind: str = "jpeg", skip=None):
         """hash_files for files lo..hi of what read_ahead returned; ``skip``: a mask of files to leave alone (status 1)."""
-        return self.ctx.jpeg_hash(None, want_dhash=True, kind=kind, ahead=(held, lo, hi), skip=skip)
+        return self.ctx.hash(None, want_dhash=True, kind=kind, ahead=(held, lo, hi), skip=skip)
 
     def hash_one(self, arr):
         """(phash, dhash) or None for an image that did not fit a staging buffer."""
@@ -411,34 +404,23 @@ class _Pipeline:
         on the GPU.  Runs on a pool thread (the classification is a pass of the interpreter over the batch, the reading is the
         library's): {"jpeg" / "png" / "bmp" / "gif" / "tiff" / "webp": positions (arrays, ascending), "blobs": position -> future of the file's bytes for
         a stage without ``hash_files``, "ahead": the context's FilesAhead holding [JPEG | PNG | BMP | GIF | TIFF | WebP files] or None}."""
-        gpu_jpeg = os.environ.get("KE_GPU_JPEG", "1") != "0"
-        gpu_png = os.environ.get("KE_GPU_PNG", "1") != "0"
-        gpu_bmp = os.environ.get("KE_GPU_BMP", "1") != "0"
-        gpu_gif = os.environ.get("KE_GPU_GIF", "1") != "0"
-        gpu_tiff = os.environ.get("KE_GPU_TIFF", "1") != "0"
-        gpu_webp = os.environ.get("KE_GPU_WEBP", "1") != "0"
+        enabled = {k for k, _ in enabled_kinds("hash")}
         by_path = hasattr(self.stage, "hash_files")          # the library reads the files itself, into page-locked memory
         stop = min(start + self.batch, len(self.tasks))
         tails = [p[-5:].lower() for p in self.paths[start:stop]]
-        kind = np.fromiter((1 if t.endswith(JPEG_SUFFIXES) else 2 if t.endswith(PNG_SUFFIXES) else 3 if t.endswith(BMP_SUFFIXES) else 4 if t.endswith(GIF_SUFFIXES) else 5 if t.endswith(TIFF_SUFFIXES) else 6 if t.endswith(WEBP_SUFFIXES) else 0
-                            for t in tails), np.int8, stop - start)
-        jpeg = start + np.nonzero(kind == 1)[0] if gpu_jpeg else np.zeros(0, np.int64)
-        png = start + np.nonzero(kind == 2)[0] if gpu_png else np.zeros(0, np.int64)
-        bmp = start + np.nonzero(kind == 3)[0] if gpu_bmp else np.zeros(0, np.int64)
-        gif = start + np.nonzero(kind == 4)[0] if gpu_gif else np.zeros(0, np.int64)
-        tiff = start + np.nonzero(kind == 5)[0] if gpu_tiff else np.zeros(0, np.int64)
-        webp = start + np.nonzero(kind == 6)[0] if gpu_webp else np.zeros(0, np.int64)
-        reads = {"jpeg": jpeg, "png": png, "bmp": bmp, "gif": gif, "tiff": tiff, "webp": webp, "blobs": {}, "ahead": None}
-        order = np.concatenate([reads[k] for k in GPU_KINDS]).tolist()
+        code = np.fromiter((_KIND_CODE.get(t[t.rfind("."):], 0) for t in tails), np.int8, stop - start)
+        reads = {k: start + np.nonzero(code == j + 1)[0] if k in enabled else np.zeros(0, np.int64) for j, k in enumerate(BASE_KINDS)}
+        reads.update(blobs={}, ahead=None)
+        order = np.concatenate([reads[k] for k in BASE_KINDS]).tolist()
         if not by_path:
             reads["blobs"] = {int(k): self.pool.submit(_read_bytes, self.paths[k]) for k in order}
         elif order and hasattr(self.stage, "read_ahead") and os.environ.get("KE_READ_AHEAD", "1") != "0":
-            ends = np.cumsum([len(reads[k]) for k in GPU_KINDS]).tolist()
+            ends = np.cumsum([len(reads[k]) for k in BASE_KINDS]).tolist()
             try:
                 # headers parsed ahead as well, where that takes work off the decode call: not WebP's -- its probe reads
                 # the container and the 10-byte frame tag only (the boolean-coded header is the decode call's own work)
                 reads["ahead"] = self.stage.read_ahead([self.paths[k] for k in order],
-                                                       tuple((k, e - len(reads[k]), e) for k, e in zip(GPU_KINDS, ends) if k != "webp"))
+                                                       tuple((k, e - len(reads[k]), e) for k, e in zip(BASE_KINDS, ends) if k != "webp"))
             except Exception:
                 reads["ahead"] = None                      # the decode call reads the files itself
         return reads
@@ -489,8 +471,9 @@ class _Pipeline:
         held = reads["ahead"]
         refused: list = []
         first = 0
+        offered = {k for k, _ in enabled_kinds("hash")}
         try:
-            for kind in GPU_KINDS:
+            for kind in BASE_KINDS:
                 positions = reads[kind]
                 if len(positions) == 0:
                     continue
@@ -517,8 +500,8 @@ class _Pipeline:
                 except (RuntimeError, ValueError, MemoryError):      # e.g. no room on the device for this batch: Pillow decodes it
                     refused.extend(positions.tolist())
                     continue
-                for follow_up, variable in FOLLOW_UPS.get(kind, ()):     # what the kind's decoder refused: the opt-in decoders
-                    if os.environ.get(variable, "0") == "1":
+                for follow_up in follow_ups(kind):                   # what the kind's decoder refused: the opt-in decoders
+                    if follow_up in offered:
                         p, d, st = self._offer_to(follow_up, held, lo, first, positions, None if by_path or held is not None else blobs, p, d, st)
                 good = np.asarray(st) == 0
                 at = positions[good] - start
@@ -533,7 +516,7 @@ class _Pipeline:
         return refused
 
     def _offer_to(self, follow_up: str, held, lo: int, hi: int, positions, blobs, p, d, st):
-        """The files of a kind still UNSUPPORTED after the decoders before it, offered to ``follow_up`` (FOLLOW_UPS) -- "webpl", the
+        """The files of a kind still UNSUPPORTED after the decoders before it, offered to ``follow_up`` (formats.follow_ups) -- "webpl", the
         lossless WebP decoder (``KE_GPU_WEBP_LOSSLESS=1``), "webpa", the one for lossy files with an alpha plane
         (``KE_GPU_WEBP_ALPHA=1``), or "tiffc", the one for LZW and PackBits TIFF files (``KE_GPU_TIFF_COMPRESSED=1``) --
         over the same files -- the read-ahead range with the files already taken masked, their paths, or their bytes --
@@ -729,12 +712,12 @@ class _Pipeline:
                 ph, dh = np.zeros(stop - start, np.int64), np.zeros(stop - start, np.int64)
                 ok = np.zeros(stop - start, bool)
                 taken = np.zeros(stop - start, bool)
-                for k in GPU_KINDS:
+                for k in BASE_KINDS:
                     taken[reads[k] - start] = True
                 skips = {}
                 if reads["ahead"] is not None:
-                    ends = np.cumsum([len(reads[k]) for k in GPU_KINDS]).tolist()
-                    for kind, e in zip(GPU_KINDS, ends):
+                    ends = np.cumsum([len(reads[k]) for k in BASE_KINDS]).tolist()
+                    for kind, e in zip(BASE_KINDS, ends):
                         if kind in ("png", "gif") and len(reads[kind]):
                             mask = self._png_for_pillow(reads["ahead"], e - len(reads[kind]), e, kind)
                             if mask is not None:

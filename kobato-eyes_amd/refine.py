@@ -16,6 +16,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
+from .formats import enabled_kinds
 from .image_io import MAX_SIDE, load_rgb
 
 _phash = importlib.import_module(".phash", __package__)   # the package also exports a function named phash
@@ -105,24 +106,9 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
     out: list = [None] * len(pairs)
     count = {"decodes": 0, "gpu_decodes": 0, "fit_launches": 0, "ssim_launches": 0, "pairs": len(pairs)}
 
-    gpu_kinds = {}
-    if os.environ.get("KE_GPU_REFINE_DECODE", "1") != "0":
-        if os.environ.get("KE_GPU_JPEG", "1") != "0":
-            gpu_kinds["jpeg"] = (".jpg", ".jpeg", ".jpe", ".jfif")
-        if os.environ.get("KE_GPU_PNG", "1") != "0":
-            gpu_kinds["png"] = (".png", ".apng")
-        if os.environ.get("KE_GPU_BMP", "1") != "0":
-            gpu_kinds["bmp"] = (".bmp",)
-        if os.environ.get("KE_GPU_TIFF", "1") != "0":
-            gpu_kinds["tiff"] = (".tif", ".tiff")
-            if os.environ.get("KE_GPU_TIFF_COMPRESSED", "0") == "1":    # after the unpacker: the LZW and PackBits files it left out
-                gpu_kinds["tiffc"] = (".tif", ".tiff")
-        if os.environ.get("KE_GPU_WEBP", "1") != "0":
-            gpu_kinds["webp"] = (".webp",)
-            if os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":      # after the lossy decoder: what that one did not place
-                gpu_kinds["webpl"] = (".webp",)
-            if os.environ.get("KE_GPU_WEBP_ALPHA", "0") == "1":         # lossy files with an alpha plane: RGBA, composited below
-                gpu_kinds["webpa"] = (".webp",)
+    # follow-ups come after their base: tiffc takes the LZW and PackBits files the unpacker left out, webpl what the lossy
+    # decoder did not place, webpa lossy files with an alpha plane (RGBA, composited below)
+    gpu_kinds = dict(enabled_kinds("refine"))
 
     def decode_on_gpu(need: list, placed: dict, buffers: list) -> None:
         """JPEG / PNG / BMP / TIFF / WebP files whose pixels the reference's loader would hand over exactly as Image.open yields them -- RGB, no

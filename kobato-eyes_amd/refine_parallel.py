@@ -21,6 +21,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import _native
+from .formats import enabled_kinds
 
 _phash = importlib.import_module(".phash", __package__)
 log = logging.getLogger("ui.dup_refine")
@@ -70,31 +71,20 @@ def _thumbnails(arrays: Sequence[np.ndarray], side: int, device: int) -> list:
     return out
 
 
-_GPU_SUFFIXES = {"jpeg": (".jpg", ".jpeg", ".jpe", ".jfif"), "png": (".png", ".apng"), "bmp": (".bmp",), "gif": (".gif",), "tiff": (".tif", ".tiff"),
-                 "webp": (".webp",)}
-
-
 def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) -> dict:
     """{path: side x side BILINEAR luma thumbnail} for the JPEG / PNG / BMP / GIF / TIFF / WebP files whose pixels ``_decode`` would return exactly as
     the GPU decoders do -- every kind they take, unless the file carries an EXIF orientation to apply (ke_*_caveats).  The
     files are read, decoded and shrunk without their pixels ever being in host memory; files left out (other formats,
     refused, damaged, turned) are for ``_decode``.  ``KE_GPU_REFINE_DECODE=0`` turns the route off."""
     out: dict = {}
-    if os.environ.get("KE_GPU_REFINE_DECODE", "1") == "0":
+    # after each suffix's own decoder the opt-in ones, for the files that one left out: tiffc (LZW and PackBits), webpl (lossless),
+    # webpa (lossy files with an alpha plane: convert("L") of RGBA ignores alpha)
+    kinds = enabled_kinds("refine_parallel")
+    if not kinds:
         return out
     ctx = _native.get_context(device)
     not_laid = np.uint64(0xFFFFFFFFFFFFFFFF)
-    kinds = list(_GPU_SUFFIXES.items())
-    if os.environ.get("KE_GPU_TIFF_COMPRESSED", "0") == "1":         # after the unpacker: the LZW and PackBits files that one left out
-        kinds.append(("tiffc", _GPU_SUFFIXES["tiff"]))
-    if os.environ.get("KE_GPU_WEBP_LOSSLESS", "0") == "1":           # after the lossy decoder: the files that one left out
-        kinds.append(("webpl", _GPU_SUFFIXES["webp"]))
-    if os.environ.get("KE_GPU_WEBP_ALPHA", "0") == "1":              # lossy files with an alpha plane: convert("L") of RGBA ignores alpha
-        kinds.append(("webpa", _GPU_SUFFIXES["webp"]))
     for kind, suffixes in kinds:
-        if os.environ.get({"jpeg": "KE_GPU_JPEG", "png": "KE_GPU_PNG", "bmp": "KE_GPU_BMP", "gif": "KE_GPU_GIF", "tiff": "KE_GPU_TIFF", "tiffc": "KE_GPU_TIFF",
-                        "webp": "KE_GPU_WEBP", "webpl": "KE_GPU_WEBP", "webpa": "KE_GPU_WEBP"}[kind], "1") == "0":
-            continue
         mine = [p for p in paths if str(p).lower().endswith(suffixes) and p not in out]
         at = 0
         while at < len(mine):

@@ -37,6 +37,39 @@ def test_library_exports_every_declared_symbol(K):
     assert lib.ke_abi_version() == 1
 
 
+def test_format_table_offers_each_seam_the_kinds_it_always_did(K, monkeypatch):
+    """formats.enabled_kinds against the literals the three seams used to carry (fastsig's *_SUFFIXES / GPU_KINDS / FOLLOW_UPS,
+    refine's ladder of KE_GPU_* variables, refine_parallel's _GPU_SUFFIXES and its kind -> variable dict), written out here:
+    the same kinds, in the same order, with the same suffix tuples, for nothing set, each off-switch alone, each opt-in alone,
+    and an opt-in whose base decoder is switched off.  refine never offers gif; refine_parallel runs the base kinds first."""
+    from kobato_eyes_amd.formats import enabled_kinds
+
+    suffixes = {"jpeg": (".jpg", ".jpeg", ".jpe", ".jfif"), "png": (".png", ".apng"), "bmp": (".bmp",), "gif": (".gif",),
+                "tiff": (".tif", ".tiff"), "tiffc": (".tif", ".tiff"), "webp": (".webp",), "webpl": (".webp",), "webpa": (".webp",)}
+    cases = [      # environment, hashing seam, refine, refine_parallel
+        ({}, "jpeg png bmp gif tiff webp", "jpeg png bmp tiff webp", "jpeg png bmp gif tiff webp"),
+        ({"KE_GPU_JPEG": "0"}, "png bmp gif tiff webp", "png bmp tiff webp", "png bmp gif tiff webp"),
+        ({"KE_GPU_PNG": "0"}, "jpeg bmp gif tiff webp", "jpeg bmp tiff webp", "jpeg bmp gif tiff webp"),
+        ({"KE_GPU_BMP": "0"}, "jpeg png gif tiff webp", "jpeg png tiff webp", "jpeg png gif tiff webp"),
+        ({"KE_GPU_GIF": "0"}, "jpeg png bmp tiff webp", "jpeg png bmp tiff webp", "jpeg png bmp tiff webp"),
+        ({"KE_GPU_TIFF": "0"}, "jpeg png bmp gif webp", "jpeg png bmp webp", "jpeg png bmp gif webp"),
+        ({"KE_GPU_WEBP": "0"}, "jpeg png bmp gif tiff", "jpeg png bmp tiff", "jpeg png bmp gif tiff"),
+        ({"KE_GPU_TIFF_COMPRESSED": "1"}, "jpeg png bmp gif tiff tiffc webp", "jpeg png bmp tiff tiffc webp", "jpeg png bmp gif tiff webp tiffc"),
+        ({"KE_GPU_WEBP_LOSSLESS": "1"}, "jpeg png bmp gif tiff webp webpl", "jpeg png bmp tiff webp webpl", "jpeg png bmp gif tiff webp webpl"),
+        ({"KE_GPU_WEBP_ALPHA": "1"}, "jpeg png bmp gif tiff webp webpa", "jpeg png bmp tiff webp webpa", "jpeg png bmp gif tiff webp webpa"),
+        ({"KE_GPU_TIFF": "0", "KE_GPU_TIFF_COMPRESSED": "1"}, "jpeg png bmp gif webp", "jpeg png bmp webp", "jpeg png bmp gif webp"),
+        ({"KE_GPU_REFINE_DECODE": "0"}, "jpeg png bmp gif tiff webp", "", ""),
+    ]
+    variables = sorted({v for env, *_ in cases for v in env})
+    for env, *expected in cases:
+        for v in variables:
+            monkeypatch.delenv(v, raising=False)
+        for v, value in env.items():
+            monkeypatch.setenv(v, value)
+        for seam, kinds in zip(("hash", "refine", "refine_parallel"), expected):
+            assert enabled_kinds(seam) == [(k, suffixes[k]) for k in kinds.split()], (env, seam)
+
+
 def test_host_side_file_batching_needs_no_gpu(K, tmp_path):
     """ke_host_read_files / ke_host_pack are plain host code (threads, read(2), memcpy): a batch of paths lands back to back
     in the caller's buffer, unreadable or empty files with size 0, and a buffer that is too small is reported, not overrun."""
