@@ -26,7 +26,8 @@ for n in [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "16384,65536").
         t = {}
         t0 = time.perf_counter()
         with ctx._lock:
-            flat, offsets, sizes = ctx._pack_blobs_pinned(blobs)
+            packed = ctx._packed(blobs)
+            flat, offsets, sizes = packed.flat, packed.offsets, packed.sizes
             t["pack"] = time.perf_counter() - t0; t1 = time.perf_counter()
             w, hh, c, st = (np.zeros(n, np.int32) for _ in range(4))
             lib.ke_jpeg_probe(_native._addr(flat), _native._addr(offsets), _native._addr(sizes), n, _native._addr(w), _native._addr(hh), _native._addr(c), _native._addr(st))

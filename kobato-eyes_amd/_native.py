@@ -184,30 +184,102 @@ def _leave_bombs_to_pillow(w, h, st, sizes) -> None:
         sizes[bombs] = 0
 
 
-def _lay_out16(nbytes):
-    """Byte offsets of items of ``nbytes`` (int64 array) laid back to back, each on a 16-byte boundary (see keyes.h), and the
-    bytes they take together."""
-    padded = (nbytes + 15) & ~np.int64(15)
-    offsets = np.zeros(len(nbytes), np.uint64)
-    offsets[1:] = np.cumsum(padded[:-1]).astype(np.uint64)
-    return offsets, int(padded.sum())
+NOT_LAID = np.uint64(0xFFFFFFFFFFFFFFFF)        # lay_out's offset of an item that has no place in the buffer
 
 
-class FilesAhead:
-    """The files of a batch in one of a context's read-ahead buffers (Context.read_files_ahead): file i is
-    ``flat[offsets[i]:offsets[i] + sizes[i]]`` (size 0 = unreadable).  ``release()`` hands the buffer back."""
+def lay_out(nbytes, keys=None, absent=None):
+    """Byte offsets of items of ``nbytes`` (int64 array) in one buffer, and the bytes they take together (see keyes.h).
+    Without ``keys`` the items lie in input order, each on a 16-byte boundary.  With ``keys`` (arrays as np.lexsort takes them:
+    the last one sorts first) they lie in that order, items of equal keys back to back without padding -- each such group can
+    go to the uniform-batch kernels as it is -- and a group starts on 16 bytes.  ``absent``: a mask of items that sort behind
+    all others; they and every item of no bytes get NOT_LAID."""
+    n = len(nbytes)
+    offsets = np.zeros(n, np.uint64)
+    if keys is None:
+        padded = (nbytes + 15) & ~np.int64(15)
+        offsets[1:] = np.cumsum(padded[:-1]).astype(np.uint64)
+        return offsets, int(padded.sum())
+    if n == 0:
+        return offsets, 0
+    order = np.lexsort(tuple(keys) if absent is None else tuple(keys) + (absent,))
+    size = nbytes[order].astype(np.int64)
+    cols = np.stack([np.asarray(k)[order] for k in keys], 1)
+    first = np.ones(n, bool)                                         # the items that begin a group
+    first[1:] = (cols[1:] != cols[:-1]).any(1)
+    group = np.cumsum(first) - 1
+    before = np.cumsum(size) - size                                  # bytes of the items laid before this one, unpadded
+    taken = np.add.reduceat(size, np.nonzero(first)[0])              # a group's bytes; its start: the padded groups before it
+    padded = (taken + 15) & ~np.int64(15)
+    start = np.cumsum(padded) - padded
+    offsets[order] = (start[group] + before - before[first][group]).astype(np.uint64)
+    if absent is not None:
+        offsets[nbytes == 0] = NOT_LAID
+    return offsets, int(start[-1] + taken[-1])
 
-    def __init__(self, ctx, slot: int, flat, offsets, sizes) -> None:
-        self._ctx, self._slot, self.flat, self.offsets, self.sizes = ctx, slot, flat, offsets, sizes
-        self.probed = {}                  # (kind, lo, hi) -> (widths, heights, channels, status) where the reader parsed headers too
+
+def runs_laid_out(offsets, keys):
+    """lay_out's groups back from its offsets: index arrays of the items laid out, one per run of equal ``keys``, in buffer order."""
+    laid = np.nonzero(offsets != NOT_LAID)[0]
+    laid = laid[np.argsort(offsets[laid], kind="stable")]
+    cols = np.stack([np.asarray(k)[laid] for k in keys], 1)
+    return np.split(laid, np.nonzero((cols[1:] != cols[:-1]).any(1))[0] + 1)
+
+
+def _pack_images(images):
+    """Host images of one channel count in one array, each on a 16-byte boundary: (flat, offsets, widths, heights, channels)."""
+    chans = {1 if im.ndim == 2 else im.shape[2] for im in images}
+    if len(chans) != 1:
+        raise ValueError("all images of one call must share the channel count")
+    ch = chans.pop()
+    widths = np.array([im.shape[1] for im in images], np.int32)
+    heights = np.array([im.shape[0] for im in images], np.int32)
+    sizes = widths.astype(np.int64) * heights * ch
+    offsets, total = lay_out(sizes)
+    flat = np.zeros(total, np.uint8)
+    for im, off, sz in zip(images, offsets, sizes):
+        flat[int(off):int(off) + int(sz)] = np.ascontiguousarray(im, dtype=np.uint8).reshape(-1)
+    return flat, offsets, widths, heights, ch
+
+
+class _Files:
+    """Files packed in host memory, as the probe and decode calls take them: file i is ``flat[offsets[i]:offsets[i] + sizes[i]]``
+    (size 0 = unreadable).  ``probed``: (kind, lo, hi) -> (widths, heights, channels, status) where the headers of files lo..hi
+    of the batch this one was cut from (``part``) have been parsed already.  Made from bytes (Context._packed), from paths
+    (Context._read_files_into) or as a part of a batch read ahead (FilesAhead)."""
+
+    def __init__(self, flat, offsets, sizes, probed=None, first: int = 0) -> None:
+        self.flat, self.offsets, self.sizes, self._first = flat, offsets, sizes, first
+        self.probed = {} if probed is None else probed
 
     def __len__(self) -> int:
         return len(self.sizes)
+
+    def part(self, lo: int, hi: int) -> "_Files":
+        """Files lo..hi, with sizes of their own (a decode call hides files by their size)."""
+        return _Files(self.flat, np.ascontiguousarray(self.offsets[lo:hi]), np.array(self.sizes[lo:hi], np.uint64), self.probed, self._first + lo)
+
+
+class FilesAhead(_Files):
+    """The files of a batch in one of a context's read-ahead buffers (Context.read_files_ahead).  ``release()`` hands the
+    buffer back."""
+
+    def __init__(self, ctx, slot: int, files: _Files) -> None:
+        super().__init__(files.flat, files.offsets, files.sizes)
+        self._ctx, self._slot = ctx, slot
 
     def release(self) -> None:
         if self._ctx is not None:
             self._ctx._ahead[self._slot][2] = False
             self._ctx, self.flat = None, None
+
+
+def _in_halves(run, lo: int, hi: int) -> list:
+    """[run(lo, hi)], or the same for the two halves of lo..hi -- and theirs -- where a call is _BatchTooLarge."""
+    try:
+        return [run(lo, hi)]
+    except _BatchTooLarge:
+        mid = lo + (hi - lo) // 2
+        return _in_halves(run, lo, mid) + _in_halves(run, mid, hi)
 
 
 class Context:
@@ -320,19 +392,7 @@ class Context:
         n = len(images)
         if n == 0:
             return np.empty(0, np.uint64), (np.empty(0, np.uint64) if want_dhash else None), np.empty(0, np.int32)
-        chans = {1 if im.ndim == 2 else im.shape[2] for im in images}
-        if len(chans) != 1:
-            raise ValueError("all images of one call must share the channel count")
-        ch = chans.pop()
-        widths = np.array([im.shape[1] for im in images], np.int32)
-        heights = np.array([im.shape[0] for im in images], np.int32)
-        sizes = widths.astype(np.int64) * heights * ch
-        padded = (sizes + 15) & ~np.int64(15)          # every image starts on a 16-byte boundary (see keyes.h)
-        offsets = np.zeros(n, np.uint64)
-        offsets[1:] = np.cumsum(padded[:-1]).astype(np.uint64)
-        flat = np.zeros(int(padded.sum()), np.uint8)
-        for im, off, sz in zip(images, offsets, sizes):
-            flat[int(off):int(off) + int(sz)] = np.ascontiguousarray(im, dtype=np.uint8).reshape(-1)
+        flat, offsets, widths, heights, ch = _pack_images(images)
         ph = np.empty(n, np.uint64)
         dh = np.empty(n, np.uint64) if want_dhash else None
         status = np.empty(n, np.int32)
@@ -420,14 +480,6 @@ class Context:
             cap = int(total.value)
 
     # -- file decode on the GPU (formats.FORMATS) ----------------------------------------------
-    @staticmethod
-    def _pack_blobs(blobs):
-        sizes = np.fromiter((len(b) for b in blobs), np.uint64, len(blobs))
-        offsets = np.zeros(len(blobs), np.uint64)
-        offsets[1:] = np.cumsum(sizes[:-1])
-        flat = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)     # one C-level copy; the decoder takes any alignment
-        return flat, offsets, sizes
-
     def _grow_host(self, buf: list, total: int) -> None:
         """A page-locked buffer ``[ptr, capacity, ...]`` made to hold ``total`` bytes (what it held is not kept)."""
         if total > buf[1]:
@@ -439,7 +491,28 @@ class Context:
             self._check(self._lib.ke_host_alloc(self._h, cap, C.byref(p)), "ke_host_alloc")
             buf[0], buf[1] = int(p.value), cap
 
-    def _read_files_into(self, buf: list, paths, bounded: bool = True):
+    def _packed(self, blobs, pinned: bool = True) -> _Files:
+        """Files given as bytes, back to back in the context's page-locked buffer (grown on demand, reused from call to call):
+        the copy to the device then runs at link speed.  Call with the lock held; the buffer is busy until the decode has
+        returned.  ``pinned=False``: in an array of their own instead (a probe alone copies nothing to the device)."""
+        n = len(blobs)
+        sizes = np.fromiter((len(b) for b in blobs), np.uint64, n)
+        offsets = np.zeros(n, np.uint64)
+        offsets[1:] = np.cumsum(sizes[:-1])
+        if not pinned:
+            return _Files(np.frombuffer(b"".join(blobs) + bytes(64), np.uint8), offsets, sizes)     # one C-level copy; any alignment will do
+        total = int(sizes.sum()) + 64
+        if total > self.pack_limit and n > 1:
+            raise _BatchTooLarge
+        self._grow_host(self._pack, total)
+        base = self._pack[0]
+        srcs = (C.c_char_p * n)(*blobs)                    # the buffers of the bytes objects themselves, no copies
+        if self._lib.ke_host_pack(base, srcs, _addr(offsets), _addr(sizes), n) != KE_OK:
+            raise ValueError("ke_host_pack: bad arguments")
+        C.memset(base + total - 64, 0, 64)
+        return _Files(np.ctypeslib.as_array((C.c_uint8 * total).from_address(base)), offsets, sizes)
+
+    def _read_files_into(self, buf: list, paths, bounded: bool = True) -> _Files:
         """The files themselves, read by the library's host threads straight into the page-locked buffer ``buf`` (no bytes
         objects, no interpreter loop over the files), which is grown when the batch needs it; unreadable files get size 0.
         ``bounded``: a batch of more than ``pack_limit`` bytes is _BatchTooLarge.  Nothing but ``buf`` is touched: call with the
@@ -460,8 +533,7 @@ class Context:
             rc = read()
         if rc != KE_OK:
             raise ValueError("ke_host_read_files: bad arguments")
-        flat = np.ctypeslib.as_array((C.c_uint8 * int(needed.value)).from_address(buf[0]))
-        return flat, offsets, sizes
+        return _Files(np.ctypeslib.as_array((C.c_uint8 * int(needed.value)).from_address(buf[0])), offsets, sizes)
 
     def read_files_ahead(self, paths, spans=()):
         """Read files into one of the context's two page-locked read-ahead buffers -- from any thread, while another call of the
@@ -470,8 +542,7 @@ class Context:
         are taken or the files exceed ``pack_limit`` (the caller then lets the decode call read them itself).  ``spans`` =
         [(kind, lo, hi)]: the headers of files lo..hi are parsed here as well (``ke_<kind>_probe``), off the decoding thread."""
         paths = list(paths)
-        n = len(paths)
-        if n == 0:
+        if not paths:
             return None
         with self._ahead_lock:
             slot = next((k for k, buf in enumerate(self._ahead) if not buf[2]), None)
@@ -480,142 +551,99 @@ class Context:
             self._ahead[slot][2] = True
         buf = self._ahead[slot]
         try:
-            flat, offsets, sizes = self._read_files_into(buf, paths)
+            held = FilesAhead(self, slot, self._read_files_into(buf, paths))
         except _BatchTooLarge:
             buf[2] = False
             return None
         except BaseException:
             buf[2] = False
             raise
-        held = FilesAhead(self, slot, flat, offsets, sizes)
         for kind, lo, hi in spans:
             if hi > lo:
-                w, h, c, st = (np.zeros(hi - lo, np.int32) for _ in range(4))
-                o, z = np.ascontiguousarray(offsets[lo:hi]), np.ascontiguousarray(sizes[lo:hi])
-                if getattr(self._lib, f"ke_{kind}_probe")(_addr(flat), _addr(o), _addr(z), hi - lo, _addr(w), _addr(h), _addr(c), _addr(st)) == KE_OK:
-                    held.probed[(kind, lo, hi)] = (w, h, c, st)
+                try:
+                    held.probed[(kind, lo, hi)] = self._probe(held.part(lo, hi), kind)
+                except ValueError:
+                    pass                                   # the decode call will say so
         return held
 
-    def _pack_blobs_pinned(self, blobs):
-        """The files back to back in the context's page-locked buffer (grown on demand, reused from call to call): the copy
-        to the device then runs at link speed.  Call with the lock held; the buffer is busy until the decode has returned."""
-        sizes = np.fromiter((len(b) for b in blobs), np.uint64, len(blobs))
-        offsets = np.zeros(len(blobs), np.uint64)
-        offsets[1:] = np.cumsum(sizes[:-1])
-        total = int(sizes.sum()) + 64
-        if total > self.pack_limit and len(blobs) > 1:
-            raise _BatchTooLarge
-        self._grow_host(self._pack, total)
-        base = self._pack[0]
-        flat = np.ctypeslib.as_array((C.c_uint8 * total).from_address(base))
-        n = len(blobs)
-        srcs = (C.c_char_p * n)(*blobs)                    # the buffers of the bytes objects themselves, no copies
-        if self._lib.ke_host_pack(base, srcs, _addr(offsets), _addr(sizes), n) != KE_OK:
-            raise ValueError("ke_host_pack: bad arguments")
-        C.memset(base + total - 64, 0, 64)
-        return flat, offsets, sizes
+    def _probe(self, files: _Files, kind: str):
+        """(widths, heights, channels, status) of packed files: ``ke_<kind>_probe`` (host code), or what the reader of a batch
+        read ahead has parsed already."""
+        n = len(files)
+        known = files.probed.get((kind, files._first, files._first + n))
+        if known is not None:
+            return tuple(a.copy() for a in known)
+        w, h, c, st = (np.zeros(n, np.int32) for _ in range(4))
+        if getattr(self._lib, f"ke_{kind}_probe")(_addr(files.flat), _addr(files.offsets), _addr(files.sizes), n,
+                                                  _addr(w), _addr(h), _addr(c), _addr(st)) != KE_OK:
+            raise ValueError(f"ke_{kind}_probe: bad arguments")
+        return w, h, c, st
 
     def probe(self, blobs, kind: str):
         """(widths, heights, channels, status) of files of a ``kind`` of formats.FORMATS given as bytes; status 0 = the GPU
         decoder takes the file."""
-        flat, offsets, sizes = self._pack_blobs(blobs)
-        n = len(blobs)
-        w, h, c, st = (np.zeros(n, np.int32) for _ in range(4))
-        rc = getattr(self._lib, f"ke_{kind}_probe")(_addr(flat), _addr(offsets), _addr(sizes), n, _addr(w), _addr(h), _addr(c), _addr(st))
-        if rc != KE_OK:
-            raise ValueError(f"ke_{kind}_probe: bad arguments")
-        return w, h, c, st
+        return self._probe(self._packed(blobs, pinned=False), kind)
 
-    def _to_device(self, blobs, kind: str, *, paths=None, ahead=None, skip=None):
-        """Decode what the GPU decoder takes into the context's decode buffer (device memory, grown on demand and kept:
-        allocating tens of GB per call costs up to a second): (device ptr or 0, byte offsets, widths, heights, channels,
-        status).  Call with the lock held and keep it until the pixels have been used."""
-        n = ahead[2] - ahead[1] if ahead is not None else len(blobs) if paths is None else len(paths)
-        w, h, c, st = (np.zeros(n, np.int32) for _ in range(4))
+    def _decode_packed(self, files: _Files, kind: str, *, skip=None, owned: bool = False, by_shape: bool = False):
+        """The one decode chain: probe -> bombs left to Pillow -> ``skip`` -> layout -> ``ke_<kind>_decode``, for what the GPU
+        decoder takes of ``files``: (device ptr or 0, byte offsets, widths, heights, channels, status, caveat flags or None).
+        The pixels go to the context's decode buffer (device memory, grown on demand and kept: allocating tens of GB per call
+        costs up to a second) -- call with the lock held and keep it until they have been used; a batch of more than
+        ``decode_limit`` bytes of them is _BatchTooLarge -- or, ``owned``, to an allocation the caller frees, laid out
+        ``by_shape`` if asked (lay_out's groups of one (width, height, channels)), with the files' ``ke_<kind>_caveats``."""
+        n = len(files)
         with self._lock:
-            if ahead is not None:                        # files lo..hi of a batch some thread has read already
-                held, lo, hi = ahead
-                flat, offsets, sizes = held.flat, np.ascontiguousarray(held.offsets[lo:hi]), np.array(held.sizes[lo:hi], np.uint64)
-            else:
-                flat, offsets, sizes = self._pack_blobs_pinned(blobs) if paths is None else self._read_files_into(self._pack, paths)
-            known = ahead[0].probed.get((kind, ahead[1], ahead[2])) if ahead is not None else None
-            if known is not None:
-                w, h, c, st = (a.copy() for a in known)
-            else:
-                rc = getattr(self._lib, f"ke_{kind}_probe")(_addr(flat), _addr(offsets), _addr(sizes), n, _addr(w), _addr(h), _addr(c), _addr(st))
-                if rc != KE_OK:
-                    raise ValueError(f"ke_{kind}_probe: bad arguments")
-            _leave_bombs_to_pillow(w, h, st, sizes)
+            w, h, c, st = self._probe(files, kind)
+            flags = np.zeros(n, np.int32) if owned else None
+            if owned and getattr(self._lib, f"ke_{kind}_caveats")(_addr(files.flat), _addr(files.offsets), _addr(files.sizes), n, _addr(flags)) != KE_OK:
+                raise ValueError(f"ke_{kind}_caveats: bad arguments")
+            _leave_bombs_to_pillow(w, h, st, files.sizes)
             if skip is not None:                         # files the caller keeps for another decoder: as if refused
                 skip = np.asarray(skip, bool)
                 st[skip & (st == 0)] = 1
-                sizes[skip] = 0
-            out_off, total = _lay_out16(np.where(st == 0, w.astype(np.int64) * h * c, 0))
+                files.sizes[skip] = 0
+                left_alone = st[skip]
+            nbytes = np.where(st == 0, w.astype(np.int64) * h * c, 0)
+            out_off, total = lay_out(nbytes, (w, h, c), st != 0) if by_shape else lay_out(nbytes)     # decodable files first
             if total == 0:
-                return 0, out_off, w, h, c, st
-            if total > self.decode_limit and n > 1:
-                raise _BatchTooLarge
-            if total + 64 > self._decoded_cap:
-                if self._decoded_ptr:
-                    self.free(self._decoded_ptr)
-                    self._decoded_ptr, self._decoded_cap = 0, 0
-                cap = total + total // 8 + 64
-                self._decoded_ptr, self._decoded_cap = self.malloc(cap), cap
-            dev = self._decoded_ptr
-            self._check(getattr(self._lib, f"ke_{kind}_decode")(self._h, _addr(flat), _addr(offsets), _addr(sizes), n, dev,
-                                                                _addr(out_off), _addr(st)), f"ke_{kind}_decode")
-            self.decode_kernel_ms += self.last_kernel_ms(4)
-        return dev, out_off, w, h, c, st
+                return 0, out_off, w, h, c, st, flags
+            if owned:
+                dev = self.malloc(total + 64)
+            else:
+                if total > self.decode_limit and n > 1:
+                    raise _BatchTooLarge
+                if total + 64 > self._decoded_cap:
+                    if self._decoded_ptr:
+                        self.free(self._decoded_ptr)
+                        self._decoded_ptr, self._decoded_cap = 0, 0
+                    cap = total + total // 8 + 64
+                    self._decoded_ptr, self._decoded_cap = self.malloc(cap), cap
+                dev = self._decoded_ptr
+            try:
+                self._check(getattr(self._lib, f"ke_{kind}_decode")(self._h, _addr(files.flat), _addr(files.offsets), _addr(files.sizes), n,
+                                                                    dev, _addr(out_off), _addr(st)), f"ke_{kind}_decode")
+            except Exception:
+                if owned:
+                    self.free(dev)
+                raise
+            if skip is not None:                         # the decoder's word on a hidden file is its word on an empty one
+                st[skip] = left_alone
+            if not owned:
+                self.decode_kernel_ms += self.last_kernel_ms(4)
+        return dev, out_off, w, h, c, st, flags
 
     def decode_files_owned(self, paths, kind: str = "jpeg", *, by_shape: bool = False):
         """Files on disk decoded into a device buffer of their own (the caller frees it with ``free``): (device ptr or 0, byte
         offsets, widths, heights, channels, status, caveat flags).  ``flags`` are ke_jpeg_caveats / ke_png_caveats' bits: what
         the reference's defensive loader would do to the file beyond Image.open (EXIF orientation, transparency).
         ``by_shape``: images of one (width, height, channels) lie back to back without padding, so that each such group
-        can go to the uniform-batch kernels as it is (np.unique over (w, h, c) of the decodable files gives the groups)."""
+        can go to the uniform-batch kernels as it is (runs_laid_out gives the groups back); files not decoded get NOT_LAID."""
         paths = list(paths)
-        n = len(paths)
-        w, h, c, st, flags = (np.zeros(n, np.int32) for _ in range(5))
-        out_off = np.zeros(n, np.uint64)
-        if n == 0:
-            return 0, out_off, w, h, c, st, flags
+        if not paths:
+            return (0, np.zeros(0, np.uint64)) + tuple(np.zeros(0, np.int32) for _ in range(5))
         with self._lock:
-            flat, offsets, sizes = self._read_files_into(self._pack, paths, bounded=False)     # the caller paces its batches
-            probe = getattr(self._lib, f"ke_{kind}_probe")
-            if probe(_addr(flat), _addr(offsets), _addr(sizes), n, _addr(w), _addr(h), _addr(c), _addr(st)) != KE_OK:
-                raise ValueError(f"ke_{kind}_probe: bad arguments")
-            if getattr(self._lib, f"ke_{kind}_caveats")(_addr(flat), _addr(offsets), _addr(sizes), n, _addr(flags)) != KE_OK:
-                raise ValueError(f"ke_{kind}_caveats: bad arguments")
-            _leave_bombs_to_pillow(w, h, st, sizes)
-            nbytes = np.where(st == 0, w.astype(np.int64) * h * c, 0)
-            if by_shape:
-                order = np.lexsort((w, h, c, st != 0))              # decodable files first, grouped by shape
-                sorted_bytes = nbytes[order]
-                key = np.stack([w[order], h[order], c[order]], 1)
-                new_group = np.ones(n, bool)
-                new_group[1:] = (key[1:] != key[:-1]).any(1)
-                starts = np.zeros(n, np.int64)
-                at = 0
-                for k in range(n):                                  # groups start on 16 bytes, images inside follow tightly
-                    if new_group[k]:
-                        at = (at + 15) & ~15
-                    starts[k] = at
-                    at += int(sorted_bytes[k])
-                out_off[order] = starts.astype(np.uint64)
-                out_off[nbytes == 0] = np.uint64(0xFFFFFFFFFFFFFFFF)   # not laid out (refused by the probe)
-                total = at
-            else:
-                out_off, total = _lay_out16(nbytes)
-            if total == 0:
-                return 0, out_off, w, h, c, st, flags
-            dev = self.malloc(total + 64)
-            try:
-                self._check(getattr(self._lib, f"ke_{kind}_decode")(self._h, _addr(flat), _addr(offsets), _addr(sizes), n, dev,
-                                                                    _addr(out_off), _addr(st)), f"ke_{kind}_decode")
-            except Exception:
-                self.free(dev)
-                raise
-        return dev, out_off, w, h, c, st, flags
+            files = self._read_files_into(self._pack, paths, bounded=False)     # the caller paces its batches
+            return self._decode_packed(files, kind, owned=True, by_shape=by_shape)
 
     def normalise_rgb(self, src: int, src_offsets, widths, heights, channels, orientations, *, by_shape: bool = False):
         """Images on the device (decoded files) -> a device buffer of their own (the caller frees it) holding them as the
@@ -630,19 +658,7 @@ class Context:
         turned = o >= 5
         ow, oh = np.where(turned, h, w).astype(np.int32), np.where(turned, w, h).astype(np.int32)
         nbytes = ow.astype(np.int64) * oh * 3
-        do = np.zeros(n, np.uint64)
-        if by_shape:
-            order = np.lexsort((oh, ow))
-            at, prev = 0, None
-            for k in order.tolist():
-                shape = (int(ow[k]), int(oh[k]))
-                if shape != prev:
-                    at, prev = (at + 15) & ~15, shape
-                do[k] = at
-                at += int(nbytes[k])
-            total = at
-        else:
-            do, total = _lay_out16(nbytes)
+        do, total = lay_out(nbytes, (oh, ow)) if by_shape else lay_out(nbytes)
         dev = self.malloc(total + 64)
         try:
             with self._lock:
@@ -695,21 +711,17 @@ class Context:
     def decode(self, blobs, kind: str):
         """Pixels of files of a ``kind`` of formats.FORMATS decoded on the GPU: list of ndarrays (HxW or HxWxC, see the kind's
         row) with None where the decoder refused the file (status != 0); also returns the statuses."""
-        out = [None] * len(blobs)
-        with self._lock:
-            try:
-                dev, out_off, w, h, c, st = self._to_device(blobs, kind)
-            except _BatchTooLarge:
-                half = len(blobs) // 2
-                a, sa = self.decode(blobs[:half], kind)
-                b, sb = self.decode(blobs[half:], kind)
-                return a + b, np.concatenate([sa, sb])
-            for i in range(len(blobs)):
-                if st[i] == 0:
-                    arr = np.empty((h[i], w[i], c[i]) if c[i] > 1 else (h[i], w[i]), np.uint8)
-                    self.memcpy(arr, dev + int(out_off[i]), arr.nbytes)
-                    out[i] = arr
-        return out, st
+        def run(lo: int, hi: int):
+            out = [None] * (hi - lo)
+            dev, out_off, w, h, c, st, _ = self._decode_packed(self._packed(blobs[lo:hi]), kind)
+            for i in np.nonzero(st == 0)[0].tolist():
+                out[i] = np.empty((h[i], w[i], c[i]) if c[i] > 1 else (h[i], w[i]), np.uint8)
+                self.memcpy(out[i], dev + int(out_off[i]), out[i].nbytes)
+            return out, st
+
+        with self._lock:                                 # the decode buffer is this call's until the pixels are out
+            parts = _in_halves(run, 0, len(blobs))
+        return [a for p in parts for a in p[0]], np.concatenate([p[1] for p in parts])
 
     def hash_files(self, paths, *, want_dhash=True, kind: str = "jpeg"):
         """``hash`` for files on disk: read (host threads, page-locked buffer), decoded and hashed on the GPU."""
@@ -719,24 +731,24 @@ class Context:
         """pHash / dHash of files of a ``kind`` of formats.FORMATS, decoded and hashed without the pixels leaving the GPU.
         Returns (phash u64[n], dhash u64[n] | None, status int32[n]); status != 0 = not handled here (decode the file with
         Pillow).  The files come as bytes (``blobs``), as ``paths`` the library reads, or as ``ahead = (FilesAhead, lo, hi)``:
-        files lo..hi of a batch read beforehand."""
-        n = ahead[2] - ahead[1] if ahead is not None else len(blobs) if paths is None else len(paths)
-        ph = np.zeros(n, np.uint64)
-        dh = np.zeros(n, np.uint64) if want_dhash else None
+        files lo..hi of a batch read beforehand.  ``skip``: a mask of files to leave alone (status 1)."""
+        if ahead is not None:                            # where the files come from is settled here, once
+            n = ahead[2] - ahead[1]
+            take = lambda lo, hi: ahead[0].part(ahead[1] + lo, ahead[1] + hi)
+        elif paths is not None:
+            n = len(paths)
+            take = lambda lo, hi: self._read_files_into(self._pack, paths[lo:hi])
+        else:
+            n = len(blobs)
+            take = lambda lo, hi: self._packed(blobs[lo:hi])
         if n == 0:
-            return ph, dh, np.zeros(0, np.int32)
-        with self._lock:
-            try:
-                dev, out_off, w, h, c, st = self._to_device(blobs, kind, paths=paths, ahead=ahead, skip=skip)
-            except _BatchTooLarge:
-                half = n // 2
-                parts = [self.hash(None if blobs is None else blobs[lo:hi], want_dhash=want_dhash, kind=kind,
-                                        paths=None if paths is None else paths[lo:hi],
-                                        ahead=None if ahead is None else (ahead[0], ahead[1] + lo, ahead[1] + hi),
-                                        skip=None if skip is None else np.asarray(skip, bool)[lo:hi])
-                         for lo, hi in ((0, half), (half, n))]
-                return (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]) if want_dhash else None,
-                        np.concatenate([p[2] for p in parts]))
+            return np.zeros(0, np.uint64), (np.zeros(0, np.uint64) if want_dhash else None), np.zeros(0, np.int32)
+        skip = None if skip is None else np.asarray(skip, bool)
+
+        def run(lo: int, hi: int):
+            ph = np.zeros(hi - lo, np.uint64)
+            dh = np.zeros(hi - lo, np.uint64) if want_dhash else None
+            dev, out_off, w, h, c, st, _ = self._decode_packed(take(lo, hi), kind, skip=None if skip is None else skip[lo:hi])
             for ch in (1, 3, 4):
                 idx = np.nonzero((st == 0) & (c == ch))[0]
                 if len(idx) == 0:
@@ -746,14 +758,18 @@ class Context:
                 status = np.zeros(len(idx), np.int32)
                 offs = np.ascontiguousarray(out_off[idx])
                 ws, hs = np.ascontiguousarray(w[idx]), np.ascontiguousarray(h[idx])
-                with self._lock:
-                    self._check(self._lib.ke_hash_images(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p), _addr(d),
-                                                         _addr(status)), "ke_hash_images")
+                self._check(self._lib.ke_hash_images(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p), _addr(d),
+                                                     _addr(status)), "ke_hash_images")
                 ph[idx] = p
                 if want_dhash:
                     dh[idx] = d
                 st[idx[status != 0]] = 2
-        return ph, dh, st
+            return ph, dh, st
+
+        with self._lock:                                 # the decode buffer is this call's until the pixels are hashed
+            parts = _in_halves(run, 0, n)
+        return (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]) if want_dhash else None,
+                np.concatenate([p[2] for p in parts]))
 
     # -- scan -------------------------------------------------------------------------------
     def hamming_scan(self, hashes, n: int, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4,
@@ -789,12 +805,7 @@ class Context:
         return int(out[0])
 
     def cluster_labels(self, edges: np.ndarray, n_nodes: int) -> np.ndarray:
-        edges = np.ascontiguousarray(edges, dtype=EDGE_DTYPE)
-        labels = np.empty(n_nodes, np.int64)
-        rc = self._lib.ke_cluster_labels(_addr(edges), len(edges), n_nodes, _addr(labels))
-        if rc != KE_OK:
-            raise ValueError("ke_cluster_labels: edge endpoint outside [0, n_nodes)")
-        return labels
+        return cluster_labels(edges, n_nodes)
 
     # -- ssim -------------------------------------------------------------------------------
     def ssim_set_mode(self, exact: bool) -> None:
@@ -817,19 +828,7 @@ class Context:
         """src/dup/refine.py:44-52 for pairs of images of any sizes (one channel count): common size, ImageOps.fit + BICUBIC
         of both, SSIM.  Returns (float64 scores, NaN where the status is not 0; int32 statuses KE_PAIR_*)."""
         n = len(images)
-        chans = {1 if im.ndim == 2 else im.shape[2] for im in images}
-        if len(chans) != 1:
-            raise ValueError("all images of one call must share the channel count")
-        ch = chans.pop()
-        widths = np.array([im.shape[1] for im in images], np.int32)
-        heights = np.array([im.shape[0] for im in images], np.int32)
-        sizes = widths.astype(np.int64) * heights * ch
-        padded = (sizes + 15) & ~np.int64(15)
-        offsets = np.zeros(n, np.uint64)
-        offsets[1:] = np.cumsum(padded[:-1]).astype(np.uint64)
-        flat = np.zeros(int(padded.sum()), np.uint8)
-        for im, off, sz in zip(images, offsets, sizes):
-            flat[int(off):int(off) + int(sz)] = np.ascontiguousarray(im, dtype=np.uint8).reshape(-1)
+        flat, offsets, widths, heights, ch = _pack_images(images)
         pa = np.ascontiguousarray(pair_a, dtype=np.int64)
         pb = np.ascontiguousarray(pair_b, dtype=np.int64)
         out = np.empty(len(pa), np.float64)

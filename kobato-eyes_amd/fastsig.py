@@ -334,17 +334,18 @@ _make_stage = _GpuStage
 
 
 class _Pipeline:
-    """decode (threads) -> pinned staging buffer -> H2D + hash (GPU), without a host-side copy in between; JPEG and PNG files
-    decoded on the GPU instead.
+    """decode (threads) -> pinned staging buffer -> H2D + hash (GPU), without a host-side copy in between; files of the base
+    kinds of ``formats.FORMATS`` decoded on the GPU instead.
 
     Files are taken ``KE_GPU_BATCH`` (default 32768) at a time (a batch whose compressed bytes exceed ``KE_PACK_LIMIT_BYTES`` or
     whose pixels exceed ``KE_DECODE_LIMIT_BYTES`` is halved by the context until it fits).  Within such a batch:
 
-    * JPEG and PNG files (by suffix) skip Pillow altogether: the library's host threads read the next batch's files into one
-      of the context's two page-locked read-ahead buffers (``Context.read_files_ahead``; ``KE_READ_AHEAD=0``: inside the decode
-      call instead) while this one is on the GPU, and ONE ``ke_jpeg_decode`` / ``ke_png_decode`` call per kind decodes them all,
-      pixel-identical to ``Image.open`` for the files the decoders take; the hash kernels run on the decoded pixels where they lie.  The batch is large because those decoders are one thread per image: a wave of 64 files takes as long as
-      thousands of waves side by side.  ``KE_GPU_JPEG=0`` / ``KE_GPU_PNG=0`` turn the routes off.
+    * files of the base kinds of ``formats.FORMATS`` (by suffix) skip Pillow altogether: the library's host threads read the next
+      batch's files into one of the context's two page-locked read-ahead buffers (``Context.read_files_ahead``;
+      ``KE_READ_AHEAD=0``: inside the decode call instead) while this one is on the GPU, and ONE ``ke_<kind>_decode`` call per kind
+      decodes them all, pixel-identical to ``Image.open`` for the files the decoders take; the hash kernels run on the decoded
+      pixels where they lie.  The batch is large because those decoders are one thread per image: a wave of 64 files takes as
+      long as thousands of waves side by side.  A kind's off-switch (``KE_GPU_JPEG=0`` ...) turns its route off.
     * every other file, and what the GPU decoders refuse (progressive, CMYK, palette, 16-bit, damaged ...), is decoded by
       Pillow on the thread pool ``chunk`` files at a time: the threads of chunk k write their pixels straight into one of the
       context's two page-locked staging buffers (``ke_stage_acquire``; a bump allocator hands out 16-byte aligned regions);
@@ -400,27 +401,29 @@ class _Pipeline:
 
     # ---- the GPU decoders' share of a batch
     def _start_reads(self, start: int) -> dict:
-        """The JPEG / PNG / BMP / GIF / TIFF / WebP files of the batch that begins at ``start``, on their way into memory while the batch before is
-        on the GPU.  Runs on a pool thread (the classification is a pass of the interpreter over the batch, the reading is the
-        library's): {"jpeg" / "png" / "bmp" / "gif" / "tiff" / "webp": positions (arrays, ascending), "blobs": position -> future of the file's bytes for
-        a stage without ``hash_files``, "ahead": the context's FilesAhead holding [JPEG | PNG | BMP | GIF | TIFF | WebP files] or None}."""
+        """The files of the batch that begins at ``start`` whose suffix is a base kind's of ``formats.FORMATS``, on their way into
+        memory while the batch before is on the GPU.  Runs on a pool thread (the classification is a pass of the interpreter
+        over the batch, the reading is the library's): {kind: positions (ascending) for every base kind, "spans": {kind: (lo,
+        hi)}, where the kind's files lie in the read-ahead buffer -- kind after kind --, "blobs": position -> future of the
+        file's bytes for a stage without ``hash_files``, "ahead": the context's FilesAhead holding them, or None}."""
         enabled = {k for k, _ in enabled_kinds("hash")}
         by_path = hasattr(self.stage, "hash_files")          # the library reads the files itself, into page-locked memory
         stop = min(start + self.batch, len(self.tasks))
         tails = [p[-5:].lower() for p in self.paths[start:stop]]
         code = np.fromiter((_KIND_CODE.get(t[t.rfind("."):], 0) for t in tails), np.int8, stop - start)
         reads = {k: start + np.nonzero(code == j + 1)[0] if k in enabled else np.zeros(0, np.int64) for j, k in enumerate(BASE_KINDS)}
-        reads.update(blobs={}, ahead=None)
+        ends = np.cumsum([len(reads[k]) for k in BASE_KINDS]).tolist()
+        spans = {k: (e - len(reads[k]), e) for k, e in zip(BASE_KINDS, ends)}
+        reads.update(blobs={}, ahead=None, spans=spans)
         order = np.concatenate([reads[k] for k in BASE_KINDS]).tolist()
         if not by_path:
             reads["blobs"] = {int(k): self.pool.submit(_read_bytes, self.paths[k]) for k in order}
         elif order and hasattr(self.stage, "read_ahead") and os.environ.get("KE_READ_AHEAD", "1") != "0":
-            ends = np.cumsum([len(reads[k]) for k in BASE_KINDS]).tolist()
             try:
                 # headers parsed ahead as well, where that takes work off the decode call: not WebP's -- its probe reads
                 # the container and the 10-byte frame tag only (the boolean-coded header is the decode call's own work)
                 reads["ahead"] = self.stage.read_ahead([self.paths[k] for k in order],
-                                                       tuple((k, e - len(reads[k]), e) for k, e in zip(BASE_KINDS, ends) if k != "webp"))
+                                                       tuple((k, *spans[k]) for k in BASE_KINDS if k != "webp"))
             except Exception:
                 reads["ahead"] = None                      # the decode call reads the files itself
         return reads
@@ -462,84 +465,76 @@ class _Pipeline:
         mask[order[:k]] = True
         return mask
 
+    def _hash_kind(self, kind: str, source, which=None):
+        """(phash, dhash, status) of a base kind's files from the stage's decoder of ``kind``.  ``source``: where the files are,
+        settled once per base kind -- ("ahead", (held, lo, hi)), a span of the read-ahead buffer, ("paths", [...]) or ("blobs",
+        [...]).  ``which``: a mask of the files to leave alone -- the ``skip`` of a span, left out of a list --, which come
+        back with status 1 as if refused."""
+        route, files = source
+        keep = slice(None) if which is None else ~which
+        if route == "ahead":                               # ``skip`` only where there is a mask
+            got = self.stage.hash_ahead(*files, kind) if which is None else self.stage.hash_ahead(*files, kind, skip=which)
+            got = [np.asarray(a)[keep] for a in got]
+        else:
+            some = files if which is None else [f for f, alone in zip(files, which.tolist()) if not alone]
+            got = (self.stage.hash_files if route == "paths" else self.stage.jpeg_hash)(some, kind)
+        n = len(got[2]) if which is None else len(which)
+        p, d, st = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.ones(n, np.int32)
+        p[keep], d[keep], st[keep] = got
+        return p, d, st
+
     def _decode_on_gpu(self, reads: dict, start: int, ph: np.ndarray, dh: np.ndarray, ok: np.ndarray, skips=None) -> list:
         """Fills ph / dh / ok (indexed by position - start) for the files the GPU decoders take; returns the positions they
         left to Pillow (``skips``: {kind: mask} of the PNG / GIF files the caller has given to the decoder processes already --
-        not decoded here, not returned)."""
+        not decoded here, not returned).  Every base kind's files go to its own decoder, then what that one left UNSUPPORTED
+        (status 1) to each of its enabled follow-ups (formats.follow_ups: the opt-in decoders) in turn, before Pillow."""
         skips = skips or {}
         by_path = hasattr(self.stage, "hash_files")
         held = reads["ahead"]
         refused: list = []
-        first = 0
         offered = {k for k, _ in enabled_kinds("hash")}
         try:
             for kind in BASE_KINDS:
                 positions = reads[kind]
-                if len(positions) == 0:
+                if len(positions) == 0 or self.cancelled():
                     continue
-                lo, first = first, first + len(positions)
-                if self.cancelled():
-                    continue
-                if not by_path:                            # a stage that takes bytes: files that cannot be read stay with Pillow
+                skip = skips.get(kind)
+                if held is not None:
+                    if skip is not None and skip.all():
+                        continue
+                    source = ("ahead", (held, *reads["spans"][kind]))
+                elif by_path:
+                    source = ("paths", [self.paths[k] for k in positions.tolist()])
+                else:                                      # a stage that takes bytes: files that cannot be read stay with Pillow
                     got = [(k, reads["blobs"][k].result()) for k in positions.tolist()]
                     positions = np.array([k for k, b in got if b is not None], np.int64)
-                    blobs = [b for _, b in got if b is not None]
-                    if not blobs:
+                    source = ("blobs", [b for _, b in got if b is not None])
+                    if not source[1]:
                         continue
                 try:
-                    if held is not None:                   # this kind's files are lo .. first of the buffer
-                        skip = skips.get(kind)
-                        if skip is not None and skip.all():
-                            continue
-                        p, d, st = self.stage.hash_ahead(held, lo, first, kind) if skip is None else \
-                            self.stage.hash_ahead(held, lo, first, kind, skip=skip)
-                    elif by_path:
-                        p, d, st = self.stage.hash_files([self.paths[k] for k in positions.tolist()], kind)
-                    else:
-                        p, d, st = self.stage.jpeg_hash(blobs, kind)
+                    p, d, st = self._hash_kind(kind, source, skip if held is not None else None)
                 except (RuntimeError, ValueError, MemoryError):      # e.g. no room on the device for this batch: Pillow decodes it
                     refused.extend(positions.tolist())
                     continue
-                for follow_up in follow_ups(kind):                   # what the kind's decoder refused: the opt-in decoders
-                    if follow_up in offered:
-                        p, d, st = self._offer_to(follow_up, held, lo, first, positions, None if by_path or held is not None else blobs, p, d, st)
-                good = np.asarray(st) == 0
+                for follow_up in follow_ups(kind):
+                    if follow_up in offered and (st == 1).any():
+                        try:
+                            p2, d2, st2 = self._hash_kind(follow_up, source, st != 1)
+                        except (RuntimeError, ValueError, MemoryError):
+                            continue                       # what it was offered keeps its status: Pillow decodes it, as before
+                        took = st2 == 0
+                        p[took], d[took], st[took] = p2[took], d2[took], 0
+                good = st == 0
                 at = positions[good] - start
-                ph[at] = np.asarray(p, np.uint64).view(np.int64)[good]
-                dh[at] = np.asarray(d, np.uint64).view(np.int64)[good]
+                ph[at] = p.view(np.int64)[good]
+                dh[at] = d.view(np.int64)[good]
                 ok[at] = True
-                left = ~good if skips.get(kind) is None else (~good & ~skips[kind])
+                left = ~good if skip is None else (~good & ~skip)
                 refused.extend(positions[left].tolist())   # outside the GPU decoder: Pillow decodes it, as the reference does
         finally:
             if held is not None:
                 held.release()
         return refused
-
-    def _offer_to(self, follow_up: str, held, lo: int, hi: int, positions, blobs, p, d, st):
-        """The files of a kind still UNSUPPORTED after the decoders before it, offered to ``follow_up`` (formats.follow_ups) -- "webpl", the
-        lossless WebP decoder (``KE_GPU_WEBP_LOSSLESS=1``), "webpa", the one for lossy files with an alpha plane
-        (``KE_GPU_WEBP_ALPHA=1``), or "tiffc", the one for LZW and PackBits TIFF files (``KE_GPU_TIFF_COMPRESSED=1``) --
-        over the same files -- the read-ahead range with the files already taken masked, their paths, or their bytes --
-        before they go to Pillow: (p, d, st) with its results filled in.  What it refuses keeps its status."""
-        p, d, st = np.array(p, np.uint64), np.array(d, np.uint64), np.array(st, np.int32)
-        again = st == 1
-        if not again.any():
-            return p, d, st
-        try:
-            if held is not None:
-                p2, d2, st2 = self.stage.hash_ahead(held, lo, hi, follow_up, skip=~again)
-                p2, d2, st2 = (np.asarray(a)[again] for a in (p2, d2, st2))
-            elif blobs is None:
-                p2, d2, st2 = self.stage.hash_files([self.paths[k] for k in positions[again].tolist()], follow_up)
-            else:
-                p2, d2, st2 = self.stage.jpeg_hash([b for b, a in zip(blobs, again.tolist()) if a], follow_up)
-        except (RuntimeError, ValueError, MemoryError):          # Pillow decodes them, as before
-            return p, d, st
-        took = np.nonzero(again)[0][np.asarray(st2) == 0]
-        p[took] = np.asarray(p2, np.uint64)[np.asarray(st2) == 0]
-        d[took] = np.asarray(d2, np.uint64)[np.asarray(st2) == 0]
-        st[took] = 0
-        return p, d, st
 
     # ---- the Pillow share: chunks through the two staging buffers
     def _start(self, positions: Sequence[int]):
@@ -716,12 +711,10 @@ class _Pipeline:
                     taken[reads[k] - start] = True
                 skips = {}
                 if reads["ahead"] is not None:
-                    ends = np.cumsum([len(reads[k]) for k in BASE_KINDS]).tolist()
-                    for kind, e in zip(BASE_KINDS, ends):
-                        if kind in ("png", "gif") and len(reads[kind]):
-                            mask = self._png_for_pillow(reads["ahead"], e - len(reads[kind]), e, kind)
-                            if mask is not None:
-                                skips[kind] = mask
+                    for kind in ("png", "gif"):
+                        mask = self._png_for_pillow(reads["ahead"], *reads["spans"][kind], kind) if len(reads[kind]) else None
+                        if mask is not None:
+                            skips[kind] = mask
                 todo = (start + np.nonzero(~taken)[0]).tolist()
                 for kind, mask in skips.items():
                     todo += reads[kind][mask].tolist()

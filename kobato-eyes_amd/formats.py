@@ -67,3 +67,15 @@ def enabled_kinds(seam: str) -> list:
     if seam == "refine_parallel":
         rows.sort(key=lambda f: f.follows is not None)
     return [(f.kind, f.suffixes) for f in rows]
+
+
+def files_offered(kind: str, candidates, ran: dict) -> list:
+    """``Format.follows`` at the two refine seams: of ``candidates``, the files the seam offers ``kind``'s decoder.  A base kind
+    is offered them all; a follow-up only those its base returned UNSUPPORTED (status 1) in this run -- ``ran``: {kind: (paths,
+    status)} of the decoders that have run --, nothing if its base did not run.  (No follow-up decoder takes a file its base
+    gives another status: tests/test_host_logic.py holds the probes to that.)"""
+    base = next(f.follows for f in FORMATS if f.kind == kind)
+    if base is None:
+        return list(candidates)
+    left = {p for p, s in zip(*ran.get(base, ((), ()))) if s == 1}
+    return [p for p in candidates if p in left]

@@ -16,7 +16,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
-from .formats import enabled_kinds
+from .formats import enabled_kinds, files_offered
 from .image_io import MAX_SIDE, load_rgb
 
 _phash = importlib.import_module(".phash", __package__)   # the package also exports a function named phash
@@ -114,15 +114,14 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
         """JPEG / PNG / BMP / TIFF / WebP files whose pixels the reference's loader would hand over exactly as Image.open yields them -- RGB, no
         EXIF orientation to apply, nothing to shrink (src/utils/image_io.py:107-138 are all no-ops then) -- are decoded on the
         GPU and stay there: placed[path] = (device address, width, height).  Everything else is left for Pillow."""
-        left = {}                                                    # kind -> the files its decoder returned as unsupported
+        ran = {}                                                     # kind -> (paths, status) of its decoder's call
         for kind, suffixes in gpu_kinds.items():
-            paths = [p for p in need if p.lower().endswith(suffixes) and p not in placed]
-            if kind == "tiffc":                                      # only what the unpacker left out, not what it took and the loader keeps
-                paths = [p for p in paths if p in left.get("tiff", ())]
+            # a follow-up: only what its base left out, not what that one took and the loader keeps
+            paths = files_offered(kind, [p for p in need if p.lower().endswith(suffixes) and p not in placed], ran)
             if not paths:
                 continue
             dev, off, w, h, c, st, flags = ctx.decode_files_owned(paths, kind)
-            left[kind] = {p for p, s in zip(paths, st.tolist()) if s == 1}
+            ran[kind] = (paths, st.tolist())
             if not dev:
                 continue
             buffers.append(dev)

@@ -21,7 +21,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import _native
-from .formats import enabled_kinds
+from .formats import enabled_kinds, files_offered
 
 _phash = importlib.import_module(".phash", __package__)
 log = logging.getLogger("ui.dup_refine")
@@ -83,9 +83,9 @@ def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) ->
     if not kinds:
         return out
     ctx = _native.get_context(device)
-    not_laid = np.uint64(0xFFFFFFFFFFFFFFFF)
+    ran: dict = {}                                                   # kind -> (paths, status) of its decoder's calls
     for kind, suffixes in kinds:
-        mine = [p for p in paths if str(p).lower().endswith(suffixes) and p not in out]
+        mine = files_offered(kind, [p for p in paths if str(p).lower().endswith(suffixes) and p not in out], ran)
         at = 0
         while at < len(mine):
             stop, estimate = at, 0                                   # a few GB of decoded pixels per call
@@ -101,15 +101,12 @@ def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) ->
                 dev, off, w, h, c, st, flags = ctx.decode_files_owned([str(p) for p in part], kind, by_shape=True)
             except (RuntimeError, ValueError):
                 continue                                             # the Pillow route decides about these files
+            ran.setdefault(kind, ([], []))[0].extend(part)
+            ran[kind][1].extend(st.tolist())
             if not dev:
                 continue
             try:
-                laid = np.nonzero(off != not_laid)[0]
-                laid = laid[np.argsort(off[laid], kind="stable")]   # layout order: one run per (width, height, channels)
-                shapes = np.stack([w[laid], h[laid], c[laid]], 1)
-                cuts = np.nonzero((shapes[1:] != shapes[:-1]).any(1))[0] + 1
-                for run in np.split(np.arange(len(laid)), cuts):
-                    idx = laid[run]
+                for idx in _native.runs_laid_out(off, (w, h, c)):   # one run per (width, height, channels)
                     ww, hh, cc = int(w[idx[0]]), int(h[idx[0]]), int(c[idx[0]])
                     thumbs = ctx.resize_luma_uniform(dev + int(off[idx[0]]), len(idx), ww, hh, cc, side, side, filter=1)
                     for k, i in enumerate(idx.tolist()):
@@ -118,14 +115,11 @@ def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) ->
                 # files to turn first (src/ui/dup_refine_parallel.py:67-70: ImageOps.exif_transpose before the resize -- every
                 # camera writes the tag): turned on the device into a buffer of their own, then shrunk group by group
                 orient = (flags >> 8) & 15
-                turn = np.nonzero((st == 0) & (c == 3) & ((flags & 1) == 1) & (orient >= 2) & (orient <= 8) & (off != not_laid))[0]
+                turn = np.nonzero((st == 0) & (c == 3) & ((flags & 1) == 1) & (orient >= 2) & (orient <= 8) & (off != _native.NOT_LAID))[0]
                 if len(turn):
                     dev2, off2, w2, h2 = ctx.normalise_rgb(dev, off[turn], w[turn], h[turn], c[turn], orient[turn], by_shape=True)
                     try:
-                        order = np.argsort(off2, kind="stable")
-                        shapes2 = np.stack([w2[order], h2[order]], 1)
-                        cuts2 = np.nonzero((shapes2[1:] != shapes2[:-1]).any(1))[0] + 1
-                        for run in np.split(order, cuts2):
+                        for run in _native.runs_laid_out(off2, (w2, h2)):
                             thumbs = ctx.resize_luma_uniform(dev2 + int(off2[run[0]]), len(run), int(w2[run[0]]), int(h2[run[0]]), 3, side, side, filter=1)
                             for k, j in enumerate(run.tolist()):
                                 out[part[int(turn[j])]] = thumbs[k]

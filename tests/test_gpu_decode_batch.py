@@ -120,3 +120,99 @@ def test_mixed_batch_keeps_every_status_and_pixel_at_its_index(kind, monkeypatch
             assert out[k].shape == px.shape and np.array_equal(out[k], px), (kind, k, name)
         else:
             assert out[k] is None, (kind, k, name)
+
+
+def _small_files(suffix: str):
+    """Twelve files between 8 x 8 and 33 x 17, several of one shape so that groups form: PNG files (gray, RGB, RGBA), or .webp
+    files (lossy, lossless, lossy with an alpha plane, and a lossy one cut in half)."""
+    import io
+
+    from PIL import Image
+
+    rng = np.random.default_rng(len(suffix))
+    sizes = [(8, 8), (33, 17), (8, 8), (17, 9)]
+    files = []
+    for k in range(12):
+        w, h = sizes[k % 4]
+        a = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        alpha = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        if suffix == ".png":
+            im = [Image.fromarray(a[..., 0]), Image.fromarray(a), Image.fromarray(np.dstack([a, alpha]), "RGBA")][k // 4]
+            buf = io.BytesIO()
+            im.save(buf, "PNG")
+            files.append(buf.getvalue())
+        else:
+            files.append([W.pillow_file(a, 80, 4), L.pillow_file(Image.fromarray(a)), A.pillow_file(a, alpha)][k // 4])
+    if suffix == ".webp":
+        files[1] = files[1][: len(files[1]) // 2]
+    return files
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("suffix,kinds", [(".png", ("png",)), (".webp", ("webp", "webpl", "webpa"))])
+def test_bytes_paths_and_a_span_read_ahead_are_one_decode(suffix, kinds, tmp_path):
+    """Context.hash of the same twelve files as bytes, as paths and as a span of a batch read ahead with two files skipped
+    (five files of another batch lie before the span): the same (phash, dhash, status) at every file that was not skipped,
+    status 1 at the two that were -- for a base kind and each of its follow-ups.  And decode_files_owned lays the same pixels
+    out by shape and in 16-byte slots.  Every step has a time limit of its own: a call that hangs ends the run."""
+    import faulthandler
+    from contextlib import contextmanager
+
+    from kobato_eyes_amd import _native
+
+    @contextmanager
+    def within(seconds):
+        faulthandler.dump_traceback_later(seconds, exit=True)
+        try:
+            yield
+        finally:
+            faulthandler.cancel_dump_traceback_later()
+
+    ctx = _native.get_context(0)
+    files = _small_files(suffix)
+    paths = []
+    for k, data in enumerate(files):
+        paths.append(str(tmp_path / f"f{k:02d}{suffix}"))
+        open(paths[-1], "wb").write(data)
+    skip = np.zeros(12, bool)
+    skip[[0, 7]] = True
+    taken = np.zeros(12, bool)
+    for kind in kinds:
+        with within(60):
+            p, d, st = ctx.hash(files, kind=kind)
+        assert set(st.tolist()) <= {0, 1, 2}
+        taken |= st == 0
+        with within(60):
+            p2, d2, st2 = ctx.hash_files(paths, kind=kind)
+        assert (p2.tolist(), d2.tolist(), st2.tolist()) == (p.tolist(), d.tolist(), st.tolist()), kind
+        with within(60):
+            held = ctx.read_files_ahead(paths[:5] + paths, [(kind, 5, 17)])
+            try:
+                assert held is not None and len(held) == 17 and (kind, 5, 17) in held.probed
+                p3, d3, st3 = ctx.hash(None, kind=kind, ahead=(held, 5, 17), skip=skip)
+            finally:
+                held.release()
+        assert st3[skip].tolist() == [1, 1], kind                              # left alone: as if refused
+        assert (p3[~skip].tolist(), d3[~skip].tolist(), st3[~skip].tolist()) == (p[~skip].tolist(), d[~skip].tolist(), st[~skip].tolist()), kind
+        with within(60):
+            pixels = {}
+            for by_shape in (False, True):
+                dev, off, w, h, c, st4, flags = ctx.decode_files_owned(paths, kind, by_shape=by_shape)
+                try:
+                    assert st4.tolist() == st.tolist() and flags.shape == (12,)
+                    for i in np.nonzero(st4 == 0)[0].tolist():
+                        px = np.empty((h[i], w[i], c[i]), np.uint8)
+                        ctx.memcpy(px, dev + int(off[i]), px.nbytes)
+                        pixels.setdefault(i, []).append(px)
+                    if by_shape:
+                        assert (off[st4 != 0] == _native.NOT_LAID).all()
+                        runs = _native.runs_laid_out(off, (w, h, c))
+                        assert sorted(np.concatenate(runs).tolist()) == np.nonzero(st4 == 0)[0].tolist() and any(len(r) > 1 for r in runs)
+                finally:
+                    if dev:
+                        ctx.free(dev)
+            assert pixels and all(len(v) == 2 and np.array_equal(v[0], v[1]) for v in pixels.values()), kind
+    if suffix == ".webp":
+        assert taken.tolist() == [True, False] + [True] * 10     # every file but the cut one is somebody's
+    else:
+        assert taken.all()

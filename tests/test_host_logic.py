@@ -534,6 +534,272 @@ def test_batches_read_ahead_reach_the_decoders_in_their_own_order(tmp_path, monk
     assert log["released"] == log["ahead"]
 
 
+_CHAIN_EXT = ("jpg", "png", "gif", "tif", "webp")                    # file k has suffix _CHAIN_EXT[k % 5]
+_CHAIN_BASE = {"jpg": "jpeg", "png": "png", "gif": "gif", "tif": "tiff", "webp": "webp"}
+_CHAIN_REFUSED = {15: "jpeg", 26: "png", 7: "gif", 13: "tiff", 24: "webp"}          # status 2 from the suffix's own decoder
+_CHAIN_LEFT = {"jpeg": {30}, "png": set(), "gif": set(), "tiff": {8, 23, 33}, "webp": {4, 14, 19, 29, 39}}   # status 1 from it
+_CHAIN_TAKES = {"tiffc": {8, 33}, "webpl": {4, 29}, "webpa": {14, 39}}               # 23 and 19: nobody takes them
+_CHAIN_FOLLOWS = {"tiffc": "tiff", "webpl": "webp", "webpa": "webp"}
+_CHAIN_BIG_PNG = 21                                                  # the PNG file the read-ahead reports as 10 MB
+
+
+def _chain_status(k: int, kind: str) -> int:
+    if kind in _CHAIN_TAKES:
+        return 0 if k in _CHAIN_TAKES[kind] else 1
+    return 2 if k in _CHAIN_REFUSED else 1 if k in _CHAIN_LEFT[kind] else 0
+
+
+@pytest.mark.parametrize("route", ["ahead", "ahead_png_skip", "paths", "blobs"])
+def test_follow_up_decoders_are_offered_what_their_base_left_on_every_route(tmp_path, monkeypatch, route):
+    """fastsig._Pipeline's chain base decoder -> follow-ups (formats.follow_ups) with a stand-in stage, once per way the files
+    reach it: a read-ahead buffer (``hash_ahead`` with a ``skip`` mask; one batch finds no buffer and goes through
+    ``hash_files``), paths (``hash_files`` with a filtered list) and bytes (``jpeg_hash`` with a filtered list).  File k's only
+    byte is k, its 'hashes' are (k, k + 500), and its status is a function of k and the kind (_chain_status): every follow-up
+    call must be handed exactly the files still at status 1 after the decoders before it -- never one its base gave 0 or 2 --,
+    the rows are those somebody took, every buffer comes back, and a PNG file that ``_png_for_pillow`` moves to the Pillow
+    side is neither hashed by the stage nor returned twice."""
+    from kobato_eyes_amd import fastsig as fs
+
+    n_files = 40
+    items = []
+    for k in range(n_files):
+        p = tmp_path / f"f{k:03d}.{_CHAIN_EXT[k % 5]}"
+        p.write_bytes(bytes([k]))
+        items.append((1000 + k, str(p)))
+    for v in ("KE_GPU_JPEG", "KE_GPU_PNG", "KE_GPU_BMP", "KE_GPU_GIF", "KE_GPU_TIFF", "KE_GPU_WEBP", "KE_READ_AHEAD"):
+        monkeypatch.delenv(v, raising=False)
+    for v in ("KE_GPU_TIFF_COMPRESSED", "KE_GPU_WEBP_LOSSLESS", "KE_GPU_WEBP_ALPHA"):
+        monkeypatch.setenv(v, "1")
+    monkeypatch.setenv("KE_GPU_BATCH", "8")
+    monkeypatch.setenv("KE_DECODE_PROCESSES", "0")
+    monkeypatch.setenv("KE_PNG_GPU_US_PER_BYTE", "0.9" if route == "ahead_png_skip" else "0")
+    monkeypatch.setenv("KE_GIF_GPU_US_PER_BYTE", "0")
+    monkeypatch.setenv("KE_DECODE_POOL_START_S", "0")
+    log = {"reads": 0, "held": 0, "released": 0, "offers": [], "hashed": [], "routes": set()}
+
+    def number(path: str) -> int:
+        return int(os.path.basename(path)[1:4])
+
+    def answer(ks, kind, how):
+        """What the decoder of ``kind`` says about files ``ks``; a follow-up's call is written down, and checked file by file."""
+        ks = [int(k) for k in ks]
+        log["routes"].add(how)
+        base = _CHAIN_FOLLOWS.get(kind, kind)
+        assert all(_CHAIN_BASE[_CHAIN_EXT[k % 5]] == base for k in ks), (kind, ks)
+        if kind in _CHAIN_FOLLOWS:
+            assert ks and all(_chain_status(k, base) == 1 for k in ks), (kind, ks)
+            log["offers"].append((kind, ks))
+        log["hashed"] += ks
+        num = np.array(ks, np.uint64)
+        return num, num + np.uint64(500), np.array([_chain_status(k, kind) for k in ks], np.int32)
+
+    class Held:
+        def __init__(self, paths, spans):
+            self.paths = paths
+            self.sizes = np.array([10_000_000 if number(p) == _CHAIN_BIG_PNG else 1 for p in paths], np.uint64)
+            self.probed = {(kind, lo, hi): (np.full(hi - lo, 2048, np.int32), np.full(hi - lo, 2048, np.int32), np.full(hi - lo, 3, np.int32),
+                                            np.zeros(hi - lo, np.int32)) for kind, lo, hi in spans if hi > lo}   # 12 MB each for Pillow
+            self.out = False
+
+        def release(self):
+            assert not self.out
+            self.out = True
+            log["released"] += 1
+
+    class Stage:
+        def __init__(self, device, stage_bytes, max_images):
+            self.buf = np.zeros(1 << 16, np.uint8)
+
+        def acquire(self):
+            return 0, self.buf
+
+        def submit(self, slot, offsets, widths, heights, channels):
+            raise AssertionError("nothing decodes here: the files are not images")
+
+        def wait(self, slot):
+            pass
+
+        def hash_one(self, arr):
+            return None
+
+    def read_ahead(self, paths, spans=()):
+        log["reads"] += 1
+        if log["reads"] == 2:                                  # "both buffers taken": this batch is read inside the call
+            return None
+        log["held"] += 1
+        return Held(list(paths), spans)
+
+    def hash_ahead(self, held, lo, hi, kind="jpeg", **more):
+        assert not held.out and set(more) <= {"skip"}
+        ks = np.array([number(p) for p in held.paths[lo:hi]], np.int64)
+        if "skip" not in more:
+            return answer(ks, kind, "ahead")
+        skip = np.asarray(more["skip"])                        # handed over only when there is a mask
+        assert skip.dtype == bool and skip.shape == ks.shape
+        p, d, st = (np.zeros(len(ks), np.uint64), np.zeros(len(ks), np.uint64), np.ones(len(ks), np.int32))
+        p[~skip], d[~skip], st[~skip] = answer(ks[~skip], kind, "ahead")
+        return p, d, st
+
+    def hash_files(self, paths, kind="jpeg"):
+        return answer([number(p) for p in paths], kind, "paths")
+
+    def jpeg_hash(self, blobs, kind="jpeg"):
+        assert all(len(b) == 1 for b in blobs)
+        return answer([b[0] for b in blobs], kind, "blobs")
+
+    if route == "blobs":
+        Stage.jpeg_hash = jpeg_hash
+    else:
+        Stage.hash_files = hash_files
+        if route != "paths":
+            Stage.read_ahead, Stage.hash_ahead = read_ahead, hash_ahead
+    monkeypatch.setattr(fs, "_make_stage", Stage)
+    rows = fs.compute_signatures_mp(items, max_workers=2, chunksize=8)
+
+    moved = {_CHAIN_BIG_PNG} if route == "ahead_png_skip" else set()
+    taken = set().union(*_CHAIN_TAKES.values())
+    want = [(1000 + k, k, k + 500) for k in range(n_files)
+            if k not in moved and (k in taken or _chain_status(k, _CHAIN_BASE[_CHAIN_EXT[k % 5]]) == 0)]
+    assert rows == want                                        # what nobody took is no image: Pillow drops it
+    offers = []
+    for lo in range(0, n_files, 8):                            # per batch: tiff's follow-up, then webp's two in their order
+        batch = set(range(lo, lo + 8))
+        for kind, ks in (("tiffc", _CHAIN_LEFT["tiff"]), ("webpl", _CHAIN_LEFT["webp"]),
+                         ("webpa", _CHAIN_LEFT["webp"] - _CHAIN_TAKES["webpl"])):
+            if ks & batch:
+                offers.append((kind, sorted(ks & batch)))
+    assert log["offers"] == offers
+    assert not moved & set(log["hashed"]) and len({r[0] for r in rows}) == len(rows)
+    assert sorted(k for k in log["hashed"] if k not in set().union(*_CHAIN_LEFT.values())) == \
+        sorted(set(range(n_files)) - moved - set().union(*_CHAIN_LEFT.values()))      # every other file: offered once, to its base
+    assert log["routes"] == {"ahead": {"ahead", "paths"}, "ahead_png_skip": {"ahead", "paths"}, "paths": {"paths"}, "blobs": {"blobs"}}[route]
+    if route in ("ahead", "ahead_png_skip"):
+        assert log["reads"] == 5 and log["held"] == 4 and log["released"] == 4
+    else:
+        assert log["reads"] == log["released"] == 0
+
+
+def _grouped_layout_as_decode_files_owned_wrote_it(w, h, c, st):
+    """The by_shape loop Context.decode_files_owned carried before _native.lay_out, restated literally."""
+    n = len(w)
+    nbytes = np.where(st == 0, w.astype(np.int64) * h * c, 0)
+    out_off = np.zeros(n, np.uint64)
+    order = np.lexsort((w, h, c, st != 0))
+    sorted_bytes = nbytes[order]
+    key = np.stack([w[order], h[order], c[order]], 1)
+    new_group = np.ones(n, bool)
+    new_group[1:] = (key[1:] != key[:-1]).any(1)
+    starts = np.zeros(n, np.int64)
+    at = 0
+    for k in range(n):
+        if new_group[k]:
+            at = (at + 15) & ~15
+        starts[k] = at
+        at += int(sorted_bytes[k])
+    out_off[order] = starts.astype(np.uint64)
+    out_off[nbytes == 0] = np.uint64(0xFFFFFFFFFFFFFFFF)
+    return out_off, at
+
+
+def _grouped_layout_as_normalise_rgb_wrote_it(ow, oh):
+    """The by_shape loop Context.normalise_rgb carried before _native.lay_out, restated literally."""
+    nbytes = ow.astype(np.int64) * oh * 3
+    do = np.zeros(len(ow), np.uint64)
+    order = np.lexsort((oh, ow))
+    at, prev = 0, None
+    for k in order.tolist():
+        shape = (int(ow[k]), int(oh[k]))
+        if shape != prev:
+            at, prev = (at + 15) & ~15, shape
+        do[k] = at
+        at += int(nbytes[k])
+    return do, at
+
+
+def test_one_layout_function_lays_groups_out_as_both_loops_did():
+    """_native.lay_out against the two per-image loops it replaced, on 2 000 random batches (n = 0 .. 40, shapes from at most
+    four values so that groups form, refused files, files of no bytes): the same offsets, NOT_LAID marks and totals, byte for
+    byte, in decode_files_owned's ordering and in normalise_rgb's; the plain form is 16-byte slots in input order; and
+    runs_laid_out returns the groups the layout made, in buffer order."""
+    from kobato_eyes_amd._native import NOT_LAID, lay_out, runs_laid_out
+
+    assert NOT_LAID == np.uint64(0xFFFFFFFFFFFFFFFF)
+    rng = np.random.default_rng(20260611)
+    for trial in range(2000):
+        n = trial if trial < 2 else int(rng.integers(0, 41))
+        values = rng.choice([0, 1, 3, 5, 7, 8, 16, 17, 33], size=int(rng.integers(1, 5)))
+        w, h = rng.choice(values, n).astype(np.int32), rng.choice(values, n).astype(np.int32)
+        c = rng.choice([1, 3, 4], n).astype(np.int32)
+        st = rng.choice([0, 0, 0, 1, 2], n).astype(np.int32)
+        nbytes = np.where(st == 0, w.astype(np.int64) * h * c, 0)
+        off, total = lay_out(nbytes, (w, h, c), st != 0)
+        want_off, want_total = _grouped_layout_as_decode_files_owned_wrote_it(w, h, c, st)
+        assert off.dtype == np.uint64 and np.array_equal(off, want_off) and total == want_total, trial
+        if total:                                              # the groups back: whole, of one shape, back to back, in buffer order
+            runs = runs_laid_out(off, (w, h, c))
+            assert sorted(np.concatenate(runs).tolist()) == np.nonzero(nbytes)[0].tolist()
+            shapes = [(int(w[r[0]]), int(h[r[0]]), int(c[r[0]])) for r in runs]
+            assert len(set(shapes)) == len(shapes) and all(off[r[0]] % 16 == 0 for r in runs)
+            for r, (ww, hh, cc) in zip(runs, shapes):
+                assert (w[r] == ww).all() and (h[r] == hh).all() and (c[r] == cc).all()
+                assert np.array_equal(off[r], off[r[0]] + np.arange(len(r), dtype=np.uint64) * np.uint64(ww * hh * cc))
+            assert [int(off[r[0]]) for r in runs] == sorted(int(off[r[0]]) for r in runs)
+        off, total = lay_out(w.astype(np.int64) * h * 3, (h, w))
+        want_off, want_total = _grouped_layout_as_normalise_rgb_wrote_it(w, h)
+        assert np.array_equal(off, want_off) and total == want_total, trial
+        if n and (w * h > 0).all():
+            runs = runs_laid_out(off, (w, h))
+            assert np.array_equal(np.concatenate(runs), np.argsort(off, kind="stable"))
+            assert all(len({(int(w[i]), int(h[i])) for i in r}) == 1 for r in runs)
+            assert len({(int(w[r[0]]), int(h[r[0]])) for r in runs}) == len(runs)
+        off, total = lay_out(nbytes)
+        padded = (nbytes + 15) // 16 * 16
+        assert np.array_equal(off, np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.uint64)[:n]) and total == int(padded.sum())
+
+
+def test_no_follow_up_decoder_takes_what_its_base_did_not_leave(K):
+    """The condition under which formats.files_offered changes no result at the refine seams: a follow-up decoder's probe
+    takes (status 0) no file its base's probe gives a status other than 1 -- over every file of the tiff / tiffc / webp /
+    webpl / webpa case modules, valid, refused and damaged, with the library's own ``ke_<kind>_probe`` (host code).  A decode
+    only ever turns a 0 into a 2, so what holds for the probes holds for the calls.  And the helper itself: a base kind is
+    offered every candidate, a follow-up its base's status-1 files among them, nothing where the base did not run."""
+    import _tiff_cases as T
+    import _tiffc_cases as TC
+    import _webp_cases as W
+    import _webpa_cases as WA
+    import _webpl_cases as WL
+    from kobato_eyes_amd.formats import files_offered
+
+    lib = K._native.load_library()
+
+    def files(*sets):
+        return [next(x for x in (item if isinstance(item, tuple) else (item,)) if isinstance(x, bytes)) for s in sets for item in s]
+
+    def probe(kind, blobs):
+        sizes = np.array([len(b) for b in blobs], np.uint64)
+        offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint64)
+        flat = np.frombuffer(b"".join(blobs) + bytes(64), np.uint8)
+        w, h, c, st = (np.zeros(len(blobs), np.int32) for _ in range(4))
+        assert getattr(lib, f"ke_{kind}_probe")(flat.ctypes.data, offsets.ctypes.data, sizes.ctypes.data, len(blobs), w.ctypes.data,
+                                                h.ctypes.data, c.ctypes.data, st.ctypes.data) == 0
+        return st
+
+    rng = np.random.default_rng(5)
+    tif = files(T.supported(True), T.handmade(True), T.refused(), TC.valid_cases(), TC.refused_cases(), TC.late_change_cases(),
+                TC.damaged_set(60))
+    webp = files(W.taken_cases(), W.refused_cases(), WL.taken_cases(), WL.refused_cases(), WA.all_taken(), WA.refused_cases())
+    for base in files(W.taken_cases()[:12], WL.fuzz_bases(), WA.fuzz_bases()):
+        webp += files(W.damaged(base, rng, 20), WA.damaged(base, rng, 20))
+    for base, follow_up, blobs in (("tiff", "tiffc", tif), ("webp", "webpl", webp), ("webp", "webpa", webp)):
+        st, st2 = probe(base, blobs), probe(follow_up, blobs)
+        assert (st == 0).any() and (st == 1).any() and (st == 2).any() and (st2 == 0).any()       # the sets reach every answer
+        assert not ((st != 1) & (st2 == 0)).any(), (base, follow_up, np.nonzero((st != 1) & (st2 == 0))[0][:10].tolist())
+    ran = {"webp": (["a", "b", "c", "d"], [0, 1, 2, 1])}
+    assert files_offered("webp", ["d", "b", "x"], {}) == ["d", "b", "x"] and files_offered("jpeg", [], ran) == []
+    assert files_offered("webpl", ["x", "d", "c", "b", "a"], ran) == ["d", "b"] and files_offered("webpa", ["b"], ran) == ["b"]
+    assert files_offered("tiffc", ["a", "b"], ran) == [] and files_offered("webpl", ["a", "b"], {}) == []
+
+
 def test_bench_self_launches_its_ranks_world_size_2_gloo():
     """`python bench.py --gpus 2` typed without a launcher (as the driver types it at N = 1) must start its ranks as fresh
     child processes under torch.distributed.run, relay rank 0's one JSON line on stdout and return the children's exit
