@@ -17,6 +17,7 @@
 
 #include "ke_gif_core.h"
 #include "ke_lz_copies.h"
+#include "ke_lz_records.h"
 #include "ke_lz_window.h"
 
 namespace {
@@ -31,27 +32,6 @@ struct KeGifDev {
     uint8_t lut[256];
 };
 
-constexpr uint32_t kMaxCopy = 511 + 2;            // the record's length field
-
-struct RecSink {
-    uint8_t *idx;
-    uint2 *rec;
-    uint32_t out, nrec;
-    __device__ __forceinline__ void literal(uint8_t b) { idx[out++] = b; }
-    __device__ __forceinline__ void copy(uint32_t from, uint32_t len) {
-        const uint32_t dist = out - from;
-        // A copied string has at least 2 characters; only the frame's last one can be cut to 1 -- it is recorded as 2, the
-        // second byte lands in the slack behind the frame's indices.  Pieces of at most 513, none of them a single byte.
-        if (len == 1) len = 2;
-        while (len) {
-            const uint32_t take = len > kMaxCopy ? (len - kMaxCopy == 1 ? kMaxCopy - 1 : kMaxCopy) : len;
-            rec[nrec++] = make_uint2(out, (dist << 9) | (take - 2));
-            out += take;
-            len -= take;
-        }
-    }
-};
-
 __global__ __launch_bounds__(64) void ke_gif_codes(const KeGifDev *__restrict__ imgs, int64_t n, const uint8_t *__restrict__ files,
                                                  uint8_t *__restrict__ indices, uint2 *__restrict__ records, uint2 *__restrict__ dicts,
                                                  int32_t *__restrict__ status, uint32_t *__restrict__ nrec) {
@@ -63,7 +43,7 @@ __global__ __launch_bounds__(64) void ke_gif_codes(const KeGifDev *__restrict__ 
     src.limit = d.file_size;
     src.start(d.data_off);
     HbmDict dict{dicts + (size_t)i * 4096};
-    RecSink sink{indices + d.idx_off, records + d.rec_off, 0, 0};
+    KeLzRecSink sink{indices + d.idx_off, records + d.rec_off, 0, 0};
     const uint32_t want = (uint32_t)d.width * (uint32_t)d.height;
     status[i] = ke_gif_lzw(src, d.data_off, d.file_size, d.bits, want, dict, sink);
     nrec[i] = sink.nrec;

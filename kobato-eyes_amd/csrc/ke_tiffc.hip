@@ -24,6 +24,7 @@
 #include "ke_decode_batch.h"
 
 #include "ke_lz_copies.h"
+#include "ke_lz_records.h"
 #include "ke_lz_window.h"
 #include "ke_tiffc_parse.h"
 
@@ -45,27 +46,7 @@ struct KeTiffcStripDev {
     uint32_t img, comp;
 };
 
-constexpr uint32_t kMaxCopy = 511 + 2;            // the record's length field
 constexpr uint32_t kMaxWaves = 2048;              // resident lanes: 131 072 dictionaries of 32 KB = 4 GB at most
-
-struct RecSink {
-    uint8_t *plane;
-    uint2 *rec;
-    uint32_t out, nrec;
-    __device__ __forceinline__ void literal(uint8_t b) { plane[out++] = b; }
-    __device__ __forceinline__ void copy(uint32_t from, uint32_t len) {
-        const uint32_t dist = out - from;
-        // A copy has at least 2 bytes; only a strip's last string can be cut to 1 -- it is recorded as 2, the second byte lands
-        // in the slack behind the strip's plane.  Pieces of at most 513, none of them a single byte.
-        if (len == 1) len = 2;
-        while (len) {
-            const uint32_t take = len > kMaxCopy ? (len - kMaxCopy == 1 ? kMaxCopy - 1 : kMaxCopy) : len;
-            rec[nrec++] = make_uint2(out, (dist << 9) | (take - 2));
-            out += take;
-            len -= take;
-        }
-    }
-};
 
 __global__ __launch_bounds__(64) void ke_tiffc_codes(const KeTiffcStripDev *__restrict__ strips, uint32_t n, const uint8_t *__restrict__ files,
                                                    uint8_t *__restrict__ planes, uint2 *__restrict__ records, uint2 *__restrict__ dicts,
@@ -83,7 +64,7 @@ __global__ __launch_bounds__(64) void ke_tiffc_codes(const KeTiffcStripDev *__re
             src.file = files + d.file_off;
             src.limit = d.bytes;
             src.start(0);
-            RecSink sink{planes + d.plane_off, records + d.rec_off, 0, 0};
+            KeLzRecSink sink{planes + d.plane_off, records + d.rec_off, 0, 0};
             const int st = d.comp == KE_TIFFC_LZW ? ke_tiffc_lzw(src, 0u, d.bytes, d.want, dict, sink) : ke_tiffc_packbits(src, 0u, d.bytes, d.want, sink);
             if (st != KE_TIFFC_OK) status[d.img] = st;             // any strip's failure is the image's (the same value or another: not 0)
             nrec[s] = sink.nrec;

@@ -192,6 +192,15 @@ def packbits_stream_cases():
     return out
 
 
+def sink_cases():
+    """(name, file): the copy patterns of tests/_gif_stream_cases.py that stress the sink the two LZW walkers share and the
+    copies at length bias 2 -- runs of every distance 2..17, at the start of the records and across a round of 64, and last
+    strings cut to one byte -- as one-strip gray files."""
+    import _gif_stream_cases as S
+
+    return [(name, compressed(np.zeros((h, w), np.uint8), LZW, encode=lambda d, codes=codes: Z.pack(codes))) for name, w, h, codes in S.tiff_strips()]
+
+
 def valid_cases():
     """Every file the decoder must take, (family, name, file)."""
     return ([("pillow", n, d) for n, d in pillow_cases()] + [("handmade", n, d) for n, d in handmade_cases()] +

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "ke_lz_records.h"
 #include "ke_tiffc_parse.h"
 
 extern "C" {
@@ -26,6 +27,27 @@ int tiffc_cpu_decode(const uint8_t *file, uint64_t size, uint8_t *out) {
     ke_parse_tiffc(file, (size_t)size, &strips, h);
     if (h.t.status != KE_TIFF_OK) return h.t.status;
     return ke_tiffc_decode_cpu(file, h, strips, out);
+}
+
+// The kernels' way for one strip (ke_tiffc_codes): its stream walked through the sink the kernels use (ke_lz_records.h).  plane:
+// the strip's bytes + 2, the literals land in it; rec: bytes / 2 + 2 records of two uint32; want: the bytes the strip yields.
+int tiffc_cpu_strip_records(const uint8_t *file, uint64_t size, int32_t strip, uint8_t *plane, uint32_t *rec, uint32_t *nrec, uint32_t *want_out) {
+    KeTiffcInfo h;
+    std::vector<KeTiffcStrip> strips;
+    ke_parse_tiffc(file, (size_t)size, &strips, h);
+    *nrec = *want_out = 0;
+    if (h.t.status != KE_TIFF_OK) return h.t.status;
+    if (strip < 0 || strip >= h.t.nstrips) return -1;
+    const int y0 = strip * h.t.rows_per_strip, rows = std::min(h.t.rows_per_strip, h.t.height - y0);
+    const uint32_t want = (uint32_t)((size_t)rows * h.t.width * h.t.spp);
+    KeTiffcHostSrc src{file + strips[(size_t)strip].off};
+    static thread_local KeTiffcHostDict dict;
+    KeLzRecSink sink{plane, reinterpret_cast<KeLzRec *>(rec), 0, 0};
+    const int st = h.compression == KE_TIFFC_LZW ? ke_tiffc_lzw(src, 0u, strips[(size_t)strip].bytes, want, dict, sink)
+                                                 : ke_tiffc_packbits(src, 0u, strips[(size_t)strip].bytes, want, sink);
+    *nrec = sink.nrec;
+    *want_out = want;
+    return st;
 }
 
 // the uncompressed parser next to it: its answers must not depend on the new one

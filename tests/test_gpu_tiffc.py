@@ -56,6 +56,22 @@ def test_every_valid_file_equals_pillow_in_one_shuffled_batch(ctx):
     assert len(cases) > 300 and shapes == {1, 3, 4}
 
 
+def test_the_copy_patterns_of_the_gif_streams_equal_pillow(ctx):
+    """The shared sink (csrc/ke_lz_records.h) and the copies at length bias 2 on this consumer: runs of every distance 2..17, at
+    the start of the records and across a round of 64, and last strings cut to one byte, in one call with a time limit of
+    its own (a call that hangs in native code ends the run: nothing more is started on the device)."""
+    import faulthandler
+
+    cases = A.sink_cases()
+    faulthandler.dump_traceback_later(60, exit=True)
+    try:
+        out, status = ctx.tiffc_decode([d for _, d in cases])
+    finally:
+        faulthandler.cancel_dump_traceback_later()
+    _check(cases, out, status)
+    assert len(cases) >= 100
+
+
 def test_probe_reports_what_pillow_opens(ctx):
     cases = A.pillow_cases()[::3] + A.handmade_cases()[::5]
     w, h, c, st = ctx.tiffc_probe([d for _, d in cases])

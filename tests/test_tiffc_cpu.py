@@ -39,6 +39,7 @@ def cpu(tmp_path_factory):
     lib.tiffc_cpu_probe.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p]
     lib.tiffc_cpu_decode.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p]
     lib.tiffc_cpu_probe_plain.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p]
+    lib.tiffc_cpu_strip_records.argtypes = [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     return lib
 
 
@@ -123,6 +124,36 @@ def test_streams_libtiff_never_writes_equal_pillow(cpu):
     for name, data in cases:
         _assert_equal_pillow(cpu, name, data)
     assert len(cases) > 40
+
+
+def test_the_copy_patterns_of_the_gif_streams_equal_pillow(cpu):
+    """Runs of every distance 2..17 and last strings cut to one byte (tests/_gif_stream_cases.tiff_strips) as LZW strips: the
+    direct decode equals Pillow, and so does the kernels' way on the host -- the strip through the sink the two LZW walkers
+    share (csrc/ke_lz_records.h), its records made in order byte by byte.  That the strips hold what they are named for is
+    counted from those records: a run of the longest kind at every distance 2..16, contiguous copies at 17, phase 0 at 3, 7,
+    15 and 16, runs continued at lane 0, records into the slack."""
+    import _gif_stream_cases as S
+
+    cases = A.sink_cases()
+    census = Counter()
+    for name, data in cases:
+        _assert_equal_pillow(cpu, name, data)
+        ref = A.pillow_pixels(data)
+        plane = np.zeros(ref.size + 2, np.uint8)
+        rec = np.zeros((ref.size // 2 + 2, 2), np.uint32)
+        n, want = C.c_uint32(), C.c_uint32()
+        assert cpu.tiffc_cpu_strip_records(data, len(data), 0, plane.ctypes.data, rec.ctypes.data, C.byref(n), C.byref(want)) == A.OK, name
+        assert want.value == ref.size and n.value <= ref.size // 2 + 2, name
+        for dst, word in rec[:n.value].tolist():
+            for k in range((word & 511) + 2):
+                plane[dst + k] = plane[dst + k - (word >> 9)]
+        assert np.array_equal(plane[:ref.size], ref.ravel()), name
+        census += S.records_census(rec[:n.value], ref.size)
+    missing = [f for f in [f"run_d{d}_of_{S.longest_run(d)}_copies" for d in range(2, 17)] + [f"run_d{d}_phase_0" for d in (3, 7, 15, 16)] +
+               [f"run_d{d}_continued_at_lane_0" for d in range(3, 17)] + ["contiguous_copies_at_distance_17", "record_into_the_slack", "run_behind_a_blocker"]
+               if not census[f]]
+    assert not missing, missing
+    assert len(cases) >= 140
 
 
 def test_every_valid_file_is_taken(cpu):
