@@ -265,6 +265,27 @@ int ke_tiffc_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, 
                     uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
 int ke_tiffc_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
 
+/* ---- deflate-compressed TIFF files decoded on the GPU: the same step (src/core/fastsig.py:31-34; src/dup/scanner.py:16-28 ranks the
+ * format among the keepers) for the files whose Compression is 8 ("Adobe deflate") or its old alias 32946 -- what Pillow's
+ * "tiff_adobe_deflate" / "tiff_deflate", ImageMagick, GIMP and most scanners' "ZIP" option write --, Predictor absent, 1 or 2, in
+ * the layouts of ke_tiffc_decode, under the same directory whitelist and with the same pixels.  Every strip is a zlib stream of
+ * its own: one kernel gathers the strips into aligned streams, one thread per strip inflates (the PNG path's inflate; literals
+ * to their place, matches recorded), one wave per strip makes the copies and holds the strip's Adler-32 against the stream's,
+ * the last kernel is ke_tiffc_decode's.  A strip is held to more than libtiff holds it to: one complete zlib stream that
+ * yields exactly the bytes of the strip's rows, with a matching Adler-32; bytes behind the stream are ignored.  So a stream
+ * that would yield more than the strip holds and one whose four trailer bytes are cut or missing are KE_JPEG_CORRUPT_ (2)
+ * although libtiff, which stops when the strip is full, decodes them; every other status 2 -- a wrong trailer, a stream that
+ * yields too little, raw deflate, a gzip wrapper, a preset dictionary, a strip that leaves the file -- is a file Pillow raises
+ * on.  LZW, PackBits and uncompressed files are refused here (1), as is everything ke_tiffc_decode refuses.  Arguments and
+ * conventions as ke_jpeg_probe / ke_jpeg_decode.  ke_tiffz_caveats reports no flags (files with an orientation are refused).
+ * Tuning knob (environment, read at every call): KE_TIFFZ_SCRATCH_BYTES replaces the device scratch budget of one sub-batch
+ * (default: half the free device memory, 1-32 GB); results do not depend on it. */
+int ke_tiffz_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                   int32_t *heights, int32_t *channels, int32_t *status_out);
+int ke_tiffz_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+int ke_tiffz_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
+
 /* ---- lossy WebP files decoded on the GPU: the same step (src/core/fastsig.py:31-34, src/utils/image_io.py:60-138) for WebP files
  * of one VP8 key frame -- the simple format (RIFF / WEBP / "VP8 ") and VP8X files without alpha or animation, their ICCP / EXIF /
  * "XMP " chunks skipped (Pillow applies none of them when it opens the file).  The pixels are libwebp's as Pillow drives it
@@ -502,6 +523,12 @@ int ke_synth_hashes(ke_ctx *ctx, uint64_t seed, int64_t n, uint64_t *hashes_out)
  * kind: 0 = hash kernel(s), 1 = scan kernel, 2 = ssim kernel, 3 = synth kernel, 4 = JPEG / PNG decode kernels.
  * Returns milliseconds, or a negative value if nothing was recorded.  Blocks until done. */
 double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind);
+
+/* ---- for the tests of the scratch budgets (KE_<KIND>_SCRATCH_BYTES; results do not depend on them, so nothing else shows
+ * that one was honoured): the number of sub-batches in which the last decode call on this context that runs the shared
+ * sub-batch loop (gif, tiffc, tiffz, webp, webpl, webpa; the other kinds keep loops of their own or need none) worked
+ * off the images it accepted.  0 before any such call; -1 for a NULL context. */
+int64_t ke_last_decode_sub_batches(ke_ctx *ctx);
 
 #ifdef __cplusplus
 }

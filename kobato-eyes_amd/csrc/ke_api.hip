@@ -358,6 +358,8 @@ KE_API double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind) {
     return (double)ms;
 }
 
+KE_API int64_t ke_last_decode_sub_batches(ke_ctx *ctx) { return ctx ? ctx->decode_sub_batches : -1; }
+
 // ---- hashing -------------------------------------------------------------------------------
 namespace {
 

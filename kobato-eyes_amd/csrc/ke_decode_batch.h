@@ -126,7 +126,9 @@ int ke_decode_sub_batches(ke_ctx *ctx, size_t count, Take take, Launch launch, S
     KeStreamGuard guard;                                           // st is written by a queued copy
     guard.arm(ctx);
     ke_time_begin(ctx, KE_T_JPEG);
+    ctx->decode_sub_batches = 0;
     for (size_t first = 0, last; first < count; first = last) {
+        ++ctx->decode_sub_batches;
         for (last = first; last < count && take(last, last == first); ++last) {}
         const size_t m = last - first;
         const int32_t *d_status = nullptr;

@@ -145,6 +145,7 @@ struct ke_ctx {
     size_t h_meta_bytes = 0;
     bool ssim_exact = false;         // ke_ssim_set_mode: false = integer-sum kernel (default), true = fp64-carry kernel
     float *margin_cur = nullptr;     // device array the hash kernels of the CURRENT call write tie margins to (slot = hash slot)
+    int64_t decode_sub_batches = 0;  // sub-batches the last ke_decode_sub_batches worked its images off in (ke_last_decode_sub_batches)
     bool dct_tables_ready = false;   // __constant__ tables are per device: uploaded once per context
 };
 

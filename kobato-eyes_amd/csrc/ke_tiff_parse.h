@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 enum { KE_TIFF_OK = 0, KE_TIFF_UNSUPPORTED = 1, KE_TIFF_CORRUPT = 2 };
@@ -43,11 +44,13 @@ struct KeTiffBytes {
 };
 static const int ke_tiff_unit[17] = {0, 1, 1, 2, 4, 8, 1, 1, 2, 4, 8, 4, 8, 4, 0, 0, 8};
 
-// The directory reading shared with the decoder for compressed files (ke_tiffc_parse.h).  compression == nullptr: the
-// uncompressed whitelist below, ke_parse_tiff's.  Otherwise the same reading for a file whose Compression is 5 (LZW) or 32773
-// (PackBits), written to *compression: a strip is a stream of its own there, so the raw decoder's strip rules (only the last
-// offset counts, every strip whole in the file) are the caller's to replace -- one offset per strip of RowsPerStrip rows.
-static inline void ke_parse_tiff_directory(const uint8_t *p, size_t size, std::vector<uint32_t> *strips, KeTiffInfo &info, uint32_t *compression) {
+// The directory reading shared with the decoders for compressed files (ke_tiffc_parse.h, ke_tiffz_parse.h).  compression ==
+// nullptr: the uncompressed whitelist below, ke_parse_tiff's.  Otherwise the same reading for a file whose Compression is one
+// of `accepts` -- the caller's: 5 (LZW) and 32773 (PackBits), or 8 and 32946 (deflate) --, written to *compression: a strip is a
+// stream of its own there, so the raw decoder's strip rules (only the last offset counts, every strip whole in the file) are
+// the caller's to replace -- one offset per strip of RowsPerStrip rows.
+static inline void ke_parse_tiff_directory(const uint8_t *p, size_t size, std::vector<uint32_t> *strips, KeTiffInfo &info, uint32_t *compression,
+                                           std::initializer_list<uint32_t> accepts = {}) {
     std::memset(&info, 0, sizeof info);
     info.status = KE_TIFF_CORRUPT;
     if (size < 8) return;
@@ -103,7 +106,9 @@ static inline void ke_parse_tiff_directory(const uint8_t *p, size_t size, std::v
     if (!scalar(T_COMP, 1, comp) || !scalar(T_PLANAR, 1, planar) || !scalar(T_PHOTO, 0, photo) || !scalar(T_FILL, 1, fill) ||
         !scalar(T_ORIENT, 1, orient) || !scalar(T_SPP, 1, spp))
         return;
-    if (compression ? (comp != 5 && comp != 32773) : comp != 1) return;
+    bool accepted = !compression && comp == 1;
+    for (uint32_t a : accepts) accepted = accepted || (compression && comp == a);
+    if (!accepted) return;
     if (compression) *compression = comp;
     if (planar != 1 || fill != 1 || orient != 1 || photo > 3) return;
     if (!tags[T_WIDTH].have || !tags[T_LENGTH].have || !scalar(T_WIDTH, 0, W) || !scalar(T_LENGTH, 0, H)) return;

@@ -25,19 +25,23 @@
 
 struct KeTiffcInfo {
     KeTiffInfo t;                        // t.nstrips strips of t.rows_per_strip rows (the last one of what is left)
-    int32_t compression, predictor;      // 5 / 32773; 1 / 2
+    int32_t compression, predictor;      // 5 / 32773 (ke_tiffz_parse.h: 8 / 32946); 1 / 2
 };
 struct KeTiffcStrip { uint32_t off, bytes; };      // inside the file
 
 enum { KE_TIFFC_MAX_PIXELS = 1 << 26 };            // per file: the strips' planes are scratch memory next to the pixels
 
+// The parse of a strip file whose Compression is one of `accepts`: what the decoder of deflate files (ke_tiffz_parse.h) shares
+// with this one -- libtiff's directory reader decides for both, so the whitelist above is the same; the stream rules (the
+// predictor a codec does not know, the opening of an LZW strip) go by the file's compression.
 // strips: the image's strips are appended (nothing is appended unless the status is KE_TIFF_OK)
-static inline void ke_parse_tiffc(const uint8_t *p, size_t size, std::vector<KeTiffcStrip> *strips, KeTiffcInfo &info) {
+static inline void ke_parse_tiff_compressed(const uint8_t *p, size_t size, std::vector<KeTiffcStrip> *strips, KeTiffcInfo &info,
+                                            std::initializer_list<uint32_t> accepts) {
     uint32_t comp = 0;
     std::vector<uint32_t> offs;
     info.compression = 0;
     info.predictor = 1;
-    ke_parse_tiff_directory(p, size, &offs, info.t, &comp);
+    ke_parse_tiff_directory(p, size, &offs, info.t, &comp, accepts);
     if (info.t.status != KE_TIFF_OK) return;
     KeTiffInfo &t = info.t;
     t.status = KE_TIFF_UNSUPPORTED;
@@ -83,8 +87,8 @@ static inline void ke_parse_tiffc(const uint8_t *p, size_t size, std::vector<KeT
         if (pred.type != 3 || pred.count != 1) return;
         const uint32_t v = value(pred, 0);
         if (v != 1 && v != 2) return;
-        // the tag belongs to libtiff's LZW codec: in a PackBits file libtiff does not know it and the samples stay as stored
-        info.predictor = comp == KE_TIFFC_LZW ? (int32_t)v : 1;
+        // the tag belongs to libtiff's LZW and ZIP codecs: in a PackBits file libtiff does not know it and the samples stay as stored
+        info.predictor = comp == KE_TIFFC_PACKBITS ? 1 : (int32_t)v;
     }
     if ((uint64_t)t.width * t.height > KE_TIFFC_MAX_PIXELS) return;
     const uint64_t stride = (uint64_t)t.width * t.spp;
@@ -103,6 +107,29 @@ static inline void ke_parse_tiffc(const uint8_t *p, size_t size, std::vector<KeT
         for (uint32_t s = 0; s < (uint32_t)t.nstrips; ++s) strips->push_back(KeTiffcStrip{offs[s], value(counts, s)});
     info.compression = (int32_t)comp;
     t.status = KE_TIFF_OK;
+}
+
+static inline void ke_parse_tiffc(const uint8_t *p, size_t size, std::vector<KeTiffcStrip> *strips, KeTiffcInfo &info) {
+    ke_parse_tiff_compressed(p, size, strips, info, {KE_TIFFC_LZW, KE_TIFFC_PACKBITS});
+}
+
+// One strip's rows on the host (what ke_tiffc_rows does on the GPU): predictor 2 undone in place, then ke_tiff_unpack's mapping
+// into the pixels.  plane: the strip's bytes as its stream yields them; out: height * width * channels bytes.
+static inline void ke_tiffc_strip_rows_cpu(const KeTiffcInfo &info, uint8_t *plane, int y0, int rows, uint8_t *out) {
+    const KeTiffInfo &t = info.t;
+    const size_t stride = (size_t)t.width * t.spp;
+    for (int r = 0; r < rows; ++r) {
+        uint8_t *row = plane + (size_t)r * stride;
+        if (info.predictor == 2)
+            for (size_t k = (size_t)t.spp; k < stride; ++k) row[k] = (uint8_t)(row[k] + row[k - (size_t)t.spp]);
+        uint8_t *dst = out + (size_t)(y0 + r) * t.width * t.channels;
+        if (t.spp == t.channels) {
+            for (size_t k = 0; k < stride; ++k) dst[k] = t.mapped ? t.lut[row[k]] : row[k];
+        } else {
+            for (int x = 0; x < t.width; ++x)
+                for (int c = 0; c < 3; ++c) dst[3 * (size_t)x + c] = row[4 * (size_t)x + c];
+        }
+    }
 }
 
 #ifndef __HIPCC__
@@ -139,18 +166,7 @@ static inline int ke_tiffc_decode_cpu(const uint8_t *file, const KeTiffcInfo &in
         const int st = info.compression == KE_TIFFC_LZW ? ke_tiffc_lzw(src, 0u, strips[(size_t)s].bytes, want, dict, sink)
                                                        : ke_tiffc_packbits(src, 0u, strips[(size_t)s].bytes, want, sink);
         if (st != KE_TIFFC_OK) return st;
-        for (int r = 0; r < rows; ++r) {
-            uint8_t *row = plane.data() + (size_t)r * stride;
-            if (info.predictor == 2)
-                for (size_t k = (size_t)t.spp; k < stride; ++k) row[k] = (uint8_t)(row[k] + row[k - (size_t)t.spp]);
-            uint8_t *dst = out + (size_t)(y0 + r) * t.width * t.channels;
-            if (t.spp == t.channels) {
-                for (size_t k = 0; k < stride; ++k) dst[k] = t.mapped ? t.lut[row[k]] : row[k];
-            } else {
-                for (int x = 0; x < t.width; ++x)
-                    for (int c = 0; c < 3; ++c) dst[3 * (size_t)x + c] = row[4 * (size_t)x + c];
-            }
-        }
+        ke_tiffc_strip_rows_cpu(info, plane.data(), y0, rows, out);
     }
     return KE_TIFFC_OK;
 }

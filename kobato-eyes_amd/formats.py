@@ -31,6 +31,8 @@ FORMATS = (
            f"Pixels of uncompressed 8-bit TIFF files unpacked on the GPU ({_TIFF_SHAPES})"),
     Format("tiffc", (".tif", ".tiff"), "KE_GPU_TIFF", "KE_GPU_TIFF_COMPRESSED", "tiff", False,
            "Pixels of LZW and PackBits 8-bit TIFF files decoded on the GPU (the shapes of ``tiff_decode``)"),
+    Format("tiffz", (".tif", ".tiff"), "KE_GPU_TIFF", "KE_GPU_TIFF_DEFLATE", "tiff", False,
+           "Pixels of deflate-compressed 8-bit TIFF files (Compression 8 or 32946) decoded on the GPU (the shapes of ``tiff_decode``)"),
     Format("webp", (".webp",), "KE_GPU_WEBP", None, None, False,
            'RGB pixels (HxWx3) of lossy WebP files decoded on the GPU -- what ``Image.open(f).convert("RGB")`` yields'),
     Format("webpl", (".webp",), "KE_GPU_WEBP", "KE_GPU_WEBP_LOSSLESS", "webp", False,

@@ -106,8 +106,8 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
     out: list = [None] * len(pairs)
     count = {"decodes": 0, "gpu_decodes": 0, "fit_launches": 0, "ssim_launches": 0, "pairs": len(pairs)}
 
-    # follow-ups come after their base: tiffc takes the LZW and PackBits files the unpacker left out, webpl what the lossy
-    # decoder did not place, webpa lossy files with an alpha plane (RGBA, composited below)
+    # follow-ups come after their base: tiffc takes the LZW and PackBits files the unpacker left out, tiffz the deflate ones, webpl
+    # what the lossy decoder did not place, webpa lossy files with an alpha plane (RGBA, composited below)
     gpu_kinds = dict(enabled_kinds("refine"))
 
     def decode_on_gpu(need: list, placed: dict, buffers: list) -> None:
@@ -136,7 +136,7 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
             # KE_GPU_WEBP_ALPHA=1 -- composited over white
             orient = (flags >> 8) & 15
             turn = fits & (c == 3) & ((flags & 3) == 1) & (orient >= 2) & (orient <= 8) if kind == "jpeg" else np.zeros(len(paths), bool)
-            over = fits & (c == 4) & ((flags & 3) == 0) if kind in ("png", "bmp", "tiff", "tiffc") else np.zeros(len(paths), bool)
+            over = fits & (c == 4) & ((flags & 3) == 0) if kind in ("png", "bmp", "tiff", "tiffc", "tiffz") else np.zeros(len(paths), bool)
             if kind == "webpa":                                     # every file it takes carries the transparency bit: the orientation decides
                 over = fits & (c == 4) & ((flags & 1) == 0)
             fix = np.nonzero(turn | over)[0]
