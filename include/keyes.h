@@ -203,7 +203,7 @@ int ke_png_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, co
  * `convert("L")` makes of them -- what the reference's hashes see (src/sig/phash.py:25) -- with channels = 1.  The header is
  * read as BmpImageFile._bitmap reads it (defaults for the colour count and the data offset, padded bottom-up rows unless the
  * height's top byte is 0xFF); the files go to the device as they are and one kernel writes packed top-down rows.  OS/2
- * headers, RLE, 1 / 4 / 16 bits, other masks: KE_JPEG_UNSUPPORTED_ (1) per file; pixel data that ends early:
+ * headers, RLE, 1 / 4 / 16 bits (ke_bmpx_decode), other masks: KE_JPEG_UNSUPPORTED_ (1) per file; pixel data that ends early:
  * KE_JPEG_CORRUPT_ (2) (Pillow: "image file is truncated").  Arguments and conventions as ke_jpeg_probe / ke_jpeg_decode;
  * channels is 1, 3 or 4.  ke_bmp_caveats reports no flags (the format has no orientation tag; alpha shows as channels = 4). */
 int ke_bmp_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
@@ -211,6 +211,36 @@ int ke_bmp_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *
 int ke_bmp_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                   uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
 int ke_bmp_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
+
+/* ---- RLE, 1 / 4-bit and 16-bit BMP files decoded on the GPU: the same step (src/core/fastsig.py:31-34; src/dup/scanner.py:16-28
+ * ranks the format among the keepers) for the BMP files ke_bmp_decode returns as unsupported -- for the RLE files a Python loop in
+ * Pillow (BmpImagePlugin.BmpRleDecoder: two read(1) per code), the slowest route a scan can meet.  Taken, with the header read as
+ * ke_bmp_decode reads it (the same header sizes, limits and defaults): RLE8 (compression 1 with 8 bits) and RLE4 (compression 2
+ * with 4 bits), bottom-up and top-down; uncompressed 1-bit and 4-bit palette files (Pillow's P;1 and P;4: the most significant
+ * bit or nibble first) -- all of these as the luma `convert("L")` makes of them, channels = 1, an index beyond the palette black,
+ * the indices themselves where the palette is the gray identity (mode L), 0 / 255 for the two-colour 1-bit file whose palette
+ * is black then white (mode 1); 16-bit files as RGB, channels = 3: compression 0 and BITFIELDS 0x7C00 / 0x3E0 / 0x1F as 5-5-5,
+ * BITFIELDS 0xF800 / 0x7E0 / 0x1F as 5-6-5, a field of n bits expanded as floor(v * 255 / (2^n - 1)).  The RLE stream is read
+ * as BmpRleDecoder reads it, state for state (ke_bmpx_core.h lists the rules): a run is cut at the row's end and does not wrap,
+ * an absolute run spills into the next row, an RLE4 absolute run of an odd n yields n - 1 pixels, the byte skipped behind an
+ * absolute run goes by the position in the file, what lies beyond width x height is dropped.  One thread per file walks the
+ * codes and writes records, a second kernel expands the records in parallel; 1 / 4 / 16-bit rows are unpacked by one kernel.
+ * KE_JPEG_UNSUPPORTED_ (1), left to Pillow although it opens them: RLE8 with another depth than 8 and RLE4 with another than 4;
+ * an uncompressed 1- or 4-bit file whose palette passes Pillow's grayscale test in any other way than the two-colour case above
+ * (Pillow then reads the packed bytes as 8-bit or 1-bit samples); an RLE file with the black-then-white palette; and -- Pillow
+ * raises or not -- an RLE file of more than 2 GiB, more than 256 colours, a palette that leaves the file, other 16-bit masks, compression 4 / 5, the 12-byte
+ * OS/2 header, and everything ke_bmp_decode takes.  KE_JPEG_CORRUPT_ (2), where Pillow raises: a stream that ends (end of
+ * bitmap, a missing byte) before width x height pixels ("not enough image data"), known only after the walk, so that
+ * ke_bmpx_probe can say 0 where ke_bmpx_decode says 2; uncompressed rows that leave the file ("image file is truncated"; the
+ * padding of the last stored row may be missing, as for Pillow).  No file is taken by both ke_bmp_decode and ke_bmpx_decode.
+ * Arguments and conventions as ke_jpeg_probe / ke_jpeg_decode.  ke_bmpx_caveats reports no flags.  Tuning knob (environment,
+ * read at every call): KE_BMPX_SCRATCH_BYTES replaces the device scratch budget of one sub-batch -- the RLE files' records, 16
+ * bytes per two bytes of stream, up to 8 times the streams' bytes (default: half the free device memory, 1-32 GB); results do not depend on it. */
+int ke_bmpx_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                  int32_t *heights, int32_t *channels, int32_t *status_out);
+int ke_bmpx_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                   uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+int ke_bmpx_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
 
 /* ---- GIF files on the GPU: the same step for the first frame of a GIF file -- what Image.open shows, also of an animation --
  * as the luma `convert("L")` makes of it (src/sig/phash.py:25: what the reference's hashes see), channels = 1: palette index ->
@@ -526,7 +556,7 @@ double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind);
 
 /* ---- for the tests of the scratch budgets (KE_<KIND>_SCRATCH_BYTES; results do not depend on them, so nothing else shows
  * that one was honoured): the number of sub-batches in which the last decode call on this context that runs the shared
- * sub-batch loop (gif, tiffc, tiffz, webp, webpl, webpa; the other kinds keep loops of their own or need none) worked
+ * sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa; the other kinds keep loops of their own or need none) worked
  * off the images it accepted.  0 before any such call; -1 for a NULL context. */
 int64_t ke_last_decode_sub_batches(ke_ctx *ctx);
 

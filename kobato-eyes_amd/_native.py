@@ -358,7 +358,7 @@ class Context:
         return float(self._lib.ke_last_kernel_ms(self._h, kind))
 
     def last_decode_sub_batches(self) -> int:
-        """Sub-batches of the last decode call that ran the shared sub-batch loop (gif, tiffc, tiffz, webp, webpl, webpa)."""
+        """Sub-batches of the last decode call that ran the shared sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa)."""
         return int(self._lib.ke_last_decode_sub_batches(self._h))
 
     # -- hashing ----------------------------------------------------------------------------

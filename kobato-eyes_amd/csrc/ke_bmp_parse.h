@@ -5,7 +5,7 @@
 // last as the luma `convert("L")` makes of them, which is what the reference's hashes see (src/sig/phash.py:25).  The header
 // is read the way BmpImageFile._bitmap reads it (field positions, the defaults for `colors` and for the data offset, rows of
 // ((width * bits + 31) >> 3) & ~3 bytes, bottom-up unless the height's top byte is 0xFF).  Everything else -- OS/2 headers,
-// RLE, 1 / 4 / 16 bits, other masks, odd palette sizes -- is KE_BMP_UNSUPPORTED and stays with Pillow; a file whose pixel data
+// RLE, 1 / 4 / 16 bits (ke_bmpx_parse.h takes those), other masks, odd palette sizes -- is KE_BMP_UNSUPPORTED; a file whose pixel data
 // ends early is KE_BMP_CORRUPT (Pillow: "image file is truncated", the reference drops the file, src/core/fastsig.py:36-37).
 #pragma once
 
@@ -26,36 +26,63 @@ struct KeBmpInfo {
     uint8_t lut[256];                    // 8 bits: palette index -> luma (ImagingConvert's rounded weights, as for PNG palettes)
 };
 
-static inline void ke_parse_bmp(const uint8_t *p, size_t size, KeBmpInfo &info) {
-    std::memset(&info, 0, sizeof info);
-    info.status = KE_BMP_CORRUPT;
-    if (size < 18 || p[0] != 'B' || p[1] != 'M') return;                       // Pillow: "Not a BMP file"
+// What BmpImageFile._bitmap reads of a file before it looks at the bit depth, shared with the decoder of the other depths and of
+// RLE files (ke_bmpx_parse.h): the fields, the limits, the BITFIELDS masks inside or behind the header, the defaults.
+struct KeBmpHeader {
+    uint64_t offset;                     // the data offset as the file gives it, stepped over the palette where Pillow does that
+    uint64_t width, height, colors;      // colors: the header's, or 1 << bits for the depths that have a palette
+    uint32_t bits, comp;
+    uint32_t mask[4];                    // BITFIELDS: R, G, B, A
+    size_t pos;                          // behind the header and the masks: where a palette starts
+    bool flip;                           // rows stored top to bottom
+};
+
+// KE_BMP_OK: go on with `h`; otherwise the file's status.
+static inline int ke_read_bmp_header(const uint8_t *p, size_t size, KeBmpHeader &h) {
+    if (size < 18 || p[0] != 'B' || p[1] != 'M') return KE_BMP_CORRUPT;        // Pillow: "Not a BMP file"
     auto le32 = [&](size_t o) { return (uint32_t)p[o] | ((uint32_t)p[o + 1] << 8) | ((uint32_t)p[o + 2] << 16) | ((uint32_t)p[o + 3] << 24); };
     auto le16 = [&](size_t o) { return (uint32_t)p[o] | ((uint32_t)p[o + 1] << 8); };
-    info.status = KE_BMP_UNSUPPORTED;
-    uint64_t offset = le32(10);
+    h.offset = le32(10);
     const uint32_t hs = le32(14);
-    if (!(hs == 40 || hs == 52 || hs == 56 || hs == 64 || hs == 108 || hs == 124) || 14 + (size_t)hs > size) return;
+    if (!(hs == 40 || hs == 52 || hs == 56 || hs == 64 || hs == 108 || hs == 124) || 14 + (size_t)hs > size) return KE_BMP_UNSUPPORTED;
     const size_t hd = 18;                                                       // header_data: the header without its size field
-    const bool flip = p[hd + 7] == 0xFF;
-    const uint64_t width = le32(hd), height = flip ? (1ull << 32) - le32(hd + 4) : le32(hd + 4);
-    const uint32_t bits = le16(hd + 10), comp = le32(hd + 12);
-    uint64_t colors = le32(hd + 28);
-    if (width == 0 || height == 0 || width > KE_BMP_MAX_WIDTH || height > (1u << 28) || width * height > (1ull << 28)) return;
-    size_t pos = 14 + (size_t)hs;
-    uint32_t mask[4] = {0, 0, 0, 0};
-    if (comp == 3) {                                                            // BITFIELDS
+    h.flip = p[hd + 7] == 0xFF;
+    h.width = le32(hd);
+    h.height = h.flip ? (1ull << 32) - le32(hd + 4) : le32(hd + 4);
+    h.bits = le16(hd + 10);
+    h.comp = le32(hd + 12);
+    h.colors = le32(hd + 28);
+    if (h.width == 0 || h.height == 0 || h.width > KE_BMP_MAX_WIDTH || h.height > (1u << 28) || h.width * h.height > (1ull << 28))
+        return KE_BMP_UNSUPPORTED;
+    h.pos = 14 + (size_t)hs;
+    h.mask[0] = h.mask[1] = h.mask[2] = h.mask[3] = 0;
+    if (h.comp == 3) {                                                          // BITFIELDS
         if (hs >= 52) {
-            for (int k = 0; k < 3; ++k) mask[k] = le32(hd + 36 + 4 * (size_t)k);
-            if (hs >= 56) mask[3] = le32(hd + 48);
+            for (int k = 0; k < 3; ++k) h.mask[k] = le32(hd + 36 + 4 * (size_t)k);
+            if (hs >= 56) h.mask[3] = le32(hd + 48);
         } else {
-            if (pos + 12 > size) return;
-            for (int k = 0; k < 3; ++k) mask[k] = le32(pos + 4 * (size_t)k);
-            pos += 12;
+            if (h.pos + 12 > size) return KE_BMP_UNSUPPORTED;
+            for (int k = 0; k < 3; ++k) h.mask[k] = le32(h.pos + 4 * (size_t)k);
+            h.pos += 12;
         }
     }
-    if (colors == 0) colors = 1ull << bits;
-    if (offset == 14 + (uint64_t)hs && bits <= 8) offset += 4 * colors;
+    if (h.colors == 0 && h.bits <= 8) h.colors = 1ull << h.bits;              // (only a depth with a palette uses the value)
+    if (h.offset == 14 + (uint64_t)hs && h.bits <= 8) h.offset += 4 * h.colors;
+    return KE_BMP_OK;
+}
+
+static inline void ke_parse_bmp(const uint8_t *p, size_t size, KeBmpInfo &info) {
+    std::memset(&info, 0, sizeof info);
+    KeBmpHeader hdr;
+    info.status = ke_read_bmp_header(p, size, hdr);
+    if (info.status != KE_BMP_OK) return;
+    info.status = KE_BMP_UNSUPPORTED;
+    uint64_t offset = hdr.offset;
+    const uint64_t width = hdr.width, height = hdr.height, colors = hdr.colors;
+    const uint32_t bits = hdr.bits, comp = hdr.comp;
+    const uint32_t *mask = hdr.mask;
+    const bool flip = hdr.flip;
+    size_t pos = hdr.pos;
     if (!(bits == 8 || bits == 24 || bits == 32)) return;
     info.channels = bits == 8 ? 1 : 3;
     info.pick[0] = 2; info.pick[1] = 1; info.pick[2] = 0; info.pick[3] = 3;    // BGR / BGRX
@@ -74,7 +101,7 @@ static inline void ke_parse_bmp(const uint8_t *p, size_t size, KeBmpInfo &info) 
             };
             int found = -1;
             for (int k = 0; k < 8 && found < 0; ++k)
-                if (std::memcmp(known[k].m, mask, sizeof mask) == 0) found = k;
+                if (std::memcmp(known[k].m, mask, sizeof hdr.mask) == 0) found = k;
             if (found < 0) return;
             std::memcpy(info.pick, known[found].pick, 4);
             info.channels = known[found].alpha ? 4 : 3;

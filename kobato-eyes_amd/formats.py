@@ -25,6 +25,9 @@ FORMATS = (
            "Pixels of PNG files decoded on the GPU (HxW, HxWx3 or HxWx4)"),
     Format("bmp", (".bmp",), "KE_GPU_BMP", None, None, False,
            "Pixels of uncompressed BMP files unpacked on the GPU (HxW luma of a palette file, HxWx3 or HxWx4)"),
+    Format("bmpx", (".bmp",), "KE_GPU_BMP", "KE_GPU_BMP_EXTENDED", "bmp", False,
+           "Pixels of RLE8 / RLE4, uncompressed 1- and 4-bit and 16-bit BMP files decoded on the GPU (HxW luma of a palette file, HxWx3 "
+           "of a 16-bit file)"),
     Format("gif", (".gif",), "KE_GPU_GIF", None, None, True,
            'Luma (HxW) of the first frame of GIF files decoded on the GPU -- what ``Image.open(f).convert("L")`` yields'),
     Format("tiff", (".tif", ".tiff"), "KE_GPU_TIFF", None, None, False,

@@ -106,7 +106,8 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
     out: list = [None] * len(pairs)
     count = {"decodes": 0, "gpu_decodes": 0, "fit_launches": 0, "ssim_launches": 0, "pairs": len(pairs)}
 
-    # follow-ups come after their base: tiffc takes the LZW and PackBits files the unpacker left out, tiffz the deflate ones, webpl
+    # follow-ups come after their base: bmpx takes the RLE, 1 / 4-bit and 16-bit files the BMP unpacker left out (only its 16-bit
+    # files are pictures: the rest is luma), tiffc the LZW and PackBits files the TIFF unpacker left out, tiffz the deflate ones, webpl
     # what the lossy decoder did not place, webpa lossy files with an alpha plane (RGBA, composited below)
     gpu_kinds = dict(enabled_kinds("refine"))
 

@@ -77,7 +77,8 @@ def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) ->
     files are read, decoded and shrunk without their pixels ever being in host memory; files left out (other formats,
     refused, damaged, turned) are for ``_decode``.  ``KE_GPU_REFINE_DECODE=0`` turns the route off."""
     out: dict = {}
-    # after each suffix's own decoder the opt-in ones, for the files that one left out: tiffc (LZW and PackBits), tiffz (deflate),
+    # after each suffix's own decoder the opt-in ones, for the files that one left out: bmpx (RLE, 1 / 4-bit and 16-bit BMP), tiffc
+    # (LZW and PackBits), tiffz (deflate),
     # webpl (lossless), webpa (lossy files with an alpha plane: convert("L") of RGBA ignores alpha)
     kinds = enabled_kinds("refine_parallel")
     if not kinds:
