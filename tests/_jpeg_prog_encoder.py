@@ -2,8 +2,8 @@
 writer (libjpeg-turbo) only ever produces libjpeg's default script; files from other encoders (mozjpeg: what most image hosts
 serve) order and split their scans differently -- DC scans for one, two or all components, spectral bands cut anywhere,
 successive approximation from any bit down -- and the decoder has to be held against Pillow on those too.  The entropy coding
-follows T.81 Annex G as libjpeg's jcphuff.c does (one end-of-band symbol per block, no end-of-band runs; the standard Huffman
-tables of Annex K, taken from a file Pillow writes, carry every symbol that needs)."""
+is tests/_jpeg_write.py's (T.81 Annex G as libjpeg's jcphuff.c does it); as called here it writes one end-of-band symbol per
+block, no end-of-band runs and no restarts, with the standard Huffman tables of Annex K, taken from a file Pillow writes."""
 from __future__ import annotations
 
 import io
@@ -11,6 +11,8 @@ import struct
 
 import numpy as np
 from PIL import Image
+
+import _jpeg_write as W
 
 
 def _standard_tables():
@@ -45,136 +47,14 @@ def _standard_tables():
 _TABLES, _RAW = _standard_tables()
 
 
-class _Bits:
-    def __init__(self):
-        self.out = bytearray()
-        self.acc = 0
-        self.n = 0
-
-    def put(self, value: int, length: int):
-        if length == 0:
-            return
-        self.acc = (self.acc << length) | (value & ((1 << length) - 1))
-        self.n += length
-        while self.n >= 8:
-            byte = (self.acc >> (self.n - 8)) & 255
-            self.out.append(byte)
-            if byte == 0xFF:
-                self.out.append(0)
-            self.n -= 8
-        self.acc &= (1 << self.n) - 1
-
-    def finish(self) -> bytes:
-        if self.n:
-            self.put((1 << (8 - self.n)) - 1, 8 - self.n)          # pad with ones
-        return bytes(self.out)
-
-
-def _category(v: int) -> int:
-    return int(abs(v)).bit_length()
-
-
-def _magnitude_bits(v: int, size: int) -> int:
-    return v if v >= 0 else v + (1 << size) - 1
-
-
-def encode(width: int, height: int, comps, coefs, script, qtables=None) -> bytes:
+def encode(width: int, height: int, comps, coefs, script, qtables=None, tables=None, **options) -> bytes:
     """comps: [(id, hs, vs)]; coefs[c]: int array [padded block rows][padded block columns][64] in zigzag order (padded to whole
-    MCUs); script: [(component indices, ss, se, ah, al)] -- any order T.81 allows."""
-    hmax, vmax = max(c[1] for c in comps), max(c[2] for c in comps)
-    mcus_x, mcus_y = -(-width // (8 * hmax)), -(-height // (8 * vmax))
-    out = bytearray(b"\xff\xd8" + b"\xff\xe0" + struct.pack(">H5sBBBHHBB", 16, b"JFIF\0", 1, 1, 0, 1, 1, 0, 0))
+    MCUs); script: [(component indices, ss, se, ah, al)] -- any order T.81 allows.  tables: what tests/_jpeg_write.py's `write`
+    takes as `htables` instead of the standard pair; options: its other keywords (restart intervals, end-of-band runs, ...)."""
     qtables = qtables or [np.ones(64, np.uint8), np.ones(64, np.uint8)]
-    for k, q in enumerate(qtables):
-        out += b"\xff\xdb" + struct.pack(">HB", 67, k) + bytes(int(v) for v in q)
-    out += b"\xff\xc2" + struct.pack(">HBHHB", 8 + 3 * len(comps), 8, height, width, len(comps))
-    for k, (cid, hs, vs) in enumerate(comps):
-        out += bytes([cid, (hs << 4) | vs, 0 if k == 0 else 1])
-    for key in ((0, 0), (1, 0)):
-        out += b"\xff\xc4" + struct.pack(">H", 2 + len(_RAW[key])) + _RAW[key]
-    dc, ac = _TABLES[(0, 0)], _TABLES[(1, 0)]
-    for (members, ss, se, ah, al) in script:
-        out += b"\xff\xda" + struct.pack(">HB", 6 + 2 * len(members), len(members))
-        for c in members:
-            out += bytes([comps[c][0], 0x00])
-        out += bytes([ss, se, (ah << 4) | al])
-        bits = _Bits()
-        if ss == 0:
-            pred = [0] * len(comps)
-            if len(members) > 1:
-                units = [(my, mx) for my in range(mcus_y) for mx in range(mcus_x)]
-            else:
-                c = members[0]
-                cw, ch = -(-width * comps[c][1] // hmax), -(-height * comps[c][2] // vmax)
-                units = [(by, bx) for by in range(-(-ch // 8)) for bx in range(-(-cw // 8))]
-            for (uy, ux) in units:
-                for c in members:
-                    hs, vs = (comps[c][1], comps[c][2]) if len(members) > 1 else (1, 1)
-                    for by in range(vs):
-                        for bx in range(hs):
-                            v = int(coefs[c][uy * vs + by, ux * hs + bx, 0])
-                            if ah == 0:
-                                t = v >> al                                  # arithmetic shift, as jcphuff does for DC
-                                diff = t - pred[c]
-                                pred[c] = t
-                                size = _category(diff)
-                                bits.put(*dc[size])
-                                bits.put(_magnitude_bits(diff, size), size)
-                            else:
-                                bits.put((v >> al) & 1, 1)
-        else:
-            c = members[0]
-            cw, ch = -(-width * comps[c][1] // hmax), -(-height * comps[c][2] // vmax)
-            for by in range(-(-ch // 8)):
-                for bx in range(-(-cw // 8)):
-                    blk = coefs[c][by, bx]
-                    if ah == 0:
-                        run = 0
-                        for k in range(ss, se + 1):
-                            v = int(blk[k])
-                            t = (abs(v) >> al) * (1 if v >= 0 else -1)
-                            if t == 0:
-                                run += 1
-                                continue
-                            while run > 15:
-                                bits.put(*ac[0xF0])
-                                run -= 16
-                            size = _category(t)
-                            bits.put(*ac[(run << 4) | size])
-                            bits.put(_magnitude_bits(t, size), size)
-                            run = 0
-                        if run > 0:
-                            bits.put(*ac[0x00])
-                    else:
-                        absval = [abs(int(blk[k])) >> al for k in range(64)]
-                        eob = max([k for k in range(ss, se + 1) if absval[k] == 1], default=-1)
-                        run, pending = 0, []
-                        for k in range(ss, se + 1):
-                            t = absval[k]
-                            if t == 0:
-                                run += 1
-                                continue
-                            while run > 15 and k <= eob:
-                                bits.put(*ac[0xF0])
-                                for b in pending:
-                                    bits.put(b, 1)
-                                pending = []
-                                run -= 16
-                            if t > 1:                                        # already nonzero: one more bit of it, sent behind the next symbol
-                                pending.append(t & 1)
-                                continue
-                            bits.put(*ac[(run << 4) | 1])
-                            bits.put(1 if int(blk[k]) >= 0 else 0, 1)
-                            for b in pending:
-                                bits.put(b, 1)
-                            pending = []
-                            run = 0
-                        if run > 0 or pending:
-                            bits.put(*ac[0x00])
-                            for b in pending:
-                                bits.put(b, 1)
-        out += bits.finish()
-    return bytes(out) + b"\xff\xd9"
+    standard = {key: W.Table(raw[1:17], raw[17:]) for key, raw in _RAW.items() if key[1] == 0}
+    full = [(cid, hs, vs, 0 if k == 0 else 1, 0, 0) for k, (cid, hs, vs) in enumerate(comps)]
+    return W.write(width, height, full, coefs, qtables, tables or standard, sof=0xC2, script=script, **options)[0]
 
 
 def random_script(rng, ncomp: int):

@@ -142,3 +142,71 @@ def test_progressive_files_with_any_scan_script_decode_as_pillow_does():
         assert out.shape == ref.shape and np.array_equal(out, ref), name
         n += 1
     assert n == 120
+
+
+# ---- hand-written entropy streams (tests/_jpeg_write.py, tests/_jpeg_stream_cases.py) ----------------------------------------------
+def test_hand_written_streams_cover_what_they_are_for():
+    """The coverage assertions of every family, from the writer's facts: code lengths 1..16 for DC and AC symbols, the 9/10-bit
+    edge, stuffed pairs at every window offset, the EOI at every lane and step edge of the end search, EOB0..EOB14, ..."""
+    import _jpeg_stream_cases as S
+
+    counts = S.coverage()
+    assert sum(counts.values()) == len(S.valid()) and min(counts.values()) >= 10, counts
+
+
+def test_valid_hand_written_streams_decode_as_pillow_does():
+    """Every V case is taken, with Pillow's shape and pixels: nothing is left out."""
+    import _jpeg_stream_cases as S
+
+    L = _lib()
+    refs = S.references()
+    for name, data, _ in S.valid():
+        ref = refs[name]
+        assert ref is not None, name
+        st, out = _decode(L, data)
+        assert st == 0, name
+        assert out.shape == ref.shape and np.array_equal(out, ref), name
+
+
+def test_tolerated_streams_get_their_pinned_status_or_pillows_pixels():
+    """What libjpeg patches up without an error: Pillow yields pixels, the decoder gives the pinned status -- and where that is
+    0, Pillow's pixels."""
+    import _jpeg_stream_cases as S
+
+    L = _lib()
+    refs = S.references()
+    for name, data, expected, why in S.tolerated():
+        assert refs[name] is not None, name
+        st, out = _decode(L, data)
+        assert st == expected, (name, st, why)
+        if st == 0:
+            assert out.shape == refs[name].shape and np.array_equal(out, refs[name]), name
+    assert len(S.tolerated()) == 13
+
+
+def test_unusable_huffman_tables_are_refused_where_pillow_raises():
+    import _jpeg_stream_cases as S
+
+    L = _lib()
+    for name, data in S.refused():
+        assert S.pillow(data) is None, name
+        assert _decode(L, data)[0] == 2, name
+    assert len(S.refused()) == 5
+
+
+def test_progressive_encoder_still_writes_the_same_files():
+    """tests/_jpeg_prog_encoder.py goes through tests/_jpeg_write.py now: the files of J.scripted and E.random_file are the ones
+    from before, byte for byte (the census pinned in fuzz_jpeg_damage and the scripted tests depend on them)."""
+    import hashlib
+
+    import _jpeg_prog_encoder as E
+
+    h = hashlib.sha256()
+    for _, data, _ in J.scripted(120, 5):
+        h.update(data)
+    assert h.hexdigest() == "4ea1c80e73af5a8154369c3052d092cc99c0c759f3072e3f695e75008594b143"
+    h = hashlib.sha256()
+    rng = np.random.default_rng(77)
+    for k in range(40):
+        h.update(E.random_file(rng, 10 + k, 7 + k, ("444", "422", "420", "440")[k % 4], k % 5 == 0)[0])
+    assert h.hexdigest() == "2d981e17b932967bf1e2d3dd98420a225c24a29f94d4ddf5113898967a44bfda"
