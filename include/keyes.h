@@ -430,8 +430,10 @@ int ke_luma_tiles_uniform(ke_ctx *ctx, const uint8_t *pixels, int64_t n, int32_t
  * `part_index` (one shard per GPU; 0/1 = everything).
  * edges_out: capacity entries (host or device); *n_edges_out = edges found, which may exceed
  * capacity -- the caller then retries with a larger buffer.  Edge order is unspecified.
- * counters_out (nullable, 4 x u64, host): [0] pairs i < j evaluated by this shard (counted by the kernel, one atomic per
- * tile, and checked against the host's closed form: the call fails if they differ),
+ * counters_out (nullable, 4 x u64, host): [0] pairs i < j this shard stands for (counted by the tile kernel, one atomic per
+ * tile -- the bucket path adds the host's closed form once on the device -- and checked against that closed form: the call
+ * fails if they differ; on the bucket path this is the tile partition's count, not the pairs whose edges this shard reports
+ * (there a pair (a, b) is reported by shard (a + b) mod part_count): only the sum over all shards, n (n - 1) / 2, has a meaning),
  * [1] sum over emitted edges of the number of shared bands (the reference's "ham=" funnel
  * counter, src/dup/scanner.py:292-299), [2] edges emitted, [3] bucket pairs of the WHOLE table (the same on every
  * shard): sum over bands and band values of C(bucket size, 2) for the buckets the reference walks (size >= 2, under
@@ -559,6 +561,13 @@ double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind);
  * sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa; the other kinds keep loops of their own or need none) worked
  * off the images it accepted.  0 before any such call; -1 for a NULL context. */
 int64_t ke_last_decode_sub_batches(ke_ctx *ctx);
+
+/* ---- for the tests of the scan's two paths (the result does not depend on the path): which one the last ke_hamming_scan
+ * on this context with n >= 2 took, as chosen on the device: 0 = all-pairs tiles, 1 = band buckets.  -1 before any such
+ * call and for a NULL context.  KE_SCAN_MODE=auto|tiles|buckets (environment, read once per process) forces a path;
+ * `buckets` still runs tiles where the bucket path is not built (band tables over 2^18 bins, n >= 2^32, no memory for the
+ * sorted copy of the table: 12 bytes per hash and band). */
+int32_t ke_last_scan_path(ke_ctx *ctx);
 
 #ifdef __cplusplus
 }

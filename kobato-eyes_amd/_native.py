@@ -34,7 +34,7 @@ EXPORTS = (
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
     "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode",
     "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash", "ke_sad_pairs", "ke_synth_rgb", "ke_synth_rgb_indexed",
-    "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches",
+    "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches", "ke_last_scan_path",
 ) + tuple(f"ke_{kind}_{call}" for kind in KINDS for call in ("probe", "decode", "caveats"))
 
 _lib: Optional[C.CDLL] = None
@@ -153,6 +153,8 @@ def load_library() -> C.CDLL:
         lib.ke_last_kernel_ms.restype = dbl
         lib.ke_last_decode_sub_batches.argtypes = [vp]
         lib.ke_last_decode_sub_batches.restype = C.c_int64
+        lib.ke_last_scan_path.argtypes = [vp]
+        lib.ke_last_scan_path.restype = i32
         _lib = lib
         return lib
 
@@ -360,6 +362,10 @@ class Context:
     def last_decode_sub_batches(self) -> int:
         """Sub-batches of the last decode call that ran the shared sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa)."""
         return int(self._lib.ke_last_decode_sub_batches(self._h))
+
+    def last_scan_path(self) -> int:
+        """Path the last hamming_scan with n >= 2 took, chosen on the device: 0 = all-pairs tiles, 1 = band buckets."""
+        return int(self._lib.ke_last_scan_path(self._h))
 
     # -- hashing ----------------------------------------------------------------------------
     def hash_uniform(self, pixels, n: int, width: int, height: int, channels: int, *, want_phash=True,

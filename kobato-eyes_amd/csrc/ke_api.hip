@@ -360,6 +360,8 @@ KE_API double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind) {
 
 KE_API int64_t ke_last_decode_sub_batches(ke_ctx *ctx) { return ctx ? ctx->decode_sub_batches : -1; }
 
+KE_API int32_t ke_last_scan_path(ke_ctx *ctx) { return ctx ? ctx->scan_path : -1; }
+
 // ---- hashing -------------------------------------------------------------------------------
 namespace {
 
@@ -879,16 +881,14 @@ KE_API int ke_hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *i
         KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_EDGES, (size_t)capacity * sizeof(ke_edge), &tmp));
         d_edges = (ke_edge *)tmp;
     }
-    KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_CNT, 4 * sizeof(unsigned long long), &tmp));
-    unsigned long long *d_cnt = (unsigned long long *)tmp;
-    KE_HIP(ctx, hipMemsetAsync(d_cnt, 0, 4 * sizeof(unsigned long long), ctx->stream));
-    unsigned long long pairs = 0;
+    unsigned long long *d_cnt = nullptr, pairs = 0;
     KE_TRY(ke_launch_scan(ctx, (const uint64_t *)d_h, (const int64_t *)d_ids, (const int64_t *)d_sizes, n, part_index,
                           part_count, threshold, band_bits, band_count, size_ratio, bucket_pair_cap, d_edges, capacity,
-                          d_cnt, &pairs, counters_out != nullptr));
-    unsigned long long h_cnt[4];
+                          &d_cnt, &pairs, counters_out != nullptr));
+    unsigned long long h_cnt[KE_SCAN_STATE_WORDS];
     KE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, ctx->stream));
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->scan_path = (int)h_cnt[4];
     *n_edges_out = (int64_t)h_cnt[2];
     if (h_cnt[0] != pairs)    // the kernel's own count of the pairs its tiles stand for against the host's closed form
         return ke_fail(ctx, KE_EHIP, "scan evaluated %llu pairs, expected %llu", h_cnt[0], pairs);

@@ -90,8 +90,9 @@ enum {
     KE_BUF_SCAN_IN,
     KE_BUF_SCAN_AUX,
     KE_BUF_SCAN_EDGES,
-    KE_BUF_SCAN_CNT,
-    KE_BUF_SCAN_HIST,
+    KE_BUF_SCAN_CNT,     // scan state, zeroed by one memset per call: counters, path word, block sums, band histogram
+    KE_BUF_SCAN_HIST,    // wide bands only: per-hash bucket lengths
+    KE_BUF_SCAN_SORT,    // bucket path: hashes sorted by band value band by band, per-bin offsets, their positions
     KE_BUF_SCAN_EXP,     // hashes expanded to matrix-core operands (64 B each)
     KE_BUF_SSIM_IN,
     KE_BUF_SSIM_AUX,
@@ -143,6 +144,7 @@ struct ke_ctx {
     size_t h_comm_bytes = 0;
     void *h_meta = nullptr;          // page-locked per-image records of a decode batch on their way to the device, and the statuses back
     size_t h_meta_bytes = 0;
+    int scan_path = -1;              // path of the last ke_hamming_scan: 0 tiles, 1 buckets (ke_last_scan_path)
     bool ssim_exact = false;         // ke_ssim_set_mode: false = integer-sum kernel (default), true = fp64-carry kernel
     float *margin_cur = nullptr;     // device array the hash kernels of the CURRENT call write tie margins to (slot = hash slot)
     int64_t decode_sub_batches = 0;  // sub-batches the last ke_decode_sub_batches worked its images off in (ke_last_decode_sub_batches)
@@ -204,8 +206,9 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
                                     int band_count, double ratio, int64_t bucket_pair_cap, unsigned long long *d_out);
 int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
                    int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
-                   int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long *d_counters,
+                   int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
                    unsigned long long *pairs_evaluated, bool want_bucket_pairs);
+constexpr int KE_SCAN_STATE_WORDS = 5;   // what ke_hamming_scan reads back: counters [0..3] and the path word
 int ke_launch_ssim(ke_ctx *ctx, const uint8_t *d_images, int w, int h, int channels, const int64_t *d_pa,
                    const int64_t *d_pb, int64_t n_pairs, double *d_out);
 int ke_launch_synth_rgb(ke_ctx *ctx, uint64_t seed, int64_t first, const int64_t *d_indices, int64_t n, int w, int h,

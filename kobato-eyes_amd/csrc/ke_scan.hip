@@ -14,6 +14,9 @@
 // re-inspect it and apply the full predicate (band lanes, ids, size ratio, bucket cap) to the original
 // 64-bit hashes and append edges through one atomic cursor.  The VALU version of the same loop
 // (2 xor + 2 popcount + min per pair) topped out at 7-8 Tpairs/s on VALU issue.
+//
+// Tables whose band buckets hold few pairs and no long bucket skip all of that: the bucket kernels further down visit only the
+// pairs inside buckets, and the choice between the two paths is made per call on the device (kPathWord).
 #include <cmath>
 
 #include <hipcub/hipcub.hpp>
@@ -51,26 +54,35 @@ struct ScanArgs {
     unsigned long long cap;
     ke_edge *edges;
     int64_t capacity;
-    unsigned long long *counters;  // [0] pairs, [1] sum of shared bands, [2] edges
+    unsigned long long *counters;  // [0] pairs, [1] sum of shared bands, [2] edges, [3] bucket pairs, [4] path (kPathWord)
     int xcd_remap;
 };
 
+// counters[kPathWord]: 0 = the all-pairs tile kernel does the scan, 1 = the bucket kernels do.  Zeroed with the counters,
+// written once per call on the device (ke_bucket_offsets) before any kernel that reads it; each path's kernels return at
+// their first instruction when it names the other.  counters[kLongestWord]: longest bucket the reference would walk.
+constexpr int kPathWord = 4, kLongestWord = 5;
+
 __device__ __forceinline__ int popc64(uint32_t lo, uint32_t hi) { return __popc(lo) + __popc(hi); }
 
-// Full predicate for one pair that already passed popcount <= threshold.
-__device__ void consider_pair(const ScanArgs &a, int64_t gi, int64_t gj, uint64_t x, uint64_t y, int pc) {
-    if (gi >= gj || gj >= a.n) return;
-    if (a.ids && a.ids[gi] == a.ids[gj]) return;                       // src/dup/scanner.py:266
+// Full predicate for one pair that already passed popcount <= threshold: true when the pair is an edge, with its bands
+// mask and the number of bands it shares.  only_band >= 0 (bucket path, which meets a pair once per band it shares): true
+// only when that band is the lowest one counted here, so that the pair appears once.  The index is kept beside the mask
+// because bands >= 31 share the mask's bit 31.
+__device__ bool pair_is_edge(const ScanArgs &a, int64_t gi, int64_t gj, uint64_t x, uint64_t y, int only_band, int *bands_out,
+                             int *shared_out) {
+    if (gi >= gj || gj >= a.n) return false;
+    if (a.ids && a.ids[gi] == a.ids[gj]) return false;                 // src/dup/scanner.py:266
     if (a.sizes && a.size_ratio > 0.0) {                               // :358-370
         const int64_t sa = a.sizes[gi], sb = a.sizes[gj];
         if (sa > 0 && sb > 0) {
             const int64_t small = sa < sb ? sa : sb, large = sa < sb ? sb : sa;
-            if (!((double)small / (double)large >= a.size_ratio)) return;
+            if (!((double)small / (double)large >= a.size_ratio)) return false;
         }
     }
     const uint64_t d = x ^ y;
     const uint64_t mask = a.band_bits >= 64 ? ~0ull : ((1ull << a.band_bits) - 1ull);
-    int bands = 0, shared = 0;
+    int bands = 0, shared = 0, first = -1;
     for (int b = 0; b < a.band_count; ++b) {
         const int sh = b * a.band_bits;
         if (((d >> sh) & mask) != 0) continue;
@@ -80,9 +92,18 @@ __device__ void consider_pair(const ScanArgs &a, int64_t gi, int64_t gj, uint64_
             if (len * (len - 1) / 2 > a.cap) continue;
         }
         bands |= 1 << (b < 31 ? b : 31);
+        if (first < 0) first = b;
         ++shared;
     }
-    if (!shared) return;
+    if (!shared) return false;
+    if (only_band >= 0 && first != only_band) return false;
+    *bands_out = bands; *shared_out = shared;
+    return true;
+}
+
+__device__ void consider_pair(const ScanArgs &a, int64_t gi, int64_t gj, uint64_t x, uint64_t y, int pc, int only_band = -1) {
+    int bands, shared;
+    if (!pair_is_edge(a, gi, gj, x, y, only_band, &bands, &shared)) return;
     atomicAdd(&a.counters[1], (unsigned long long)shared);
     const unsigned long long slot = atomicAdd(&a.counters[2], 1ull);
     if ((int64_t)slot < a.capacity) {
@@ -104,7 +125,8 @@ __device__ __forceinline__ uint32_t spread8(uint32_t b) {
 // g = 0, 1: bits 0..31 / 32..63 of x; g = 2, 3: the same bits of ~x.  A and B operands use the same image
 // (the k <-> (group, nibble) map of the instruction is the same for both, so any fixed order works).
 __global__ __launch_bounds__(256) void ke_scan_expand(const uint64_t *__restrict__ hashes, int64_t n, int64_t n_pad,
-                                                       ke_v4i *__restrict__ out) {
+                                                       ke_v4i *__restrict__ out, const unsigned long long *path) {
+    if (*path) return;                                             // the bucket kernels do this call's scan
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;     // = tile * 64 + lane
     if (e >= n_pad * 4) return;
     const int64_t i = (e >> 6) * 16 + (e & 15);
@@ -121,6 +143,7 @@ __global__ __launch_bounds__(256) void ke_scan_expand(const uint64_t *__restrict
 
 __global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) {
     __shared__ ke_v4i s_b[2][kChunk / 16 * 64];      // two chunks of 16 operand tiles
+    if (a.counters[kPathWord]) return;               // the bucket kernels do this call's scan
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // workgroup b runs on XCD b mod 8 (round-robin dispatch), each XCD has its own L2: XCD x takes the x-th eighth of this
     // launch's tiles, consecutive tiles (which share their row operands) on one L2 instead of on eight.  KE_SCAN_XCD=0: off.
@@ -246,6 +269,179 @@ __global__ void ke_hist_pairs(const uint32_t *__restrict__ hist, size_t bins, un
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0 && (part[0] | part[1] | part[2] | part[3])) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
+}
+
+// ---- bucket path: visit only the pairs that share a bucket -----------------------------------------------------------
+// consider_pair drops every pair that shares no band, so an edge exists only inside a bucket of some band -- the
+// reference's own candidate generation (src/dup/scanner.py:227-290).  The positions are counting-sorted by band value per
+// band (histogram -> exclusive offsets -> scatter of (hash, position)), then one thread per slot of a sorted run compares
+// its hash with the later members of its bucket.  Tables up to kBucketMaxBins bins: one 1024-bin block per workgroup of the two histogram
+// passes, at most 256 block sums, so a workgroup of ke_bucket_offsets adds its predecessors' sums with one value per thread.
+constexpr int kBinsPerBlock = 1024;
+constexpr size_t kBucketMaxBins = (size_t)1 << 18;
+constexpr size_t kStateBytes = 128;                                 // counters [0..3], path, longest bucket, padding
+constexpr size_t kBlockSumBytes = kBucketMaxBins / kBinsPerBlock * sizeof(uint32_t);
+// The rule between the paths (set from the sweep recorded there): buckets when the table has at least
+// kBucketMinN hashes (below, both paths cost about their launches), the walked bucket pairs are at most 1/kBucketRatio of all
+// pairs and no walked bucket is longer than kBucketLongest (one thread walks the rest of its bucket), else tiles.
+constexpr unsigned long long kBucketRatio = 6000, kBucketLongest = 260;
+constexpr int64_t kBucketMinN = 50000;
+
+__device__ __forceinline__ unsigned long long block_sum_256(unsigned long long v, unsigned long long *s4) {
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s4[0] + s4[1] + s4[2] + s4[3];
+}
+
+// per 1024-bin block: members (for the offsets), C(len, 2) over the walked buckets (counters[3], as ke_hist_pairs) and the
+// longest walked bucket
+__global__ __launch_bounds__(256) void ke_bucket_stats(const uint32_t *__restrict__ hist, size_t bins, unsigned long long cap,
+                                                        uint32_t *__restrict__ block_sums, unsigned long long *state) {
+    unsigned long long members = 0, pairs = 0, longest = 0;
+    for (int k = 0; k < kBinsPerBlock / 256; ++k) {
+        const size_t i = (size_t)blockIdx.x * kBinsPerBlock + (size_t)k * 256 + threadIdx.x;
+        if (i >= bins) break;
+        const unsigned long long len = hist[i];
+        const unsigned long long p = len * (len - 1) / 2;
+        members += len;
+        if (len >= 2 && (!cap || p <= cap)) { pairs += p; longest = len > longest ? len : longest; }
+    }
+    __shared__ unsigned long long s_m[4], s_p[4], s_l[4];
+    members = block_sum_256(members, s_m);
+    pairs = block_sum_256(pairs, s_p);
+    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_down(longest, d); longest = o > longest ? o : longest; }
+    if ((threadIdx.x & 63) == 0) s_l[threadIdx.x >> 6] = longest;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        block_sums[blockIdx.x] = (uint32_t)members;
+        if (pairs) atomicAdd(&state[3], pairs);
+        longest = max(max(s_l[0], s_l[1]), max(s_l[2], s_l[3]));
+        if (longest) atomicMax(&state[kLongestWord], longest);
+    }
+}
+
+// Chooses the path (every workgroup evaluates the same rule on the same words; workgroup 0 publishes it for the later
+// kernels and, in bucket mode, adds the pairs this shard stands for to counters[0] -- the host's closed form, which the
+// tile kernel would have counted tile by tile) and, in bucket mode, turns the histogram into exclusive offsets.  Offsets
+// are taken modulo 2^32 over the whole table: band b's run starts at b * n, and (offset - b * n) mod 2^32 is the place
+// inside the band's run for every n < 2^32.
+__global__ __launch_bounds__(256) void ke_bucket_offsets(const uint32_t *__restrict__ hist, size_t bins,
+                                                          const uint32_t *__restrict__ block_sums, uint32_t *__restrict__ offsets,
+                                                          unsigned long long *state, int forced, unsigned long long pairs_limit,
+                                                          unsigned long long shard_pairs) {
+    const bool buckets = forced == 2 || (state[3] <= pairs_limit && state[kLongestWord] <= kBucketLongest);
+    if (!buckets) return;                          // the path word stays 0: tiles
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (blockIdx.x == 0 && tid == 0) {
+        state[kPathWord] = 1;
+        state[0] = shard_pairs;
+    }
+    __shared__ unsigned long long s_b[4];
+    __shared__ uint32_t s_w[4];
+    const uint32_t base = (uint32_t)block_sum_256(tid < (int)blockIdx.x ? block_sums[tid] : 0u, s_b);
+    const size_t i0 = (size_t)blockIdx.x * kBinsPerBlock + (size_t)tid * 4;
+    uint32_t v[4], mine = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = i0 + k < bins ? hist[i0 + k] : 0u; mine += v[k]; }
+    uint32_t inc = mine;                           // inclusive scan over the wave, then over the four waves
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d); if (lane >= d) inc += t; }
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    uint32_t run = base + inc - mine;
+    for (int w = 0; w < wv; ++w) run += s_w[w];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (i0 + k < bins) offsets[i0 + k] = run;
+        run += v[k];
+    }
+}
+
+// Counting sort per band: slot b * n + place holds a member's hash and its position, so that a bucket is one contiguous run
+// of hashes.  The order inside a run is whatever the atomics give.
+__global__ void ke_bucket_scatter(const uint64_t *__restrict__ hashes, int64_t n, int band_bits, int band_count,
+                                  uint32_t *__restrict__ offsets, uint64_t *__restrict__ sorted_hash, uint32_t *__restrict__ sorted_pos,
+                                  const unsigned long long *state) {
+    if (!state[kPathWord]) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t x = hashes[i];
+    const uint64_t mask = (1ull << band_bits) - 1ull;
+    for (int b = 0; b < band_count; ++b) {
+        const uint32_t slot = atomicAdd(&offsets[((size_t)b << band_bits) + (size_t)((x >> (b * band_bits)) & mask)], 1u);
+        const uint32_t place = slot - (uint32_t)((uint64_t)b * (uint64_t)n);
+        if ((int64_t)place < n) {
+            sorted_hash[(size_t)b * (size_t)n + place] = x;
+            sorted_pos[(size_t)b * (size_t)n + place] = (uint32_t)i;
+        }
+    }
+}
+
+// One thread per slot of a band's sorted run: its hash against the later slots of the run for as long as their band value is
+// its own, all of it read from neighbouring addresses (lane l walks slots l + 1, l + 2, ... beside lane l + 1's).  The
+// scatter's order inside a run differs from rank to rank, so the shards cannot divide the slots: every shard walks all of
+// them (cheap) and a pair belongs to the shard named by its two positions.  A bucket over the pair cap is skipped as a whole
+// (src/dup/scanner.py:262-263).
+// A workgroup takes kPairSlots slots of one band (blockIdx.y) and collects its edges in LDS: one add per workgroup to the
+// edge cursor and to the shared-bands sum.  On a uniform table the edges are few and far apart, one in a wave at most, so
+// consider_pair's two adds per edge all went to one address one by one: 13 000 of them were the 120 us this kernel took at
+// n = 100 000.  Edges beyond the staging buffer (skewed tables, where a wave's adds combine) go through consider_pair.
+constexpr int kPairSlots = 1024, kPairStage = 256;
+
+__global__ __launch_bounds__(256) void ke_bucket_pairs(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
+                                                        const uint32_t *__restrict__ sorted_pos, int part_index, int part_count) {
+    if (!a.counters[kPathWord]) return;
+    __shared__ ke_edge s_edges[kPairStage];
+    __shared__ unsigned int s_count, s_shared;
+    __shared__ unsigned long long s_base;
+    if (threadIdx.x == 0) { s_count = 0; s_shared = 0; }
+    __syncthreads();
+    const int b = blockIdx.y, sh = b * a.band_bits;
+    const uint64_t mask = (1ull << a.band_bits) - 1ull;
+    const uint64_t *run = sorted_hash + (size_t)b * (size_t)a.n;
+    const uint32_t *pos = sorted_pos + (size_t)b * (size_t)a.n;
+    for (int c = 0; c < kPairSlots / 256; ++c) {
+        const int64_t r = (int64_t)blockIdx.x * kPairSlots + c * 256 + threadIdx.x;
+        if (r >= a.n) break;
+        const uint64_t x = run[r], key = (x >> sh) & mask;
+        if (a.cap) {
+            const unsigned long long len = a.hist[((size_t)b << a.band_bits) + (size_t)key];
+            if (len * (len - 1) / 2 > a.cap) continue;
+        }
+        int64_t pi = -1;
+        for (int64_t k = r + 1; k < a.n; ++k) {
+            const uint64_t y = run[k];
+            if (((y >> sh) & mask) != key) break;
+            const int pc = __popcll(x ^ y);
+            if (pc > a.threshold) continue;
+            if (pi < 0) pi = pos[r];
+            const int64_t pj = pos[k];
+            const int64_t lo = pi < pj ? pi : pj, hi = pi < pj ? pj : pi;
+            if (hi >= a.n || (lo + hi) % part_count != part_index) continue;
+            const uint64_t xl = pi < pj ? x : y, xh = pi < pj ? y : x;
+            int bands, shared;
+            if (!pair_is_edge(a, lo, hi, xl, xh, b, &bands, &shared)) continue;
+            const unsigned int at = atomicAdd(&s_count, 1u);
+            if (at < (unsigned)kPairStage) {
+                atomicAdd(&s_shared, (unsigned)shared);
+                ke_edge e;
+                e.a = lo; e.b = hi; e.h = pc; e.bands = bands;
+                s_edges[at] = e;
+            } else {
+                consider_pair(a, lo, hi, xl, xh, pc, b);
+            }
+        }
+    }
+    __syncthreads();
+    const unsigned int staged = s_count < (unsigned)kPairStage ? s_count : (unsigned)kPairStage;
+    if (staged == 0) return;
+    if (threadIdx.x == 0) {
+        atomicAdd(&a.counters[1], (unsigned long long)s_shared);
+        s_base = atomicAdd(&a.counters[2], (unsigned long long)staged);
+    }
+    __syncthreads();
+    for (unsigned int i = threadIdx.x; i < staged; i += 256)
+        if ((int64_t)(s_base + i) < a.capacity) a.edges[s_base + i] = s_edges[i];
 }
 
 // Wide bands (2^band_bits bins do not fit a table): the band values are sorted together with their positions and the
@@ -379,9 +575,44 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
     return KE_OK;
 }
 
+// pairs i < j < n that shard part_index of part_count stands for (host, O(row blocks)): per row block, the chunks right of
+// the diagonal are full rectangles, the kCPR chunks on the diagonal hold a partial triangle.
+static unsigned long long shard_pairs(int64_t n, int nb, int ncc, int part_index, int part_count) {
+    unsigned long long pairs = 0;
+    for (int64_t rb = 0; rb < nb; ++rb) {
+        const int64_t off = rb * ncc - (int64_t)kCPR * rb * (rb - 1) / 2;
+        const int64_t row0 = rb * kTile, rows = std::min<int64_t>(kTile, n - row0);
+        // sum over d in [0, m) of min(rows, d): the pairs of a diagonal chunk's columns row0 .. row0 + m - 1
+        auto below = [rows](int64_t m) { return m <= rows ? m * (m - 1) / 2 : rows * (rows - 1) / 2 + (m - rows) * rows; };
+        for (int64_t cc = kCPR * rb; cc < ncc; ++cc) {
+            const int64_t t = off + (cc - kCPR * rb);
+            const bool diagonal = cc < kCPR * (rb + 1);
+            if (!diagonal) {
+                // every remaining chunk is a full rectangle except possibly the last one: count them arithmetically
+                const int64_t last = ncc - 1;
+                const int64_t t_last = off + (last - kCPR * rb);
+                // chunks cc .. last-1 (full width)
+                const int64_t first_full_t = t, end_full_t = t_last;   // [first_full_t, end_full_t)
+                if (end_full_t > first_full_t) {
+                    // count t in [first_full_t, end_full_t) with t % part_count == part_index
+                    auto upto = [&](int64_t x) { return x <= part_index ? 0 : (x - part_index + part_count - 1) / part_count; };
+                    pairs += (unsigned long long)(upto(end_full_t) - upto(first_full_t)) * (unsigned long long)(rows * kCols);
+                }
+                if (t_last % part_count == part_index && last >= cc)
+                    pairs += (unsigned long long)(rows * std::min<int64_t>(kCols, n - last * kCols));
+                break;
+            }
+            if (t % part_count != part_index) continue;
+            const int64_t col0 = cc * kCols, cols = std::min<int64_t>(kCols, n - col0);
+            pairs += (unsigned long long)(below(col0 - row0 + cols) - below(col0 - row0));
+        }
+    }
+    return pairs;
+}
+
 int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
                    int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
-                   int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long *d_counters,
+                   int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
                    unsigned long long *pairs_evaluated, bool want_bucket_pairs) {
     ScanArgs a;
     a.hashes = d_hashes; a.ids = d_ids; a.sizes = (size_ratio > 0.0) ? d_sizes : nullptr;
@@ -395,20 +626,67 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
     a.size_ratio = size_ratio;
     a.hist = nullptr; a.blen = nullptr;
     a.cap = bucket_pair_cap > 0 ? (unsigned long long)bucket_pair_cap : 0ull;
-    a.edges = d_edges; a.capacity = capacity; a.counters = d_counters;
-    // Bucket sizes per band: needed by the pair cap, and they give the reference's "pairs total" counter (counters[3]).
-    if ((bucket_pair_cap > 0 || want_bucket_pairs) && band_bits <= 24) {
-        void *h;
-        const size_t bins = (size_t)band_count << band_bits, bytes = bins * sizeof(uint32_t);
-        KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_HIST, bytes, &h));
-        KE_HIP(ctx, hipMemsetAsync(h, 0, bytes, ctx->stream));
+    a.edges = d_edges; a.capacity = capacity;
+    const unsigned long long pairs = shard_pairs(n, a.nb, a.ncc, part_index, part_count);
+    *pairs_evaluated = pairs;
+    // KE_SCAN_MODE=auto|tiles|buckets, read once: auto lets the device choose per call; the other two force a path
+    // (buckets still means tiles where the bucket path is not built).  Must be the same on every rank of a sharded scan.
+    static const int forced = [] {
+        const char *e = std::getenv("KE_SCAN_MODE");
+        return !e ? 0 : !std::strcmp(e, "tiles") ? 1 : !std::strcmp(e, "buckets") ? 2 : 0;
+    }();
+    const bool table = band_bits <= 24;
+    const size_t bins = table ? (size_t)band_count << band_bits : 0;
+    bool bucket_path = table && bins <= kBucketMaxBins && n <= 0xffffffffLL && forced != 1 && (forced == 2 || n >= kBucketMinN);
+    // [sorted hashes | per-bin offsets | sorted positions]; a table too large for it is scanned by the tile kernel
+    void *srt = nullptr;
+    const size_t slots = (size_t)band_count * (size_t)n;
+    if (bucket_path && ke_reserve(ctx, KE_BUF_SCAN_SORT, slots * 12 + bins * sizeof(uint32_t), &srt) != KE_OK) {
+        (void)hipGetLastError();
+        ctx->err.clear();                          // not a failure of this call: the tile kernel needs no such buffer
+        bucket_path = false;
+    }
+    uint64_t *sorted_hash = (uint64_t *)srt;
+    uint32_t *offsets = (uint32_t *)(sorted_hash + slots), *sorted_pos = offsets + bins;
+    const bool need_hist = table && (bucket_path || bucket_pair_cap > 0 || want_bucket_pairs);
+    // One allocation, one memset: [counters, path, longest bucket | block sums | histogram]
+    const size_t hist_at = kStateBytes + kBlockSumBytes;
+    const size_t state_bytes = (hist_at + (need_hist ? bins * sizeof(uint32_t) : 0) + 15) & ~(size_t)15;
+    void *st;
+    KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_CNT, state_bytes, &st));
+    unsigned long long *state = (unsigned long long *)st;
+    uint32_t *block_sums = (uint32_t *)((uint8_t *)st + kStateBytes), *hist = (uint32_t *)((uint8_t *)st + hist_at);
+    a.counters = state;
+    *d_counters_out = state;
+    const int64_t my_tiles = a.n_tiles > part_index ? (a.n_tiles - part_index + part_count - 1) / part_count : 0;
+    const int64_t n_pad = (int64_t)a.nb * kTile;     // the kernel reads whole tiles: operands beyond n are zero
+    void *exp;
+    KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_EXP, (size_t)n_pad * 64, &exp));
+    a.expanded = (const ke_v4i *)exp;
+    ke_time_begin(ctx, KE_T_SCAN);
+    KE_HIP(ctx, hipMemsetAsync(st, 0, state_bytes, ctx->stream));
+    // Bucket sizes per band: needed by the bucket path and the pair cap, and they give the reference's "pairs total"
+    // counter (counters[3]).
+    if (need_hist) {
         hipLaunchKernelGGL(ke_band_hist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, band_bits,
-                           band_count, (uint32_t *)h);
+                           band_count, hist);
         KE_HIP(ctx, hipGetLastError());
-        a.hist = (const uint32_t *)h;
-        if (want_bucket_pairs) {
+        a.hist = hist;
+        if (bucket_path) {
+            const unsigned blocks = (unsigned)((bins + kBinsPerBlock - 1) / kBinsPerBlock);
+            const unsigned long long all_pairs = (unsigned long long)n * (unsigned long long)(n - 1) / 2;
+            hipLaunchKernelGGL(ke_bucket_stats, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins, a.cap, block_sums,
+                               state);
+            hipLaunchKernelGGL(ke_bucket_offsets, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins,
+                               (const uint32_t *)block_sums, offsets, state, forced, all_pairs / kBucketRatio, pairs);
+            hipLaunchKernelGGL(ke_bucket_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, band_bits,
+                               band_count, offsets, sorted_hash, sorted_pos, (const unsigned long long *)state);
+            hipLaunchKernelGGL(ke_bucket_pairs, dim3((unsigned)((n + kPairSlots - 1) / kPairSlots), (unsigned)band_count), dim3(256), 0, ctx->stream, a,
+                               (const uint64_t *)sorted_hash, (const uint32_t *)sorted_pos, part_index, part_count);
+            KE_HIP(ctx, hipGetLastError());
+        } else if (want_bucket_pairs) {
             const unsigned blocks = (unsigned)std::min<size_t>((bins + 1023) / 1024, 256);
-            hipLaunchKernelGGL(ke_hist_pairs, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)h, bins, a.cap, d_counters + 3);
+            hipLaunchKernelGGL(ke_hist_pairs, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins, a.cap, state + 3);
             KE_HIP(ctx, hipGetLastError());
         }
     } else if (bucket_pair_cap > 0 || want_bucket_pairs) {
@@ -431,20 +709,14 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
             hipLaunchKernelGGL(ke_band_keys, grid, blk, 0, ctx->stream, d_hashes, n, b * band_bits, mask, k_in, p_in);
             KE_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, k_in, k_out, p_in, p_out, (int)n, 0, band_bits, ctx->stream));
             hipLaunchKernelGGL(ke_run_lengths, grid, blk, 0, ctx->stream, k_out, p_out, n, a.cap, (uint32_t *)lens + (size_t)b * n,
-                               want_bucket_pairs ? d_counters + 3 : d_counters + 3);
+                               state + 3);
             KE_HIP(ctx, hipGetLastError());
         }
         a.blen = (const uint32_t *)lens;
     }
-    const int64_t my_tiles = a.n_tiles > part_index ? (a.n_tiles - part_index + part_count - 1) / part_count : 0;
-    const int64_t n_pad = (int64_t)a.nb * kTile;     // the kernel reads whole tiles: operands beyond n are zero
-    void *exp;
-    KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_EXP, (size_t)n_pad * 64, &exp));
-    a.expanded = (const ke_v4i *)exp;
-    ke_time_begin(ctx, KE_T_SCAN);
     if (my_tiles > 0) {
         hipLaunchKernelGGL(ke_scan_expand, dim3((unsigned)((n_pad * 4 + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, n_pad,
-                           (ke_v4i *)exp);
+                           (ke_v4i *)exp, (const unsigned long long *)(state + kPathWord));
         if (my_tiles > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
         static const int xcd = [] { const char *e = std::getenv("KE_SCAN_XCD"); return e ? std::atoi(e) : 0; }();
         a.xcd_remap = xcd;
@@ -454,36 +726,5 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
         KE_HIP(ctx, hipGetLastError());
     }
     ke_time_end(ctx, KE_T_SCAN);
-    // pairs evaluated by this shard (host, O(row blocks)): per row block, the chunks right of the diagonal are
-    // full rectangles, the kCPR chunks on the diagonal hold a partial triangle.
-    unsigned long long pairs = 0;
-    for (int64_t rb = 0; rb < a.nb; ++rb) {
-        const int64_t off = rb * a.ncc - (int64_t)kCPR * rb * (rb - 1) / 2;
-        const int64_t row0 = rb * kTile, rows = std::min<int64_t>(kTile, n - row0);
-        for (int64_t cc = kCPR * rb; cc < a.ncc; ++cc) {
-            const int64_t t = off + (cc - kCPR * rb);
-            const bool diagonal = cc < kCPR * (rb + 1);
-            if (!diagonal) {
-                // every remaining chunk is a full rectangle except possibly the last one: count them arithmetically
-                const int64_t last = a.ncc - 1;
-                const int64_t t_last = off + (last - kCPR * rb);
-                // chunks cc .. last-1 (full width)
-                const int64_t first_full_t = t, end_full_t = t_last;   // [first_full_t, end_full_t)
-                if (end_full_t > first_full_t) {
-                    // count t in [first_full_t, end_full_t) with t % part_count == part_index
-                    auto upto = [&](int64_t x) { return x <= part_index ? 0 : (x - part_index + part_count - 1) / part_count; };
-                    pairs += (unsigned long long)(upto(end_full_t) - upto(first_full_t)) * (unsigned long long)(rows * kCols);
-                }
-                if (t_last % part_count == part_index && last >= cc)
-                    pairs += (unsigned long long)(rows * std::min<int64_t>(kCols, n - last * kCols));
-                break;
-            }
-            if (t % part_count != part_index) continue;
-            const int64_t col0 = cc * kCols, cols = std::min<int64_t>(kCols, n - col0);
-            for (int64_t j = col0; j < col0 + cols; ++j)
-                pairs += (unsigned long long)std::max<int64_t>(0, std::min<int64_t>(rows, j - row0));
-        }
-    }
-    *pairs_evaluated = pairs;
     return KE_OK;
 }
