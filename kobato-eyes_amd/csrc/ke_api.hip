@@ -6,13 +6,13 @@
 #include <algorithm>
 #include <cmath>
 #include <numeric>
-#include <unordered_map>
 
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include "ke_internal.h"
+#include "ke_group_plan.h"
 
 static thread_local std::string g_create_err;
 
@@ -453,6 +453,12 @@ KE_API int ke_luma_tiles_uniform(ke_ctx *ctx, const uint8_t *pixels, int64_t n, 
     return hash_uniform_impl(ctx, pixels, n, width, height, channels, nullptr, nullptr, tile32_out, tile98_out);
 }
 
+// A planned shape group as the launchers take it: its [offsets | output slots] block is at d_meta + meta_at.
+static KeHashGroup hash_group(const KeShapeGroup &sg, const uint8_t *d_px, const uint64_t *d_meta) {
+    const uint64_t *d_off = d_meta + sg.meta_at;
+    return KeHashGroup{d_px, d_off, (uint64_t)sg.w * sg.h * sg.channels, (const int64_t *)(d_off + sg.n), sg.n, sg.w, sg.h, sg.channels, sg.misaligned};
+}
+
 static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths,
                             const int32_t *heights, int32_t channels, int64_t n, uint64_t *phash_out,
                             uint64_t *dhash_out, int32_t *status_out, float *margin_out) {
@@ -470,49 +476,17 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
     trim_coeff_cache(ctx);
     // byte offset of every image, then group equal shapes (one launch group per distinct size)
     std::vector<uint64_t> off((size_t)n);
+    std::vector<uint8_t> take((size_t)n);
     uint64_t run = 0;
     for (int64_t i = 0; i < n; ++i) {
         off[i] = offsets ? offsets[i] : run;
-        if (widths[i] > 0 && heights[i] > 0) run += (uint64_t)widths[i] * heights[i] * channels;
+        take[i] = widths[i] > 0 && heights[i] > 0;
+        if (take[i]) run += (uint64_t)widths[i] * heights[i] * channels;
+        if (status_out) status_out[i] = take[i] ? KE_IMG_OK : KE_IMG_BAD_SHAPE;
     }
-    // size groups: an image's group id comes from a one-entry cache or a hash lookup (the shape list of a library is short),
-    // the members are then laid out by a counting sort -- linear in n with small constants (a million-image call spends its
-    // host time here)
-    std::map<std::pair<int, int>, std::vector<int64_t>> groups;
-    {
-        std::unordered_map<uint64_t, int32_t> ids;
-        std::vector<int32_t> gid((size_t)n, -1);
-        std::vector<int64_t> counts;
-        std::vector<std::pair<int, int>> shapes;
-        uint64_t last_key = ~0ull;
-        int32_t last_id = -1;
-        for (int64_t i = 0; i < n; ++i) {
-            const bool ok = widths[i] > 0 && heights[i] > 0;
-            if (status_out) status_out[i] = ok ? KE_IMG_OK : KE_IMG_BAD_SHAPE;
-            if (!ok) continue;
-            const uint64_t key = ((uint64_t)(uint32_t)widths[i] << 32) | (uint32_t)heights[i];
-            if (key != last_key) {
-                auto it = ids.find(key);
-                if (it == ids.end()) {
-                    it = ids.emplace(key, (int32_t)shapes.size()).first;
-                    shapes.emplace_back(widths[i], heights[i]);
-                    counts.push_back(0);
-                }
-                last_key = key;
-                last_id = it->second;
-            }
-            gid[i] = last_id;
-            ++counts[last_id];
-        }
-        std::vector<std::vector<int64_t> *> slots(shapes.size());
-        for (size_t k = 0; k < shapes.size(); ++k) {
-            auto &v = groups[shapes[k]];
-            v.reserve((size_t)counts[k]);
-            slots[k] = &v;
-        }
-        for (int64_t i = 0; i < n; ++i)
-            if (gid[i] >= 0) slots[gid[i]]->push_back(i);
-    }
+    std::vector<uint64_t> meta_h((size_t)2 * n);
+    size_t cursor = 0;
+    const auto groups = ke_plan_shape_groups(off.data(), widths, heights, nullptr, channels, take.data(), n, (uintptr_t)pixels, meta_h.data(), &cursor);
     const bool in_dev = ke_is_device_ptr(pixels);
     const bool p_dev = phash_out && ke_is_device_ptr(phash_out), d_dev = dhash_out && ke_is_device_ptr(dhash_out);
     // outputs are produced in a device array of n slots, then copied out once
@@ -539,18 +513,6 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
     if (in_dev) {
         // device-resident batch: one metadata upload for all shape groups ([offsets | output slots] per group),
         // then the groups are launched back to back with no host synchronisation in between
-        std::vector<uint64_t> meta_h((size_t)2 * n);
-        size_t cursor = 0;
-        std::vector<std::pair<size_t, size_t>> spans;   // (meta offset, count) per group, in map order
-        for (auto &kv : groups) {
-            const std::vector<int64_t> &idx = kv.second;
-            spans.emplace_back(cursor, idx.size());
-            for (size_t k = 0; k < idx.size(); ++k) {
-                meta_h[cursor + k] = off[idx[k]];
-                meta_h[cursor + idx.size() + k] = (uint64_t)idx[k];
-            }
-            cursor += 2 * idx.size();
-        }
         void *meta;
         KE_TRY(ke_reserve(ctx, KE_BUF_META, std::max<size_t>(cursor, 2) * 8, &meta));
         if (cursor) KE_HIP(ctx, hipMemcpyAsync(meta, meta_h.data(), cursor * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -571,21 +533,9 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
             KE_HIP(ctx, hipEventRecord(ctx->side_fork, ctx->stream));          // outputs zeroed, metadata in place
             for (int k = 0; k < 2; ++k) KE_HIP(ctx, hipStreamWaitEvent(ctx->side[k], ctx->side_fork, 0));
         }
-        size_t gi = 0;
         int rc_groups = KE_OK;
-        for (auto &kv : groups) {
-            const int w = kv.first.first, h = kv.first.second;
-            const uint64_t *d_off = (const uint64_t *)meta + spans[gi].first;
-            const int64_t m = (int64_t)spans[gi].second;
-            KeHashGroup g{pixels, d_off, (uint64_t)w * h * channels, (const int64_t *)(d_off + m), m, w, h, channels};
-            // the dword loaders of the single-pass and aligned banded kernels want every image of the group on a dword
-            // boundary; a packed stream loses that after the first image whose byte size is not a multiple of 4
-            for (int64_t idx : kv.second)
-                if (((uintptr_t)pixels + off[idx]) % 4 != 0) { g.misaligned = true; break; }
-            rc_groups = ke_launch_hash_group(ctx, g, d_ph, d_dh, nullptr, nullptr, overlap ? ctx->side[gi & 1] : nullptr);
-            if (rc_groups != KE_OK) break;
-            ++gi;
-        }
+        for (size_t gi = 0; gi < groups.size() && rc_groups == KE_OK; ++gi)
+            rc_groups = ke_launch_hash_group(ctx, hash_group(groups[gi], pixels, (const uint64_t *)meta), d_ph, d_dh, nullptr, nullptr, overlap ? ctx->side[gi & 1] : nullptr);
         if (overlap) {                                                          // join, also on the error path
             for (int k = 0; k < 2; ++k) {
                 KE_HIP(ctx, hipEventRecord(ctx->side_join[k], ctx->side[k]));
@@ -594,15 +544,14 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
         }
         KE_TRY(rc_groups);
     } else {
-        for (auto &kv : groups) {
-            const int w = kv.first.first, h = kv.first.second;
-            const size_t img_bytes = (size_t)w * h * channels;
-            const std::vector<int64_t> &idx = kv.second;
+        for (const KeShapeGroup &sg : groups) {
+            const size_t img_bytes = (size_t)sg.w * sg.h * channels;
+            const uint64_t *idx = meta_h.data() + sg.meta_at + sg.n;   // the group's images
             const int64_t chunk = std::max<int64_t>(1, (int64_t)(kStageBytes / img_bytes));
-            for (size_t first = 0; first < idx.size(); first += (size_t)chunk) {
-                const int64_t m = (int64_t)std::min<size_t>((size_t)chunk, idx.size() - first);
+            for (size_t first = 0; first < (size_t)sg.n; first += (size_t)chunk) {
+                const int64_t m = (int64_t)std::min<size_t>((size_t)chunk, (size_t)sg.n - first);
                 std::vector<uint64_t> goff((size_t)m);
-                std::vector<int64_t> gidx(idx.begin() + first, idx.begin() + first + m);
+                std::vector<int64_t> gidx(idx + first, idx + first + m);
                 // pack this chunk of host images into the staging buffer
                 KE_TRY(ke_reserve(ctx, KE_BUF_PIXELS, (size_t)m * img_bytes, &tmp));
                 for (int64_t k = 0; k < m; ++k) {
@@ -616,7 +565,7 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
                 KE_HIP(ctx, hipMemcpyAsync((uint8_t *)meta + (size_t)m * 8, gidx.data(), (size_t)m * 8,
                                            hipMemcpyHostToDevice, ctx->stream));
                 KeHashGroup g{(const uint8_t *)tmp, (const uint64_t *)meta, img_bytes,
-                              (const int64_t *)((uint8_t *)meta + (size_t)m * 8), m, w, h, channels};
+                              (const int64_t *)((uint8_t *)meta + (size_t)m * 8), m, sg.w, sg.h, channels};
                 KE_TRY(ke_launch_hash_group(ctx, g, d_ph, d_dh, nullptr, nullptr));
                 KE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // goff/gidx and the staging buffers are reused
             }
@@ -778,29 +727,18 @@ KE_API int ke_stage_submit_hash(ke_ctx *ctx, int32_t slot, const uint64_t *offse
     trim_coeff_cache(ctx);
     // size groups over (width, height, channels); metadata goes into the slot's pinned block so nothing here has to
     // outlive the call on the stack
-    std::map<std::tuple<int, int, int>, std::vector<int64_t>> groups;
+    std::vector<uint8_t> take((size_t)n);
     size_t used = 0;
     for (int64_t i = 0; i < n; ++i) {
         const int c = channels[i];
         const bool ok = widths[i] > 0 && heights[i] > 0 && (c == 1 || c == 3 || c == 4);
         const size_t bytes = ok ? (size_t)widths[i] * heights[i] * c : 0;
-        const bool inside = ok && offsets[i] <= st->bytes && bytes <= st->bytes - offsets[i];
-        if (status_out) status_out[i] = inside ? KE_IMG_OK : KE_IMG_BAD_SHAPE;
-        if (!inside) continue;
-        groups[std::make_tuple(widths[i], heights[i], c)].push_back(i);
-        used = std::max(used, (size_t)offsets[i] + bytes);
+        take[i] = ok && offsets[i] <= st->bytes && bytes <= st->bytes - offsets[i];    // the image lies inside the slot
+        if (status_out) status_out[i] = take[i] ? KE_IMG_OK : KE_IMG_BAD_SHAPE;
+        if (take[i]) used = std::max(used, (size_t)offsets[i] + bytes);
     }
     size_t cursor = 0;
-    std::vector<std::pair<size_t, size_t>> spans;
-    for (auto &kv : groups) {
-        const std::vector<int64_t> &idx = kv.second;
-        spans.emplace_back(cursor, idx.size());
-        for (size_t k = 0; k < idx.size(); ++k) {
-            s.h_meta[cursor + k] = offsets[idx[k]];
-            s.h_meta[cursor + idx.size() + k] = (uint64_t)idx[k];
-        }
-        cursor += 2 * idx.size();
-    }
+    const auto groups = ke_plan_shape_groups(offsets, widths, heights, channels, 0, take.data(), n, (uintptr_t)s.d_px, s.h_meta, &cursor);
     // copy stream: pixels + metadata to the slot's device twin
     if (used) KE_HIP(ctx, hipMemcpyAsync(s.d_px, s.h_px, used, hipMemcpyHostToDevice, st->copy_stream));
     if (cursor) KE_HIP(ctx, hipMemcpyAsync(s.d_meta, s.h_meta, cursor * 8, hipMemcpyHostToDevice, st->copy_stream));
@@ -813,17 +751,8 @@ KE_API int ke_stage_submit_hash(ke_ctx *ctx, int32_t slot, const uint64_t *offse
     MarginScope margin_scope{ctx};
     ctx->margin_cur = margin_out ? s.d_mg : nullptr;
     ke_time_begin(ctx, KE_T_HASH);
-    size_t gi = 0;
-    for (auto &kv : groups) {
-        const int w = std::get<0>(kv.first), h = std::get<1>(kv.first), c = std::get<2>(kv.first);
-        const uint64_t *d_off = s.d_meta + spans[gi].first;
-        const int64_t m = (int64_t)spans[gi].second;
-        KeHashGroup g{s.d_px, d_off, (uint64_t)w * h * c, (const int64_t *)(d_off + m), m, w, h, c};
-        for (int64_t idx : kv.second)
-            if (((uintptr_t)s.d_px + offsets[idx]) % 4 != 0) { g.misaligned = true; break; }
-        KE_TRY(ke_launch_hash_group(ctx, g, phash_out ? s.d_ph : nullptr, dhash_out ? s.d_dh : nullptr, nullptr, nullptr));
-        ++gi;
-    }
+    for (const KeShapeGroup &sg : groups)
+        KE_TRY(ke_launch_hash_group(ctx, hash_group(sg, s.d_px, s.d_meta), phash_out ? s.d_ph : nullptr, dhash_out ? s.d_dh : nullptr, nullptr, nullptr));
     ke_time_end(ctx, KE_T_HASH);
     if (phash_out) KE_HIP(ctx, hipMemcpyAsync(s.h_ph, s.d_ph, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (dhash_out) KE_HIP(ctx, hipMemcpyAsync(s.h_dh, s.d_dh, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1072,8 +1001,7 @@ KE_API int ke_ssim_pairs(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *off
             const int sw = g.first.first, sh = g.first.second;
             const int64_t gb = group_base[g.first], m = (int64_t)g.second.size();
             KeHashGroup hg{(const uint8_t *)d_px, (const uint64_t *)meta + gb, (uint64_t)sw * sh * channels, nullptr, m, sw, sh, channels};
-            for (int64_t i : g.second)
-                if (((uintptr_t)d_px + off[i]) % 4 != 0) { hg.misaligned = true; break; }
+            hg.misaligned = ke_any_misaligned((uintptr_t)d_px, meta_h.data() + gb, m);
             float box[4];
             if (fit_box(sw, sh, w, h, box) != KE_OK) return ke_fail(ctx, KE_EINVAL, "crop box outside the image");
             KE_TRY(ke_launch_resize_group(ctx, hg, w, h, KE_FILTER_BICUBIC, (uint8_t *)planes + (size_t)gb * plane, box));

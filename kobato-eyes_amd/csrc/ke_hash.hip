@@ -25,6 +25,7 @@
 
 #include "ke_internal.h"
 #include "dct_table.h"
+#include "ke_hash_select.h"
 
 namespace {
 
@@ -592,69 +593,6 @@ struct KeBandPlan {
     int hs_hp, hsd_hp;
 };
 
-template <int W64, int KS, bool DH, bool GEN = false, int C = 3, bool UNAL = false>
-int launch_fused_mx(ke_ctx *ctx, const KeHashGroup &g, const KeAxisCoeffs *ch, const KeAxisCoeffs *cv, uint64_t *d_phash,
-                    uint8_t *d_tile32, uint64_t *d_dhash, uint8_t *d_tile98, const KeBandPlan *plan = nullptr) {
-    const int W = g.w;
-    if (GEN ? (W > 64 * W64 || W <= 64 * (W64 - 1) || (W % 4 != 0) != UNAL) : W != 64 * W64) return KE_EUNSUPPORTED;
-    const KeMxTable *mx = ke_get_mx(ctx, ch, KS);     // at least KS steps per tile (zero-padded)
-    if (!mx) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    if (mx->tiles != 2 || mx->ks != KS) return KE_EUNSUPPORTED;
-    KeFusedArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.out_idx = g.out_idx; a.h = g.h;
-    a.h_bias = ch->d_bias;
-    a.v_packed = cv->d_packed; a.v_start = cv->d_start; a.v_bias = cv->d_bias;
-    a.ndwv = cv->ndw;
-    a.mx_frag = mx->d_frag; a.mx_base0 = mx->base[0]; a.mx_base1 = mx->base[1];
-    const int rows_padded = plan ? plan->band_rows : ((g.h + kRTM - 1) / kRTM) * kRTM;
-    if (plan) { a.bands = plan->bands; a.band_rows = plan->band_rows; a.hs = plan->hs; a.hsd = plan->hsd; a.hs_hp = plan->hs_hp; a.hsd_hp = plan->hsd_hp; }
-    // one tile buffer: 32 padded rows + the part of the last row's operand window that overhangs the row
-    constexpr int KD = (W64 + 1) / 2;
-    const int overhang = std::max(0, std::max(std::max(mx->base[0], mx->base[1]) + 64 * KS, DH ? 128 * KD : 0) - W);
-    a.qw = (W + 3) / 4;
-    a.w = W; a.row_bytes = W * C;
-    a.qw_inv = (int)(uint32_t)((0x100000000ull + (uint64_t)a.qw - 1) / (uint64_t)a.qw);
-    // row pitch: an odd number of 16-byte units, so the 16 rows of an operand land in distinct bank groups
-    a.lp = GEN ? (((W + 15) / 16 + 1) | 1) * 16 : W + 16;
-    a.lt_half = (kRTM * a.lp + overhang + 15) & ~15;
-    a.lt_bytes = 2 * a.lt_half;
-    a.hp = ((std::max(plan ? 0 : cv->span, rows_padded) + 7) & ~7) + 8;
-    a.hpd = 8;
-    a.phash = d_phash; a.tile32_out = d_tile32; a.margin = ctx->margin_cur;
-    size_t lds = std::max<size_t>((size_t)a.lt_bytes + (size_t)32 * a.hp, 4096);
-    if (DH) {
-        const KeAxisCoeffs *chd = ke_get_coeffs(ctx, g.w, 9), *cvd = ke_get_coeffs(ctx, g.h, 8);
-        if (!chd || !cvd) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-        const KeMxTable *mxd = ke_get_mx(ctx, chd, 2 * KD);     // the whole row in two halves of KD steps
-        const KeChunkTable *tv = ke_get_chunks(ctx, cvd, 3);
-        if (!mxd || !tv) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-        if (mxd->tiles != 1 || mxd->base[0] != 0 || mxd->ks != 2 * KD) return KE_EUNSUPPORTED;
-        a.mxd_frag = mxd->d_frag;
-        a.hd_bias = chd->d_bias;
-        a.vd_cpacked = tv->d_cpacked; a.vd_cstart = tv->d_cstart; a.vd_bias = cvd->d_bias;
-        a.ndwcv = tv->ndwc;
-        a.hpd = ((std::max(plan ? 0 : tv->cspan, rows_padded) + 7) & ~7) + 8;
-        a.dhash = d_dhash; a.tile98_out = d_tile98;
-        lds += (size_t)9 * a.hpd;
-        lds = (lds + 15) & ~(size_t)15;
-        a.x_off = (int)lds;
-        lds += 4096;
-    }
-    // up to 80 KB two workgroups share a CU.  A tall image (its 32 x H transposed columns) would need more and run one
-    // per CU; if cutting it into bands brings the columns back under that line, decline: the caller then runs this
-    // kernel per band (measured 5.4-6.0 TB/s against 3.9-4.9 for one workgroup per CU)
-    if (lds > 150 * 1024) return KE_EUNSUPPORTED;
-    if (!plan && lds > 80 * 1024 && lds - (size_t)(32 * (a.hp - 136)) - (DH ? (size_t)(9 * (a.hpd - 136)) : 0) <= 80 * 1024) return KE_EUNSUPPORTED;
-    if (lds > 64 * 1024)
-        KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&ke_phash_fused_mx<W64, KS, DH, GEN, C, UNAL>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (g.n * (plan ? plan->bands : 1) > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch");
-    hipLaunchKernelGGL((ke_phash_fused_mx<W64, KS, DH, GEN, C, UNAL>), dim3((unsigned)(g.n * (plan ? plan->bands : 1))), dim3(256), lds, ctx->stream, a);
-    KE_HIP(ctx, hipGetLastError());
-    return KE_OK;
-}
-
 // ---------------------------------------------------------------------------------------
 // Wide rows (up to 2048 pixels): the same chain with the work cut differently.  A 32-row tile of such a row
 // no longer fits LDS twice and one wave cannot hold the operands of a whole output tile, so: 16-row tiles,
@@ -838,64 +776,6 @@ __global__ __launch_bounds__(512, 1) void ke_phash_fused_wide(const KeFusedArgs 
     // the tail is written for 256 threads; the other four waves are done (ended waves leave the barrier count)
     if (tid >= 256) return;
     fused_tail<(DH ? 1 : 0)>(a, Lt, HT, HTd, tid, img);
-}
-
-template <int KSH, int QPT, bool DH, int KDW, int C = 3, bool UNAL = false>
-int launch_fused_wide(ke_ctx *ctx, const KeHashGroup &g, const KeAxisCoeffs *ch, const KeAxisCoeffs *cv, uint64_t *d_phash,
-                      uint8_t *d_tile32, uint64_t *d_dhash, uint8_t *d_tile98, const KeBandPlan *plan = nullptr) {
-    const int W = g.w;
-    if ((W % 4 != 0) != UNAL || kRTW * ((W + 3) / 4) > 512 * QPT) return KE_EUNSUPPORTED;
-    const KeMxTable *mx = ke_get_mx(ctx, ch, 4 * KSH);
-    if (!mx) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    if (mx->tiles != 2 || mx->ks != 4 * KSH) return KE_EUNSUPPORTED;
-    KeFusedArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.out_idx = g.out_idx; a.h = g.h;
-    a.h_bias = ch->d_bias;
-    a.v_packed = cv->d_packed; a.v_start = cv->d_start; a.v_bias = cv->d_bias;
-    a.ndwv = cv->ndw;
-    a.mx_frag = mx->d_frag; a.mx_base0 = mx->base[0]; a.mx_base1 = mx->base[1];
-    const int rows_padded = plan ? plan->band_rows : ((g.h + kRTW - 1) / kRTW) * kRTW;
-    if (plan) { a.bands = plan->bands; a.band_rows = plan->band_rows; a.hs = plan->hs; a.hsd = plan->hsd; a.hs_hp = plan->hs_hp; a.hsd_hp = plan->hsd_hp; }
-    const int overhang = std::max(0, std::max(std::max(mx->base[0], mx->base[1]) + 64 * 4 * KSH, DH ? 512 * KDW : 0) - W);
-    a.qw = (W + 3) / 4;
-    a.w = W; a.row_bytes = W * C;
-    a.qw_inv = (int)(uint32_t)((0x100000000ull + (uint64_t)a.qw - 1) / (uint64_t)a.qw);
-    a.lp = (((W + 15) / 16 + 1) | 1) * 16;
-    a.lt_half = (kRTW * a.lp + overhang + 15) & ~15;
-    a.lt_bytes = 2 * a.lt_half;
-    a.hp = ((std::max(plan ? 0 : cv->span, rows_padded) + 7) & ~7) + 8;
-    a.hpd = 8;
-    a.phash = d_phash; a.tile32_out = d_tile32; a.margin = ctx->margin_cur;
-    size_t lds = (size_t)a.lt_bytes + (size_t)32 * a.hp;
-    if (DH) {
-        const KeAxisCoeffs *chd = ke_get_coeffs(ctx, g.w, 9), *cvd = ke_get_coeffs(ctx, g.h, 8);
-        if (!chd || !cvd) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-        const KeMxTable *mxd = ke_get_mx(ctx, chd, 8 * KDW);    // the whole row in eight parts of KDW steps
-        const KeChunkTable *tv = ke_get_chunks(ctx, cvd, 3);
-        if (!mxd || !tv) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-        if (mxd->tiles != 1 || mxd->base[0] != 0 || mxd->ks != 8 * KDW) return KE_EUNSUPPORTED;
-        a.mxd_frag = mxd->d_frag;
-        a.hd_bias = chd->d_bias;
-        a.vd_cpacked = tv->d_cpacked; a.vd_cstart = tv->d_cstart; a.vd_bias = cvd->d_bias;
-        a.ndwcv = tv->ndwc;
-        a.hpd = ((std::max(plan ? 0 : tv->cspan, rows_padded) + 7) & ~7) + 8;
-        a.dhash = d_dhash; a.tile98_out = d_tile98;
-        lds += (size_t)9 * a.hpd;
-    }
-    lds = (lds + 15) & ~(size_t)15;
-    a.x_off = (int)lds;
-    lds += 2 * 2 * 3 * 1024 + (DH ? 2 * 7 * 1024 : 0);
-    if (lds > 150 * 1024) return KE_EUNSUPPORTED;     // one workgroup per CU
-    // ... unless bands of rows bring it under 80 KB (two per CU): then the caller runs this kernel per band
-    if (!plan && lds > 80 * 1024 && lds - (size_t)(32 * (a.hp - 136)) - (DH ? (size_t)(9 * (a.hpd - 136)) : 0) <= 80 * 1024) return KE_EUNSUPPORTED;
-    if (lds > 64 * 1024)
-        KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&ke_phash_fused_wide<KSH, QPT, DH, KDW, C, UNAL>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (g.n * (plan ? plan->bands : 1) > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch");
-    hipLaunchKernelGGL((ke_phash_fused_wide<KSH, QPT, DH, KDW, C, UNAL>), dim3((unsigned)(g.n * (plan ? plan->bands : 1))), dim3(512), lds, ctx->stream, a);
-    KE_HIP(ctx, hipGetLastError());
-    return KE_OK;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1556,161 +1436,110 @@ int resample_generic(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t 
     return KE_OK;
 }
 
+// The single-pass kernels behind the rows of ke_hash_select.h: the same list expanded a second time, for the pointers alone.
+using KeFusedKernel = void (*)(KeFusedArgs);
+#define KE_SP_KERNEL(F, A0, A1, A2, A3, A4, A5, LO, HI) ke_phash_fused_##F<A0, A1, A2, A3, A4, A5>,
+const KeFusedKernel kSpKernels[] = {KE_SINGLE_PASS_ROWS(KE_SP_KERNEL)};
+#undef KE_SP_KERNEL
+static_assert(sizeof(kSpKernels) / sizeof(kSpKernels[0]) == kKeSpRowCount, "one kernel per row");
 
-// Picks the single-pass kernel for a group (row length, bytes per pixel, one or both hashes) and launches it.
+// Launches row r of the table on a group, or declines (KE_EUNSUPPORTED) where the row's tables or its LDS needs do not
+// fit.  Both families take the same KeFusedArgs; they differ in the tile (32 rows by 256 threads, 16 by 512), in how
+// the operand steps are counted, and in the exchange area behind the columns.
+int launch_fused(ke_ctx *ctx, int r, const KeHashGroup &g, const KeAxisCoeffs *ch, const KeAxisCoeffs *cv, uint64_t *d_phash,
+                 uint8_t *d_tile32, uint64_t *d_dhash, uint8_t *d_tile98, const KeBandPlan *plan) {
+    const KeSpRow &row = kKeSpRows[r];
+    const bool wide = row.family == KE_SP_WIDE, DH = row.dh();
+    const int W = g.w, C = row.channels();
+    const int rt = wide ? kRTW : kRTM, threads = wide ? 512 : 256;
+    const int ks = wide ? 4 * row.t[0] : row.t[1];                     // operand steps per output tile: a quarter per wave, or KS
+    // dHash steps: the whole row in eight parts of KDW steps, or in two halves of KD = ceil(W64 / 2) steps
+    const int ksd = wide ? 8 * row.t[3] : 2 * ((row.t[0] + 1) / 2);
+    const bool exact = !wide && !row.t[3];                             // compile-time row length
+    if ((W % 4 != 0) != row.unal() || (wide ? kRTW * ((W + 3) / 4) > 512 * row.t[1] : W < row.w_lo || W > row.w_hi)) return KE_EUNSUPPORTED;
+    const KeMxTable *mx = ke_get_mx(ctx, ch, ks);     // at least ks steps per tile (zero-padded)
+    if (!mx) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+    if (mx->tiles != 2 || mx->ks != ks) return KE_EUNSUPPORTED;
+    KeFusedArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.out_idx = g.out_idx; a.h = g.h;
+    a.h_bias = ch->d_bias;
+    a.v_packed = cv->d_packed; a.v_start = cv->d_start; a.v_bias = cv->d_bias;
+    a.ndwv = cv->ndw;
+    a.mx_frag = mx->d_frag; a.mx_base0 = mx->base[0]; a.mx_base1 = mx->base[1];
+    const int rows_padded = plan ? plan->band_rows : ((g.h + rt - 1) / rt) * rt;
+    if (plan) { a.bands = plan->bands; a.band_rows = plan->band_rows; a.hs = plan->hs; a.hsd = plan->hsd; a.hs_hp = plan->hs_hp; a.hsd_hp = plan->hsd_hp; }
+    // one tile buffer: rt padded rows + the part of the last row's operand window that overhangs the row
+    const int overhang = std::max(0, std::max(std::max(mx->base[0], mx->base[1]) + 64 * ks, DH ? 64 * ksd : 0) - W);
+    a.qw = (W + 3) / 4;
+    a.w = W; a.row_bytes = W * C;
+    a.qw_inv = (int)(uint32_t)((0x100000000ull + (uint64_t)a.qw - 1) / (uint64_t)a.qw);
+    // row pitch: an odd number of 16-byte units, so the 16 rows of an operand land in distinct bank groups
+    a.lp = exact ? W + 16 : (((W + 15) / 16 + 1) | 1) * 16;
+    a.lt_half = (rt * a.lp + overhang + 15) & ~15;
+    a.lt_bytes = 2 * a.lt_half;
+    a.hp = ((std::max(plan ? 0 : cv->span, rows_padded) + 7) & ~7) + 8;
+    a.hpd = 8;
+    a.phash = d_phash; a.tile32_out = d_tile32; a.margin = ctx->margin_cur;
+    size_t lds = (size_t)a.lt_bytes + (size_t)32 * a.hp;
+    if (!wide) lds = std::max<size_t>(lds, 4096);
+    if (DH) {
+        const KeAxisCoeffs *chd = ke_get_coeffs(ctx, g.w, 9), *cvd = ke_get_coeffs(ctx, g.h, 8);
+        if (!chd || !cvd) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+        const KeMxTable *mxd = ke_get_mx(ctx, chd, ksd);
+        const KeChunkTable *tv = ke_get_chunks(ctx, cvd, 3);
+        if (!mxd || !tv) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+        if (mxd->tiles != 1 || mxd->base[0] != 0 || mxd->ks != ksd) return KE_EUNSUPPORTED;
+        a.mxd_frag = mxd->d_frag;
+        a.hd_bias = chd->d_bias;
+        a.vd_cpacked = tv->d_cpacked; a.vd_cstart = tv->d_cstart; a.vd_bias = cvd->d_bias;
+        a.ndwcv = tv->ndwc;
+        a.hpd = ((std::max(plan ? 0 : tv->cspan, rows_padded) + 7) & ~7) + 8;
+        a.dhash = d_dhash; a.tile98_out = d_tile98;
+        lds += (size_t)9 * a.hpd;
+    }
+    // the exchange area X behind the columns: the wide kernel's waves always meet there (12 KB, and 14 KB more for the
+    // dHash leg), the narrow kernel's only for its dHash leg (4 KB)
+    if (wide || DH) {
+        lds = (lds + 15) & ~(size_t)15;
+        a.x_off = (int)lds;
+        lds += wide ? 2 * 2 * 3 * 1024 + (DH ? 2 * 7 * 1024 : 0) : 4096;
+    }
+    // up to 80 KB two workgroups share a CU.  A tall image (its 32 x H transposed columns) would need more and run one
+    // per CU; if cutting it into bands brings the columns back under that line, decline: the caller then runs this
+    // kernel per band (measured 5.4-6.0 TB/s against 3.9-4.9 for one workgroup per CU)
+    if (lds > 150 * 1024) return KE_EUNSUPPORTED;
+    if (!plan && lds > 80 * 1024 && lds - (size_t)(32 * (a.hp - 136)) - (DH ? (size_t)(9 * (a.hpd - 136)) : 0) <= 80 * 1024) return KE_EUNSUPPORTED;
+    if (lds > 64 * 1024)
+        KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kSpKernels[r]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (g.n * (plan ? plan->bands : 1) > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch");
+    hipLaunchKernelGGL(kSpKernels[r], dim3((unsigned)(g.n * (plan ? plan->bands : 1))), dim3(threads), lds, ctx->stream, a);
+    KE_HIP(ctx, hipGetLastError());
+    return KE_OK;
+}
+
+// Picks the single-pass kernel for a group (row length, bytes per pixel, one or both hashes) and launches it: the rows
+// ke_single_pass_candidates lists, in its order, until one does not decline.
 // plan == NULL: one workgroup per image, hashes (and optional tiles) written directly.  plan != NULL: band mode, the
 // transposed columns go to plan->hs / plan->hsd and the caller finishes with ke_vtile.  *did_d: dHash was covered too.
 // Returns KE_EUNSUPPORTED when no single-pass kernel takes the shape (or its LDS needs exceed the CU).
 int dispatch_single_pass(ke_ctx *ctx, const KeHashGroup &g, bool want_d, uint64_t *d_phash, uint8_t *d_t32, uint64_t *d_dhash,
                          uint8_t *d_t98, const KeBandPlan *plan, bool *did_d) {
     *did_d = false;
-    const bool unal = g.w % 4 != 0;                // rows that do not end on a 4-pixel boundary: RGB, pHash leg only
-    if (g.misaligned) return KE_EUNSUPPORTED;      // some image of the group does not start on a dword boundary: banded funnel-shift loader
-    if (g.w <= 64 || g.w > (unal ? 1024 : g.channels == 3 ? 2816 : 2048) || g.h == 32 || g.h < 16 || (unal && g.channels != 3) ||
-        (!plan && g.h > 4096) || (int64_t)g.h > (int64_t)g.w * 100 ||
-        (!unal && ((uintptr_t)g.pixels % 4 || !(g.offsets || g.stride % 4 == 0))) ||
-        (int64_t)g.w * g.h * g.channels >= (1LL << 31))
-        return KE_EUNSUPPORTED;
     // ragged groups: ke_hash_images checks every offset and sets g.misaligned when one is not a multiple of 4
+    const KeSpShape shape{g.w, g.h, g.channels, g.misaligned, (uintptr_t)g.pixels % 4 == 0, g.offsets || g.stride % 4 == 0,
+                          want_d, plan != nullptr};
+    int rows[kKeSpMaxCandidates];
+    const int n = ke_single_pass_candidates(shape, rows);
+    if (!n) return KE_EUNSUPPORTED;
     const KeAxisCoeffs *ch = ke_get_coeffs(ctx, g.w, 32);
     const KeAxisCoeffs *cv = ke_get_coeffs(ctx, g.h, 32);
     if (!ch || !cv) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    const bool both = want_d && g.h != 8 && g.channels == 3 && !unal;
-    int rc = KE_EUNSUPPORTED;
-#define KE_MX(W64, KS, DH, GEN, C) rc = launch_fused_mx<W64, KS, DH, GEN, C>(ctx, g, ch, cv, d_phash, d_t32, DH ? d_dhash : nullptr, DH ? d_t98 : nullptr, plan)
-#define KE_WIDE(KSH, QPT, DH, KDW, C) rc = launch_fused_wide<KSH, QPT, DH, KDW, C>(ctx, g, ch, cv, d_phash, d_t32, DH ? d_dhash : nullptr, DH ? d_t98 : nullptr, plan)
-    if (unal) {
-        if (g.w <= 704) {
-            switch ((g.w + 63) / 64) {
-                case 2: rc = launch_fused_mx<2, 2, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                case 3: rc = launch_fused_mx<3, 2, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                case 4: rc = launch_fused_mx<4, 3, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                case 5: rc = launch_fused_mx<5, 3, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                case 6: rc = launch_fused_mx<6, 4, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                case 7: rc = launch_fused_mx<7, 5, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                case 8: rc = launch_fused_mx<8, 5, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                case 9: rc = launch_fused_mx<9, 6, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                case 10: rc = launch_fused_mx<10, 6, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-                default: rc = launch_fused_mx<11, 7, false, true, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan); break;
-            }
-            if (rc != KE_EUNSUPPORTED) return rc;
-        }
-        // wider rows stay on the banded kernel (funnel-shift loader): measured 3.9 TB/s here at 1599 pixels against 5.3 there
-        if (g.w <= 1024) rc = launch_fused_wide<3, 8, false, 1, 3, true>(ctx, g, ch, cv, d_phash, d_t32, nullptr, nullptr, plan);
-        return rc;
+    for (int k = 0; k < n; ++k) {
+        const bool dh = kKeSpRows[rows[k]].dh();
+        const int rc = launch_fused(ctx, rows[k], g, ch, cv, d_phash, d_t32, dh ? d_dhash : nullptr, dh ? d_t98 : nullptr, plan);
+        if (rc != KE_EUNSUPPORTED) { *did_d = dh && rc == KE_OK; return rc; }
     }
-    // ---- rows up to 768 pixels: 256-thread kernel, 32-row tiles
-    if (g.w <= 768) {
-        if (both && g.w <= 512) {                  // pHash + dHash in one pass over the pixels
-            switch (g.w) {
-                case 256: KE_MX(4, 3, true, false, 3); break;
-                case 384: KE_MX(6, 4, true, false, 3); break;
-                case 512: KE_MX(8, 5, true, false, 3); break;
-                default:
-                    switch ((g.w + 63) / 64) {
-                        case 2: KE_MX(2, 2, true, true, 3); break;
-                        case 3: KE_MX(3, 2, true, true, 3); break;
-                        case 4: KE_MX(4, 3, true, true, 3); break;
-                        case 5: KE_MX(5, 3, true, true, 3); break;
-                        case 6: KE_MX(6, 4, true, true, 3); break;
-                        case 7: KE_MX(7, 5, true, true, 3); break;
-                        case 8: KE_MX(8, 5, true, true, 3); break;
-                        default: break;
-                    }
-            }
-            if (rc == KE_OK) { *did_d = true; return KE_OK; }
-            if (rc != KE_EUNSUPPORTED) return rc;
-            if (!plan) return KE_EUNSUPPORTED;     // both legs did not fit one workgroup per image: per band they do (one pass)
-        }
-        // both hashes of RGB rows of 516..768 pixels: the wide-row kernel below has a dHash leg for them, this one does not
-        if (g.channels == 3 && !(both && g.w > 512)) {
-            switch (g.w) {          // widths with their own instantiation: compile-time row length
-                case 256: KE_MX(4, 3, false, false, 3); break;
-                case 384: KE_MX(6, 4, false, false, 3); break;
-                case 512: KE_MX(8, 5, false, false, 3); break;
-                case 640: KE_MX(10, 6, false, false, 3); break;
-                case 768: KE_MX(12, 7, false, false, 3); break;
-                default:
-                    switch ((g.w + 63) / 64) {   // any other multiple of 4: run-time row length, operand steps of the bucket
-                        case 2: KE_MX(2, 2, false, true, 3); break;
-                        case 3: KE_MX(3, 2, false, true, 3); break;
-                        case 4: KE_MX(4, 3, false, true, 3); break;
-                        case 5: KE_MX(5, 3, false, true, 3); break;
-                        case 6: KE_MX(6, 4, false, true, 3); break;
-                        case 7: KE_MX(7, 5, false, true, 3); break;
-                        case 8: KE_MX(8, 5, false, true, 3); break;
-                        case 9: KE_MX(9, 6, false, true, 3); break;
-                        case 10: KE_MX(10, 6, false, true, 3); break;
-                        case 11: KE_MX(11, 7, false, true, 3); break;
-                        default: break;          // 708..764: 8 operand steps do not fit the register file beside the pixel loads
-                    }
-            }
-            if (rc != KE_EUNSUPPORTED) return rc;
-        }
-        if (g.channels == 1) {                     // 1-byte pixels: the luma step is a sign flip, 4-byte loads
-            switch ((g.w + 63) / 64) {
-                case 2: KE_MX(2, 2, false, true, 1); break;
-                case 3: KE_MX(3, 2, false, true, 1); break;
-                case 4: KE_MX(4, 3, false, true, 1); break;
-                case 5: KE_MX(5, 3, false, true, 1); break;
-                case 6: KE_MX(6, 4, false, true, 1); break;
-                case 7: KE_MX(7, 5, false, true, 1); break;
-                case 8: KE_MX(8, 5, false, true, 1); break;
-                case 9: KE_MX(9, 6, false, true, 1); break;
-                case 10: KE_MX(10, 6, false, true, 1); break;
-                case 11: KE_MX(11, 7, false, true, 1); break;
-                case 12: KE_MX(12, 8, false, true, 1); break;
-                default: break;
-            }
-            if (rc != KE_EUNSUPPORTED) return rc;
-        }
-        if (g.channels == 4 && g.w <= 640) {       // RGBX / RGBA rows: run-time row length per 64-pixel bucket
-            switch ((g.w + 63) / 64) {
-                case 2: KE_MX(2, 2, false, true, 4); break;
-                case 3: KE_MX(3, 2, false, true, 4); break;
-                case 4: KE_MX(4, 3, false, true, 4); break;
-                case 5: KE_MX(5, 3, false, true, 4); break;
-                case 6: KE_MX(6, 4, false, true, 4); break;
-                case 7: KE_MX(7, 5, false, true, 4); break;
-                case 8: KE_MX(8, 5, false, true, 4); break;
-                case 9: KE_MX(9, 6, false, true, 4); break;
-                case 10: KE_MX(10, 6, false, true, 4); break;
-                default: break;
-            }
-            if (rc != KE_EUNSUPPORTED) return rc;
-        }
-    }
-    // ---- wide rows (and what the kernel above left): 512-thread kernel, 16-row tiles
-    if (g.w > (g.channels == 4 ? 640 : g.channels == 1 ? 768 : both ? 512 : 704)) {
-        if (both && g.w <= 2048) {                 // both hashes in one pass
-            if (g.w <= 1024) KE_WIDE(3, 8, true, 2, 3);
-            else if (g.w <= 1536) KE_WIDE(4, 12, true, 3, 3);
-            else KE_WIDE(5, 16, true, 4, 3);
-            if (rc == KE_OK) { *did_d = true; return KE_OK; }
-            if (rc != KE_EUNSUPPORTED) return rc;
-            if (!plan) return KE_EUNSUPPORTED;     // as above
-        }
-        if (g.channels == 4) {
-            if (g.w <= 1024) KE_WIDE(3, 8, false, 1, 4);
-            else if (g.w <= 1536) KE_WIDE(4, 12, false, 1, 4);
-            else KE_WIDE(5, 16, false, 1, 4);
-        } else if (g.channels == 1) {
-            if (g.w <= 1024) KE_WIDE(3, 8, false, 1, 1);
-            else if (g.w <= 1536) KE_WIDE(4, 12, false, 1, 1);
-            else KE_WIDE(5, 16, false, 1, 1);
-        } else {
-            if (g.w <= 1024) KE_WIDE(3, 8, false, 1, 3);
-            else if (g.w <= 1536) KE_WIDE(4, 12, false, 1, 3);
-            else if (g.w <= 2048) KE_WIDE(5, 16, false, 1, 3);
-            else if (g.w <= 2560) KE_WIDE(6, 20, false, 1, 3);      // 2560x1440-class rows: below the strip kernel's range
-            else KE_WIDE(7, 22, false, 1, 3);
-        }
-        if (rc != KE_EUNSUPPORTED) return rc;
-    }
-#undef KE_MX
-#undef KE_WIDE
-    // rows of 516..768 with both hashes wanted that the wide kernel could not take (LDS): pHash alone from the narrow one
-    if (both && g.w > 512 && g.w <= 768) return dispatch_single_pass(ctx, g, false, d_phash, d_t32, nullptr, nullptr, plan, did_d);
     return KE_EUNSUPPORTED;
 }
 
