@@ -210,3 +210,51 @@ def test_progressive_encoder_still_writes_the_same_files():
     for k in range(40):
         h.update(E.random_file(rng, 10 + k, 7 + k, ("444", "422", "420", "440")[k % 4], k % 5 == 0)[0])
     assert h.hexdigest() == "2d981e17b932967bf1e2d3dd98420a225c24a29f94d4ddf5113898967a44bfda"
+
+
+# ---- hand-written files for the IDCT bound, the planes' padding and the colour cube (tests/_jpeg_sample_cases.py) --------------------
+def test_sample_cases_cover_what_they_are_for():
+    """From the coefficients and from Pillow alone: 600+ blocks within 1 384 of the bound on the inside, 300+ files with one
+    block within 1 116 on the outside, both signs, both shortcuts, every component and block position; padding that differs
+    from the last real column / row in every padded file, chroma samples of 0 and 255 and steps of 100 in 100+ files each;
+    all 65 536 pairs of the two ramp planes in every colour file."""
+    import _jpeg_sample_cases as C
+
+    fig = C.coverage()
+    assert fig["taken_blocks"] >= 600 and fig["handed_back_blocks"] >= 300, fig
+    assert max(fig["closest_inside"].values()) <= 8 and max(fig["closest_outside"].values()) <= 8, fig
+    assert all(n == 65536 for name, n in fig["colour_pairs"].items() if name.endswith("noise")), fig
+
+
+def test_extremes_predicts_the_host_builds_status_for_every_bound_case():
+    """The plain-integer restatement of what ke_idct_islow tracks (C.extremes, which built the cases) and the host build agree
+    on which side of the bound every file lies: 0 for a file whose blocks are all narrow, 1 for one with a block outside."""
+    import _jpeg_sample_cases as C
+
+    L = _lib()
+    n = [0, 0]
+    for name, data, facts in C.bound_cases():
+        tq = [c[3] for c in facts.comps] if hasattr(facts, "comps") else [0, 1, 1]
+        predicted = int(not all(C.narrow(plane[at], facts.q[tq[j]]) for j, plane in enumerate(facts.coefs) for at in np.ndindex(plane.shape[:2])))
+        assert predicted == facts.status, name
+        assert _decode(L, data)[0] == predicted, name
+        n[predicted] += 1
+    assert n[0] >= 300 and n[1] >= 350, n
+
+
+def test_taken_padding_and_colour_cases_decode_as_pillow_does():
+    """The host build takes every file inside the bound, every padding file and every colour file with Pillow's pixels, and
+    hands back every file with a block outside (status 1)."""
+    import _jpeg_sample_cases as C
+
+    L = _lib()
+    refs = C.references()
+    for name, data, facts in C.bound_cases() + C.padding_cases() + C.colour_cases():
+        st, out = _decode(L, data)
+        ref = refs[name]
+        assert ref is not None, name
+        if getattr(facts, "status", 0):
+            assert st == 1, name
+            continue
+        assert st == 0, name
+        assert out.shape == ref.shape and np.array_equal(out, ref), name
