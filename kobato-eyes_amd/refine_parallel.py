@@ -21,7 +21,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import _native
-from .formats import enabled_kinds, files_offered
+from .formats import AS_DECODED, TURN, Offers, decoded_bytes_estimate, seam_actions
 
 _phash = importlib.import_module(".phash", __package__)
 log = logging.getLogger("ui.dup_refine")
@@ -72,29 +72,21 @@ def _thumbnails(arrays: Sequence[np.ndarray], side: int, device: int) -> list:
 
 
 def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) -> dict:
-    """{path: side x side BILINEAR luma thumbnail} for the JPEG / PNG / BMP / GIF / TIFF / WebP files whose pixels ``_decode`` would return exactly as
-    the GPU decoders do -- every kind they take, unless the file carries an EXIF orientation to apply (ke_*_caveats).  The
-    files are read, decoded and shrunk without their pixels ever being in host memory; files left out (other formats,
-    refused, damaged, turned) are for ``_decode``.  ``KE_GPU_REFINE_DECODE=0`` turns the route off."""
+    """{path: side x side BILINEAR luma thumbnail} for the files a GPU decoder of formats.FORMATS takes and whose pixels
+    ``_decode`` would return as that decoder does, or as it does once they are turned (formats.seam_actions).  The files are
+    read, decoded and shrunk without their pixels ever being in host memory; files left out (other formats, refused, damaged,
+    flagged) are for ``_decode``.  ``KE_GPU_REFINE_DECODE=0`` turns the route off."""
     out: dict = {}
-    # after each suffix's own decoder the opt-in ones, for the files that one left out: bmpx (RLE, 1 / 4-bit and 16-bit BMP), tiffc
-    # (LZW and PackBits), tiffz (deflate),
-    # webpl (lossless), webpa (lossy files with an alpha plane: convert("L") of RGBA ignores alpha)
-    kinds = enabled_kinds("refine_parallel")
-    if not kinds:
+    offers = Offers("refine_parallel", paths, out)
+    if not offers.kinds:
         return out
     ctx = _native.get_context(device)
-    ran: dict = {}                                                   # kind -> (paths, status) of its decoder's calls
-    for kind, suffixes in kinds:
-        mine = files_offered(kind, [p for p in paths if str(p).lower().endswith(suffixes) and p not in out], ran)
+    for kind, mine in offers:
         at = 0
         while at < len(mine):
             stop, estimate = at, 0                                   # a few GB of decoded pixels per call
             while stop < len(mine) and stop - at < 8192 and (estimate < (4 << 30) or stop == at):
-                try:
-                    estimate += 48 * os.path.getsize(mine[stop])
-                except OSError:
-                    pass
+                estimate += decoded_bytes_estimate(mine[stop])
                 stop += 1
             part = mine[at:stop]
             at = stop
@@ -102,21 +94,20 @@ def _thumbnails_decoded_on_gpu(paths: Sequence[Path], side: int, device: int) ->
                 dev, off, w, h, c, st, flags = ctx.decode_files_owned([str(p) for p in part], kind, by_shape=True)
             except (RuntimeError, ValueError):
                 continue                                             # the Pillow route decides about these files
-            ran.setdefault(kind, ([], []))[0].extend(part)
-            ran[kind][1].extend(st.tolist())
+            offers.ran(kind, part, st)
             if not dev:
                 continue
             try:
+                action, orient = seam_actions(kind, "refine_parallel", w, h, c, st, flags)
                 for idx in _native.runs_laid_out(off, (w, h, c)):   # one run per (width, height, channels)
                     ww, hh, cc = int(w[idx[0]]), int(h[idx[0]]), int(c[idx[0]])
                     thumbs = ctx.resize_luma_uniform(dev + int(off[idx[0]]), len(idx), ww, hh, cc, side, side, filter=1)
                     for k, i in enumerate(idx.tolist()):
-                        if st[i] == 0 and not flags[i] & (3 if kind == "webpl" else 1):     # an RGBA WebP file stays with the loader
+                        if action[i] == AS_DECODED:
                             out[part[i]] = thumbs[k]
                 # files to turn first (src/ui/dup_refine_parallel.py:67-70: ImageOps.exif_transpose before the resize -- every
                 # camera writes the tag): turned on the device into a buffer of their own, then shrunk group by group
-                orient = (flags >> 8) & 15
-                turn = np.nonzero((st == 0) & (c == 3) & ((flags & 1) == 1) & (orient >= 2) & (orient <= 8) & (off != _native.NOT_LAID))[0]
+                turn = np.nonzero((action == TURN) & (off != _native.NOT_LAID))[0]
                 if len(turn):
                     dev2, off2, w2, h2 = ctx.normalise_rgb(dev, off[turn], w[turn], h[turn], c[turn], orient[turn], by_shape=True)
                     try:
@@ -194,7 +185,7 @@ def refine_by_tilehash_parallel(clusters: Sequence, grid: int = 4, tile: int = 8
             if done == total1 and done % 64:
                 tick(done, total1, phase=1)
 
-    # JPEG / PNG files first, thousands at a time, decoded and shrunk on the GPU; what that route leaves goes through Pillow
+    # the files of formats.FORMATS first, thousands at a time, decoded and shrunk on the GPU; what that route leaves goes through Pillow
     todo = []
     for lo in range(0, total1, 4096):
         if is_cancelled and is_cancelled():
@@ -282,7 +273,7 @@ def refine_by_pixels_parallel(clusters: Sequence, mae_thr: float = 0.006, thumb_
     out = []
     ctx = _native.get_context(device)
     pixels = thumb_size * thumb_size
-    # the JPEG / PNG members of all clusters first, thousands at a time: read, decoded and shrunk on the GPU (the per-cluster
+    # the members of all clusters that are files of formats.FORMATS first, thousands at a time: read, decoded and shrunk on the GPU (the per-cluster
     # loop below then only decodes what that route left out)
     ready: dict = {}
     distinct = list(dict.fromkeys(_norm_path(e.file.path) for cl in clusters for e in cl.files))
