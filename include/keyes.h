@@ -387,6 +387,35 @@ int ke_webpa_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, 
                     uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
 int ke_webpa_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
 
+/* The first frame of animated WebP files (VP8X with the animation flag, ANIM, ANMF chunks) decoded on the GPU -- replaces
+ * `Image.open(path)` + pixel access of the reference's batch hasher (src/core/fastsig.py:31-34), which for an animation yields
+ * frame 0, for the last class of the WebP files the reference ranks with its keepers (src/dup/scanner.py:16-28) that stayed with
+ * Pillow.  The pixels are Pillow's, bit for bit: an all-zero canvas of the VP8X size, channels = 4 where the VP8X alpha flag is
+ * set and 3 otherwise whatever the frame carries, the frame's rectangle holding what ke_webp_decode / ke_webpa_decode /
+ * ke_webpl_decode give for the same sub-chunks as a still file (unpremultiplied; alpha 255 for a lossy frame without a plane;
+ * alpha dropped on an RGB canvas).  Frame 0 is a key frame: its blend and dispose bits and the ANIM background colour change
+ * nothing.  The whole container is walked with the demuxer's rules on the host's threads, since Pillow opens an animation only
+ * if all of it demuxes; frame 0 runs through the still decoders' kernels as they are, and one workgroup per (image, tile of
+ * rows) writes the canvas.  A batch may mix the three codecs.  Refused per file with KE_JPEG_UNSUPPORTED_ (1): files without
+ * the animation flag (the still decoders'), a canvas over 2^24 pixels, an odd RIFF size, a VP8X chunk of another size than 10,
+ * an ANMF header whose size is not its bitstream's, an ANMF chunk without an image, fewer than 8 stray bytes at the end, and
+ * whatever the still decoders refuse for the frame; with KE_JPEG_CORRUPT_ (2), as Pillow fails them: a file cut anywhere inside
+ * the RIFF size, reserved VP8X flag bits, the flag without a frame, ALPH / "VP8 " / VP8L / VP8X chunks outside an ANMF chunk,
+ * ANMF before ANIM, an ANIM chunk under 6 or an ANMF chunk under 16 bytes, a frame outside the canvas, sub-chunks that run past
+ * their ANMF chunk, an ALPH chunk behind its frame or beside a VP8L image, an image in any frame whose first bytes the demuxer
+ * fails, and what the still decoders call corrupt in frame 0.
+ * Arguments and conventions as ke_webpa_probe / ke_webpa_decode; ke_webpn_probe reports the canvas, reads the container and
+ * frame 0's tag, ALPH header byte or stream header only, ke_webpn_decode's statuses are final (the frame's where that fails,
+ * else the plane's).  ke_webpn_caveats sets KE_CAVEAT_ORIENTATION for an EXIF or XMP chunk (unread: the loader decides) and
+ * KE_CAVEAT_TRANSPARENCY where channels = 4.  The upload is the span of the taken files, later frames included.  Scratch per
+ * frame as the still decoder of its codec; the canvas needs none; KE_WEBP_SCRATCH_BYTES caps the device scratch of one
+ * sub-batch here too; results do not depend on it. */
+int ke_webpn_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
+                   int32_t *heights, int32_t *channels, int32_t *status_out);
+int ke_webpn_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+int ke_webpn_caveats(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *flags_out);
+
 /* What `Image.open` alone does not tell about a file but the reference's defensive loader acts on (src/utils/image_io.py:60-138:
  * EXIF orientation applied, alpha composited over white): per file a set of KE_CAVEAT_* bits, so that a caller who wants that
  * loader's pixels sends flagged files through it and only the rest through ke_jpeg_decode / ke_png_decode.  ORIENTATION: the
@@ -558,7 +587,7 @@ double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind);
 
 /* ---- for the tests of the scratch budgets (KE_<KIND>_SCRATCH_BYTES; results do not depend on them, so nothing else shows
  * that one was honoured): the number of sub-batches in which the last decode call on this context that runs the shared
- * sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa; the other kinds keep loops of their own or need none) worked
+ * sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa, webpn; the other kinds keep loops of their own or need none) worked
  * off the images it accepted.  0 before any such call; -1 for a NULL context. */
 int64_t ke_last_decode_sub_batches(ke_ctx *ctx);
 

@@ -360,7 +360,7 @@ class Context:
         return float(self._lib.ke_last_kernel_ms(self._h, kind))
 
     def last_decode_sub_batches(self) -> int:
-        """Sub-batches of the last decode call that ran the shared sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa)."""
+        """Sub-batches of the last decode call that ran the shared sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa, webpn)."""
         return int(self._lib.ke_last_decode_sub_batches(self._h))
 
     def last_scan_path(self) -> int:

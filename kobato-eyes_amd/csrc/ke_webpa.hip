@@ -25,20 +25,10 @@
 
 #include "ke_decode_batch.h"
 #include "ke_webp_launch.h"
-#include "ke_webpa_parse.h"
+#include "ke_webpa_launch.h"
 #include "ke_webpl_transform.h"
 
 namespace {
-
-struct KeWebpaDev {
-    uint64_t alph_off;       // what follows the ALPH header byte, inside the uploaded bytes
-    uint64_t plane_off;      // bytes into the scratch (16-aligned): the stream decoder's memory, or a raw plane's bytes
-    uint64_t plane_words;    // ke_webpa_plane_words
-    uint64_t out_off;        // bytes into the caller's pixel buffer
-    uint32_t alph_size;
-    int32_t method, filter;  // KE_ALPH_*, KE_ALPH_FILTER_*
-    int32_t width, height;
-};
 
 __global__ __launch_bounds__(64) void ke_webpa_entropy_k(const KeWebpaDev *__restrict__ planes, const int32_t *__restrict__ order, int64_t n,
                                                         const uint8_t *__restrict__ files, uint8_t *__restrict__ scratch,
@@ -191,6 +181,19 @@ __global__ __launch_bounds__(256) void ke_webpa_colour_k(const KeWebpDev *__rest
 
 }  // namespace
 
+int ke_webpa_launch_planes(ke_ctx *ctx, const KeWebpaDev *d_planes, const int32_t *d_order, int64_t m, int64_t m1, int max_gradient_height,
+                           const uint8_t *d_files, uint8_t *d_scratch, KeVp8lPlan *d_plans, const int32_t *d_status_f, int32_t *d_status_a) {
+    if (m1) {
+        hipLaunchKernelGGL(ke_webpa_entropy_k, dim3((unsigned)((m1 + 63) / 64)), dim3(64), 0, ctx->stream, d_planes, d_order, m1, d_files, d_scratch,
+                           d_plans, d_status_a);
+        hipLaunchKernelGGL(ke_webpa_transform_k, dim3((unsigned)m1), dim3(kPlaneThreads), 0, ctx->stream, d_planes, d_order, d_scratch,
+                           (const KeVp8lPlan *)d_plans, (const int32_t *)d_status_a);
+    }
+    hipLaunchKernelGGL(ke_webpa_filter_k, dim3((unsigned)m), dim3(kPlaneThreads), (size_t)3 * max_gradient_height, ctx->stream, d_planes, d_files,
+                       d_scratch, d_status_f, (const int32_t *)d_status_a);
+    return KE_OK;
+}
+
 KE_API int ke_webpa_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                           int32_t *heights, int32_t *channels, int32_t *status_out) {
     return ke_probe_each(files, offsets, sizes, n, widths, heights, channels, status_out,
@@ -296,14 +299,8 @@ KE_API int ke_webpa_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *of
         if (m1) KE_HIP(ctx, hipMemcpyAsync((uint8_t *)d_meta + at_order, order.data(), (size_t)m1 * 4, hipMemcpyHostToDevice, ctx->stream));
         KE_HIP(ctx, hipMemsetAsync(d_status_a, 0, (size_t)m * 4, ctx->stream));      // planes without a stream have nothing to fail
         KE_TRY(ke_webp_launch_frames(ctx, d_imgs, m, (const uint8_t *)d_files, (uint8_t *)d_scratch, d_status_f));
-        if (m1) {
-            hipLaunchKernelGGL(ke_webpa_entropy_k, dim3((unsigned)((m1 + 63) / 64)), dim3(64), 0, ctx->stream, d_planes, d_order, m1,
-                               (const uint8_t *)d_files, (uint8_t *)d_scratch, (KeVp8lPlan *)d_plans, d_status_a);
-            hipLaunchKernelGGL(ke_webpa_transform_k, dim3((unsigned)m1), dim3(kPlaneThreads), 0, ctx->stream, d_planes, d_order, (uint8_t *)d_scratch,
-                               (const KeVp8lPlan *)d_plans, (const int32_t *)d_status_a);
-        }
-        hipLaunchKernelGGL(ke_webpa_filter_k, dim3((unsigned)m), dim3(kPlaneThreads), (size_t)3 * max_filtered, ctx->stream, d_planes,
-                           (const uint8_t *)d_files, (uint8_t *)d_scratch, (const int32_t *)d_status_f, (const int32_t *)d_status_a);
+        KE_TRY(ke_webpa_launch_planes(ctx, d_planes, d_order, m, m1, max_filtered, (const uint8_t *)d_files, (uint8_t *)d_scratch, (KeVp8lPlan *)d_plans,
+                                      (const int32_t *)d_status_f, d_status_a));
         const KeRowTiles tiles = ke_row_tiles(max_height, kRowsPerBlock);
         hipLaunchKernelGGL(ke_webpa_colour_k, dim3((unsigned)m, tiles.grid_y), dim3(256), 0, ctx->stream, d_imgs,
                            d_planes, (const uint8_t *)d_files, (const uint8_t *)d_scratch, (const int32_t *)d_status_f,

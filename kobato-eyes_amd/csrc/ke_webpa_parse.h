@@ -86,6 +86,20 @@ static inline int ke_webpa_container(const uint8_t *p, size_t size, uint32_t &vp
     return have_vp8 ? KE_WEBPA_OK : KE_WEBPA_UNSUPPORTED;
 }
 
+// The ALPH chunk's header byte and what the plane needs of the payload h.alph_off / h.alph_size name, beside a frame whose tag
+// passed -- whichever container walk found the two (this file's, or ke_webpn_parse.h's inside an ANMF chunk).
+static inline void ke_webpa_alph_at(const uint8_t *p, KeWebpaHeader &h) {
+    if (h.f.status != KE_WEBP_OK) return;
+    if (h.alph_size < 2) { h.f.status = KE_WEBPA_CORRUPT; return; }
+    KeAlphHeader a;
+    h.f.status = ke_alph_header(p[h.alph_off], a);
+    if (h.f.status != KE_WEBPA_OK) return;
+    h.method = a.method; h.filter = a.filter; h.pre = a.pre;
+    h.alph_off += 1;
+    h.alph_size -= 1;
+    if (h.method == KE_ALPH_RAW && (uint64_t)h.alph_size < (uint64_t)h.f.width * h.f.height) h.f.status = KE_WEBPA_CORRUPT;
+}
+
 // The container, the frame tag and the ALPH header: status, size, what ke_webpa_probe reports.  A file that passes here can
 // still be refused by ke_parse_webpa (the frame's boolean-coded header) and by the decode (the token partitions, the plane's
 // stream).
@@ -96,15 +110,7 @@ static inline void ke_webpa_tag(const uint8_t *p, size_t size, KeWebpaHeader &h)
     h.f.status = ke_webpa_container(p, size, h.f.vp8_off, h.f.vp8_size, h.alph_off, h.alph_size, have_alph, cw, ch, h.f.meta);
     if (h.f.status != KE_WEBPA_OK) return;
     ke_webp_frame_tag_at(p, h.f, cw, ch);
-    if (h.f.status != KE_WEBP_OK || !have_alph) return;
-    if (h.alph_size < 2) { h.f.status = KE_WEBPA_CORRUPT; return; }
-    KeAlphHeader a;
-    h.f.status = ke_alph_header(p[h.alph_off], a);
-    if (h.f.status != KE_WEBPA_OK) return;
-    h.method = a.method; h.filter = a.filter; h.pre = a.pre;
-    h.alph_off += 1;
-    h.alph_size -= 1;
-    if (h.method == KE_ALPH_RAW && (uint64_t)h.alph_size < (uint64_t)h.f.width * h.f.height) h.f.status = KE_WEBPA_CORRUPT;
+    if (have_alph) ke_webpa_alph_at(p, h);
 }
 
 static inline void ke_parse_webpa(const uint8_t *p, size_t size, KeWebpaHeader &h) {

@@ -17,18 +17,10 @@
 #include <vector>
 
 #include "ke_decode_batch.h"
-#include "ke_webpl_parse.h"
+#include "ke_webpl_launch.h"
 #include "ke_webpl_transform.h"
 
 namespace {
-
-struct KeWebplDev {
-    KeWebplHeader h;
-    uint64_t file_off;       // the file inside the uploaded bytes
-    uint64_t scratch_off;    // bytes into the scratch (16-aligned)
-    uint64_t scratch_words;  // ke_vp8l_scratch_words(width, height)
-    uint64_t out_off;        // bytes into the caller's pixel buffer
-};
 
 __global__ __launch_bounds__(64) void ke_webpl_entropy_k(const KeWebplDev *__restrict__ imgs, int64_t n, const uint8_t *__restrict__ files,
                                                         uint8_t *__restrict__ scratch, KeVp8lPlan *__restrict__ plans,
@@ -68,6 +60,14 @@ __global__ __launch_bounds__(256) void ke_webpl_output_k(const KeWebplDev *__res
 }
 
 }  // namespace
+
+int ke_webpl_launch_images(ke_ctx *ctx, const KeWebplDev *d_imgs, int64_t m, const uint8_t *d_files, uint8_t *d_scratch, KeVp8lPlan *d_plans,
+                           int32_t *d_status) {
+    hipLaunchKernelGGL(ke_webpl_entropy_k, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, d_imgs, m, d_files, d_scratch, d_plans, d_status);
+    hipLaunchKernelGGL(ke_webpl_transform_k, dim3((unsigned)m), dim3(kTransformThreads), 0, ctx->stream, d_imgs, d_scratch, (const KeVp8lPlan *)d_plans,
+                       (const int32_t *)d_status);
+    return KE_OK;
+}
 
 KE_API int ke_webpl_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n, int32_t *widths,
                           int32_t *heights, int32_t *channels, int32_t *status_out) {
@@ -146,10 +146,8 @@ KE_API int ke_webpl_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *of
         KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, m * 4, &d_status));
         KE_TRY(ke_reserve(ctx, KE_BUF_OUT1, m * sizeof(KeVp8lPlan), &d_plans));
         KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs.data(), m * sizeof(KeWebplDev), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(ke_webpl_entropy_k, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (const KeWebplDev *)d_imgs, (int64_t)m,
-                           (const uint8_t *)d_files, (uint8_t *)d_scratch, (KeVp8lPlan *)d_plans, (int32_t *)d_status);
-        hipLaunchKernelGGL(ke_webpl_transform_k, dim3((unsigned)m), dim3(kTransformThreads), 0, ctx->stream, (const KeWebplDev *)d_imgs,
-                           (uint8_t *)d_scratch, (const KeVp8lPlan *)d_plans, (const int32_t *)d_status);
+        KE_TRY(ke_webpl_launch_images(ctx, (const KeWebplDev *)d_imgs, (int64_t)m, (const uint8_t *)d_files, (uint8_t *)d_scratch, (KeVp8lPlan *)d_plans,
+                                      (int32_t *)d_status));
         const KeRowTiles tiles = ke_row_tiles(max_height, kRowsPerBlock);
         hipLaunchKernelGGL(ke_webpl_output_k, dim3((unsigned)m, tiles.grid_y), dim3(256), 0, ctx->stream,
                            (const KeWebplDev *)d_imgs, (const uint8_t *)d_scratch, (const int32_t *)d_status, pixels_out, tiles.rows);

@@ -32,6 +32,23 @@ inline uint32_t le32(const uint8_t *p) { return le24(p) | ((uint32_t)p[3] << 24)
 inline bool tag(const uint8_t *p, const char *t) { return std::memcmp(p, t, 4) == 0; }
 }  // namespace ke_webpl_detail
 
+// The 5-byte header of the VP8L payload h.off / h.size name, whichever container walk found it (this file's, or
+// ke_webpn_parse.h's inside an ANMF chunk); cw x ch: the size the container wants of the image, 0 where it names none.
+static inline void ke_webpl_stream_header(const uint8_t *p, KeWebplHeader &h, int cw, int ch) {
+    using namespace ke_webpl_detail;
+    h.status = KE_WEBPL_UNSUPPORTED;
+    const uint8_t *f = p + h.off;
+    if (h.size < 5 || f[0] != 0x2f) { h.status = KE_WEBPL_CORRUPT; return; }
+    const uint32_t bits = le32(f + 1);
+    h.width = (int)(bits & 0x3fff) + 1;
+    h.height = (int)((bits >> 14) & 0x3fff) + 1;
+    h.channels = ((bits >> 28) & 1) ? 4 : 3;
+    if ((bits >> 29) != 0) return;                                     // version
+    if (cw && (cw != h.width || ch != h.height)) return;
+    if ((int64_t)h.width * h.height > kWebplMaxPixels) return;
+    h.status = KE_WEBPL_OK;
+}
+
 static inline void ke_parse_webpl(const uint8_t *p, size_t size, KeWebplHeader &h) {
     using namespace ke_webpl_detail;
     std::memset(&h, 0, sizeof h);
@@ -73,16 +90,7 @@ static inline void ke_parse_webpl(const uint8_t *p, size_t size, KeWebplHeader &
         pos = next;
     }
     if (!have) return;
-    const uint8_t *f = p + h.off;
-    if (h.size < 5 || f[0] != 0x2f) { h.status = KE_WEBPL_CORRUPT; return; }
-    const uint32_t bits = le32(f + 1);
-    h.width = (int)(bits & 0x3fff) + 1;
-    h.height = (int)((bits >> 14) & 0x3fff) + 1;
-    h.channels = ((bits >> 28) & 1) ? 4 : 3;
-    if ((bits >> 29) != 0) return;                                     // version
-    if (extended && (canvas_w != h.width || canvas_h != h.height)) return;
-    if ((int64_t)h.width * h.height > kWebplMaxPixels) return;
-    h.status = KE_WEBPL_OK;
+    ke_webpl_stream_header(p, h, extended ? canvas_w : 0, canvas_h);
 }
 
 // One pixel's bytes: R, G, B and, with four channels, A.

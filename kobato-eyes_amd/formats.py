@@ -28,6 +28,7 @@ class Format(NamedTuple):
     orientation_number: bool = False            # the caveats carry the orientation itself: the seams can turn the file on the device
     rgba_leave: Optional[int] = None            # refine: the flag bits that send an RGBA file to the loader, not over white on the device (None: always)
     luma_leave: int = CAVEAT_ORIENTATION        # refine_parallel: the flag bits that keep a file from being used as decoded
+    hash_only: bool = False                     # only the hashing seam offers the decoder its files; at the refine seams they go to the loader
 
 
 _TIFF_SHAPES = "HxW gray or luma of a palette file, HxWx3, HxWx4"
@@ -59,6 +60,9 @@ FORMATS = (
            "RGBA pixels (HxWx4) of lossy WebP files with an alpha plane (one VP8 key frame + an ALPH chunk, or the VP8X alpha "
            "flag alone) decoded on the GPU, as ``Image.open(f)`` yields them",
            rgba_leave=CAVEAT_ORIENTATION),       # every file it takes carries the transparency bit: the orientation decides
+    Format("webpn", (".webp",), "KE_GPU_WEBP", "KE_GPU_WEBP_ANIMATED", "webp", False,
+           "Frame 0 of animated WebP files decoded on the GPU, as ``Image.open(f)`` yields it -- the zeroed canvas with the frame in "
+           "its rectangle, HxWx4 RGBA where the VP8X alpha flag is set, HxWx3 RGB otherwise", hash_only=True),
 )
 KINDS = tuple(f.kind for f in FORMATS)
 # the kinds a file's suffix alone assigns it to -- the order in which a hashing batch's files lie in the read-ahead buffer
@@ -76,14 +80,15 @@ def enabled_kinds(seam: str) -> list:
     ``seam``: "hash" (fastsig's batch hasher), "refine" (refine.refine_pairs) or "refine_parallel" (the thumbnail route).  A
     decoder is on unless its off-switch is "0" -- which also takes the decoders that follow it --, an opt-in decoder only when
     its variable is "1".  ``KE_GPU_REFINE_DECODE=0`` turns both refine routes off; "refine" compares pictures and leaves out
-    the luma-only decoders; "refine_parallel" runs every suffix's own decoder before any follow-up."""
+    the luma-only decoders; "refine_parallel" runs every suffix's own decoder before any follow-up; neither refine route offers
+    a ``hash_only`` decoder anything."""
     if seam not in ("hash", "refine", "refine_parallel"):
         raise ValueError(f"unknown seam {seam!r}")
     if seam != "hash" and os.environ.get("KE_GPU_REFINE_DECODE", "1") == "0":
         return []
     rows = [f for f in FORMATS
             if os.environ.get(f.off_switch, "1") != "0" and (f.opt_in is None or os.environ.get(f.opt_in, "0") == "1")
-            and not (seam == "refine" and f.luma_only)]
+            and not (seam == "refine" and f.luma_only) and not (seam != "hash" and f.hash_only)]
     if seam == "refine_parallel":
         rows.sort(key=lambda f: f.follows is not None)
     return [(f.kind, f.suffixes) for f in rows]
