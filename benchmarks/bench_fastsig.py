@@ -4,7 +4,13 @@ on disk -> signatures rows in SQLite.  Two runs of the same call: JPEG / PNG fil
 `KE_GPU_JPEG=0 ... KE_GPU_WEBP=0` (Pillow on the thread pool, pixels through the pinned staging buffers -- the route every other
 format takes); both hash on the GPU.
     python benchmarks/bench_fastsig.py [--images 16384 --format jpeg|png|mixed --content corpus|drawing]
-One JSON line."""
+One JSON line.
+
+    python benchmarks/bench_fastsig.py --devices none --devices 0 --devices 0,0 [--repeats 5]
+instead times the same call under each ``devices`` value (``none``: the single-device path; a list: the rank workers of
+kobato_eyes_amd/ranks.py): one call to start the pool and grow the buffers, then the median, lowest and highest of ``--repeats``
+calls, one JSON line per value.  ``none`` against ``0`` is the cost of the process boundary.  A list that names a device more than
+once is a rehearsal on one GPU, not a scaling measurement, and its line says so."""
 from __future__ import annotations
 
 import argparse
@@ -33,6 +39,9 @@ def main():
     ap.add_argument("--distinct", type=int, default=128, help="distinct images behind the files")
     ap.add_argument("--content", choices=["corpus", "drawing"], default="corpus")
     ap.add_argument("--pillow-sample", type=int, default=4096, help="files of the batch given to the Pillow-route run")
+    ap.add_argument("--devices", action="append", default=None, metavar="none|D[,D...]",
+                    help="time the call under this devices= value instead of the two decode routes; may be given several times")
+    ap.add_argument("--repeats", type=int, default=5, help="timed calls per --devices value")
     args = ap.parse_args()
     from PIL import Image
 
@@ -72,6 +81,8 @@ def main():
         db = os.path.join(root, "sig.db")
         with sqlite3.connect(db) as conn:
             conn.execute("CREATE TABLE signatures (file_id INTEGER PRIMARY KEY, phash_u64 INTEGER NOT NULL, dhash_u64 INTEGER NOT NULL)")
+        if args.devices:
+            return time_devices(args, fastsig, db, items, nbytes)
         # first call: includes growing the context's page-locked packing buffer and its device decode buffer to the batch size
         # (hipHostMalloc / hipMalloc of gigabytes: 0.3-0.7 s, once per process); the second call is what a large library sees
         t0 = time.perf_counter()
@@ -97,6 +108,30 @@ def main():
                           "same_rows": True}))
     finally:
         shutil.rmtree(root, ignore_errors=True)
+
+
+def time_devices(args, fastsig, db, items, nbytes):
+    want = None
+    for spec in args.devices:
+        devices = None if spec.strip().lower() == "none" else [int(d) for d in spec.split(",") if d.strip()]
+        rows = fastsig.fast_fill_missing_signatures(db, items, apply_to_db=False, devices=devices)    # pool started, buffers grown
+        want = rows if want is None else want
+        assert rows == want and len(rows) == args.images           # the same rows under every value
+        walls = []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            fastsig.fast_fill_missing_signatures(db, items, devices=devices)
+            walls.append(time.perf_counter() - t0)
+        rates = sorted(args.images / w for w in walls)
+        shared = devices is not None and len(set(devices)) < len(devices)
+        print(json.dumps({"case": "fast_fill_missing_signatures_devices", "devices": devices, "format": args.format, "content": args.content,
+                          "images": args.images, "side": args.side, "file_mb": nbytes / 1e6, "repeats": args.repeats,
+                          "median_images_per_s": float(np.median(rates)), "lowest_images_per_s": rates[0], "highest_images_per_s": rates[-1],
+                          "wall_ms": [w * 1e3 for w in walls], "decode_threads": max(1, fastsig._usable_cpus() - 1),
+                          "what": "single-device path" if devices is None else
+                                  "rehearsal: workers share one GPU, not a scaling measurement" if shared else
+                                  "one worker process: against devices=None, the cost of the process boundary" if len(devices) == 1 else
+                                  "one worker process per device"}), flush=True)
 
 
 if __name__ == "__main__":

@@ -56,14 +56,17 @@ def compute_signature(image_or_path, *, device: int = 0) -> tuple[int, int]:
 def find_duplicates(files: Iterable, *, hamming_threshold: int = 8, ssim_threshold: Optional[float] = None,
                     size_ratio: Optional[float] = None, band_bits: int = 16, band_count: int = 4,
                     scanner_factory: Callable[[DuplicateScanConfig], DuplicateScanner] = DuplicateScanner,
-                    device: int = 0) -> list:
+                    device: Optional[int] = None, devices: Optional[Sequence[int]] = None) -> list:
     """Clusters of near-duplicates.
 
     ``files``: DuplicateFile objects or row mappings (anything ``DuplicateFile.from_row`` takes;
     malformed rows are skipped as at src/ui/dup_workers.py:205-209).  With ``ssim_threshold``
     set, every candidate edge is re-checked with the SSIM kernel on the files' pixels and only
-    edges with ``ssim >= ssim_threshold`` survive into the clusters.
+    edges with ``ssim >= ssim_threshold`` survive into the clusters.  ``devices``: the SSIM re-check is spread over one worker
+    process per entry (``refine_pairs``); the scan stays in this process, on ``device`` (default ``devices[0]``, else 0).
     """
+    if device is None:
+        device = int(devices[0]) if devices else 0
     parsed: list[DuplicateFile] = []
     for item in files:
         if isinstance(item, DuplicateFile):
@@ -90,15 +93,20 @@ def find_duplicates(files: Iterable, *, hamming_threshold: int = 8, ssim_thresho
     by_id = {f.file_id: f for f in candidates}
     # every file decoded once, one fit + one SSIM launch per size group (refine_pairs), not one of each per edge
     matches = _refine.refine_pairs([(e.file_id_a, e.file_id_b, by_id[e.file_id_a].path, by_id[e.file_id_b].path) for e in edges],
-                                   thresholds=_refine.RefinementThresholds(ssim=ssim_threshold), device=device)
+                                   thresholds=_refine.RefinementThresholds(ssim=ssim_threshold), device=device, devices=devices)
     kept = [e for e, m in zip(edges, matches) if m is not None and m.is_duplicate]
     return assemble_clusters(candidates, kept) if kept else []
 
 
 def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None, config: Optional[DuplicateScanConfig] = None,
                        progress: Optional[Callable[[str, int, int], None]] = None,
-                       cancel_fn: Optional[Callable[[], bool]] = None, device: int = 0) -> list:
-    """Headless ``DuplicateScanRunnable.run``: stage names and order as the reference emits them."""
+                       cancel_fn: Optional[Callable[[], bool]] = None, device: Optional[int] = None,
+                       devices: Optional[Sequence[int]] = None) -> list:
+    """Headless ``DuplicateScanRunnable.run``: stage names and order as the reference emits them.  ``devices``: the missing
+    signatures are computed by one worker process per entry (``fast_fill_missing_signatures``); the scan and the clusters stay
+    in this process, on ``device`` (default ``devices[0]``, else 0)."""
+    if device is None:
+        device = int(devices[0]) if devices else 0
     def tick(stage, done, total):
         if progress:
             progress(stage, done, total)
@@ -110,7 +118,8 @@ def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None
     if missing:
         filled = fastsig.fast_fill_missing_signatures(
             db_path or ":memory:", missing, max_workers=8, chunksize=64, apply_to_db=db_path is not None,
-            progress=lambda d, t: tick("Computing signatures", d, t), cancel_fn=cancel_fn, device=device)
+            progress=lambda d, t: tick("Computing signatures", d, t), cancel_fn=cancel_fn, device=device,
+            devices=devices)
         by_id = {fid: ph for fid, ph, _ in filled}
         for r in rows:
             fid = int(r.get("file_id", r.get("id")))

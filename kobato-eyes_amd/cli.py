@@ -1,7 +1,7 @@
 """Headless duplicate scan over a kobato-eyes SQLite database.
 
     python -m kobato_eyes_amd.cli scan-dups --db kobato.db --hamming 8 [--like '%/photos/%'] [--size-ratio 0.5]
-                                            [--refine] [--csv out.csv]
+                                            [--refine] [--csv out.csv] [--device 0] [--devices 0,1,2]
 
 Reproduces the call sequence of DuplicateScanRunnable.run (src/ui/dup_workers.py:148-239) without Qt: rows in
 the shape of db.repository.iter_files_for_dup (src/db/repository.py:416-454), missing signatures filled and
@@ -49,9 +49,15 @@ def export_duplicate_clusters_csv(clusters: Sequence, file_path) -> None:
 
 
 def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, path_like: Optional[str] = None,
-                  refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: int = 0, progress=None) -> list:
+                  refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
+                  devices: Optional[Sequence[int]] = None) -> list:
+    """``devices``: the missing signatures are computed by one worker process per entry; the scan and the tile-aHash / MAE
+    refine stay in this process, on ``device`` (default ``devices[0]``, else 0)."""
     from . import DuplicateFile, DuplicateScanConfig, DuplicateScanner, fast_fill_missing_signatures
     from .refine_parallel import refine_by_pixels_parallel, refine_by_tilehash_parallel
+
+    if device is None:
+        device = int(devices[0]) if devices else 0
 
     def tick(stage, done, total):
         if progress:
@@ -68,7 +74,8 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
         workers = int(os.environ.get("KE_SIG_WORKERS", "8"))
         chunk = int(os.environ.get("KE_SIG_CHUNK", "64"))
         filled = fast_fill_missing_signatures(db_path, missing, max_workers=workers, chunksize=chunk,
-                                              progress=lambda d, t: tick("Computing signatures", d, t), device=device)
+                                              progress=lambda d, t: tick("Computing signatures", d, t), device=device,
+                                              devices=devices)
         by_id = {fid: ph for fid, ph, _ in filled}
         for r in rows:
             if r["phash_u64"] is None:
@@ -103,12 +110,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("--tile-max-bits", type=int, default=32)
     sp.add_argument("--mae-thr", type=float, default=0.004)
     sp.add_argument("--csv", default=None)
-    sp.add_argument("--device", type=int, default=0)
+    sp.add_argument("--device", type=int, default=None, help="where the scan and the refine run (default: the first of --devices, else 0)")
+    sp.add_argument("--devices", default=None, type=lambda text: [int(d) for d in text.split(",") if d.strip()],
+                    help="e.g. 0,1,2: missing signatures are computed by one worker process per entry (at most 15)")
     sp.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARNING)
     clusters = scan_database(args.db, hamming_threshold=args.hamming, size_ratio=args.size_ratio, path_like=args.like,
-                             refine=args.refine, tile_max_bits=args.tile_max_bits, mae_thr=args.mae_thr, device=args.device)
+                             refine=args.refine, tile_max_bits=args.tile_max_bits, mae_thr=args.mae_thr, device=args.device,
+                             devices=args.devices)
     if args.csv:
         export_duplicate_clusters_csv(clusters, args.csv)
     members = sum(len(c.files) for c in clusters)

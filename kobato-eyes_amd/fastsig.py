@@ -761,13 +761,26 @@ class _SignedRows(list):
 
 def compute_signatures_mp(tasks: List[Task], *, max_workers: Optional[int] = None, chunksize: int = 64,
                           progress: Optional[Callable[[int, int], None]] = None,
-                          cancel_fn: Optional[Callable[[], bool]] = None, device: int = 0) -> List[Row]:
-    """[(file_id, path)] -> [(file_id, phash_s64, dhash_s64)], input order, failures omitted."""
+                          cancel_fn: Optional[Callable[[], bool]] = None, device: int = 0,
+                          devices: Optional[Sequence[int]] = None, rank_chunk: Optional[int] = None) -> List[Row]:
+    """[(file_id, path)] -> [(file_id, phash_s64, dhash_s64)], input order, failures omitted.
+
+    ``devices`` (e.g. ``[0, 1, 2]``; at most 15 entries): the tasks are cut into contiguous chunks of ``rank_chunk`` (default
+    ``min(16 384, ceil(total / N))``) that one worker process per entry takes on demand, each through this pipeline on its own
+    device with ``max_workers // N`` decoders (``ranks.py``).  Order, progress marks and the prefix a ``cancel_fn`` leaves are
+    those of the single-device path, where ``done`` counts the files finished on any worker and a cancelled run returns whole
+    chunks.  A worker that dies or falls silent ends the call with ``RuntimeError``; nothing is dealt again.  Naming one device
+    several times (``[0, 0]``) rehearses the path on a one-GPU box; it is not a way to go faster."""
+    workers = max_workers or max(1, _usable_cpus() - 1)
+    if devices is not None:
+        from . import ranks
+
+        return ranks.compute_signatures(tasks, devices, max_workers=workers, chunksize=chunksize, rank_chunk=rank_chunk,
+                                        progress=progress, cancel_fn=cancel_fn)
     total = len(tasks)
     rows: List[Row] = _SignedRows()
     if total == 0:
         return rows
-    workers = max_workers or max(1, _usable_cpus() - 1)
     def report(seen: int) -> None:
         try:
             progress(seen, total)
@@ -828,10 +841,12 @@ def bulk_upsert_signatures(conn: sqlite3.Connection, rows: Iterable[Row]) -> int
 def fast_fill_missing_signatures(db_path: str, items: List[Task], *, max_workers: Optional[int] = None, chunksize: int = 64,
                                  progress: Optional[Callable[[int, int], None]] = None, apply_to_db: bool = True,
                                  unsafe_fast: bool = True, cancel_fn: Optional[Callable[[], bool]] = None,
-                                 device: int = 0) -> List[Row]:
-    """Hash the files that have no signature yet and (optionally) upsert them; returns the computed rows."""
+                                 device: int = 0, devices: Optional[Sequence[int]] = None,
+                                 rank_chunk: Optional[int] = None) -> List[Row]:
+    """Hash the files that have no signature yet and (optionally) upsert them; returns the computed rows.  ``devices`` /
+    ``rank_chunk``: as ``compute_signatures_mp`` takes them; the upsert stays here, one connection and one transaction."""
     rows = compute_signatures_mp(items, max_workers=max_workers, chunksize=chunksize, progress=progress, cancel_fn=cancel_fn,
-                                 device=device)
+                                 device=device, devices=devices, rank_chunk=rank_chunk)
     if rows and apply_to_db:
         with sqlite3.connect(db_path) as conn:
             if unsafe_fast:

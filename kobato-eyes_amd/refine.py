@@ -188,7 +188,8 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
 
 
 def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThresholds] = None, device: int = 0,
-                 io_workers: int = 8, max_decoded_bytes: int = 1 << 30, stats: Optional[dict] = None) -> list:
+                 io_workers: int = 8, max_decoded_bytes: int = 1 << 30, stats: Optional[dict] = None,
+                 devices: Optional[Sequence[int]] = None, _after_run=None) -> list:
     """``refine_pair`` for a list of ``(file_id_a, file_id_b, path_a, path_b)``: the same ``RefinedMatch`` (or ``None``)
     per pair, in input order -- but every file is decoded once however many pairs share it, and the kernels see groups
     instead of single pairs: one ``ke_fit_luma_uniform`` launch per (source size, channels, common size) and one
@@ -197,7 +198,18 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
 
     Pairs are worked off in runs whose decoded files stay below ``max_decoded_bytes``.  ``stats`` (optional dict)
     receives the launch and decode counts.
+
+    ``devices`` (e.g. ``[0, 1, 2]``; at most 15 entries): the pairs are cut into one contiguous block of about equal
+    ``decoded_bytes_estimate`` per entry, and one worker process per entry runs this function on its block on its own device
+    with ``io_workers // N`` loaders (``ranks.py``).  The answers are those of ``devices=None`` -- the SSIM partial sums are
+    integers --, in input order; ``stats`` holds the workers' counters summed, so ``decodes`` counts a file once per worker
+    that needed it.  A worker that dies or falls silent ends the call with ``RuntimeError``.
     """
+    if devices is not None:
+        from . import ranks
+
+        return ranks.refine_pairs(pairs, devices, thresholds=thresholds, io_workers=io_workers,
+                                  max_decoded_bytes=max_decoded_bytes, stats=stats)
     from concurrent.futures import ThreadPoolExecutor
 
     cfg = thresholds or RefinementThresholds()
@@ -229,6 +241,8 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
                 for dev in buffers:
                     ctx.free(dev)
             start = stop
+            if _after_run is not None:                             # a rank worker says how far it has come
+                _after_run(stop)
     if stats is not None:
         stats.update(count)
     return out
