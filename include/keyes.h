@@ -177,6 +177,14 @@ int ke_jpeg_probe(const uint8_t *files, const uint64_t *offsets, const uint64_t 
                   int32_t *heights, int32_t *channels, int32_t *status_out);
 int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                    uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+/* ke_jpeg_decode at a reduced size: file i is decoded at 1 / denoms[i] (1, 2, 4 or 8; anything else: KE_EINVAL) -- the pixels
+ * Pillow yields after `im.draft(...)` has set that scale up (libjpeg's scale_num / scale_denom: the reduced transforms of
+ * jidctred.c per component, upsampling and colour at the reduced sizes; the reference's loader, src/utils/image_io.py:86-88).
+ * Image i is ceil(heights[i] / denoms[i]) rows of ceil(widths[i] / denoms[i]) pixels at pixels_out + out_offsets[i].  A file
+ * with a block outside the bound of its transform is KE_JPEG_UNSUPPORTED_ as at full size (csrc/ke_jpeg_core.h).  With every
+ * denominator 1 the bytes are ke_jpeg_decode's.  Everything else as ke_jpeg_decode. */
+int ke_jpeg_decode_scaled(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                          const int32_t *denoms, uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
 
 /* ---- PNG decode on the GPU: the same step for PNG files, Adam7-interlaced or not: 8-bit grayscale ("L"), RGB and RGBA pixels as
  * they are; palette files (1 / 2 / 4 / 8 bits) and grayscale of 1 / 2 / 4 bits as the luma `convert("L")` makes of them --
@@ -440,6 +448,16 @@ int ke_normalise_rgb(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offset
  * (out_w, out_h) as Image.thumbnail does (aspect preserved).  src and dst are device memory. */
 int ke_thumbnail_rgb(ke_ctx *ctx, const uint8_t *src, int32_t width, int32_t height, int32_t out_w, int32_t out_h, int32_t filter,
                      uint8_t *dst);
+
+/* What Image.thumbnail does to an image more than four times its target (reducing_gap = 2.0; PIL/Image.py resize), on the
+ * device: first ke_reduce_rgb -- Image.reduce((fx, fy)) for packed RGB, bit for bit: width x height at src -> ceil(width / fx)
+ * x ceil(height / fy) at dst, every pixel the mean of its fx x fy cell in Pillow's fixed point, the partial cells of the last
+ * column and row averaged over the pixels they have; fx, fy in 1..255, each on its own -- then ke_thumbnail_rgb_box:
+ * ke_thumbnail_rgb through the source rectangle box = {x0, y0, x1, y1} (Pillow's resize box, fractional: (0, 0, w / fx, h / fy)
+ * of the reduced image; inside the image or KE_EINVAL).  src and dst are device memory, box is a host array.  Both block. */
+int ke_reduce_rgb(ke_ctx *ctx, const uint8_t *src, int32_t width, int32_t height, int32_t fx, int32_t fy, uint8_t *dst);
+int ke_thumbnail_rgb_box(ke_ctx *ctx, const uint8_t *src, int32_t width, int32_t height, int32_t out_w, int32_t out_h, int32_t filter,
+                         const float *box, uint8_t *dst);
 
 /* Debug/parity hook: the resampled luma tiles the hashes are computed from
  * (reference sig.phash._to_grayscale, src/sig/phash.py:21-26).  tile32_out: n*1024 bytes

@@ -32,7 +32,7 @@ EXPORTS = (
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
-    "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode",
+    "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_thumbnail_rgb_box", "ke_reduce_rgb", "ke_jpeg_decode_scaled", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode",
     "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash", "ke_sad_pairs", "ke_synth_rgb", "ke_synth_rgb_indexed",
     "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches", "ke_last_scan_path",
 ) + tuple(f"ke_{kind}_{call}" for kind in KINDS for call in ("probe", "decode", "caveats"))
@@ -135,6 +135,9 @@ def load_library() -> C.CDLL:
             getattr(lib, f"ke_{kind}_caveats").argtypes = [vp, vp, vp, i64, vp]
         lib.ke_normalise_rgb.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
         lib.ke_thumbnail_rgb.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
+        lib.ke_thumbnail_rgb_box.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
+        lib.ke_reduce_rgb.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+        lib.ke_jpeg_decode_scaled.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp]
         lib.ke_band_pairs_after_size.argtypes = [vp, vp, vp, i64, i32, i32, dbl, i64, vp]
         lib.ke_hamming_scan.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, dbl, i64, vp, i64,
                                         C.POINTER(i64), vp]
@@ -188,7 +191,32 @@ def _leave_bombs_to_pillow(w, h, st, sizes) -> None:
         sizes[bombs] = 0
 
 
-NOT_LAID = np.uint64(0xFFFFFFFFFFFFFFFF)        # lay_out's offset of an item that has no place in the buffer
+def draft_scale(widths, heights, max_side: int):
+    """The denominators ``im.draft("RGB", (max_side, max_side))`` sets libjpeg up with, per file (int32): the largest of 8, 4,
+    2, 1 that is at most min(width // max_side, height // max_side) -- 1 below twice ``max_side`` on either side (PIL
+    JpegImagePlugin.draft; the reference's loader, src/utils/image_io.py:86-88)."""
+    q = np.minimum(np.asarray(widths, np.int64) // max_side, np.asarray(heights, np.int64) // max_side)
+    return np.select([q >= 8, q >= 4, q >= 2], [8, 4, 2], 1).astype(np.int32)
+
+
+def thumbnail_size(width: int, height: int, box: int):
+    """The size ``Image.thumbnail((box, box))`` gives a width x height image (aspect preserved; PIL/Image.py
+    ``preserve_aspect_ratio``)."""
+    import math
+
+    def round_aspect(number, key):
+        return max(min(math.floor(number), math.ceil(number), key=key), 1)
+
+    x = y = box
+    aspect = width / height
+    if x / y >= aspect:
+        x = round_aspect(y * aspect, key=lambda n: abs(aspect - n / y))
+    else:
+        y = round_aspect(x / aspect, key=lambda n: 0 if n == 0 else abs(aspect - x / n))
+    return x, y
+
+
+NOT_LAID = np.uint64(0xFFFFFFFFFFFFFFFF)       # lay_out's offset of an item that has no place in the buffer
 
 
 def lay_out(nbytes, keys=None, absent=None):
@@ -596,9 +624,12 @@ class Context:
         decoder takes the file."""
         return self._probe(self._packed(blobs, pinned=False), kind)
 
-    def _decode_packed(self, files: _Files, kind: str, *, skip=None, owned: bool = False, by_shape: bool = False):
+    def _decode_packed(self, files: _Files, kind: str, *, skip=None, owned: bool = False, by_shape: bool = False, denoms=None):
         """The one decode chain: probe -> bombs left to Pillow -> ``skip`` -> layout -> ``ke_<kind>_decode``, for what the GPU
         decoder takes of ``files``: (device ptr or 0, byte offsets, widths, heights, channels, status, caveat flags or None).
+        ``denoms`` (JPEG only; int32 per file, or a function of the probed (widths, heights) that gives them): the files are
+        decoded at 1 / denoms[i] by ``ke_jpeg_decode_scaled``, the widths and heights returned are those of the reduced images,
+        and the denominators come back as an eighth item.
         The pixels go to the context's decode buffer (device memory, grown on demand and kept: allocating tens of GB per call
         costs up to a second) -- call with the lock held and keep it until they have been used; a batch of more than
         ``decode_limit`` bytes of them is _BatchTooLarge -- or, ``owned``, to an allocation the caller frees, laid out
@@ -615,10 +646,18 @@ class Context:
                 st[skip & (st == 0)] = 1
                 files.sizes[skip] = 0
                 left_alone = st[skip]
+            if denoms is not None:
+                if kind != "jpeg":
+                    raise ValueError("only the jpeg decoder decodes at a reduced size")
+                denoms = np.ascontiguousarray(denoms(w, h) if callable(denoms) else denoms, dtype=np.int32)
+                if len(denoms) != n or not np.isin(denoms, (1, 2, 4, 8)).all():
+                    raise ValueError("one denominator of 1, 2, 4 or 8 per file")
+                w, h = ((w + denoms - 1) // denoms).astype(np.int32), ((h + denoms - 1) // denoms).astype(np.int32)
             nbytes = np.where(st == 0, w.astype(np.int64) * h * c, 0)
             out_off, total = lay_out(nbytes, (w, h, c), st != 0) if by_shape else lay_out(nbytes)     # decodable files first
+            scaled = () if denoms is None else (denoms,)
             if total == 0:
-                return 0, out_off, w, h, c, st, flags
+                return (0, out_off, w, h, c, st, flags) + scaled
             if owned:
                 dev = self.malloc(total + 64)
             else:
@@ -632,8 +671,12 @@ class Context:
                     self._decoded_ptr, self._decoded_cap = self.malloc(cap), cap
                 dev = self._decoded_ptr
             try:
-                self._check(getattr(self._lib, f"ke_{kind}_decode")(self._h, _addr(files.flat), _addr(files.offsets), _addr(files.sizes), n,
-                                                                    dev, _addr(out_off), _addr(st)), f"ke_{kind}_decode")
+                if denoms is not None:
+                    self._check(self._lib.ke_jpeg_decode_scaled(self._h, _addr(files.flat), _addr(files.offsets), _addr(files.sizes), n,
+                                                                _addr(denoms), dev, _addr(out_off), _addr(st)), "ke_jpeg_decode_scaled")
+                else:
+                    self._check(getattr(self._lib, f"ke_{kind}_decode")(self._h, _addr(files.flat), _addr(files.offsets), _addr(files.sizes), n,
+                                                                        dev, _addr(out_off), _addr(st)), f"ke_{kind}_decode")
             except Exception:
                 if owned:
                     self.free(dev)
@@ -642,20 +685,23 @@ class Context:
                 st[skip] = left_alone
             if not owned:
                 self.decode_kernel_ms += self.last_kernel_ms(4)
-        return dev, out_off, w, h, c, st, flags
+        return (dev, out_off, w, h, c, st, flags) + scaled
 
-    def decode_files_owned(self, paths, kind: str = "jpeg", *, by_shape: bool = False):
+    def decode_files_owned(self, paths, kind: str = "jpeg", *, by_shape: bool = False, draft_side: Optional[int] = None):
         """Files on disk decoded into a device buffer of their own (the caller frees it with ``free``): (device ptr or 0, byte
         offsets, widths, heights, channels, status, caveat flags).  ``flags`` are ke_jpeg_caveats / ke_png_caveats' bits: what
         the reference's defensive loader would do to the file beyond Image.open (EXIF orientation, transparency).
         ``by_shape``: images of one (width, height, channels) lie back to back without padding, so that each such group
-        can go to the uniform-batch kernels as it is (runs_laid_out gives the groups back); files not decoded get NOT_LAID."""
+        can go to the uniform-batch kernels as it is (runs_laid_out gives the groups back); files not decoded get NOT_LAID.
+        ``draft_side`` (JPEG files): each file is decoded at the scale the loader's ``draft`` towards that side picks
+        (``draft_scale``), the widths and heights are those of the reduced images, and the denominators follow as an eighth item."""
         paths = list(paths)
         if not paths:
-            return (0, np.zeros(0, np.uint64)) + tuple(np.zeros(0, np.int32) for _ in range(5))
+            return (0, np.zeros(0, np.uint64)) + tuple(np.zeros(0, np.int32) for _ in range(5 if draft_side is None else 6))
+        denoms = None if draft_side is None else (lambda w, h: draft_scale(w, h, draft_side))
         with self._lock:
             files = self._read_files_into(self._pack, paths, bounded=False)     # the caller paces its batches
-            return self._decode_packed(files, kind, owned=True, by_shape=by_shape)
+            return self._decode_packed(files, kind, owned=True, by_shape=by_shape, denoms=denoms)
 
     def normalise_rgb(self, src: int, src_offsets, widths, heights, channels, orientations, *, by_shape: bool = False):
         """Images on the device (decoded files) -> a device buffer of their own (the caller frees it) holding them as the
@@ -685,17 +731,7 @@ class Context:
         """An RGB image on the device -> what ``Image.thumbnail((box, box), LANCZOS)`` makes of it, in a device buffer of its own
         (the caller frees it): (device ptr, width, height).  The size is Image.thumbnail's (aspect preserved, PIL/Image.py
         ``preserve_aspect_ratio``); ke_thumbnail_rgb resamples each band as Pillow does."""
-        import math
-
-        def round_aspect(number, key):
-            return max(min(math.floor(number), math.ceil(number), key=key), 1)
-
-        x = y = box
-        aspect = width / height
-        if x / y >= aspect:
-            x = round_aspect(y * aspect, key=lambda n: abs(aspect - n / y))
-        else:
-            y = round_aspect(x / aspect, key=lambda n: 0 if n == 0 else abs(aspect - x / n))
+        x, y = thumbnail_size(width, height, box)
         dev = self.malloc(x * y * 3 + 64)
         try:
             with self._lock:
@@ -704,6 +740,63 @@ class Context:
             self.free(dev)
             raise
         return dev, x, y
+
+    def reduce_rgb(self, src: int, width: int, height: int, fx: int, fy: int):
+        """An RGB image on the device -> ``Image.reduce((fx, fy))`` of it in a device buffer of its own (the caller frees it):
+        (device ptr, width, height) -- ke_reduce_rgb, factors 1..255 per axis."""
+        ow, oh = -(-width // fx), -(-height // fy)
+        dev = self.malloc(ow * oh * 3 + 64)
+        try:
+            with self._lock:
+                self._check(self._lib.ke_reduce_rgb(self._h, src, width, height, fx, fy, dev), "ke_reduce_rgb")
+        except Exception:
+            self.free(dev)
+            raise
+        return dev, ow, oh
+
+    def thumbnail_rgb_box(self, src: int, width: int, height: int, out_w: int, out_h: int, box, filter: int = 0):
+        """An RGB image on the device resampled to out_w x out_h through the source rectangle ``box`` = (x0, y0, x1, y1), as
+        ``Image.resize((out_w, out_h), filter, box=box)`` does, into a device buffer of its own (the caller frees it)."""
+        box = np.ascontiguousarray(box, dtype=np.float32)
+        dev = self.malloc(out_w * out_h * 3 + 64)
+        try:
+            with self._lock:
+                self._check(self._lib.ke_thumbnail_rgb_box(self._h, src, width, height, out_w, out_h, filter, _addr(box), dev),
+                            "ke_thumbnail_rgb_box")
+        except Exception:
+            self.free(dev)
+            raise
+        return dev
+
+    def thumbnail_rgb_reduced(self, src: int, width: int, height: int, box: int):
+        """``Image.thumbnail((box, box), LANCZOS)`` of an RGB image on the device of any size, with what Pillow's
+        ``reducing_gap`` of 2.0 does to one more than four times its target: ``Image.reduce`` by (fx, fy) first, then the
+        resample through the fractional source box (0, 0, width / fx, height / fy) of the reduced image.  Returns (device ptr
+        -- the caller frees it --, width, height, (fx, fy)); with both factors 1 the result is ``thumbnail_rgb``'s."""
+        x, y = thumbnail_size(width, height, box)
+        fx, fy = int(width / x / 2.0) or 1, int(height / y / 2.0) or 1
+        if fx == 1 and fy == 1:
+            return self.thumbnail_rgb(src, width, height, box) + ((1, 1),)
+        small, sw, sh = self.reduce_rgb(src, width, height, fx, fy)
+        try:
+            return self.thumbnail_rgb_box(small, sw, sh, x, y, (0.0, 0.0, width / fx, height / fy)), x, y, (fx, fy)
+        finally:
+            self.free(small)
+
+    def jpeg_decode_scaled(self, blobs, denoms=None, *, max_side: Optional[int] = None):
+        """JPEG files (bytes) decoded on the GPU at 1 / denoms[i] (1, 2, 4 or 8) -- the pixels Pillow yields after ``draft`` has
+        set that scale up --, or, with ``max_side`` instead, at the scale the reference's loader drafts each file to
+        (``draft_scale``).  Returns (list of ndarrays, None where status != 0; statuses; the denominators)."""
+        if (denoms is None) == (max_side is None):
+            raise ValueError("either denoms or max_side")
+        with self._lock:
+            dev, out_off, w, h, c, st, _, used = self._decode_packed(
+                self._packed(blobs), "jpeg", denoms=denoms if denoms is not None else (lambda w, h: draft_scale(w, h, max_side)))
+            out = [None] * len(blobs)
+            for i in np.nonzero(st == 0)[0].tolist():
+                out[i] = np.empty((h[i], w[i], c[i]) if c[i] > 1 else (h[i], w[i]), np.uint8)
+                self.memcpy(out[i], dev + int(out_off[i]), out[i].nbytes)
+        return out, st, used
 
     def release_decode_buffers(self) -> None:
         """Give back the page-locked packing buffer and the device decode buffer (they are kept between calls otherwise)."""

@@ -729,6 +729,87 @@ __global__ __launch_bounds__(256) void ke_jpeg_colour(const KeJpegDev *__restric
     }
 }
 
+// ---- reduced-size decoding (ke_jpeg_decode_scaled): the coefficients are those of the full-size decode; each component's
+// blocks go through the transform of its size at the file's scale (ke_jpeg_core.h, KeJpegScaled) into planes of that size,
+// and upsampling and colour run over the reduced image.  Planes lie where the full-size ones would (they are smaller).
+__global__ __launch_bounds__(256) void ke_jpeg_idct_scaled(const KeJpegDev *__restrict__ imgs, const KeJpegScaled *__restrict__ geo, int64_t n_imgs,
+                                                           const int16_t *__restrict__ coefs, uint8_t *__restrict__ planes, int32_t *status) {
+    const int64_t img = (int64_t)blockIdx.z * 65535 + blockIdx.y;
+    if (img >= n_imgs) return;
+    const KeJpegDev &d = imgs[img];
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= d.blocks_total) return;
+    const KeJpegInfo &in = d.info;
+    const KeJpegScaled &g = geo[img];
+    int c = 0;
+    if (in.ncomp == 3) c = b >= d.block_base[2] ? 2 : (b >= d.block_base[1] ? 1 : 0);
+    const int local = b - d.block_base[c];
+    const int bpr = in.plane_w[c] >> 3;
+    const int brow = local / bpr, bcol = local - brow * bpr;
+    const int16_t *src = coefs + d.coef_off + (size_t)b * 64;
+    int blk[64];
+    constexpr uint8_t nat[64] = KE_ZZ;                                   // zigzag order in memory, as for ke_jpeg_idct
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int4 v = reinterpret_cast<const int4 *>(src)[k];
+        const int w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            blk[nat[8 * k + 2 * j]] = (int)(int16_t)(w[j] & 0xFFFF) * (int)in.quant[c][nat[8 * k + 2 * j]];
+            blk[nat[8 * k + 2 * j + 1]] = (w[j] >> 16) * (int)in.quant[c][nat[8 * k + 2 * j + 1]];
+        }
+    }
+    uint8_t rows[64];
+    const int ss = g.ss[c], pw = g.plane_w[c];
+    if (!ke_idct_scaled<int[64], IdctMul24>(blk, ss, rows, 8) && status[img] == KE_JPEG_OK) status[img] = KE_JPEG_UNSUPPORTED;
+    uint8_t *dst = planes + d.plane_off[c] + (size_t)(brow * ss) * pw + bcol * ss;
+    if (ss == 8) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            uint2 v;
+            v.x = rows[8 * r] | (rows[8 * r + 1] << 8) | (rows[8 * r + 2] << 16) | ((uint32_t)rows[8 * r + 3] << 24);
+            v.y = rows[8 * r + 4] | (rows[8 * r + 5] << 8) | (rows[8 * r + 6] << 16) | ((uint32_t)rows[8 * r + 7] << 24);
+            *reinterpret_cast<uint2 *>(dst + (size_t)r * pw) = v;
+        }
+    } else {
+        for (int r = 0; r < ss; ++r)
+            for (int x = 0; x < ss; ++x) dst[(size_t)r * pw + x] = rows[8 * r + x];
+    }
+}
+
+// one thread per 4 pixels of a row, as ke_jpeg_colour; the samples are read one by one (planes of a reduced component are as
+// narrow as one byte per block, so nothing here may assume a dword inside a row)
+__global__ __launch_bounds__(256) void ke_jpeg_colour_scaled(const KeJpegDev *__restrict__ imgs, const KeJpegScaled *__restrict__ geo, int64_t n_imgs,
+                                                             int xblocks, const uint8_t *__restrict__ planes, uint8_t *__restrict__ out) {
+    const int64_t img = (int64_t)blockIdx.z * 65535 + blockIdx.y;
+    if (img >= n_imgs) return;
+    const KeJpegDev &d = imgs[img];
+    const KeJpegScaled &g = geo[img];
+    const int ncomp = d.info.ncomp;
+    const int r = threadIdx.x >> 6, q = threadIdx.x & 63;
+    const int block_x = (int)(blockIdx.x % (unsigned)xblocks), block_y = (int)(blockIdx.x / (unsigned)xblocks);
+    const int x0 = block_x * 256 + q * 4;
+    if (x0 >= g.out_w) return;
+    const uint8_t *Y = planes + d.plane_off[0], *Cb = planes + d.plane_off[1], *Cr = planes + d.plane_off[2];
+    uint8_t *dst = out + d.out_off;
+    const int npx = min(4, g.out_w - x0);
+    for (int turn = 0; turn < kColourRows / 4; ++turn) {
+        const int y = block_y * kColourRows + turn * 4 + r;
+        if (y >= g.out_h) break;
+        for (int k = 0; k < npx; ++k) {
+            const int x = x0 + k;
+            const int luma = Y[(size_t)y * g.plane_w[0] + x];
+            if (ncomp == 1) {
+                dst[(size_t)y * g.out_w + x] = (uint8_t)luma;
+                continue;
+            }
+            const int cb = ke_upsample_scaled_at(Cb, g.plane_w[1], g.comp_w[1], g.comp_h[1], g.hfac[1], g.vfac[1], g.fancy, x, y);
+            const int cr = ke_upsample_scaled_at(Cr, g.plane_w[2], g.comp_w[2], g.comp_h[2], g.hfac[2], g.vfac[2], g.fancy, x, y);
+            ke_ycc_to_rgb(luma, cb, cr, dst + ((size_t)y * g.out_w + x) * 3);
+        }
+    }
+}
+
 }  // namespace
 
 // (not ke_probe_each: the parser interns Huffman tables, and a pool lives as long as one thread's range of one call)
@@ -795,8 +876,10 @@ KE_API int ke_jpeg_caveats(const uint8_t *files, const uint64_t *offsets, const 
     });
 }
 
-KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
-                          uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
+// The decode call.  denoms = NULL: ke_jpeg_decode, exactly as before.  Otherwise file i is decoded at 1 / denoms[i]
+// (ke_jpeg_decode_scaled): the same parse, order, entropy kernels and scratch, the IDCT and colour kernels of the reduced sizes.
+static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                             const int32_t *denoms, uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
     KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "compressed files are parsed"));
     if (n == 0) return KE_OK;
     const bool trace = std::getenv("KE_TRACE") != nullptr;
@@ -830,7 +913,8 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
     KeJpegTables tables;                              // one pool for the batch: every part's tables interned again
     std::vector<KeJpegScan> scans;                    // of the progressive files, image after image
     std::vector<int32_t> prog_list;
-    KeStreamGuard guard;                                           // after the host vectors it waits for
+    std::vector<KeJpegScaled> geo;                    // with denoms: the reduced geometry, in device order as devs
+    KeStreamGuard guard;                                          // after the host vectors it waits for
     void *d_files;
     KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));   // the stream windows read up to 64 bytes past a file
     std::unique_ptr<KeJpegDev[]> all(new KeJpegDev[(size_t)n]);           // record i <-> file i; status != OK = not decodable
@@ -913,6 +997,10 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
         }
     });
     all.reset();
+    if (denoms) {
+        geo.resize((size_t)total);
+        for (int64_t k = 0; k < total; ++k) ke_jpeg_scaled_geometry(devs[k].info, denoms[order[(size_t)k].i], geo[(size_t)k]);
+    }
     lap("records into device order");
     void *d_tables;
     KE_TRY(ke_reserve(ctx, KE_BUF_JPEG_TABLES, tables.pool.size() * sizeof(KeHuffTable), &d_tables));
@@ -960,8 +1048,8 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
             d.blocks_total = (int32_t)blocks;
             coef_units += blocks * 64;
             max_blocks = std::max(max_blocks, (int)blocks);
-            max_w = std::max(max_w, d.info.width);
-            max_h = std::max(max_h, d.info.height);
+            max_w = std::max(max_w, denoms ? geo[(size_t)last].out_w : d.info.width);
+            max_h = std::max(max_h, denoms ? geo[(size_t)last].out_h : d.info.height);
             ++last;
         }
         const int64_t m = last - first;
@@ -1012,11 +1100,22 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
                                (int32_t *)d_status, lanes);
         }
         const unsigned gy = (unsigned)std::min<int64_t>(m, 65535), gz = (unsigned)((m + 65534) / 65535);
-        hipLaunchKernelGGL(ke_jpeg_idct, dim3((unsigned)((max_blocks + 255) / 256), gy, gz), dim3(256), 0, ctx->stream,
-                           (const KeJpegDev *)d_imgs, m, (const int16_t *)d_coef, (uint8_t *)d_planes, (int32_t *)d_status);
         const int xblocks = (max_w + 255) / 256, yblocks = (max_h + kColourRows - 1) / kColourRows;
-        hipLaunchKernelGGL(ke_jpeg_colour, dim3((unsigned)(xblocks * yblocks), gy, gz), dim3(256), 0, ctx->stream,
-                           (const KeJpegDev *)d_imgs, m, xblocks, (const uint8_t *)d_planes, pixels_out);
+        if (!denoms) {
+            hipLaunchKernelGGL(ke_jpeg_idct, dim3((unsigned)((max_blocks + 255) / 256), gy, gz), dim3(256), 0, ctx->stream,
+                               (const KeJpegDev *)d_imgs, m, (const int16_t *)d_coef, (uint8_t *)d_planes, (int32_t *)d_status);
+            hipLaunchKernelGGL(ke_jpeg_colour, dim3((unsigned)(xblocks * yblocks), gy, gz), dim3(256), 0, ctx->stream,
+                               (const KeJpegDev *)d_imgs, m, xblocks, (const uint8_t *)d_planes, pixels_out);
+        } else {
+            void *d_geo;
+            KE_TRY(ke_reserve(ctx, KE_BUF_OUT2, (size_t)m * sizeof(KeJpegScaled), &d_geo));
+            KE_HIP(ctx, hipMemcpyAsync(d_geo, geo.data() + first, (size_t)m * sizeof(KeJpegScaled), hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(ke_jpeg_idct_scaled, dim3((unsigned)((max_blocks + 255) / 256), gy, gz), dim3(256), 0, ctx->stream,
+                               (const KeJpegDev *)d_imgs, (const KeJpegScaled *)d_geo, m, (const int16_t *)d_coef, (uint8_t *)d_planes,
+                               (int32_t *)d_status);
+            hipLaunchKernelGGL(ke_jpeg_colour_scaled, dim3((unsigned)(xblocks * yblocks), gy, gz), dim3(256), 0, ctx->stream,
+                               (const KeJpegDev *)d_imgs, (const KeJpegScaled *)d_geo, m, xblocks, (const uint8_t *)d_planes, pixels_out);
+        }
         KE_HIP(ctx, hipGetLastError());
         KE_HIP(ctx, hipMemcpyAsync(h_st + first, d_status, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
         lap("enqueue");
@@ -1028,4 +1127,20 @@ KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *off
     ke_time_end(ctx, KE_T_JPEG);
     guard.disarm();
     return KE_OK;
+}
+
+KE_API int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                          uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
+    return jpeg_decode_batch(ctx, files, offsets, sizes, n, nullptr, pixels_out, out_offsets, status_out);
+}
+
+KE_API int ke_jpeg_decode_scaled(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                                 const int32_t *denoms, uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
+    if (!ctx) return KE_EINVAL;
+    if (n > 0 && !denoms) return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    for (int64_t i = 0; i < n; ++i)
+        if (denoms[i] != 1 && denoms[i] != 2 && denoms[i] != 4 && denoms[i] != 8)
+            return ke_fail(ctx, KE_EINVAL, "file %lld: scale 1/%d (1, 2, 4 or 8)", (long long)i, denoms[i]);
+    if (n == 0) denoms = nullptr;
+    return jpeg_decode_batch(ctx, files, offsets, sizes, n, denoms, pixels_out, out_offsets, status_out);
 }

@@ -516,3 +516,178 @@ KE_HD void ke_ycc_to_rgb(int y, int cb, int cr, uint8_t *rgb) {
     rgb[1] = (uint8_t)(g < 0 ? 0 : (g > 255 ? 255 : g));
     rgb[2] = (uint8_t)(b < 0 ? 0 : (b > 255 ? 255 : b));
 }
+
+// ---- reduced-size decoding: libjpeg asked for scale 1 / denom (denom 1, 2, 4 or 8), what Pillow's `draft` sets up for the
+// reference's loader (src/utils/image_io.py:86-88).  jdmaster.c jpeg_calc_output_dimensions: the image is ceil(w / denom) x
+// ceil(h / denom), blocks come out of the IDCT `8 / denom` samples wide -- except that a subsampled component's transform
+// doubles as long as both of its sampling ratios allow it, so that 4:2:0 chroma at 1/2 is transformed at 8x8 and needs no
+// upsampling at all; the reduced transforms are jidctred.c's.  jdsample.c: fancy upsampling only while the smallest transform
+// is larger than 1x1 (scale 1/8: plain replication).  The entropy decoding is that of the full-size decode.
+struct KeJpegScaled {
+    int32_t denom;
+    int32_t out_w, out_h;              // the decoded image
+    int32_t ss[3];                     // samples per block side after the component's IDCT (_DCT_scaled_size)
+    int32_t comp_w[3], comp_h[3];      // the component's size in samples (downsampled_width / _height)
+    int32_t plane_w[3];                // bytes per row of its plane: blocks per row * ss
+    int32_t hfac[3], vfac[3];          // upsampling factors from the component to the image
+    int32_t fancy;                     // triangle filters (1) or replication (0) where a factor is 2
+};
+
+KE_HD int ke_jpeg_scaled_side(int side, int denom) { return (side + denom - 1) / denom; }
+
+KE_HD void ke_jpeg_scaled_geometry(const KeJpegInfo &in, int denom, KeJpegScaled &g) {
+    const int smin = 8 / denom;
+    g.denom = denom;
+    g.out_w = ke_jpeg_scaled_side(in.width, denom);
+    g.out_h = ke_jpeg_scaled_side(in.height, denom);
+    g.fancy = smin > 1 ? 1 : 0;
+    for (int c = 0; c < 3; ++c) {
+        g.ss[c] = smin; g.comp_w[c] = g.comp_h[c] = g.plane_w[c] = 0; g.hfac[c] = g.vfac[c] = 1;
+        if (c >= in.ncomp) continue;
+        int ss = smin;
+        while (ss < 8 && (in.hmax * smin) % (in.hs[c] * ss * 2) == 0 && (in.vmax * smin) % (in.vs[c] * ss * 2) == 0) ss *= 2;
+        g.ss[c] = ss;
+        g.comp_w[c] = (int32_t)(((int64_t)in.width * in.hs[c] * ss + (int64_t)in.hmax * 8 - 1) / ((int64_t)in.hmax * 8));
+        g.comp_h[c] = (int32_t)(((int64_t)in.height * in.vs[c] * ss + (int64_t)in.vmax * 8 - 1) / ((int64_t)in.vmax * 8));
+        g.plane_w[c] = (in.plane_w[c] >> 3) * ss;
+        g.hfac[c] = in.hmax * smin / (in.hs[c] * ss);        // 1 or 2 for the samplings the parser takes
+        g.vfac[c] = in.vmax * smin / (in.vs[c] * ss);
+    }
+}
+
+#define KE_FIX_0_211164243 1730
+#define KE_FIX_0_509795579 4176
+#define KE_FIX_0_601344887 4926
+#define KE_FIX_0_720959822 5906
+#define KE_FIX_0_850430095 6967
+#define KE_FIX_1_061594337 8697
+#define KE_FIX_1_272758580 10426
+#define KE_FIX_1_451774981 11893
+#define KE_FIX_2_172734803 17799
+#define KE_FIX_3_624509785 29692
+
+// libjpeg's range_limit table as the C transforms index it (`x & RANGE_MASK`, 10 bits): clamp(x + 128, 0, 255) for x in
+// [-512, 511], and what the table's wrapped halves hold beyond -- the 1x1 transform has no SIMD form, so this is what Pillow
+// yields for any DC value.
+KE_HD uint8_t ke_range_limit_masked(int x) {
+    x &= 1023;
+    return (uint8_t)(x < 128 ? x + 128 : (x < 512 ? 255 : (x < 896 ? 0 : x - 896)));
+}
+
+// The bound of the reduced transforms is ke_idct_islow's, applied to what each of them computes: every dequantised
+// coefficient of the block and every result of the column pass inside (-2^14, 2^14).  libjpeg-turbo's SIMD forms of the 4x4
+// and 2x2 transforms (jidctred) dequantise in 16 bits, shift the DC term of an all-DC block in 16 bits and pack the column
+// pass's results to 16 bits with saturation; inside the bound none of that differs from jidctred.c's 32-bit arithmetic, and
+// a block outside it sends the file back (KE_JPEG_UNSUPPORTED), as at full size.  The samples are clamped as the SIMD forms
+// pack them.
+// The transforms' 32-bit sums hold only inside the bound (2^14 * 2^14 for the shifted DC term alone), so the host build
+// returns at the first value outside and leaves `out` unwritten (KE_IDCT_LEAVE).  The device build computes on in wrapping
+// arithmetic and discards the result, as ke_idct_islow does: with the returns in place hipcc 7 compiled ke_jpeg_idct_scaled
+// so that the store of the 2x2 transform's last sample took its address from a register set on the other branch only.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define KE_IDCT_LEAVE(ok)
+#else
+#define KE_IDCT_LEAVE(ok) if (!(ok)) return false
+#endif
+KE_HD bool ke_idct_bound_ok(const int *v, int n) {
+    int hi = 0, lo = 0;
+    for (int k = 0; k < n; ++k) {
+        hi = v[k] > hi ? v[k] : hi;
+        lo = v[k] < lo ? v[k] : lo;
+    }
+    return hi < (1 << kKeIdctBoundBits) && lo > -(1 << kKeIdctBoundBits);
+}
+
+// jidctred.c jpeg_idct_4x4: rows and columns 0..3 and 5..7 of the block (the fourth is not used); out: 4 rows of 4 samples
+template <typename Blk, typename M = KeMulPlain>
+KE_HD bool ke_idct_4x4(Blk &blk, uint8_t *out, int stride) {
+    bool ok = ke_idct_bound_ok(blk, 64);
+    KE_IDCT_LEAVE(ok);
+    int ws[32];                                      // 4 rows of 8 columns
+    for (int c = 0; c < 8; ++c) {
+        if (c == 4) { ws[c] = ws[8 + c] = ws[16 + c] = ws[24 + c] = 0; continue; }
+        const int tmp0 = blk[c] * 16384;             // << (CONST_BITS + 1)
+        const int e = M::mul(blk[16 + c], KE_FIX_1_847759065) + M::mul(blk[48 + c], -KE_FIX_0_765366865);
+        const int tmp10 = tmp0 + e, tmp12 = tmp0 - e;
+        const int z1 = blk[56 + c], z2 = blk[40 + c], z3 = blk[24 + c], z4 = blk[8 + c];
+        const int o0 = M::mul(z1, -KE_FIX_0_211164243) + M::mul(z2, KE_FIX_1_451774981) + M::mul(z3, -KE_FIX_2_172734803) +
+                       M::mul(z4, KE_FIX_1_061594337);
+        const int o2 = M::mul(z1, -KE_FIX_0_509795579) + M::mul(z2, -KE_FIX_0_601344887) + M::mul(z3, KE_FIX_0_899976223) +
+                       M::mul(z4, KE_FIX_2_562915447);
+        ws[c] = ke_descale(tmp10 + o2, 12);          // CONST_BITS - PASS1_BITS + 1
+        ws[24 + c] = ke_descale(tmp10 - o2, 12);
+        ws[8 + c] = ke_descale(tmp12 + o0, 12);
+        ws[16 + c] = ke_descale(tmp12 - o0, 12);
+    }
+    ok = ok && ke_idct_bound_ok(ws, 32);
+    KE_IDCT_LEAVE(ok);
+    for (int r = 0; r < 4; ++r) {
+        const int *w = ws + 8 * r;
+        uint8_t *o = out + (long)r * stride;
+        const int tmp0 = w[0] * 16384;
+        const int e = M::mul(w[2], KE_FIX_1_847759065) + M::mul(w[6], -KE_FIX_0_765366865);
+        const int tmp10 = tmp0 + e, tmp12 = tmp0 - e;
+        const int z1 = w[7], z2 = w[5], z3 = w[3], z4 = w[1];
+        const int o0 = M::mul(z1, -KE_FIX_0_211164243) + M::mul(z2, KE_FIX_1_451774981) + M::mul(z3, -KE_FIX_2_172734803) +
+                       M::mul(z4, KE_FIX_1_061594337);
+        const int o2 = M::mul(z1, -KE_FIX_0_509795579) + M::mul(z2, -KE_FIX_0_601344887) + M::mul(z3, KE_FIX_0_899976223) +
+                       M::mul(z4, KE_FIX_2_562915447);
+        o[0] = ke_range_limit(ke_descale(tmp10 + o2, 19));       // CONST_BITS + PASS1_BITS + 3 + 1
+        o[3] = ke_range_limit(ke_descale(tmp10 - o2, 19));
+        o[1] = ke_range_limit(ke_descale(tmp12 + o0, 19));
+        o[2] = ke_range_limit(ke_descale(tmp12 - o0, 19));
+    }
+    return ok;
+}
+
+// jidctred.c jpeg_idct_2x2: rows and columns 0, 1, 3, 5, 7; out: 2 rows of 2 samples
+template <typename Blk, typename M = KeMulPlain>
+KE_HD bool ke_idct_2x2(Blk &blk, uint8_t *out, int stride) {
+    bool ok = ke_idct_bound_ok(blk, 64);
+    KE_IDCT_LEAVE(ok);
+    int ws[16];                                      // 2 rows of 8 columns
+    for (int c = 0; c < 8; ++c) {
+        if (c == 2 || c == 4 || c == 6) { ws[c] = ws[8 + c] = 0; continue; }
+        const int tmp10 = blk[c] * 32768;            // << (CONST_BITS + 2)
+        const int o = M::mul(blk[56 + c], -KE_FIX_0_720959822) + M::mul(blk[40 + c], KE_FIX_0_850430095) +
+                      M::mul(blk[24 + c], -KE_FIX_1_272758580) + M::mul(blk[8 + c], KE_FIX_3_624509785);
+        ws[c] = ke_descale(tmp10 + o, 13);           // CONST_BITS - PASS1_BITS + 2
+        ws[8 + c] = ke_descale(tmp10 - o, 13);
+    }
+    ok = ok && ke_idct_bound_ok(ws, 16);
+    KE_IDCT_LEAVE(ok);
+    for (int r = 0; r < 2; ++r) {
+        const int *w = ws + 8 * r;
+        uint8_t *o = out + (long)r * stride;
+        const int tmp10 = w[0] * 32768;
+        const int t = M::mul(w[7], -KE_FIX_0_720959822) + M::mul(w[5], KE_FIX_0_850430095) + M::mul(w[3], -KE_FIX_1_272758580) +
+                      M::mul(w[1], KE_FIX_3_624509785);
+        o[0] = ke_range_limit(ke_descale(tmp10 + t, 20));        // CONST_BITS + PASS1_BITS + 3 + 2
+        o[1] = ke_range_limit(ke_descale(tmp10 - t, 20));
+    }
+    return ok;
+}
+
+// jidctred.c jpeg_idct_1x1: the DC term alone
+template <typename Blk>
+KE_HD bool ke_idct_1x1(Blk &blk, uint8_t *out) {
+    out[0] = ke_range_limit_masked(ke_descale(blk[0], 3));
+    return blk[0] < (1 << kKeIdctBoundBits) && blk[0] > -(1 << kKeIdctBoundBits);
+}
+
+#undef KE_IDCT_LEAVE
+
+// the component's transform at `ss` samples per block side; out: ss rows of ss samples
+template <typename Blk, typename M = KeMulPlain>
+KE_HD bool ke_idct_scaled(Blk &blk, int ss, uint8_t *out, int stride) {
+    if (ss == 8) return ke_idct_islow<Blk, M>(blk, out, stride);
+    if (ss == 4) return ke_idct_4x4<Blk, M>(blk, out, stride);
+    if (ss == 2) return ke_idct_2x2<Blk, M>(blk, out, stride);
+    return ke_idct_1x1(blk, out);
+}
+
+// ke_upsample_at at a reduced size: jinit_upsampler's choice with do_fancy off is replication for every factor
+KE_HD int ke_upsample_scaled_at(const uint8_t *plane, int pw, int cw, int ch, int hfac, int vfac, int fancy, int x, int y) {
+    if (!fancy) return plane[(long)(y / vfac) * pw + x / hfac];
+    return ke_upsample_at(plane, pw, cw, ch, hfac, vfac, x, y);
+}

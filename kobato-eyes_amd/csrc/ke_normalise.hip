@@ -14,6 +14,7 @@
 // Without this, every phone photograph (they all carry an orientation tag) and every RGBA PNG left the GPU route of the refine
 // stage and was decoded a second time by Pillow on the host.
 #include "ke_internal.h"
+#include "ke_reduce_core.h"
 
 namespace {
 
@@ -84,10 +85,53 @@ __global__ __launch_bounds__(256) void ke_merge_rgb(const uint8_t *__restrict__ 
     }
 }
 
+// Image.reduce((fx, fy)) on packed RGB: a thread per output pixel walks its cell once for the three channels (rows of the
+// cell are contiguous bytes; neighbouring threads read neighbouring cells).  The arithmetic is ke_reduce_core.h's.
+__global__ __launch_bounds__(256) void ke_reduce_rgb_kernel(const uint8_t *__restrict__ src, int width, int height, int fx, int fy, int ow,
+                                                            int64_t out_px, uint8_t *__restrict__ dst) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < out_px; e += (int64_t)gridDim.x * 256) {
+        const int oy = (int)(e / ow), ox = (int)(e - (int64_t)oy * ow);
+        ke_reduce_rgb_pixel(src, width, height, fx, fy, ox, oy, dst + 3 * e);
+    }
+}
+
 }  // namespace
+
+KE_API int ke_reduce_rgb(ke_ctx *ctx, const uint8_t *src, int32_t width, int32_t height, int32_t fx, int32_t fy, uint8_t *dst) {
+    if (!ctx) return KE_EINVAL;
+    if (!src || !dst) return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    if (width <= 0 || height <= 0) return ke_fail(ctx, KE_EINVAL, "sizes must be positive");
+    if (fx < 1 || fy < 1 || fx > 255 || fy > 255) return ke_fail(ctx, KE_EINVAL, "factors (%d, %d) outside 1..255", fx, fy);
+    if (!ke_is_device_ptr(src) || !ke_is_device_ptr(dst)) return ke_fail(ctx, KE_EINVAL, "src and dst are device memory");
+    KE_HIP(ctx, hipSetDevice(ctx->device));
+    const int ow = ke_reduced_side(width, fx), oh = ke_reduced_side(height, fy);
+    const int64_t out_px = (int64_t)ow * oh;
+    const unsigned grid = (unsigned)std::min<int64_t>((out_px + 255) / 256, 1 << 16);
+    hipLaunchKernelGGL(ke_reduce_rgb_kernel, dim3(grid), dim3(256), 0, ctx->stream, src, width, height, fx, fy, ow, out_px, dst);
+    KE_HIP(ctx, hipGetLastError());
+    KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KE_OK;
+}
+
+static int thumbnail_rgb(ke_ctx *ctx, const uint8_t *src, int32_t width, int32_t height, int32_t out_w, int32_t out_h, int32_t filter,
+                         const float *box, uint8_t *dst);
 
 KE_API int ke_thumbnail_rgb(ke_ctx *ctx, const uint8_t *src, int32_t width, int32_t height, int32_t out_w, int32_t out_h, int32_t filter,
                             uint8_t *dst) {
+    return thumbnail_rgb(ctx, src, width, height, out_w, out_h, filter, nullptr, dst);
+}
+
+KE_API int ke_thumbnail_rgb_box(ke_ctx *ctx, const uint8_t *src, int32_t width, int32_t height, int32_t out_w, int32_t out_h,
+                                int32_t filter, const float *box, uint8_t *dst) {
+    if (!ctx) return KE_EINVAL;
+    if (!box) return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    if (!(box[0] >= 0.0f && box[1] >= 0.0f && box[2] <= (float)width && box[3] <= (float)height && box[0] < box[2] && box[1] < box[3]))
+        return ke_fail(ctx, KE_EINVAL, "box (%g, %g, %g, %g) outside the %dx%d image", box[0], box[1], box[2], box[3], width, height);
+    return thumbnail_rgb(ctx, src, width, height, out_w, out_h, filter, box, dst);
+}
+
+static int thumbnail_rgb(ke_ctx *ctx, const uint8_t *src, int32_t width, int32_t height, int32_t out_w, int32_t out_h, int32_t filter,
+                         const float *box, uint8_t *dst) {
     if (!ctx) return KE_EINVAL;
     if (!src || !dst) return ke_fail(ctx, KE_EINVAL, "NULL argument");
     if (width <= 0 || height <= 0 || out_w <= 0 || out_h <= 0) return ke_fail(ctx, KE_EINVAL, "sizes must be positive");
@@ -102,7 +146,7 @@ KE_API int ke_thumbnail_rgb(ke_ctx *ctx, const uint8_t *src, int32_t width, int3
     const unsigned gin = (unsigned)std::min<int64_t>((in_px + 255) / 256, 1 << 16), gout = (unsigned)std::min<int64_t>((out_px + 255) / 256, 1 << 16);
     hipLaunchKernelGGL(ke_split_rgb, dim3(gin), dim3(256), 0, ctx->stream, src, in_px, (uint8_t *)planes_in);
     KeHashGroup g{(const uint8_t *)planes_in, nullptr, (uint64_t)in_px, nullptr, 3, width, height, 1};
-    KE_TRY(ke_launch_resize_group(ctx, g, out_w, out_h, filter, (uint8_t *)planes_out, nullptr));
+    KE_TRY(ke_launch_resize_group(ctx, g, out_w, out_h, filter, (uint8_t *)planes_out, box));
     hipLaunchKernelGGL(ke_merge_rgb, dim3(gout), dim3(256), 0, ctx->stream, (const uint8_t *)planes_out, out_px, dst);
     KE_HIP(ctx, hipGetLastError());
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -136,11 +136,26 @@ def decoded_bytes_estimate(path) -> int:
         return 0
 
 
-LEAVE, AS_DECODED, NORMALISE, SHRINK, TURN_SHRINK = range(5)         # seam_actions' answers
+LEAVE, AS_DECODED, NORMALISE, SHRINK, TURN_SHRINK, SHRINK_OVERSIZE = range(6)    # seam_actions' answers
 TURN = NORMALISE                                                     # at the luma seam, where there is no alpha to composite
+# what SHRINK_OVERSIZE takes: a decoded image (for a JPEG file: as drafted) of at most this many pixels.  It is the JPEG
+# parser's own limit; the route holds the image, its turned copy and the reduced one or the three planes at once, at most
+# 9 bytes a pixel (2.4 GB at the bound).
+OVERSIZE_MAX_PIXELS = 1 << 28
+# ... with a longer side of at most this many times ``max_side``: ke_reduce_rgb's factors end at 255.  The longer side's factor
+# is int(longer / max_side / 2); the shorter side's target is its share of max_side brought to a whole number of at least 1,
+# which is never below two thirds of that share, so its factor does not pass 1.5 * longer / max_side / 2 = 192 here.
+OVERSIZE_MAX_RATIO = 256
+# ... and only for a ``max_side`` up to this: the resampler behind ke_thumbnail_rgb_box writes at most 4096 samples per side.
+OVERSIZE_MAX_SIDE = 4096
 
 
-def seam_actions(kind: str, seam: str, w, h, c, st, flags, max_side: Optional[int] = None):
+def oversize_enabled() -> bool:
+    """``KE_GPU_REFINE_OVERSIZE=1``: the refine seam shrinks files of any size on the device (SHRINK_OVERSIZE)."""
+    return os.environ.get("KE_GPU_REFINE_OVERSIZE", "0") == "1"
+
+
+def seam_actions(kind: str, seam: str, w, h, c, st, flags, max_side: Optional[int] = None, *, oversize: bool = False):
     """What a refine seam does with each file of one decode call of ``kind`` (the arrays decode_files_owned returned): (actions,
     orientations) -- the orientation to apply where the action turns the file, 1 elsewhere.
 
@@ -164,4 +179,15 @@ def seam_actions(kind: str, seam: str, w, h, c, st, flags, max_side: Optional[in
     longest = np.maximum(w, h)
     fits, big = taken & (longest <= max_side), taken & (longest > max_side) & (longest < 2 * max_side - 256)
     actions = np.select([fits & plain, fits & (turn | over), big & plain, big & turn], [AS_DECODED, NORMALISE, SHRINK, TURN_SHRINK], LEAVE)
+    if oversize:
+        # past that window: SHRINK_OVERSIZE does what thumbnail's reducing_gap adds (Image.reduce, then the resample through a
+        # fractional box), after the turn where ``orientations`` says so; the JPEG seam has decoded the file as drafted, so
+        # (w, h) are the drafted sizes.  RGBA files (Pillow resamples them premultiplied), gray files and images of more than
+        # OVERSIZE_MAX_PIXELS, or longer than OVERSIZE_MAX_RATIO times max_side, stay with the loader, and so does every file
+        # when max_side is over OVERSIZE_MAX_SIDE: what the kernels behind the action refuse is not sent to them.
+        # Below max_side = 256 the window above is empty (`2 * max_side - 256` is under max_side): the action then starts right
+        # behind the `fits` cells, which it never overrides -- the loader shrinks nothing that fits.
+        huge = taken & (longest > max_side) & (longest >= 2 * max_side - 256) & (w.astype(np.int64) * h <= OVERSIZE_MAX_PIXELS)
+        huge &= (longest.astype(np.int64) <= OVERSIZE_MAX_RATIO * max_side) & (max_side <= OVERSIZE_MAX_SIDE)
+        actions = np.where(huge & (plain | turn), SHRINK_OVERSIZE, actions)
     return actions, np.where(turn, orient, 1)

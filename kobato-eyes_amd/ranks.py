@@ -458,7 +458,7 @@ def join_blocks(blocks: Sequence[Tuple[int, int]], replies: Sequence[dict], coun
 
 
 def refine_pairs(pairs: Sequence[tuple], devices, *, thresholds=None, io_workers: int = 8, max_decoded_bytes: int = 1 << 30,
-                 stats: Optional[dict] = None) -> list:
+                 stats: Optional[dict] = None, max_side: Optional[int] = None) -> list:
     """``refine.refine_pairs`` with ``devices``: one contiguous block per worker, the answers joined in input order."""
     devices = check_devices(devices)
     pairs = [(a, b, str(pa), str(pb)) for a, b, pa, pb in pairs]
@@ -476,7 +476,7 @@ def refine_pairs(pairs: Sequence[tuple], devices, *, thresholds=None, io_workers
             todo.discard(k)
             lo, hi = blocks[k]
             return k, {"op": "refine", "pairs": pairs[lo:hi], "thresholds": thresholds, "io_workers": per_rank,
-                       "max_decoded_bytes": int(max_decoded_bytes)}
+                       "max_decoded_bytes": int(max_decoded_bytes), "max_side": max_side}
 
         def on_message(k, kind, payload) -> None:
             if kind == "done":
@@ -526,9 +526,10 @@ def _op_refine(request: dict, device: int, send, stop_asked) -> dict:
     from .refine import refine_pairs as on_this_device
 
     stats: dict = {}
+    extra = {} if request.get("max_side") is None else {"max_side": request["max_side"]}
     matches = on_this_device(request["pairs"], thresholds=request["thresholds"], device=device, io_workers=request["io_workers"],
                              max_decoded_bytes=request["max_decoded_bytes"], stats=stats,
-                             _after_run=lambda stop: send(("run", stop)))
+                             _after_run=lambda stop: send(("run", stop)), **extra)
     return {"matches": matches, "stats": stats}
 
 

@@ -15,7 +15,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native
-from .formats import AS_DECODED, NORMALISE, SHRINK, TURN_SHRINK, Offers, decoded_bytes_estimate, seam_actions
+from .formats import (AS_DECODED, LEAVE, NORMALISE, SHRINK, SHRINK_OVERSIZE, TURN_SHRINK, Offers, decoded_bytes_estimate,
+                      oversize_enabled, seam_actions)
 from .image_io import MAX_SIDE, load_rgb
 
 _phash = importlib.import_module(".phash", __package__)   # the package also exports a function named phash
@@ -87,19 +88,32 @@ def _decide(file_id_a: int, file_id_b: int, ssim_value: Optional[float], errors:
     return RefinedMatch(file_id_a, file_id_b, ssim_value, None, bool(reasons), reason)
 
 
-def _decode_on_gpu(ctx, need: list, placed: dict, buffers: list, count: dict) -> None:
+def _decode_on_gpu(ctx, need: list, placed: dict, buffers: list, count: dict, max_side: int = MAX_SIDE) -> None:
     """The files of ``need`` that a GPU decoder of formats.FORMATS takes and formats.seam_actions does not leave to the loader
     are decoded on the GPU and stay there, as the reference's loader would hand them over (src/utils/image_io.py:107-138):
     placed[path] = (device address, width, height), every buffer that holds one in ``buffers``.  Everything else is left
-    for Pillow."""
+    for Pillow.
+
+    With ``KE_GPU_REFINE_OVERSIZE=1`` files of any size stay: JPEG files are decoded at the scale the loader's ``draft`` picks
+    (a 12 000 x 9 000 file is never held at full size), and what is still more than four times ``max_side`` is reduced by
+    whole factors before the LANCZOS pass, as ``Image.thumbnail`` does (SHRINK_OVERSIZE)."""
+    oversize = oversize_enabled()
     offers = Offers("refine", need, placed)
     for kind, paths in offers:
-        dev, off, w, h, c, st, flags = ctx.decode_files_owned(paths, kind)
+        if oversize and kind == "jpeg":
+            dev, off, w, h, c, st, flags, denoms = ctx.decode_files_owned(paths, kind, draft_side=max_side)
+        else:
+            dev, off, w, h, c, st, flags = ctx.decode_files_owned(paths, kind)
+            denoms = np.ones(len(paths), np.int32)
         offers.ran(kind, paths, st)
         if not dev:
             continue
         buffers.append(dev)
-        action, orient = seam_actions(kind, "refine", w, h, c, st, flags, MAX_SIDE)
+        action, orient = seam_actions(kind, "refine", w, h, c, st, flags, max_side, oversize=oversize)
+        # the files the oversize route kept from the loader: shrunk from beyond the window, or drafted into it
+        drafted = int(np.count_nonzero((denoms > 1) & (action != LEAVE) & (action != SHRINK_OVERSIZE)))
+        if drafted:
+            count["gpu_oversize"] = count.get("gpu_oversize", 0) + drafted
         ok = np.nonzero(action == AS_DECODED)[0]
         for k, o, ww, hh in zip(ok.tolist(), off[ok].tolist(), w[ok].tolist(), h[ok].tolist()):
             placed[paths[k]] = (dev + o, ww, hh)
@@ -114,24 +128,28 @@ def _decode_on_gpu(ctx, need: list, placed: dict, buffers: list, count: dict) ->
                 placed[paths[k]] = (dev2 + int(o2), ww, hh)
             count["gpu_decodes"] += len(fix)
             count["gpu_normalised"] = count.get("gpu_normalised", 0) + len(fix)
-        for k in np.nonzero((action == SHRINK) | (action == TURN_SHRINK))[0].tolist():
+        for k in np.nonzero((action == SHRINK) | (action == TURN_SHRINK) | (action == SHRINK_OVERSIZE))[0].tolist():
             addr, ww, hh, held = dev + int(off[k]), int(w[k]), int(h[k]), None
             try:
-                if action[k] == TURN_SHRINK:
+                if action[k] == TURN_SHRINK or (action[k] == SHRINK_OVERSIZE and orient[k] != 1):
                     held, o2, w2, h2 = ctx.normalise_rgb(dev, off[k:k + 1], w[k:k + 1], h[k:k + 1], c[k:k + 1], orient[k:k + 1])
                     addr, ww, hh = held + int(o2[0]), int(w2[0]), int(h2[0])
-                small, sw, sh = ctx.thumbnail_rgb(addr, ww, hh, MAX_SIDE)
+                if action[k] == SHRINK_OVERSIZE:
+                    small, sw, sh, _ = ctx.thumbnail_rgb_reduced(addr, ww, hh, max_side)
+                else:
+                    small, sw, sh = ctx.thumbnail_rgb(addr, ww, hh, max_side)
             finally:
                 if held is not None:
                     ctx.free(held)
             buffers.append(small)
             placed[paths[k]] = (small, sw, sh)
             count["gpu_decodes"] += 1
-            count["gpu_shrunk"] = count.get("gpu_shrunk", 0) + 1
+            key = "gpu_oversize" if action[k] == SHRINK_OVERSIZE else "gpu_shrunk"
+            count[key] = count.get(key, 0) + 1
 
 
-def _load(p: str):
-    img = load_rgb(p)
+def _load(p: str, max_side: int = MAX_SIDE):
+    img = load_rgb(p, max_side=max_side)
     if img is None:
         return None
     arr = _phash.image_to_array(img)
@@ -189,7 +207,7 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
 
 def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThresholds] = None, device: int = 0,
                  io_workers: int = 8, max_decoded_bytes: int = 1 << 30, stats: Optional[dict] = None,
-                 devices: Optional[Sequence[int]] = None, _after_run=None) -> list:
+                 devices: Optional[Sequence[int]] = None, max_side: int = MAX_SIDE, _after_run=None) -> list:
     """``refine_pair`` for a list of ``(file_id_a, file_id_b, path_a, path_b)``: the same ``RefinedMatch`` (or ``None``)
     per pair, in input order -- but every file is decoded once however many pairs share it, and the kernels see groups
     instead of single pairs: one ``ke_fit_luma_uniform`` launch per (source size, channels, common size) and one
@@ -197,7 +215,10 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
     runs the metric pair by pair (src/dup/refine.py:82-98).
 
     Pairs are worked off in runs whose decoded files stay below ``max_decoded_bytes``.  ``stats`` (optional dict)
-    receives the launch and decode counts.
+    receives the launch and decode counts.  ``max_side``: the side the loader shrinks a larger picture to
+    (``safe_load_image(max_side=...)``), for Pillow's route and the GPU's alike; with ``KE_GPU_REFINE_OVERSIZE=1`` the files
+    that are shrunk on the device from beyond the window of ``formats.seam_actions``, and the JPEG files drafted into or below
+    it, are counted as ``gpu_oversize`` (``formats.OVERSIZE_*``: the bounds beyond which a file still takes the loader).
 
     ``devices`` (e.g. ``[0, 1, 2]``; at most 15 entries): the pairs are cut into one contiguous block of about equal
     ``decoded_bytes_estimate`` per entry, and one worker process per entry runs this function on its block on its own device
@@ -209,7 +230,7 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
         from . import ranks
 
         return ranks.refine_pairs(pairs, devices, thresholds=thresholds, io_workers=io_workers,
-                                  max_decoded_bytes=max_decoded_bytes, stats=stats)
+                                  max_decoded_bytes=max_decoded_bytes, stats=stats, max_side=max_side)
     from concurrent.futures import ThreadPoolExecutor
 
     cfg = thresholds or RefinementThresholds()
@@ -231,9 +252,9 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
             placed: dict = {}
             buffers: list = []
             try:
-                _decode_on_gpu(ctx, need, placed, buffers, count)
+                _decode_on_gpu(ctx, need, placed, buffers, count, max_side)
                 rest = [p for p in need if p not in placed]
-                arrays = dict(zip(rest, pool.map(_load, rest)))
+                arrays = dict(zip(rest, pool.map(lambda p: _load(p, max_side), rest)))
                 count["decodes"] += len(need)
                 _upload(ctx, arrays, placed, buffers)
                 _score(ctx, pairs, range(start, stop), placed, out, count, cfg)
