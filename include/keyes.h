@@ -491,6 +491,22 @@ int ke_hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, con
                     int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
                     int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out);
 
+/* The same scan over the pairs that touch newly added entries.  The table is [library | added]: positions
+ * first_new .. n-1 are new.  The edge set is exactly { e of ke_hamming_scan(same arguments) : e.b >= first_new } (edges
+ * have a < b, so b is the pair's later position), each edge with the h and bands it has there: the pairs between two
+ * library entries, which an earlier scan of the library judged, are not visited -- about (n - first_new) * n pairs
+ * instead of n^2 / 2, through a trapezoid of the same tiles or the same buckets (KE_SCAN_MODE applies).
+ * What depends on the whole table stays whole-table: the bucket sizes bucket_pair_cap is held against (a cap can
+ * therefore drop an edge that the library's own scan had, buckets grow with the table) and counters_out[3].
+ * counters_out: [0] pairs i < j with j >= first_new this shard stands for, counted and checked as above; over all
+ * shards n (n - 1) / 2 - f (f - 1) / 2 with f = first_new.  [1], [2] over the emitted edges.  [3] as above.
+ * first_new = 0 is ke_hamming_scan; first_new = n gives no edge and counters_out[0] = 0; outside [0, n] is KE_EINVAL.
+ * part_index / part_count, capacity and *n_edges_out behave as above. */
+int ke_hamming_scan_from(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
+                         int64_t first_new, int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
+                         int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
+                         int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out);
+
 /* The reference's "size=" funnel counter (src/dup/scanner.py:268-270 with _passes_size_ratio, :358-370): over every band
  * and band value whose bucket the reference walks (>= 2 members, under the pair cap), the member pairs that pass the size
  * filter -- pairs of equal file id included (the host takes those out, as for counters_out[3] of ke_hamming_scan).  A log

@@ -28,7 +28,7 @@ EXPORTS = (
     "ke_abi_version", "ke_create", "ke_create_error", "ke_destroy", "ke_last_error", "ke_set_stream",
     "ke_get_stream", "ke_synchronize", "ke_device_info", "ke_malloc", "ke_free", "ke_memcpy",
     "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan",
-    "ke_band_pairs_after_size",
+    "ke_hamming_scan_from", "ke_band_pairs_after_size",
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
@@ -141,6 +141,8 @@ def load_library() -> C.CDLL:
         lib.ke_band_pairs_after_size.argtypes = [vp, vp, vp, i64, i32, i32, dbl, i64, vp]
         lib.ke_hamming_scan.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, dbl, i64, vp, i64,
                                         C.POINTER(i64), vp]
+        lib.ke_hamming_scan_from.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, dbl, i64, vp, i64,
+                                             C.POINTER(i64), vp]
         lib.ke_cluster_labels.argtypes = [vp, i64, i64, vp]
         lib.ke_ssim_pairs_uniform.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
         lib.ke_ssim_set_mode.argtypes = [vp, i32]
@@ -879,8 +881,10 @@ class Context:
     # -- scan -------------------------------------------------------------------------------
     def hamming_scan(self, hashes, n: int, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4,
                      size_ratio: float = 0.0, bucket_pair_cap: int = 0, part_index=0, part_count=1,
-                     capacity: Optional[int] = None):
-        """Returns (edges[EDGE_DTYPE] on the host, counters u64[4]).  hashes/ids/sizes: host arrays or device ptrs."""
+                     capacity: Optional[int] = None, first_new: int = 0):
+        """Returns (edges[EDGE_DTYPE] on the host, counters u64[4]).  hashes/ids/sizes: host arrays or device ptrs.
+        first_new > 0: only the edges whose later position is at least first_new (ke_hamming_scan_from); counters[0] is
+        then the region's pair count, [1] and [2] are over those edges, [3] stays the whole table's."""
         def host(a, dt):
             return np.ascontiguousarray(a, dtype=dt) if isinstance(a, (np.ndarray, list, tuple)) else a
 
@@ -891,10 +895,16 @@ class Context:
         while True:
             edges = np.empty(cap, EDGE_DTYPE)
             with self._lock:
-                self._check(self._lib.ke_hamming_scan(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, part_index,
-                                                      part_count, threshold, band_bits, band_count, float(size_ratio),
-                                                      int(bucket_pair_cap), _addr(edges), cap, C.byref(n_edges),
-                                                      _addr(counters)), "ke_hamming_scan")
+                if first_new:
+                    self._check(self._lib.ke_hamming_scan_from(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, int(first_new),
+                                                               part_index, part_count, threshold, band_bits, band_count,
+                                                               float(size_ratio), int(bucket_pair_cap), _addr(edges), cap,
+                                                               C.byref(n_edges), _addr(counters)), "ke_hamming_scan_from")
+                else:
+                    self._check(self._lib.ke_hamming_scan(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, part_index,
+                                                          part_count, threshold, band_bits, band_count, float(size_ratio),
+                                                          int(bucket_pair_cap), _addr(edges), cap, C.byref(n_edges),
+                                                          _addr(counters)), "ke_hamming_scan")
             if n_edges.value <= cap:
                 return edges[: n_edges.value], counters
             cap = int(n_edges.value)  # overflow protocol: retry with the reported size

@@ -53,6 +53,36 @@ def compute_signature(image_or_path, *, device: int = 0) -> tuple[int, int]:
     return _phash.phash_dhash(image_or_path, device=device)
 
 
+def _parse_files(files: Iterable) -> list:
+    """DuplicateFile objects or row mappings -> DuplicateFile objects; malformed rows are skipped (src/ui/dup_workers.py:205-209)."""
+    parsed: list[DuplicateFile] = []
+    for item in files:
+        if isinstance(item, DuplicateFile):
+            parsed.append(item)
+            continue
+        try:
+            parsed.append(DuplicateFile.from_row(item))
+        except ValueError:
+            logger.debug("skipping row without a usable hash")
+    return parsed
+
+
+def _make_scanner(scanner_factory, config: DuplicateScanConfig, device: int):
+    try:
+        return scanner_factory(config, device=device)         # one process per GPU: scan on the caller's device
+    except TypeError:
+        return scanner_factory(config)                        # a foreign factory with the reference's one-argument signature
+
+
+def _ssim_kept(edges: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, device: int, devices) -> list:
+    """The edges whose two files pass the SSIM re-check: every file decoded once, one fit + one SSIM launch per size group
+    (refine_pairs), not one of each per edge."""
+    by_id = {f.file_id: f for f in candidates}
+    matches = _refine.refine_pairs([(e.file_id_a, e.file_id_b, by_id[e.file_id_a].path, by_id[e.file_id_b].path) for e in edges],
+                                   thresholds=_refine.RefinementThresholds(ssim=ssim_threshold), device=device, devices=devices)
+    return [e for e, m in zip(edges, matches) if m is not None and m.is_duplicate]
+
+
 def find_duplicates(files: Iterable, *, hamming_threshold: int = 8, ssim_threshold: Optional[float] = None,
                     size_ratio: Optional[float] = None, band_bits: int = 16, band_count: int = 4,
                     scanner_factory: Callable[[DuplicateScanConfig], DuplicateScanner] = DuplicateScanner,
@@ -67,21 +97,10 @@ def find_duplicates(files: Iterable, *, hamming_threshold: int = 8, ssim_thresho
     """
     if device is None:
         device = int(devices[0]) if devices else 0
-    parsed: list[DuplicateFile] = []
-    for item in files:
-        if isinstance(item, DuplicateFile):
-            parsed.append(item)
-            continue
-        try:
-            parsed.append(DuplicateFile.from_row(item))
-        except ValueError:
-            logger.debug("skipping row without a usable hash")
+    parsed = _parse_files(files)
     config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
                                  band_count=band_count)
-    try:
-        scanner = scanner_factory(config, device=device)      # one process per GPU: scan on the caller's device
-    except TypeError:
-        scanner = scanner_factory(config)                     # a foreign factory with the reference's one-argument signature
+    scanner = _make_scanner(scanner_factory, config, device)
     if ssim_threshold is None:
         return scanner.build_clusters(parsed)
     from .scanner import assemble_clusters
@@ -90,12 +109,49 @@ def find_duplicates(files: Iterable, *, hamming_threshold: int = 8, ssim_thresho
     if len(candidates) < 2:
         return []
     edges = list(scanner.candidate_edges(candidates).values())
-    by_id = {f.file_id: f for f in candidates}
-    # every file decoded once, one fit + one SSIM launch per size group (refine_pairs), not one of each per edge
-    matches = _refine.refine_pairs([(e.file_id_a, e.file_id_b, by_id[e.file_id_a].path, by_id[e.file_id_b].path) for e in edges],
-                                   thresholds=_refine.RefinementThresholds(ssim=ssim_threshold), device=device, devices=devices)
-    kept = [e for e, m in zip(edges, matches) if m is not None and m.is_duplicate]
+    kept = _ssim_kept(edges, candidates, ssim_threshold, device, devices)
     return assemble_clusters(candidates, kept) if kept else []
+
+
+def find_new_duplicates(library: Iterable, added: Iterable, *, previous: Optional[Sequence[DuplicateCluster]] = None,
+                        hamming_threshold: int = 8, ssim_threshold: Optional[float] = None, size_ratio: Optional[float] = None,
+                        band_bits: int = 16, band_count: int = 4,
+                        scanner_factory: Callable[[DuplicateScanConfig], DuplicateScanner] = DuplicateScanner,
+                        device: Optional[int] = None, devices: Optional[Sequence[int]] = None) -> list:
+    """The clusters that contain at least one file of ``added``, from a scan of only the pairs that touch an added file:
+    the pairs between two ``library`` files, which an earlier run judged, are neither scanned nor re-checked.
+
+    ``library`` / ``added``: as ``files`` of ``find_duplicates``.  ``previous``: the clusters an earlier
+    ``find_duplicates(library, ...)`` returned under the same thresholds.  With it and without ``ssim_threshold`` the
+    result equals the clusters of ``find_duplicates(library + added, ...)`` that contain an added file
+    (``DuplicateScanner.extend_clusters``, which also says when it raises ValueError).  With ``ssim_threshold`` only the
+    new edges go to ``refine_pairs``; ``previous``' memberships stand for the library's own edges as they are, so they
+    should come from a run with the same ``ssim_threshold``.  Without ``previous`` the clusters are assembled from the
+    new edges alone: a link between two library files is then absent, so two library files appear together only when an
+    added file (or a chain of them) connects them, and a library member's best_hamming is taken over its new edges only.
+    """
+    if device is None:
+        device = int(devices[0]) if devices else 0
+    old, new = _parse_files(library), _parse_files(added)
+    config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
+                                 band_count=band_count)
+    scanner = _make_scanner(scanner_factory, config, device)
+    from .scanner import assemble_clusters
+
+    if previous is not None and ssim_threshold is None:
+        clusters = scanner.extend_clusters(old, new, previous)
+    else:
+        old = [f for f in old if f.phash is not None]
+        new = [f for f in new if f.phash is not None]
+        candidates = old + new
+        if not new or len(candidates) < 2:
+            return []
+        edges = list(scanner.candidate_edges(candidates, first_new=len(old)).values())
+        if ssim_threshold is not None and edges:
+            edges = _ssim_kept(edges, candidates, ssim_threshold, device, devices)
+        clusters = assemble_clusters(candidates, edges, previous=previous or ())
+    new_ids = {f.file_id for f in new}
+    return [c for c in clusters if any(e.file.file_id in new_ids for e in c.files)]
 
 
 def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None, config: Optional[DuplicateScanConfig] = None,
@@ -138,4 +194,4 @@ def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None
     return DuplicateScanner(config or DuplicateScanConfig(), device=device).build_clusters(files)
 
 
-__all__ = ["DedupSettings", "compute_signature", "find_duplicates", "run_duplicate_scan", "ClusterBuilder"]
+__all__ = ["DedupSettings", "compute_signature", "find_duplicates", "find_new_duplicates", "run_duplicate_scan", "ClusterBuilder"]

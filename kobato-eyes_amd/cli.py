@@ -1,7 +1,8 @@
 """Headless duplicate scan over a kobato-eyes SQLite database.
 
     python -m kobato_eyes_amd.cli scan-dups --db kobato.db --hamming 8 [--like '%/photos/%'] [--size-ratio 0.5]
-                                            [--refine] [--csv out.csv] [--device 0] [--devices 0,1,2]
+                                            [--added-like '%/incoming/%'] [--refine] [--csv out.csv] [--device 0]
+                                            [--devices 0,1,2]
 
 Reproduces the call sequence of DuplicateScanRunnable.run (src/ui/dup_workers.py:148-239) without Qt: rows in
 the shape of db.repository.iter_files_for_dup (src/db/repository.py:416-454), missing signatures filled and
@@ -23,17 +24,25 @@ from typing import Iterator, Optional, Sequence
 CSV_HEADER = ["group", "file_id", "path", "size", "width", "height", "keeper", "hamming"]
 
 
-def iter_files_for_dup(conn: sqlite3.Connection, path_like: Optional[str]) -> Iterator[dict]:
-    """Plain dicts with file_id, path, size, width, height, phash_u64 for every present file, by id."""
+def iter_files_for_dup(conn: sqlite3.Connection, path_like: Optional[str], added_like: Optional[str] = None) -> Iterator[dict]:
+    """Plain dicts with file_id, path, size, width, height, phash_u64 for every present file, by id.  With ``added_like``
+    each dict also says under "added" whether the path matches that LIKE pattern."""
     sql = ("SELECT f.id AS file_id, f.path AS path, COALESCE(f.size, 0) AS size, f.width AS width, f.height AS height, "
-           "s.phash_u64 AS phash_u64 FROM files f LEFT JOIN signatures s ON s.file_id = f.id WHERE f.is_present = 1")
+           "s.phash_u64 AS phash_u64")
     params: list = []
+    if added_like:
+        sql += ", f.path LIKE ? ESCAPE '\\' AS added"
+        params.append(added_like)
+    sql += " FROM files f LEFT JOIN signatures s ON s.file_id = f.id WHERE f.is_present = 1"
     if path_like:
         sql += " AND f.path LIKE ? ESCAPE '\\'"
         params.append(path_like)
     sql += " ORDER BY f.id"
     for row in conn.execute(sql, params):
-        yield {"file_id": row[0], "path": row[1], "size": row[2], "width": row[3], "height": row[4], "phash_u64": row[5]}
+        item = {"file_id": row[0], "path": row[1], "size": row[2], "width": row[3], "height": row[4], "phash_u64": row[5]}
+        if added_like:
+            item["added"] = bool(row[6])
+        yield item
 
 
 def export_duplicate_clusters_csv(clusters: Sequence, file_path) -> None:
@@ -50,9 +59,12 @@ def export_duplicate_clusters_csv(clusters: Sequence, file_path) -> None:
 
 def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, path_like: Optional[str] = None,
                   refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
-                  devices: Optional[Sequence[int]] = None) -> list:
+                  devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None) -> list:
     """``devices``: the missing signatures are computed by one worker process per entry; the scan and the tile-aHash / MAE
-    refine stay in this process, on ``device`` (default ``devices[0]``, else 0)."""
+    refine stay in this process, on ``device`` (default ``devices[0]``, else 0).  ``added_like``: the files of the
+    selection whose path matches this LIKE pattern are the added set, the rest the library; only the pairs that touch an
+    added file are scanned and only the clusters with an added member come back (``find_new_duplicates`` without
+    ``previous``: a link between two library files is absent)."""
     from . import DuplicateFile, DuplicateScanConfig, DuplicateScanner, fast_fill_missing_signatures
     from .refine_parallel import refine_by_pixels_parallel, refine_by_tilehash_parallel
 
@@ -65,7 +77,7 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
 
     conn = sqlite3.connect(db_path)
     try:
-        rows = list(iter_files_for_dup(conn, path_like))
+        rows = list(iter_files_for_dup(conn, path_like, added_like))
     finally:
         conn.close()
     tick("Loading files", len(rows), len(rows))
@@ -88,8 +100,15 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
         except ValueError:
             continue                                   # rows still without a hash are skipped, as the reference does
     tick("Clustering duplicates", 0, len(files))
-    clusters = DuplicateScanner(DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio),
-                                device=device).build_clusters(files)
+    if added_like:
+        from .api import find_new_duplicates
+
+        added_ids = {r["file_id"] for r in rows if r["added"]}
+        clusters = find_new_duplicates([f for f in files if f.file_id not in added_ids], [f for f in files if f.file_id in added_ids],
+                                       hamming_threshold=hamming_threshold, size_ratio=size_ratio, device=device)
+    else:
+        clusters = DuplicateScanner(DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio),
+                                    device=device).build_clusters(files)
     if refine and clusters:
         clusters = refine_by_tilehash_parallel(clusters, max_bits=tile_max_bits, device=device,
                                                tick=lambda d, t, phase: tick(f"Refining (tile hash {phase}/2)", d, t))
@@ -106,6 +125,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("--hamming", type=int, default=8)
     sp.add_argument("--size-ratio", type=float, default=None)
     sp.add_argument("--like", default=None, help="SQL LIKE pattern on files.path")
+    sp.add_argument("--added-like", default=None,
+                    help="SQL LIKE pattern: the matching files of the selection are newly added, the rest is the library; only "
+                         "pairs with an added file are scanned and only groups with an added file are reported")
     sp.add_argument("--refine", action="store_true", help="run the tile-aHash + pixel-MAE refine pipeline on the clusters")
     sp.add_argument("--tile-max-bits", type=int, default=32)
     sp.add_argument("--mae-thr", type=float, default=0.004)
@@ -118,7 +140,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARNING)
     clusters = scan_database(args.db, hamming_threshold=args.hamming, size_ratio=args.size_ratio, path_like=args.like,
                              refine=args.refine, tile_max_bits=args.tile_max_bits, mae_thr=args.mae_thr, device=args.device,
-                             devices=args.devices)
+                             devices=args.devices, added_like=args.added_like)
     if args.csv:
         export_duplicate_clusters_csv(clusters, args.csv)
     members = sum(len(c.files) for c in clusters)

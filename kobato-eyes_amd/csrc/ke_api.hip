@@ -764,12 +764,14 @@ KE_API int ke_stage_submit_hash(ke_ctx *ctx, int32_t slot, const uint64_t *offse
 }
 
 // ---- scan ------------------------------------------------------------------------------------
-KE_API int ke_hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
-                           int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
-                           int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
-                           int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
+// ke_hamming_scan (first_new = 0) and ke_hamming_scan_from: one body, the region is ke_launch_scan's business
+static int hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n, int64_t first_new,
+                        int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
+                        int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
+                        int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
     if (!ctx) return KE_EINVAL;
     if (n < 0 || (n > 0 && !hashes)) return ke_fail(ctx, KE_EINVAL, "hashes is NULL");
+    if (first_new < 0 || first_new > n) return ke_fail(ctx, KE_EINVAL, "first_new %lld outside [0, %lld]", (long long)first_new, (long long)n);
     if (!n_edges_out) return ke_fail(ctx, KE_EINVAL, "n_edges_out is NULL");
     // DuplicateScanConfig.__post_init__ / DuplicateScanner.__init__ (src/dup/scanner.py:155-166, 208)
     if (band_bits <= 0) return ke_fail(ctx, KE_EINVAL, "band_bits must be positive");
@@ -813,7 +815,7 @@ KE_API int ke_hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *i
     unsigned long long *d_cnt = nullptr, pairs = 0;
     KE_TRY(ke_launch_scan(ctx, (const uint64_t *)d_h, (const int64_t *)d_ids, (const int64_t *)d_sizes, n, part_index,
                           part_count, threshold, band_bits, band_count, size_ratio, bucket_pair_cap, d_edges, capacity,
-                          &d_cnt, &pairs, counters_out != nullptr));
+                          &d_cnt, &pairs, counters_out != nullptr, first_new));
     unsigned long long h_cnt[KE_SCAN_STATE_WORDS];
     KE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, ctx->stream));
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -831,6 +833,22 @@ KE_API int ke_hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *i
         }
     }
     return KE_OK;
+}
+
+KE_API int ke_hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
+                           int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
+                           int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
+                           int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
+    return hamming_scan(ctx, hashes, ids, sizes, n, 0, part_index, part_count, threshold, band_bits, band_count, size_ratio,
+                        bucket_pair_cap, edges_out, capacity, n_edges_out, counters_out);
+}
+
+KE_API int ke_hamming_scan_from(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
+                                int64_t first_new, int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
+                                int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
+                                int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
+    return hamming_scan(ctx, hashes, ids, sizes, n, first_new, part_index, part_count, threshold, band_bits, band_count, size_ratio,
+                        bucket_pair_cap, edges_out, capacity, n_edges_out, counters_out);
 }
 
 KE_API int ke_band_pairs_after_size(ke_ctx *ctx, const uint64_t *hashes, const int64_t *sizes, int64_t n, int32_t band_bits,

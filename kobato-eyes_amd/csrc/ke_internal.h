@@ -207,7 +207,7 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
 int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
                    int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
                    int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
-                   unsigned long long *pairs_evaluated, bool want_bucket_pairs);
+                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new);
 constexpr int KE_SCAN_STATE_WORDS = 5;   // what ke_hamming_scan reads back: counters [0..3] and the path word
 int ke_launch_ssim(ke_ctx *ctx, const uint8_t *d_images, int w, int h, int channels, const int64_t *d_pa,
                    const int64_t *d_pb, int64_t n_pairs, double *d_out);

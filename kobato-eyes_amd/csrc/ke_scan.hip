@@ -22,6 +22,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "ke_internal.h"
+#include "ke_scan_region.h"
 
 namespace {
 
@@ -29,6 +30,7 @@ constexpr int kThreads = 512;               // 8 waves
 constexpr int kRT = 8;                      // 16-hash row tiles per wave
 constexpr int kTile = 8 * kRT * 16;         // 1024 rows per workgroup ...
 constexpr int kCols = 1024;                 // ... against 1024 columns
+static_assert(kTile == kKeScanTile && kCols == kKeScanCols, "ke_scan_region.h describes this tiling");
 constexpr int kCPR = kTile / kCols;         // column chunks per row block
 constexpr int kChunk = 256;                 // columns staged in LDS at a time (16 operand tiles, 16 KB)
 
@@ -141,7 +143,13 @@ __global__ __launch_bounds__(256) void ke_scan_expand(const uint64_t *__restrict
     out[e] = v;
 }
 
-__global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) {
+// The tile kernel's body.  kFrom = false is ke_scan_tiles, the whole triangle; kFrom = true is ke_scan_tiles_from, a scan
+// from first_new: the tile comes from the enumeration of the trapezoid of tiles that hold a pair with j >= first_new
+// (region, ke_scan_region.h) and the columns below first_new are left out -- whole chunks and 16-column blocks by where
+// the loops start (wave-uniform), the lanes of the block first_new lies in at the rare path.  Every kFrom branch is
+// compile-time, region is not read without it.
+template <bool kFrom>
+__device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRegion region) {
     __shared__ ke_v4i s_b[2][kChunk / 16 * 64];      // two chunks of 16 operand tiles
     if (a.counters[kPathWord]) return;               // the bucket kernels do this call's scan
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -157,16 +165,24 @@ __global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) {
     if (t >= a.n_tiles) return;
     // Tiles of the upper triangle, row-major: row block rb owns column chunks kCPR*rb .. ncc-1, so
     // offset(rb) = rb*ncc - kCPR*rb*(rb-1)/2.  Invert with a float estimate and an exact fix-up.
-    const double hc = 0.5 * kCPR, bq = (double)a.ncc + hc;
-    int64_t rb = (int64_t)floor((bq - sqrt(fmax(bq * bq - 4.0 * hc * (double)t, 0.0))) / (2.0 * hc));
-    if (rb < 0) rb = 0;
-    if (rb >= a.nb) rb = a.nb - 1;
-    while (rb > 0 && rb * a.ncc - kCPR * rb * (rb - 1) / 2 > t) --rb;
-    while (rb + 1 < a.nb && (rb + 1) * a.ncc - kCPR * (rb + 1) * rb / 2 <= t) ++rb;
-    const int64_t cc = kCPR * rb + (t - (rb * a.ncc - kCPR * rb * (rb - 1) / 2));
+    int64_t rb, cc;
+    if constexpr (kFrom) {
+        ke_region_tile(region, t, &rb, &cc);         // the same inversion behind the region's rectangle (ke_scan_region.h)
+    } else {
+        const double hc = 0.5 * kCPR, bq = (double)a.ncc + hc;
+        rb = (int64_t)floor((bq - sqrt(fmax(bq * bq - 4.0 * hc * (double)t, 0.0))) / (2.0 * hc));
+        if (rb < 0) rb = 0;
+        if (rb >= a.nb) rb = a.nb - 1;
+        while (rb > 0 && rb * a.ncc - kCPR * rb * (rb - 1) / 2 > t) --rb;
+        while (rb + 1 < a.nb && (rb + 1) * a.ncc - kCPR * (rb + 1) * rb / 2 <= t) ++rb;
+        cc = kCPR * rb + (t - (rb * a.ncc - kCPR * rb * (rb - 1) / 2));
+    }
     const int64_t row0 = rb * kTile, col0 = cc * kCols;
     const int64_t wrow0 = row0 + (int64_t)wv * (kRT * 16);          // this wave's 128 rows
-    if (tid == 0) {
+    if constexpr (kFrom) {
+        // pairs i < j, j >= first_new of this tile: over the shards n (n - 1) / 2 - f (f - 1) / 2
+        if (tid == 0) atomicAdd(&a.counters[0], (unsigned long long)ke_region_tile_pairs(region, rb, cc));
+    } else if (tid == 0) {
         // pairs i < j < n this tile stands for, counted where they are evaluated: the shards' counts must add up to
         // n (n - 1) / 2 (counters[0]; the host checks it against its own arithmetic)
         const int64_t rows = min((int64_t)kTile, a.n - row0), cols = min((int64_t)kCols, a.n - col0);
@@ -185,16 +201,23 @@ __global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) {
     // integers: the running maximum is an integer max (a float max would first canonicalise every input).
     const int thr_bits = __float_as_int((float)(64 - a.threshold));
     const int nchunks = (int)((min((int64_t)kCols, a.n - col0) + kChunk - 1) / kChunk);
+    // the first chunk to walk: (kFrom) the one first_new lies in; a tile of the region has a column >= first_new, so
+    // c_lo < nchunks
+    int c_lo = 0;
+    if constexpr (kFrom) {
+        const int64_t skip = (region.first_new - col0) / kChunk;            // whole chunks below first_new (cc = cc0 only)
+        c_lo = skip > 0 ? (int)skip : 0;
+    }
     // column operands: 16 KB per chunk, two 16-byte pieces per thread, next chunk in flight during the products
     const ke_v4i *cbase = a.expanded + (col0 / 16) * 64;
-    ke_v4i pre0 = cbase[tid], pre1 = cbase[kThreads + tid];
-    s_b[0][tid] = pre0;
-    s_b[0][kThreads + tid] = pre1;
+    ke_v4i pre0 = cbase[c_lo * (kChunk / 16 * 64) + tid], pre1 = cbase[c_lo * (kChunk / 16 * 64) + kThreads + tid];
+    s_b[c_lo & 1][tid] = pre0;
+    s_b[c_lo & 1][kThreads + tid] = pre1;
     // every load so far has landed from here on: without this hipcc re-waits for the row operands inside the
     // loop with counts that also drain the column prefetch issued at the top of each iteration
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
     __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
+    for (int c = c_lo; c < nchunks; ++c) {
         {   // unconditional (the last iteration re-reads its own chunk): a guarded load is waited for at once
             const int cn = c + 1 < nchunks ? c + 1 : c;
             pre0 = cbase[cn * (kChunk / 16 * 64) + tid];
@@ -204,7 +227,11 @@ __global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) {
         // diagonal tiles: a 128 x 16 block whose every column index is below the wave's first row holds no pair i < j --
         // the wave starts at the first block that can (wave-uniform)
         const int64_t below = wrow0 - (col0 + (int64_t)c * kChunk) - 15;
-        const int ct0 = below < 0 ? 0 : (int)min((int64_t)(kChunk / 16), below / 16 + 1);
+        int ct0 = below < 0 ? 0 : (int)min((int64_t)(kChunk / 16), below / 16 + 1);
+        if constexpr (kFrom) {   // and at the first block that reaches first_new
+            const int64_t before = region.first_new - (col0 + (int64_t)c * kChunk);
+            if (before > 0) ct0 = max(ct0, (int)min((int64_t)(kChunk / 16), before / 16));
+        }
         for (int ct = ct0; ct < kChunk / 16; ++ct) {
             const ke_v4i bv = bt[ct * 64 + lane];
             const ke_v8i b = {bv[0], bv[1], bv[2], bv[3], 0, 0, 0, 0};
@@ -228,6 +255,7 @@ __global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) {
                     for (int i = 0; i < 4; ++i) hits |= __float_as_int(acc[r][i]) >= thr_bits ? 1u << (4 * r + i) : 0u;
                 const int64_t gj = col0 + (int64_t)c * kChunk + ct * 16 + (lane & 15);
                 if (gj >= a.n) hits = 0;
+                if constexpr (kFrom) { if (gj < region.first_new) hits = 0; }
                 const uint64_t y = hits ? a.hashes[gj] : 0ull;
                 while (hits) {
                     const int k = __ffs(hits) - 1;
@@ -244,6 +272,12 @@ __global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) {
         s_b[(c + 1) & 1][kThreads + tid] = pre1;
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) { scan_tiles_body<false>(a, KeScanRegion{}); }
+
+__global__ __launch_bounds__(kThreads) void ke_scan_tiles_from(const ScanArgs a, const KeScanRegion region) {
+    scan_tiles_body<true>(a, region);
 }
 
 __global__ void ke_band_hist(const uint64_t *__restrict__ hashes, int64_t n, int band_bits, int band_count,
@@ -286,6 +320,11 @@ constexpr size_t kBlockSumBytes = kBucketMaxBins / kBinsPerBlock * sizeof(uint32
 // pairs and no walked bucket is longer than kBucketLongest (one thread walks the rest of its bucket), else tiles.
 constexpr unsigned long long kBucketRatio = 6000, kBucketLongest = 260;
 constexpr int64_t kBucketMinN = 50000;
+// The same rule for a scan from first_new, with the region's pairs in place of all pairs and a ratio of its own: the bucket
+// kernels walk every bucket of the table however thin the region is, so their time does not shrink with it, while the
+// tile kernel's does.  Between the rows of the record (tiles ahead at region pairs / bucket pairs = 33 and
+// 312, level at 325, buckets ahead from 2 978) the ratio sits at the geometric middle.
+constexpr unsigned long long kBucketRatioFrom = 1000;
 
 __device__ __forceinline__ unsigned long long block_sum_256(unsigned long long v, unsigned long long *s4) {
     for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
@@ -388,8 +427,12 @@ __global__ void ke_bucket_scatter(const uint64_t *__restrict__ hashes, int64_t n
 // n = 100 000.  Edges beyond the staging buffer (skewed tables, where a wave's adds combine) go through consider_pair.
 constexpr int kPairSlots = 1024, kPairStage = 256;
 
-__global__ __launch_bounds__(256) void ke_bucket_pairs(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
-                                                        const uint32_t *__restrict__ sorted_pos, int part_index, int part_count) {
+// kFrom (ke_bucket_pairs_from): a pair is kept only when its later position is at least first_new; its shard stays
+// (lo + hi) mod part_count.
+template <bool kFrom>
+__device__ __forceinline__ void bucket_pairs_body(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
+                                                  const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
+                                                  int64_t first_new) {
     if (!a.counters[kPathWord]) return;
     __shared__ ke_edge s_edges[kPairStage];
     __shared__ unsigned int s_count, s_shared;
@@ -418,6 +461,7 @@ __global__ __launch_bounds__(256) void ke_bucket_pairs(const ScanArgs a, const u
             const int64_t pj = pos[k];
             const int64_t lo = pi < pj ? pi : pj, hi = pi < pj ? pj : pi;
             if (hi >= a.n || (lo + hi) % part_count != part_index) continue;
+            if constexpr (kFrom) { if (hi < first_new) continue; }
             const uint64_t xl = pi < pj ? x : y, xh = pi < pj ? y : x;
             int bands, shared;
             if (!pair_is_edge(a, lo, hi, xl, xh, b, &bands, &shared)) continue;
@@ -442,6 +486,17 @@ __global__ __launch_bounds__(256) void ke_bucket_pairs(const ScanArgs a, const u
     __syncthreads();
     for (unsigned int i = threadIdx.x; i < staged; i += 256)
         if ((int64_t)(s_base + i) < a.capacity) a.edges[s_base + i] = s_edges[i];
+}
+
+__global__ __launch_bounds__(256) void ke_bucket_pairs(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
+                                                        const uint32_t *__restrict__ sorted_pos, int part_index, int part_count) {
+    bucket_pairs_body<false>(a, sorted_hash, sorted_pos, part_index, part_count, 0);
+}
+
+__global__ __launch_bounds__(256) void ke_bucket_pairs_from(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
+                                                             const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
+                                                             int64_t first_new) {
+    bucket_pairs_body<true>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
 }
 
 // Wide bands (2^band_bits bins do not fit a table): the band values are sorted together with their positions and the
@@ -575,51 +630,20 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
     return KE_OK;
 }
 
-// pairs i < j < n that shard part_index of part_count stands for (host, O(row blocks)): per row block, the chunks right of
-// the diagonal are full rectangles, the kCPR chunks on the diagonal hold a partial triangle.
-static unsigned long long shard_pairs(int64_t n, int nb, int ncc, int part_index, int part_count) {
-    unsigned long long pairs = 0;
-    for (int64_t rb = 0; rb < nb; ++rb) {
-        const int64_t off = rb * ncc - (int64_t)kCPR * rb * (rb - 1) / 2;
-        const int64_t row0 = rb * kTile, rows = std::min<int64_t>(kTile, n - row0);
-        // sum over d in [0, m) of min(rows, d): the pairs of a diagonal chunk's columns row0 .. row0 + m - 1
-        auto below = [rows](int64_t m) { return m <= rows ? m * (m - 1) / 2 : rows * (rows - 1) / 2 + (m - rows) * rows; };
-        for (int64_t cc = kCPR * rb; cc < ncc; ++cc) {
-            const int64_t t = off + (cc - kCPR * rb);
-            const bool diagonal = cc < kCPR * (rb + 1);
-            if (!diagonal) {
-                // every remaining chunk is a full rectangle except possibly the last one: count them arithmetically
-                const int64_t last = ncc - 1;
-                const int64_t t_last = off + (last - kCPR * rb);
-                // chunks cc .. last-1 (full width)
-                const int64_t first_full_t = t, end_full_t = t_last;   // [first_full_t, end_full_t)
-                if (end_full_t > first_full_t) {
-                    // count t in [first_full_t, end_full_t) with t % part_count == part_index
-                    auto upto = [&](int64_t x) { return x <= part_index ? 0 : (x - part_index + part_count - 1) / part_count; };
-                    pairs += (unsigned long long)(upto(end_full_t) - upto(first_full_t)) * (unsigned long long)(rows * kCols);
-                }
-                if (t_last % part_count == part_index && last >= cc)
-                    pairs += (unsigned long long)(rows * std::min<int64_t>(kCols, n - last * kCols));
-                break;
-            }
-            if (t % part_count != part_index) continue;
-            const int64_t col0 = cc * kCols, cols = std::min<int64_t>(kCols, n - col0);
-            pairs += (unsigned long long)(below(col0 - row0 + cols) - below(col0 - row0));
-        }
-    }
-    return pairs;
-}
-
 int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
                    int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
                    int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
-                   unsigned long long *pairs_evaluated, bool want_bucket_pairs) {
+                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new) {
+    // first_new > 0: only the pairs i < j with j >= first_new (ke_hamming_scan_from), through kernels of their own;
+    // first_new == 0 launches what it always did
+    const bool from = first_new > 0;
+    const KeScanRegion region = ke_scan_region(n, first_new);
     ScanArgs a;
     a.hashes = d_hashes; a.ids = d_ids; a.sizes = (size_ratio > 0.0) ? d_sizes : nullptr;
     a.n = n;
     a.nb = (int)((n + kTile - 1) / kTile);
     a.ncc = (int)((n + kCols - 1) / kCols);
-    a.n_tiles = (int64_t)a.nb * a.ncc - (int64_t)kCPR * a.nb * (a.nb - 1) / 2;
+    a.n_tiles = from ? region.n_tiles : (int64_t)a.nb * a.ncc - (int64_t)kCPR * a.nb * (a.nb - 1) / 2;
     a.first_tile = part_index;
     a.tile_step = part_count;
     a.threshold = threshold; a.band_bits = band_bits; a.band_count = band_count;
@@ -627,7 +651,8 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
     a.hist = nullptr; a.blen = nullptr;
     a.cap = bucket_pair_cap > 0 ? (unsigned long long)bucket_pair_cap : 0ull;
     a.edges = d_edges; a.capacity = capacity;
-    const unsigned long long pairs = shard_pairs(n, a.nb, a.ncc, part_index, part_count);
+    // pairs of the region this shard stands for (host, O(row blocks); first_new = 0: the pairs i < j < n)
+    const unsigned long long pairs = ke_region_shard_pairs(region, part_index, part_count);
     *pairs_evaluated = pairs;
     // KE_SCAN_MODE=auto|tiles|buckets, read once: auto lets the device choose per call; the other two force a path
     // (buckets still means tiles where the bucket path is not built).  Must be the same on every rank of a sharded scan.
@@ -674,15 +699,22 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
         a.hist = hist;
         if (bucket_path) {
             const unsigned blocks = (unsigned)((bins + kBinsPerBlock - 1) / kBinsPerBlock);
-            const unsigned long long all_pairs = (unsigned long long)n * (unsigned long long)(n - 1) / 2;
+            // the rule's yardstick is what the tile kernel would have to visit: the region's pairs
+            const unsigned long long all_pairs = (unsigned long long)n * (unsigned long long)(n - 1) / 2 -
+                                                 (unsigned long long)first_new * (unsigned long long)(first_new > 0 ? first_new - 1 : 0) / 2;
             hipLaunchKernelGGL(ke_bucket_stats, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins, a.cap, block_sums,
                                state);
             hipLaunchKernelGGL(ke_bucket_offsets, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins,
-                               (const uint32_t *)block_sums, offsets, state, forced, all_pairs / kBucketRatio, pairs);
+                               (const uint32_t *)block_sums, offsets, state, forced, all_pairs / (from ? kBucketRatioFrom : kBucketRatio), pairs);
             hipLaunchKernelGGL(ke_bucket_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, band_bits,
                                band_count, offsets, sorted_hash, sorted_pos, (const unsigned long long *)state);
-            hipLaunchKernelGGL(ke_bucket_pairs, dim3((unsigned)((n + kPairSlots - 1) / kPairSlots), (unsigned)band_count), dim3(256), 0, ctx->stream, a,
-                               (const uint64_t *)sorted_hash, (const uint32_t *)sorted_pos, part_index, part_count);
+            const dim3 pair_grid((unsigned)((n + kPairSlots - 1) / kPairSlots), (unsigned)band_count);
+            if (from)
+                hipLaunchKernelGGL(ke_bucket_pairs_from, pair_grid, dim3(256), 0, ctx->stream, a, (const uint64_t *)sorted_hash,
+                                   (const uint32_t *)sorted_pos, part_index, part_count, first_new);
+            else
+                hipLaunchKernelGGL(ke_bucket_pairs, pair_grid, dim3(256), 0, ctx->stream, a,
+                                   (const uint64_t *)sorted_hash, (const uint32_t *)sorted_pos, part_index, part_count);
             KE_HIP(ctx, hipGetLastError());
         } else if (want_bucket_pairs) {
             const unsigned blocks = (unsigned)std::min<size_t>((bins + 1023) / 1024, 256);
@@ -722,7 +754,12 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
         a.xcd_remap = xcd;
         // with the remap the grid is padded to a multiple of 8 so that every slot exists on some workgroup
         const int64_t grid = xcd ? (my_tiles + 7) / 8 * 8 : my_tiles;
-        hipLaunchKernelGGL(ke_scan_tiles, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a);
+        // one workgroup per tile on either kernel: splitting a thin region's tiles over 2 or 4 workgroups was measured and
+        // did not pay
+        if (from)
+            hipLaunchKernelGGL(ke_scan_tiles_from, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
+        else
+            hipLaunchKernelGGL(ke_scan_tiles, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a);
         KE_HIP(ctx, hipGetLastError());
     }
     ke_time_end(ctx, KE_T_SCAN);

@@ -193,8 +193,10 @@ class DuplicateScanner:
         self._funnel: Optional[tuple] = None
 
     # -- candidate edges ---------------------------------------------------------------------
-    def candidate_edges(self, candidates: Sequence[DuplicateFile]) -> dict:
-        """{(id_lo, id_hi): DuplicateEdge} exactly as the reference's ``edges`` dict ends up."""
+    def candidate_edges(self, candidates: Sequence[DuplicateFile], first_new: int = 0) -> dict:
+        """{(id_lo, id_hi): DuplicateEdge} exactly as the reference's ``edges`` dict ends up.  With ``first_new`` > 0 the
+        candidates are [library | added] and only the pairs with a member at position >= first_new are scanned and
+        returned (``ke_hamming_scan_from``): the pairs between two library files are not visited."""
         cfg = self._config
         n = len(candidates)
         hashes = np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=n)
@@ -207,7 +209,7 @@ class DuplicateScanner:
         raw, counters = ctx.hamming_scan(
             hashes, n, ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
             band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
-            part_index=self._part[0], part_count=self._part[1])
+            part_index=self._part[0], part_count=self._part[1], **({"first_new": int(first_new)} if first_new else {}))
         return self._edges_from_raw(candidates, hashes, ids, raw, counters, sizes=sizes, ratio=ratio, cap=cap)
 
     # -- the reference's funnel counters (src/dup/scanner.py:258-299) ---------------------------------------------
@@ -296,7 +298,10 @@ class DuplicateScanner:
     def last_counters(self) -> Optional[dict]:
         """The funnel of the last scan: "pairs total" = the device's bucket-pair count (band histograms) minus bucket pairs of
         equal file id; "size" = the same with the size filter (``ke_band_pairs_after_size``).  A shard reports the whole
-        table's figures for these two (they do not depend on the tiles it was dealt), its own share for the rest."""
+        table's figures for these two (they do not depend on the tiles it was dealt), its own share for the rest.
+        After ``candidate_edges(..., first_new)`` the same split holds for the region: ``pairs_evaluated``, ``after_ham``,
+        ``after_cosine`` and ``edges`` are taken over the pairs with a member at position >= first_new, ``pair_total`` and
+        ``after_size`` remain the whole table's (bucket sizes are a property of the table, not of the region)."""
         if self._counters is None and self._funnel is not None:
             hashes, ids, sizes, ratio, cap, counters, after_cos, n_edges = self._funnel
             same_total, same_sized = self._same_id_bucket_pairs(hashes, ids, sizes if sizes is not None else np.zeros(len(ids), np.int64),
@@ -358,6 +363,48 @@ class DuplicateScanner:
             if paused:
                 gc.enable()
 
+    def extend_clusters(self, library: Iterable[DuplicateFile], added: Iterable[DuplicateFile], previous: Iterable[DuplicateCluster]) -> list:
+        """The clusters of ``build_clusters(list(library) + list(added))`` -- membership, order, keepers and best_hamming
+        -- from ``previous`` = what ``build_clusters(library)`` returned under the same config, and a scan of only the
+        pairs that touch an added file.  Connectivity among library files comes from ``previous``' memberships, an old
+        member's best_hamming is the minimum of its previous value and its new edges.
+
+        ValueError where that equality cannot hold: with KE_DUP_BUCKET_PAIR_CAP set (buckets grow with the table, so an
+        edge between two library files can vanish under the cap and ``previous`` would keep it), with a file id that
+        occurs twice across library + added (the first-writer-wins rule between equal ids needs the pairs this scan leaves
+        out), and when ``previous`` names a file that is not in ``library``."""
+        cfg = self._config
+        if _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP")) is not None:
+            raise ValueError("extend_clusters: KE_DUP_BUCKET_PAIR_CAP is set; under a bucket pair cap edges between library "
+                             "files can disappear as the table grows, so previous clusters cannot be extended")
+        old = [f for f in library if f.phash is not None]
+        new = [f for f in added if f.phash is not None]
+        candidates = old + new
+        previous = list(previous)
+        seen: set = set()
+        for f in candidates:
+            if f.file_id in seen:
+                raise ValueError(f"extend_clusters: file id {f.file_id} occurs twice across library + added")
+            seen.add(f.file_id)
+        old_ids = {f.file_id for f in old}
+        for cluster in previous:
+            for entry in cluster.files:
+                if entry.file.file_id not in old_ids:
+                    raise ValueError(f"extend_clusters: previous names file id {entry.file.file_id}, which is not in library")
+        logger.info("dup: extend library=%d added=%d previous_clusters=%d ham_th=%d", len(old), len(new), len(previous),
+                    cfg.hamming_threshold)
+        if len(candidates) < 2:
+            return []
+        paused = gc.isenabled()
+        gc.disable()
+        try:
+            edges = self.candidate_edges(candidates, first_new=len(old)) if new and old else \
+                self.candidate_edges(candidates) if new else {}
+            return assemble_clusters(candidates, edges.values(), previous=previous)
+        finally:
+            if paused:
+                gc.enable()
+
     @staticmethod
     def _choose_keeper(entries: Sequence[DuplicateClusterEntry]) -> int:
         return min(entries, key=_keeper_key).file.file_id
@@ -376,11 +423,19 @@ def _file_keys(f: DuplicateFile) -> tuple:
     return head + (suffix, name, f.file_id), head + (name, f.file_id)
 
 
-def assemble_clusters(candidates: Sequence[DuplicateFile], edges: Iterable[DuplicateEdge]) -> list:
+def assemble_clusters(candidates: Sequence[DuplicateFile], edges: Iterable[DuplicateEdge], previous: Sequence[DuplicateCluster] = ()) -> list:
     """Edges -> ordered clusters (src/dup/scanner.py:304-356).  Components come from the library's host union-find over
     compacted file ids; best_hamming and the grouping are array work, Python only touches the members of each cluster once
-    (a million-file table leaves some 60 000 clusters: their keys, not the union-find, are the time)."""
+    (a million-file table leaves some 60 000 clusters: their keys, not the union-find, are the time).
+
+    ``previous``: clusters of an earlier call over a part of ``candidates`` whose edges are not among ``edges``
+    (``extend_clusters``).  Each stands in for its edges: its members are linked (to its first member, without a
+    distance) and each member's best_hamming starts from the value it had there."""
     edges = list(edges)
+    carried = [(e.file.file_id, e.best_hamming) for c in previous if len(c.files) > 1 for e in c.files]
+    for c in previous:
+        head = c.files[0].file.file_id
+        edges.extend(DuplicateEdge(head, e.file.file_id, None) for e in c.files[1:])
     if not edges:
         return []
     m = len(edges)
@@ -398,6 +453,10 @@ def assemble_clusters(candidates: Sequence[DuplicateFile], edges: Iterable[Dupli
     known = ham >= 0
     np.minimum.at(best, inverse[:m][known], ham[known])
     np.minimum.at(best, inverse[m:][known], ham[known])
+    carried = [(i, b) for i, b in carried if b is not None]
+    if carried:
+        at = np.searchsorted(node_ids, np.fromiter((i for i, _ in carried), np.int64, len(carried)))
+        np.minimum.at(best, at, np.fromiter((b for _, b in carried), np.int64, len(carried)))
     order = np.argsort(labels, kind="stable")
     sorted_labels = labels[order]
     cuts = np.nonzero(np.concatenate(([True], sorted_labels[1:] != sorted_labels[:-1], [True])))[0].tolist()
