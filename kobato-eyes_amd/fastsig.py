@@ -21,6 +21,7 @@ import sqlite3
 import threading
 from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
 from concurrent.futures.process import BrokenProcessPool
+from dataclasses import dataclass
 from itertools import chain
 from pathlib import Path
 from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
@@ -118,15 +119,6 @@ def _read_pixels(path_text: str, room: Optional[int] = None):
 
 # suffix -> 1 + its place in BASE_KINDS (0: not a GPU decoder's file).  Every suffix is one dot and up to four letters.
 _KIND_CODE = {suffix: 1 + BASE_KINDS.index(f.kind) for f in FORMATS if f.follows is None for suffix in f.suffixes}
-
-
-def _read_bytes(path_text: str):
-    """The file as it is (JPEG route: the GPU decodes it), or None."""
-    try:
-        with open(path_text, "rb") as fh:
-            return fh.read()
-    except OSError:
-        return None
 
 
 # ---- decoder processes.  Pillow's per-file work in Python (opening, plugin dispatch, conversions) holds the interpreter lock,
@@ -264,21 +256,62 @@ class _SharedBuffers:
         self.close()
 
 
-class _GpuStage:
-    """The context's pinned staging buffers (``ke_stage_*``) behind the four calls the pipeline needs; tests of the host
-    logic put a stand-in here (``_make_stage``)."""
+class _Stage:
+    """What the pipeline asks of its stage, and all it asks: ``_GpuStage`` puts the device behind these calls, tests of the
+    host logic a stand-in (``_make_stage``); both are built as ``(device, stage_bytes, max_images)``."""
+
+    shared_paths = None      # slot k of the staging buffers is the file shared_paths[k], for decoder processes to map; None: threads only
+    stage_bytes = 0          # size of one staging buffer
+
+    def acquire(self):
+        """(slot, uint8 view of the whole buffer) of the next staging buffer in rotation, once its last batch is done."""
+        raise NotImplementedError
+
+    def submit(self, slot, offsets, widths, heights, channels):
+        """Enqueues copy + hash of the images placed in buffer ``slot``; {"phash", "dhash", "status"}, filled after wait(slot)."""
+        raise NotImplementedError
+
+    def wait(self, slot: int) -> None:
+        """Until what was submitted from ``slot`` is done (-1: from every buffer)."""
+        raise NotImplementedError
+
+    def hash_one(self, arr):
+        """(phash, dhash) or None for an image that did not fit a staging buffer."""
+        raise NotImplementedError
+
+    def hash_files(self, paths, kind: str):
+        """(phash, dhash, status) of files on disk from the GPU decoder of ``kind``; status != 0: the file is left to a
+        follow-up decoder (1 only) or to Pillow."""
+        raise NotImplementedError
+
+    def read_ahead(self, paths, spans=()):
+        """The files read into a buffer that hash_ahead takes spans of and whose ``release()`` gives it back (any thread), or
+        None: no buffer is free, or the stage reads no files ahead -- hash_files then reads them inside the decode call."""
+        return None
+
+    def hash_ahead(self, held, lo: int, hi: int, kind: str, skip=None):
+        """hash_files for files lo..hi of what read_ahead returned; ``skip``: a mask of files to leave alone (status 1)."""
+        raise NotImplementedError
+
+
+_staging: dict = {}      # device -> ((stage_bytes, max_images, shared), _SharedBuffers | None) its staging context was last set up with
+
+
+class _GpuStage(_Stage):
+    """``_Stage`` on the device: the context's pinned staging buffers (``ke_stage_*``) and its decode calls."""
 
     def __init__(self, device: int, stage_bytes: int, max_images: int) -> None:
         self.device = device
         self.ctx = _native.get_context(device)                  # GPU decode calls, read-ahead buffers
         # the staging route lives on a context of its own (own stream, lock, scratch): the decoder processes' buffers are
-        # copied and hashed while a GPU decode call -- seconds for large PNG streams -- holds the main one
+        # copied and hashed while a GPU decode call -- seconds for large PNG streams -- holds the main one.  Nobody else sets
+        # that context's staging up, so what this module remembers of it (_staging) is what is in place
         self.sctx = _native.get_context(device, "staging")
         stage_bytes = (int(stage_bytes) + 4095) & ~4095
         shared = os.environ.get("KE_DECODE_PROCESSES", "1") != "0" and os.path.isdir("/dev/shm")
-        geom = (stage_bytes, max_images, shared)
-        if getattr(self.sctx, "_stage_geom", None) != geom:
-            old = getattr(self.sctx, "_stage_shared", None)    # stays mapped until the library has let go of it
+        geom, old = _staging.get(device, (None, None))
+        if geom != (stage_bytes, max_images, shared):
+            _staging[device] = None, old                        # a set-up that fails half way leaves nothing to rely on
             buffers = None
             if shared:
                 try:
@@ -290,11 +323,10 @@ class _GpuStage:
                     buffers, shared = None, False
             if not shared:
                 self.sctx.stage_create(stage_bytes, max_images, 2)
-            self.sctx._stage_shared = buffers
-            self.sctx._stage_geom = (stage_bytes, max_images, shared)
-            if old is not None:
+            _staging[device] = (stage_bytes, max_images, shared), buffers
+            if old is not None:                                 # stayed mapped until the library had let go of it
                 old.close()
-        buffers = getattr(self.sctx, "_stage_shared", None)
+        buffers = _staging[device][1]
         self.shared_paths = buffers.paths if buffers is not None else None     # slot k <-> shared_paths[k]
         self.stage_bytes = stage_bytes
 
@@ -307,13 +339,9 @@ class _GpuStage:
     def wait(self, slot: int) -> None:
         self.sctx.stage_wait(slot)
 
-    def jpeg_hash(self, blobs, kind: str = "jpeg"):
-        """(phash, dhash, status) of JPEG / PNG files decoded on the GPU (``ke_jpeg_decode`` / ``ke_png_decode`` ->
-        ``ke_hash_images``); status != 0: the decoder leaves the file to Pillow."""
-        return self.ctx.hash(blobs, want_dhash=True, kind=kind)
-
     def hash_files(self, paths, kind: str = "jpeg"):
-        """jpeg_hash for files on disk: the library reads them (host threads, page-locked memory), no bytes objects."""
+        """The library reads the files itself (host threads, page-locked memory) and decodes them (``ke_<kind>_decode`` ->
+        ``ke_hash_images``)."""
         return self.ctx.hash_files(paths, want_dhash=True, kind=kind)
 
     def read_ahead(self, paths, spans=()):
@@ -332,10 +360,93 @@ class _GpuStage:
 
 _make_stage = _GpuStage
 
+# the kinds whose GPU decoder is one lane per stream (_largest_for_pillow): kind -> (knob, default) of its GPU rate, in
+# microseconds per compressed byte
+_SPLIT_RATES = {"png": ("KE_PNG_GPU_US_PER_BYTE", "0.9"), "gif": ("KE_GIF_GPU_US_PER_BYTE", "0.75")}
+
+
+@dataclass(frozen=True)
+class _Knobs:
+    """The KE_* settings of one call, read once when its pipeline is built (the format switches: formats.enabled_kinds, per
+    batch; KE_DECODE_PROCESSES: _GpuStage)."""
+    gpu_batch: int                 # KE_GPU_BATCH
+    gpu_batch_cancellable: int     # KE_GPU_BATCH_CANCELLABLE
+    stage_bytes: int               # KE_STAGE_BYTES
+    stage_bytes_set: bool          # ... given by the caller: the staging buffers are not grown to what the files announce
+    process_min: int               # KE_DECODE_PROCESS_MIN
+    read_ahead: bool               # KE_READ_AHEAD
+    gpu_s_per_byte: dict           # kind of _SPLIT_RATES -> its knob, in seconds per compressed byte
+    pillow_mb_per_s: float         # KE_PILLOW_MB_PER_S
+    pool_start_s: float            # KE_DECODE_POOL_START_S
+
+    @classmethod
+    def read(cls) -> "_Knobs":
+        env = os.environ.get
+        return cls(gpu_batch=int(env("KE_GPU_BATCH", "32768")), gpu_batch_cancellable=int(env("KE_GPU_BATCH_CANCELLABLE", "4096")),
+                   stage_bytes=int(env("KE_STAGE_BYTES", str(256 << 20))), stage_bytes_set="KE_STAGE_BYTES" in os.environ,
+                   process_min=int(env("KE_DECODE_PROCESS_MIN", "256")), read_ahead=env("KE_READ_AHEAD", "1") != "0",
+                   gpu_s_per_byte={kind: float(env(*knob)) * 1e-6 for kind, knob in _SPLIT_RATES.items()},
+                   pillow_mb_per_s=float(env("KE_PILLOW_MB_PER_S", "250")), pool_start_s=float(env("KE_DECODE_POOL_START_S", "1.5")))
+
+
+def _largest_for_pillow(sizes, probed, gpu_s_per_byte: float, host_s_per_byte: float, pool_start_s: float):
+    """Which PNG (or GIF) files of a batch the decoder processes should take instead of the GPU (a mask over the files, or None
+    = the GPU takes them all).  ``sizes``: their compressed sizes; ``probed``: (w, h, c, st) from their headers, or None where
+    nobody parsed them; ``host_s_per_byte``: per decoded byte, all decoders together; ``pool_start_s``: what starting the decoder
+    processes still costs (0 once they run).
+
+    ``ke_png_inflate`` is one lane per stream and a deflate stream is sequential, so a batch takes as long as its longest
+    stream whatever its size -- about 0.45 us per symbol, i.e. 0.9 us per compressed byte of a textured image -- while a
+    decoder process gets through about 250 MB of decoded pixels per second.  2 048 textured 2048 x 2048 files: 5.1 s on
+    the GPU, 6.2 s on 16 host threads; 512 of them: 5.7 s against 1.5 s.  With the sizes known (the files are in memory,
+    their headers parsed) the k largest files go to the processes, k minimising the larger of (longest stream left for the
+    GPU) and (decoded bytes moved to the processes) in those terms -- the two shares are worked off side by side.  KE_PNG_GPU_US_PER_BYTE / KE_PILLOW_MB_PER_S set the two rates;
+    KE_PNG_GPU_US_PER_BYTE=0 sends every PNG file to the GPU, as before.  The LZW walk of ``ke_gif_codes`` has the same shape (one lane per
+    stream, ~0.65 us per code = 0.75 us per compressed byte: a 512 x 512 frame is 40 ms whatever the batch; KE_GIF_GPU_US_PER_BYTE)."""
+    if gpu_s_per_byte <= 0.0 or probed is None or len(sizes) == 0:
+        return None
+    w, h, c, st = probed
+    sizes = np.where(st == 0, np.asarray(sizes, np.float64), 0.0)
+    decoded = np.where(st == 0, w.astype(np.float64) * h * c, 0.0)
+    order = np.argsort(-sizes, kind="stable")
+    longest_left = np.concatenate([sizes[order] * gpu_s_per_byte + 4e-3, [0.0]])   # + the launches' fixed cost
+    moved = np.concatenate([[0.0], np.cumsum(decoded[order]) * host_s_per_byte])
+    moved[1:] += pool_start_s
+    k = int(np.argmin(np.maximum(longest_left, moved)))     # the two shares run side by side (run_batches)
+    if k == 0:
+        return None
+    mask = np.zeros(len(sizes), bool)
+    mask[order[:k]] = True
+    return mask
+
+
+@dataclass
+class _BatchReads:
+    """The GPU decoders' share of a batch (_Pipeline._start_reads)."""
+    positions: dict                # base kind -> positions of its files among the tasks, ascending (every base kind has an entry)
+    spans: dict                    # base kind -> (lo, hi): where its files lie in ``ahead``, kind after kind
+    ahead: object = None           # the read-ahead buffer that holds them, or None: the decode call reads the files itself
+
+    def release(self) -> None:
+        """Gives the read-ahead buffer back, once however often it is called."""
+        held, self.ahead = self.ahead, None
+        if held is not None:
+            held.release()
+
+
+@dataclass
+class _Round:
+    """What one staging buffer carries to the GPU while the next one is filled."""
+    slot: int
+    positions: list                # of the images placed in the buffer, in the order of the handle's arrays
+    handle: Optional[dict]         # of the stage's submit: phash / dhash / status, filled after wait(slot); None: nothing placed
+    spills: list                   # (position, pixels) of images that found no room in the buffer
+
 
 class _Pipeline:
     """decode (threads) -> pinned staging buffer -> H2D + hash (GPU), without a host-side copy in between; files of the base
-    kinds of ``formats.FORMATS`` decoded on the GPU instead.
+    kinds of ``formats.FORMATS`` decoded on the GPU instead.  The device is behind ``self.stage``, and ``_Stage`` lists what that
+    has to provide; the KE_* knobs named below are read once, when the pipeline is built (``_Knobs``).
 
     Files are taken ``KE_GPU_BATCH`` (default 32768) at a time (a batch whose compressed bytes exceed ``KE_PACK_LIMIT_BYTES`` or
     whose pixels exceed ``KE_DECODE_LIMIT_BYTES`` is halved by the context until it fits).  Within such a batch:
@@ -357,18 +468,19 @@ class _Pipeline:
     def __init__(self, tasks: Sequence[Task], workers: int, chunk: int, device: int,
                  cancel_fn: Optional[Callable[[], bool]] = None) -> None:
         self.tasks, self.chunk, self.device = tasks, max(1, int(chunk)), device
-        self.batch = max(self.chunk, int(os.environ.get("KE_GPU_BATCH", "32768")))
+        self.knobs = _Knobs.read()
+        self.batch = max(self.chunk, self.knobs.gpu_batch)
         self.cancel_fn = cancel_fn
         self.stopped = False
         if cancel_fn is not None:
             # somebody may want to stop: the reference asks after every file (src/core/fastsig.py:86-90).  Here the question is
             # put between the chunks / rounds of the Pillow route and before every GPU decode call, and a batch is small
             # enough that even a batch of slow files is abandoned within a chunk's time
-            self.batch = max(self.chunk, min(self.batch, int(os.environ.get("KE_GPU_BATCH_CANCELLABLE", "4096"))))
+            self.batch = max(self.chunk, min(self.batch, self.knobs.gpu_batch_cancellable))
         self.workers = max(1, workers)
         self.pool = ThreadPoolExecutor(max_workers=self.workers)
-        self.stage = _make_stage(device, int(os.environ.get("KE_STAGE_BYTES", str(256 << 20))), max(self.chunk, 4096))
-        self.process_min = int(os.environ.get("KE_DECODE_PROCESS_MIN", "256"))
+        self.stage = _make_stage(device, self.knobs.stage_bytes, max(self.chunk, 4096))
+        self.process_min = self.knobs.process_min          # out of reach once the decoder processes have failed
         self.bytes_per_image = 1 << 20                     # running estimate of a decoded image, for sizing the workers' jobs
         # per-file bookkeeping is array work: a library scan is hundreds of thousands of files, and a microsecond of
         # interpreter per file and step was a third of the seam's wall clock
@@ -400,126 +512,85 @@ class _Pipeline:
         return (off, w, h, 1 if arr.ndim == 2 else arr.shape[2])
 
     # ---- the GPU decoders' share of a batch
-    def _start_reads(self, start: int) -> dict:
+    def _start_reads(self, start: int) -> _BatchReads:
         """The files of the batch that begins at ``start`` whose suffix is a base kind's of ``formats.FORMATS``, on their way into
         memory while the batch before is on the GPU.  Runs on a pool thread (the classification is a pass of the interpreter
-        over the batch, the reading is the library's): {kind: positions (ascending) for every base kind, "spans": {kind: (lo,
-        hi)}, where the kind's files lie in the read-ahead buffer -- kind after kind --, "blobs": position -> future of the
-        file's bytes for a stage without ``hash_files``, "ahead": the context's FilesAhead holding them, or None}."""
+        over the batch, the reading is the library's, into page-locked memory)."""
         enabled = {k for k, _ in enabled_kinds("hash")}
-        by_path = hasattr(self.stage, "hash_files")          # the library reads the files itself, into page-locked memory
         stop = min(start + self.batch, len(self.tasks))
         tails = [p[-5:].lower() for p in self.paths[start:stop]]
         code = np.fromiter((_KIND_CODE.get(t[t.rfind("."):], 0) for t in tails), np.int8, stop - start)
-        reads = {k: start + np.nonzero(code == j + 1)[0] if k in enabled else np.zeros(0, np.int64) for j, k in enumerate(BASE_KINDS)}
-        ends = np.cumsum([len(reads[k]) for k in BASE_KINDS]).tolist()
-        spans = {k: (e - len(reads[k]), e) for k, e in zip(BASE_KINDS, ends)}
-        reads.update(blobs={}, ahead=None, spans=spans)
-        order = np.concatenate([reads[k] for k in BASE_KINDS]).tolist()
-        if not by_path:
-            reads["blobs"] = {int(k): self.pool.submit(_read_bytes, self.paths[k]) for k in order}
-        elif order and hasattr(self.stage, "read_ahead") and os.environ.get("KE_READ_AHEAD", "1") != "0":
+        positions = {k: start + np.nonzero(code == j + 1)[0] if k in enabled else np.zeros(0, np.int64) for j, k in enumerate(BASE_KINDS)}
+        ends = np.cumsum([len(positions[k]) for k in BASE_KINDS]).tolist()
+        reads = _BatchReads(positions, {k: (e - len(positions[k]), e) for k, e in zip(BASE_KINDS, ends)})
+        order = np.concatenate([positions[k] for k in BASE_KINDS]).tolist()
+        if order and self.knobs.read_ahead:
             try:
                 # headers parsed ahead as well, where that takes work off the decode call: not WebP's -- its probe reads
                 # the container and the 10-byte frame tag only (the boolean-coded header is the decode call's own work)
-                reads["ahead"] = self.stage.read_ahead([self.paths[k] for k in order],
-                                                       tuple((k, *spans[k]) for k in BASE_KINDS if k != "webp"))
+                reads.ahead = self.stage.read_ahead([self.paths[k] for k in order],
+                                                    tuple((k, *reads.spans[k]) for k in BASE_KINDS if k != "webp"))
             except Exception:
-                reads["ahead"] = None                      # the decode call reads the files itself
+                reads.ahead = None                         # the decode call reads the files itself
         return reads
 
-    def _png_for_pillow(self, held, lo: int, hi: int, kind: str = "png"):
-        """Which PNG (or GIF) files of a batch the decoder processes should take instead of the GPU (a mask over files lo..hi of
-        the read-ahead buffer, or None = the GPU takes them all).
+    def _for_pillow(self, reads: _BatchReads, kind: str):
+        """_largest_for_pillow for the batch's files of ``kind`` (of _SPLIT_RATES), where they were read ahead: a mask over
+        ``reads.positions[kind]``, or None."""
+        held, (lo, hi) = reads.ahead, reads.spans[kind]
+        probed = getattr(held, "probed", {}).get((kind, lo, hi))        # None also for a buffer that comes without headers
+        if probed is None:
+            return None
+        return _largest_for_pillow(held.sizes[lo:hi], probed, self.knobs.gpu_s_per_byte[kind],
+                                   1.0 / (max(1, self.workers) * self.knobs.pillow_mb_per_s * 1e6),
+                                   # starting the decoder processes costs about a second and a half, once
+                                   0.0 if self.workers in _pools else self.knobs.pool_start_s)
 
-        ``ke_png_inflate`` is one lane per stream and a deflate stream is sequential, so a batch takes as long as its longest
-        stream whatever its size -- about 0.45 us per symbol, i.e. 0.9 us per compressed byte of a textured image -- while a
-        decoder process gets through about 250 MB of decoded pixels per second.  2 048 textured 2048 x 2048 files: 5.1 s on
-        the GPU, 6.2 s on 16 host threads; 512 of them: 5.7 s against 1.5 s.  With the sizes known (the files are in memory,
-        their headers parsed) the k largest files go to the processes, k minimising the larger of (longest stream left for the
-        GPU) and (decoded bytes moved to the processes) in those terms -- the two shares are worked off side by side.  KE_PNG_GPU_US_PER_BYTE / KE_PILLOW_MB_PER_S set the two rates;
-        KE_PNG_GPU_US_PER_BYTE=0 sends every PNG file to the GPU, as before.  The LZW walk of ``ke_gif_codes`` has the same shape (one lane per
-        stream, ~0.65 us per code = 0.75 us per compressed byte: a 512 x 512 frame is 40 ms whatever the batch; KE_GIF_GPU_US_PER_BYTE)."""
-        gpu_rate = float(os.environ.get("KE_PNG_GPU_US_PER_BYTE", "0.9") if kind == "png" else os.environ.get("KE_GIF_GPU_US_PER_BYTE", "0.75")) * 1e-6
-        if gpu_rate <= 0.0:
-            return None
-        known = getattr(held, "probed", {}).get((kind, lo, hi))
-        if known is None:
-            return None
-        w, h, c, st = known
-        sizes = np.asarray(held.sizes[lo:hi], np.float64)
-        decoded = np.where(st == 0, w.astype(np.float64) * h * c, 0.0)
-        n = len(sizes)
-        if n == 0:
-            return None
-        cpu_rate = 1.0 / (max(1, self.workers) * float(os.environ.get("KE_PILLOW_MB_PER_S", "250")) * 1e6)
-        order = np.argsort(-np.where(st == 0, sizes, 0.0), kind="stable")
-        longest_left = np.concatenate([np.where(st == 0, sizes, 0.0)[order] * gpu_rate + 4e-3, [0.0]])   # + the launches' fixed cost
-        moved = np.concatenate([[0.0], np.cumsum(decoded[order]) * cpu_rate])
-        if self.workers not in _pools:                          # starting the decoder processes costs about a second and a half, once
-            moved[1:] += float(os.environ.get("KE_DECODE_POOL_START_S", "1.5"))
-        k = int(np.argmin(np.maximum(longest_left, moved)))     # the two shares run side by side (run_batches)
-        if k == 0:
-            return None
-        mask = np.zeros(n, bool)
-        mask[order[:k]] = True
-        return mask
-
-    def _hash_kind(self, kind: str, source, which=None):
-        """(phash, dhash, status) of a base kind's files from the stage's decoder of ``kind``.  ``source``: where the files are,
-        settled once per base kind -- ("ahead", (held, lo, hi)), a span of the read-ahead buffer, ("paths", [...]) or ("blobs",
-        [...]).  ``which``: a mask of the files to leave alone -- the ``skip`` of a span, left out of a list --, which come
-        back with status 1 as if refused."""
-        route, files = source
+    def _hash_kind(self, kind: str, span, paths, which=None):
+        """(phash, dhash, status) of a base kind's files from the stage's decoder of ``kind``.  Where the files are is settled
+        once per base kind: ``span``, (held, lo, hi) of the read-ahead buffer, or with ``span`` None their ``paths``.  ``which``:
+        a mask of the files to leave alone -- the ``skip`` of a span, left out of the paths --, which come back with status 1
+        as if refused."""
         keep = slice(None) if which is None else ~which
-        if route == "ahead":                               # ``skip`` only where there is a mask
-            got = self.stage.hash_ahead(*files, kind) if which is None else self.stage.hash_ahead(*files, kind, skip=which)
+        if span is not None:                               # ``skip`` only where there is a mask
+            got = self.stage.hash_ahead(*span, kind) if which is None else self.stage.hash_ahead(*span, kind, skip=which)
             got = [np.asarray(a)[keep] for a in got]
         else:
-            some = files if which is None else [f for f, alone in zip(files, which.tolist()) if not alone]
-            got = (self.stage.hash_files if route == "paths" else self.stage.jpeg_hash)(some, kind)
+            got = self.stage.hash_files(paths if which is None else [f for f, alone in zip(paths, which.tolist()) if not alone], kind)
         n = len(got[2]) if which is None else len(which)
         p, d, st = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.ones(n, np.int32)
         p[keep], d[keep], st[keep] = got
         return p, d, st
 
-    def _decode_on_gpu(self, reads: dict, start: int, ph: np.ndarray, dh: np.ndarray, ok: np.ndarray, skips=None) -> list:
+    def _decode_on_gpu(self, reads: _BatchReads, start: int, ph: np.ndarray, dh: np.ndarray, ok: np.ndarray, skips=None) -> list:
         """Fills ph / dh / ok (indexed by position - start) for the files the GPU decoders take; returns the positions they
         left to Pillow (``skips``: {kind: mask} of the PNG / GIF files the caller has given to the decoder processes already --
         not decoded here, not returned).  Every base kind's files go to its own decoder, then what that one left UNSUPPORTED
-        (status 1) to each of its enabled follow-ups (formats.follow_ups: the opt-in decoders) in turn, before Pillow."""
+        (status 1) to each of its enabled follow-ups (formats.follow_ups: the opt-in decoders) in turn, before Pillow.  The
+        read-ahead buffer goes back when the last decoder is done with it."""
         skips = skips or {}
-        by_path = hasattr(self.stage, "hash_files")
-        held = reads["ahead"]
+        held = reads.ahead
         refused: list = []
         offered = {k for k, _ in enabled_kinds("hash")}
         try:
             for kind in BASE_KINDS:
-                positions = reads[kind]
+                positions = reads.positions[kind]
                 if len(positions) == 0 or self.cancelled():
                     continue
-                skip = skips.get(kind)
-                if held is not None:
-                    if skip is not None and skip.all():
-                        continue
-                    source = ("ahead", (held, *reads["spans"][kind]))
-                elif by_path:
-                    source = ("paths", [self.paths[k] for k in positions.tolist()])
-                else:                                      # a stage that takes bytes: files that cannot be read stay with Pillow
-                    got = [(k, reads["blobs"][k].result()) for k in positions.tolist()]
-                    positions = np.array([k for k, b in got if b is not None], np.int64)
-                    source = ("blobs", [b for _, b in got if b is not None])
-                    if not source[1]:
-                        continue
-                try:
-                    p, d, st = self._hash_kind(kind, source, skip if held is not None else None)
-                except (RuntimeError, ValueError, MemoryError):      # e.g. no room on the device for this batch: Pillow decodes it
-                    refused.extend(positions.tolist())
+                which = skips.get(kind) if held is not None else None
+                skip = np.zeros(len(positions), bool) if which is None else which
+                if skip.all():
                     continue
+                span, paths = ((held, *reads.spans[kind]), None) if held is not None else (None, [self.paths[k] for k in positions.tolist()])
+                try:
+                    p, d, st = self._hash_kind(kind, span, paths, which)
+                except (RuntimeError, ValueError, MemoryError):      # e.g. no room on the device for this batch: nothing is
+                    p = d = np.zeros(len(positions), np.uint64)      # taken, no follow-up asked
+                    st = np.full(len(positions), 2, np.int32)
                 for follow_up in follow_ups(kind):
                     if follow_up in offered and (st == 1).any():
                         try:
-                            p2, d2, st2 = self._hash_kind(follow_up, source, st != 1)
+                            p2, d2, st2 = self._hash_kind(follow_up, span, paths, st != 1)
                         except (RuntimeError, ValueError, MemoryError):
                             continue                       # what it was offered keeps its status: Pillow decodes it, as before
                         took = st2 == 0
@@ -529,11 +600,10 @@ class _Pipeline:
                 ph[at] = p.view(np.int64)[good]
                 dh[at] = d.view(np.int64)[good]
                 ok[at] = True
-                left = ~good if skip is None else (~good & ~skip)
-                refused.extend(positions[left].tolist())   # outside the GPU decoder: Pillow decodes it, as the reference does
+                # outside the GPU decoders and not with the decoder processes already: Pillow decodes it, as the reference does
+                refused.extend(positions[~good & ~skip].tolist())
         finally:
-            if held is not None:
-                held.release()
+            reads.release()
         return refused
 
     # ---- the Pillow share: chunks through the two staging buffers
@@ -543,27 +613,28 @@ class _Pipeline:
         futures = [self.pool.submit(self._decode_into, self.tasks[k][1], view, alloc) for k in positions]
         return slot, futures
 
-    def _submit(self, slot: int, futures):
-        decoded = [fut.result() for fut in futures]
-        staged = [(k, d) for k, d in enumerate(decoded) if d is not None and d[0] != "spill"]
-        spills = [(k, d[1]) for k, d in enumerate(decoded) if d is not None and d[0] == "spill"]
+    def _submit(self, slot: int, positions: Sequence[int], decoded) -> _Round:
+        """Sends buffer ``slot`` on its way.  ``decoded``: per position (offset, width, height, channels) of its pixels in the
+        buffer, ("spill", pixels), or None for a file nobody could read."""
+        staged = [(k, d) for k, d in zip(positions, decoded) if d is not None and d[0] != "spill"]
+        spills = [(k, d[1]) for k, d in zip(positions, decoded) if d is not None and d[0] == "spill"]
         handle = None
         if staged:
-            handle = self.stage.submit(slot, [d[0] for _, d in staged], [d[1] for _, d in staged],
-                                       [d[2] for _, d in staged], [d[3] for _, d in staged])
-        return [k for k, _ in staged], handle, spills
+            offsets, widths, heights, channels = map(list, zip(*(d for _, d in staged)))
+            handle = self.stage.submit(slot, offsets, widths, heights, channels)
+        return _Round(slot, [k for k, _ in staged], handle, spills)
 
-    def _collect(self, slot: int, positions: Sequence[int], submitted, out: dict) -> None:
-        staged_pos, handle, spills = submitted
-        if handle is not None:
-            self.stage.wait(slot)
-            for k, p, d, st in zip(staged_pos, handle["phash"].tolist(), handle["dhash"].tolist(), handle["status"].tolist()):
+    def _collect(self, done: _Round, out: dict) -> None:
+        if done.handle is not None:
+            self.stage.wait(done.slot)
+            for k, p, d, st in zip(done.positions, done.handle["phash"].tolist(), done.handle["dhash"].tolist(),
+                                   done.handle["status"].tolist()):
                 if st == 0:
-                    out[positions[k]] = (_to_signed64(p), _to_signed64(d))
-        for k, arr in spills:                                    # larger than a staging buffer's free space
+                    out[k] = (_to_signed64(p), _to_signed64(d))
+        for k, arr in done.spills:                               # larger than a staging buffer's free space
             sig = self.stage.hash_one(arr)
             if sig is not None:
-                out[positions[k]] = (_to_signed64(sig[0]), _to_signed64(sig[1]))
+                out[k] = (_to_signed64(sig[0]), _to_signed64(sig[1]))
 
     def _decode_with_processes(self, todo: Sequence[int], out: dict) -> None:
         """The Pillow share on decoder PROCESSES: every round hands each worker a job of a few files and a region of the
@@ -577,13 +648,13 @@ class _Pipeline:
             if seen:
                 self.bytes_per_image = seen
                 want = min(2 << 30, 2 * seen * self.workers)
-                if want > self.stage.stage_bytes and "KE_STAGE_BYTES" not in os.environ:
+                if want > self.stage.stage_bytes and not self.knobs.stage_bytes_set:
                     try:
                         self.stage.wait(-1)
                         self.stage = _make_stage(self.device, want, max(self.chunk, 4096))
                     except Exception:
                         pass
-        if not getattr(self.stage, "shared_paths", None):
+        if not self.stage.shared_paths:
             return self._decode_with_threads(todo, out)
         shared_paths = self.stage.shared_paths
         queue = list(todo)
@@ -609,7 +680,7 @@ class _Pipeline:
                     job = (shared_paths[slot], r * region, region, [self.paths[k] for k in part])
                     pending.append((part, pool.submit(_decode_into_shared, job)))
                 if previous is not None:
-                    self._collect(previous[1], previous[0], previous[2], out)
+                    self._collect(previous, out)
                     previous = None
                 positions, placed, nbytes, again = [], [], 0, []
                 for part, fut in pending:
@@ -623,20 +694,16 @@ class _Pipeline:
                                 again.append(k)
                                 self.bytes_per_image = max(self.bytes_per_image, int(res[1]))
                             continue
-                        placed.append((len(positions), res))
+                        placed.append(res)
                         positions.append(k)
                         nbytes += res[1] * res[2] * res[3]
                 pending = []
                 if placed and not again:
                     self.bytes_per_image = max(1, nbytes // len(placed))
                 queue[at:at] = again                              # next round, with regions that hold them
-                handle = None
-                if placed:
-                    handle = self.stage.submit(slot, [d[0] for _, d in placed], [d[1] for _, d in placed],
-                                               [d[2] for _, d in placed], [d[3] for _, d in placed])
-                previous = (positions, slot, ([i for i, _ in placed], handle, []))
+                previous = self._submit(slot, positions, placed)
             if previous is not None:
-                self._collect(previous[1], previous[0], previous[2], out)
+                self._collect(previous, out)
                 previous = None
         finally:
             for _, fut in pending:                                # nobody may still be writing into a staging buffer
@@ -648,7 +715,7 @@ class _Pipeline:
             self._decode_with_threads(sorted(oversize), out)
 
     def _decode_with_pillow(self, todo: Sequence[int], out: dict) -> None:
-        if self.workers > 1 and len(todo) >= self.process_min and getattr(self.stage, "shared_paths", None):
+        if self.workers > 1 and len(todo) >= self.process_min and self.stage.shared_paths:
             try:
                 return self._decode_with_processes(todo, out)
             except (BrokenProcessPool, OSError):                  # e.g. a __main__ the children cannot import, a staging file
@@ -658,17 +725,17 @@ class _Pipeline:
         self._decode_with_threads(todo, out)
 
     def _decode_with_threads(self, todo: Sequence[int], out: dict) -> None:
-        previous = None                                           # (positions, slot, submitted) of the chunk on the GPU
+        previous = None                                           # the chunk on the GPU
         for c0 in range(0, len(todo), self.chunk):
             if self.cancelled():
                 break
             positions = todo[c0:c0 + self.chunk]
             slot, futures = self._start(positions)                # decode of this chunk runs on the pool from here on
             if previous is not None:                              # ... while the previous one is copied and hashed
-                self._collect(previous[1], previous[0], previous[2], out)
-            previous = (positions, slot, self._submit(slot, futures))
+                self._collect(previous, out)
+            previous = self._submit(slot, positions, [fut.result() for fut in futures])
         if previous is not None:
-            self._collect(previous[1], previous[0], previous[2], out)
+            self._collect(previous, out)
 
     def run(self) -> Iterator[Tuple[int, Optional[Tuple[int, int]]]]:
         """Yields (file_id, hashes | None) in task order."""
@@ -685,8 +752,7 @@ class _Pipeline:
             reads = future.result()
         except Exception:
             return
-        if reads and reads.get("ahead") is not None:
-            reads["ahead"].release()
+        reads.release()
 
     def run_batches(self) -> Iterator[Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]]:
         """Yields (file ids, pHash, dHash, done) of one batch after the other, in task order: int64 arrays (the hashes as the
@@ -708,16 +774,16 @@ class _Pipeline:
                 ok = np.zeros(stop - start, bool)
                 taken = np.zeros(stop - start, bool)
                 for k in BASE_KINDS:
-                    taken[reads[k] - start] = True
+                    taken[reads.positions[k] - start] = True
                 skips = {}
-                if reads["ahead"] is not None:
-                    for kind in ("png", "gif"):
-                        mask = self._png_for_pillow(reads["ahead"], *reads["spans"][kind], kind) if len(reads[kind]) else None
+                if reads.ahead is not None:
+                    for kind in _SPLIT_RATES:
+                        mask = self._for_pillow(reads, kind) if len(reads.positions[kind]) else None
                         if mask is not None:
                             skips[kind] = mask
                 todo = (start + np.nonzero(~taken)[0]).tolist()
                 for kind, mask in skips.items():
-                    todo += reads[kind][mask].tolist()
+                    todo += reads.positions[kind][mask].tolist()
                 # the Pillow share (other formats, the PNG files given to the processes) beside the GPU decoders' share: its
                 # staging route has a context of its own, so neither waits for the other's calls
                 out: dict = {}

@@ -286,7 +286,7 @@ def test_fastsig_drops_missing_files_and_reports_progress(K, monkeypatch, tmp_pa
         Image.new("RGB", (8, 8), (k, k, k)).save(p)
         paths.append((k + 1, str(p)))
     paths.insert(2, (99, str(tmp_path / "missing.png")))
-    class FakeStage:                                       # the four calls of fastsig._GpuStage, no device behind them
+    class FakeStage(fs._Stage):                            # what fastsig._Stage requires, no device behind it
         def __init__(self, device, stage_bytes, max_images):
             self.bufs, self.turn, self.submitted = [np.zeros(4096, np.uint8), np.zeros(4096, np.uint8)], 0, []
 
@@ -307,9 +307,13 @@ def test_fastsig_drops_missing_files_and_reports_progress(K, monkeypatch, tmp_pa
         def wait(self, slot):
             pass
 
-        def jpeg_hash(self, blobs, kind="jpeg"):            # "the GPU decoder refuses every file": all take the Pillow route
-            assert kind == "png" and all(b[:4] == b"\x89PNG" for b in blobs)
-            n = len(blobs)
+        def hash_files(self, paths, kind):                  # "the GPU decoder refuses every file": all take the Pillow route
+            assert kind == "png"
+            for p in paths:
+                if os.path.exists(p):                       # the missing one: refused like the rest, and Pillow drops it
+                    with open(p, "rb") as fh:
+                        assert fh.read(4) == b"\x89PNG"
+            n = len(paths)
             return np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.ones(n, np.int32)
 
         def hash_one(self, arr):
@@ -489,7 +493,7 @@ def test_batches_read_ahead_reach_the_decoders_in_their_own_order(tmp_path, monk
         n = np.array([int(os.path.basename(p)[1:4]) for p in paths], np.uint64)
         return n, n + np.uint64(500), np.where(n % 5 == 4, 1, 0).astype(np.int32)     # every fifth file is left to Pillow
 
-    class Stage:
+    class Stage(fs._Stage):
         def __init__(self, device, stage_bytes, max_images):
             self.buf = np.zeros(1 << 16, np.uint8)
 
@@ -549,14 +553,14 @@ def _chain_status(k: int, kind: str) -> int:
     return 2 if k in _CHAIN_REFUSED else 1 if k in _CHAIN_LEFT[kind] else 0
 
 
-@pytest.mark.parametrize("route", ["ahead", "ahead_png_skip", "paths", "blobs"])
+@pytest.mark.parametrize("route", ["ahead", "ahead_png_skip", "paths"])
 def test_follow_up_decoders_are_offered_what_their_base_left_on_every_route(tmp_path, monkeypatch, route):
     """fastsig._Pipeline's chain base decoder -> follow-ups (formats.follow_ups) with a stand-in stage, once per way the files
     reach it: a read-ahead buffer (``hash_ahead`` with a ``skip`` mask; one batch finds no buffer and goes through
-    ``hash_files``), paths (``hash_files`` with a filtered list) and bytes (``jpeg_hash`` with a filtered list).  File k's only
+    ``hash_files``) and paths (``hash_files`` with a filtered list).  File k's only
     byte is k, its 'hashes' are (k, k + 500), and its status is a function of k and the kind (_chain_status): every follow-up
     call must be handed exactly the files still at status 1 after the decoders before it -- never one its base gave 0 or 2 --,
-    the rows are those somebody took, every buffer comes back, and a PNG file that ``_png_for_pillow`` moves to the Pillow
+    the rows are those somebody took, every buffer comes back, and a PNG file that ``_largest_for_pillow`` moves to the Pillow
     side is neither hashed by the stage nor returned twice."""
     from kobato_eyes_amd import fastsig as fs
 
@@ -606,7 +610,7 @@ def test_follow_up_decoders_are_offered_what_their_base_left_on_every_route(tmp_
             self.out = True
             log["released"] += 1
 
-    class Stage:
+    class Stage(fs._Stage):
         def __init__(self, device, stage_bytes, max_images):
             self.buf = np.zeros(1 << 16, np.uint8)
 
@@ -621,6 +625,9 @@ def test_follow_up_decoders_are_offered_what_their_base_left_on_every_route(tmp_
 
         def hash_one(self, arr):
             return None
+
+        def hash_files(self, paths, kind="jpeg"):
+            return answer([number(p) for p in paths], kind, "paths")
 
     def read_ahead(self, paths, spans=()):
         log["reads"] += 1
@@ -640,19 +647,8 @@ def test_follow_up_decoders_are_offered_what_their_base_left_on_every_route(tmp_
         p[~skip], d[~skip], st[~skip] = answer(ks[~skip], kind, "ahead")
         return p, d, st
 
-    def hash_files(self, paths, kind="jpeg"):
-        return answer([number(p) for p in paths], kind, "paths")
-
-    def jpeg_hash(self, blobs, kind="jpeg"):
-        assert all(len(b) == 1 for b in blobs)
-        return answer([b[0] for b in blobs], kind, "blobs")
-
-    if route == "blobs":
-        Stage.jpeg_hash = jpeg_hash
-    else:
-        Stage.hash_files = hash_files
-        if route != "paths":
-            Stage.read_ahead, Stage.hash_ahead = read_ahead, hash_ahead
+    if route != "paths":
+        Stage.read_ahead, Stage.hash_ahead = read_ahead, hash_ahead
     monkeypatch.setattr(fs, "_make_stage", Stage)
     rows = fs.compute_signatures_mp(items, max_workers=2, chunksize=8)
 
@@ -672,11 +668,172 @@ def test_follow_up_decoders_are_offered_what_their_base_left_on_every_route(tmp_
     assert not moved & set(log["hashed"]) and len({r[0] for r in rows}) == len(rows)
     assert sorted(k for k in log["hashed"] if k not in set().union(*_CHAIN_LEFT.values())) == \
         sorted(set(range(n_files)) - moved - set().union(*_CHAIN_LEFT.values()))      # every other file: offered once, to its base
-    assert log["routes"] == {"ahead": {"ahead", "paths"}, "ahead_png_skip": {"ahead", "paths"}, "paths": {"paths"}, "blobs": {"blobs"}}[route]
+    assert log["routes"] == {"ahead": {"ahead", "paths"}, "ahead_png_skip": {"ahead", "paths"}, "paths": {"paths"}}[route]
     if route in ("ahead", "ahead_png_skip"):
         assert log["reads"] == 5 and log["held"] == 4 and log["released"] == 4
     else:
         assert log["reads"] == log["released"] == 0
+
+
+def test_failed_gpu_call_leaves_to_pillow_only_what_pillow_does_not_have_yet(tmp_path, monkeypatch):
+    """A GPU decode call that fails (``hash_ahead`` raises for PNG) on batches of which the cost split has already given one
+    file to the Pillow share: every file reaches ``_decode_with_pillow`` exactly once -- the moved one with the share, the
+    rest after the failure -- and the rows are those of a run in which Pillow decodes everything.  Twelve real 8 x 8 PNG files
+    of colour (k, k, k) in batches of eight; the stand-in's 'hashes' are (k, k + 500), read from the pixels that arrived in
+    the staging buffer; files 5 and 9 are reported as 10 MB of 2048 x 2048 x 3, which the split moves (one per batch)."""
+    from kobato_eyes_amd import fastsig as fs
+    from PIL import Image
+
+    items = []
+    for k in range(12):
+        p = tmp_path / f"f{k:03d}.png"
+        Image.new("RGB", (8, 8), (k, k, k)).save(p)
+        items.append((1000 + k, str(p)))
+    big = {5, 9}
+    log = {"held": 0, "released": 0, "failed": 0}
+
+    class Held:
+        def __init__(self, paths, spans):
+            self.sizes = np.array([10_000_000 if int(os.path.basename(p)[1:4]) in big else 1 for p in paths], np.uint64)
+            self.probed = {(kind, lo, hi): (np.full(hi - lo, 2048, np.int32), np.full(hi - lo, 2048, np.int32), np.full(hi - lo, 3, np.int32),
+                                            np.zeros(hi - lo, np.int32)) for kind, lo, hi in spans if hi > lo}
+            log["held"] += 1
+
+        def release(self):
+            log["released"] += 1
+
+    class Stage(fs._Stage):
+        def __init__(self, device, stage_bytes, max_images):
+            self.bufs, self.turn = [np.zeros(4096, np.uint8), np.zeros(4096, np.uint8)], 0
+
+        def acquire(self):
+            self.turn ^= 1
+            return self.turn, self.bufs[self.turn]
+
+        def submit(self, slot, offsets, widths, heights, channels):
+            k = np.array([self.bufs[slot][o] for o in offsets], np.uint64)
+            return {"phash": k, "dhash": k + np.uint64(500), "status": np.zeros(len(k), np.int32)}
+
+        def wait(self, slot):
+            pass
+
+        def hash_one(self, arr):
+            return None
+
+        def read_ahead(self, paths, spans=()):
+            return Held(paths, spans)
+
+        def hash_ahead(self, held, lo, hi, kind, skip=None):
+            assert kind == "png"
+            log["failed"] += 1
+            raise RuntimeError("no room on the device for this batch")
+
+    asked = []
+    inner = fs._Pipeline._decode_with_pillow
+
+    def spy(self, todo, out):
+        asked.extend(todo)
+        return inner(self, todo, out)
+
+    for v in ("KE_GPU_PNG", "KE_READ_AHEAD", "KE_PNG_GPU_US_PER_BYTE", "KE_PILLOW_MB_PER_S"):
+        monkeypatch.delenv(v, raising=False)
+    monkeypatch.setenv("KE_GPU_BATCH", "8")
+    monkeypatch.setenv("KE_DECODE_POOL_START_S", "0")
+    monkeypatch.setattr(fs, "_make_stage", Stage)
+    monkeypatch.setattr(fs._Pipeline, "_decode_with_pillow", spy)
+    rows = fs.compute_signatures_mp(items, max_workers=2, chunksize=8)
+    assert log["failed"] == 2 and log["held"] == log["released"] == 2
+    assert sorted(asked) == list(range(12)), asked             # nobody twice: not the files the Pillow share had already
+    assert rows == [(1000 + k, k, k + 500) for k in range(12)]
+    monkeypatch.setenv("KE_GPU_PNG", "0")                      # Pillow alone
+    assert fs.compute_signatures_mp(items, max_workers=2, chunksize=8) == rows and log["failed"] == 2
+
+
+def test_batch_reads_give_their_buffer_back_once():
+    """_BatchReads.release() however often: the read-ahead buffer is released once, and a batch without one has nothing to do."""
+    from kobato_eyes_amd.fastsig import _BatchReads
+
+    class Held:
+        released = 0
+
+        def release(self):
+            self.released += 1
+
+    held = Held()
+    reads = _BatchReads({}, {}, held)
+    reads.release()
+    reads.release()
+    assert held.released == 1 and reads.ahead is None
+    _BatchReads({}, {}).release()
+
+
+def _png_for_pillow_as_the_pipeline_carried_it(workers, pools, held, lo, hi, kind="png"):
+    """_Pipeline._png_for_pillow before fastsig._largest_for_pillow, restated literally (``workers`` / ``pools`` for
+    ``self.workers`` / the module's ``_pools``)."""
+    gpu_rate = float(os.environ.get("KE_PNG_GPU_US_PER_BYTE", "0.9") if kind == "png" else os.environ.get("KE_GIF_GPU_US_PER_BYTE", "0.75")) * 1e-6
+    if gpu_rate <= 0.0:
+        return None
+    known = getattr(held, "probed", {}).get((kind, lo, hi))
+    if known is None:
+        return None
+    w, h, c, st = known
+    sizes = np.asarray(held.sizes[lo:hi], np.float64)
+    decoded = np.where(st == 0, w.astype(np.float64) * h * c, 0.0)
+    n = len(sizes)
+    if n == 0:
+        return None
+    cpu_rate = 1.0 / (max(1, workers) * float(os.environ.get("KE_PILLOW_MB_PER_S", "250")) * 1e6)
+    order = np.argsort(-np.where(st == 0, sizes, 0.0), kind="stable")
+    longest_left = np.concatenate([np.where(st == 0, sizes, 0.0)[order] * gpu_rate + 4e-3, [0.0]])
+    moved = np.concatenate([[0.0], np.cumsum(decoded[order]) * cpu_rate])
+    if workers not in pools:
+        moved[1:] += float(os.environ.get("KE_DECODE_POOL_START_S", "1.5"))
+    k = int(np.argmin(np.maximum(longest_left, moved)))
+    if k == 0:
+        return None
+    mask = np.zeros(n, bool)
+    mask[order[:k]] = True
+    return mask
+
+
+def test_cost_split_function_moves_the_files_the_pipeline_method_moved(monkeypatch):
+    """fastsig._largest_for_pillow, fed from _Knobs and _SPLIT_RATES as the pipeline feeds it, against the method it replaced
+    on 2 000 random spans (n = 0 .. 40, statuses from {0, 1, 2} -- also all refused --, compressed sizes 1 B .. 50 MB, 1 .. 16
+    workers, decoder processes started or not, both kinds, a GPU rate of 0 and headers nobody parsed among the settings): the same
+    mask element for element, or None from both."""
+    from types import SimpleNamespace
+
+    from kobato_eyes_amd import fastsig as fs
+
+    assert fs._SPLIT_RATES == {"png": ("KE_PNG_GPU_US_PER_BYTE", "0.9"), "gif": ("KE_GIF_GPU_US_PER_BYTE", "0.75")}
+    settings = [{}, {"KE_PNG_GPU_US_PER_BYTE": "0"}, {"KE_GIF_GPU_US_PER_BYTE": "0", "KE_DECODE_POOL_START_S": "0"},
+                {"KE_PNG_GPU_US_PER_BYTE": "0.05", "KE_GIF_GPU_US_PER_BYTE": "3", "KE_PILLOW_MB_PER_S": "40"},
+                {"KE_PILLOW_MB_PER_S": "1000", "KE_DECODE_POOL_START_S": "0.01"}]
+    rng = np.random.default_rng(20261019)
+    moved_some = 0
+    for trial in range(2000):
+        if trial % 400 == 0:
+            for v in ("KE_PNG_GPU_US_PER_BYTE", "KE_GIF_GPU_US_PER_BYTE", "KE_PILLOW_MB_PER_S", "KE_DECODE_POOL_START_S"):
+                monkeypatch.delenv(v, raising=False)
+            for v, text in settings[trial // 400].items():
+                monkeypatch.setenv(v, text)
+            knobs = fs._Knobs.read()
+        n = trial % 400 if trial % 400 < 2 else int(rng.integers(0, 41))
+        kind = ("png", "gif")[int(rng.integers(0, 2))]
+        workers, started = int(rng.integers(1, 17)), bool(rng.integers(0, 2))
+        lo = int(rng.integers(0, 5))
+        sizes = np.floor(np.exp(rng.uniform(0.0, np.log(50e6), lo + n + 3))).astype(np.uint64)
+        w, h = rng.integers(1, 4097, n).astype(np.int32), rng.integers(1, 4097, n).astype(np.int32)
+        c = rng.choice([1, 3, 4], n).astype(np.int32)
+        st = (np.full(n, rng.integers(1, 3)) if trial % 7 == 0 else rng.choice([0, 0, 0, 1, 2], n)).astype(np.int32)
+        probed = None if trial % 11 == 0 else (w, h, c, st)
+        held = SimpleNamespace(sizes=sizes, probed={} if probed is None else {(kind, lo, lo + n): probed})
+        want = _png_for_pillow_as_the_pipeline_carried_it(workers, {workers: None} if started else {}, held, lo, lo + n, kind)
+        got = fs._largest_for_pillow(sizes[lo:lo + n], probed, knobs.gpu_s_per_byte[kind],
+                                     1.0 / (max(1, workers) * knobs.pillow_mb_per_s * 1e6), 0.0 if started else knobs.pool_start_s)
+        assert (got is None and want is None) or (got.dtype == bool and np.array_equal(got, want)), trial
+        moved_some += want is not None
+    assert moved_some > 200                                    # the comparison is not one of None with None
 
 
 def _grouped_layout_as_decode_files_owned_wrote_it(w, h, c, st):
