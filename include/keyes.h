@@ -185,6 +185,21 @@ int ke_jpeg_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, c
  * denominator 1 the bytes are ke_jpeg_decode's.  Everything else as ke_jpeg_decode. */
 int ke_jpeg_decode_scaled(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                           const int32_t *denoms, uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out);
+/* Restart intervals on separate lanes, opt-in.  KE_JPEG_SPLIT_RESTARTS=1 (environment, read per call; unset, empty or 0: off,
+ * and launches and results are exactly as without this path): in both decode calls above a sequential (SOF0 / SOF1) file
+ * with a DRI whose restart intervals can be dealt to two lanes or more is decoded one thread per lane instead of one thread
+ * per file -- a lane takes g consecutive intervals, g the smallest number that gives a lane at least
+ * KE_JPEG_SPLIT_MIN_MCUS MCUs (environment, default 64; a tuning knob, and the tests' way to several lanes in a tiny file)
+ * and the file at most 16 384 lanes.  Eligibility rule, checked on the device: with a marker being a position e in
+ * [scan_offset, scan_end - 1) where byte e is 0xFF and byte e + 1 is not 0, the entropy-coded segment must hold exactly one
+ * marker per interval boundary (intervals - 1 of them) and the k-th, counted from 0, must be RST(k mod 8).  Every other
+ * file -- a wrong number, a missing marker, one too many, 0xFF fill bytes in front of one, progressive files, files
+ * without DRI or with a DRI that covers the whole image -- is decoded as before and keeps the verdict it gets there.
+ * Statuses and pixels do not depend on the variables (csrc/ke_jpeg_restarts.h has the argument).
+ * ke_jpeg_last_split: of the last ke_jpeg_decode / ke_jpeg_decode_scaled call on this context, *files_split = the files that
+ * were decoded lane-wise and *lanes = the lanes launched for them (either pointer may be NULL); both 0 when the variable is
+ * unset.  KE_EINVAL for a NULL context. */
+int ke_jpeg_last_split(ke_ctx *ctx, int64_t *files_split, int64_t *lanes);
 
 /* ---- PNG decode on the GPU: the same step for PNG files, Adam7-interlaced or not: 8-bit grayscale ("L"), RGB and RGBA pixels as
  * they are; palette files (1 / 2 / 4 / 8 bits) and grayscale of 1 / 2 / 4 bits as the luma `convert("L")` makes of them --

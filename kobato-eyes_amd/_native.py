@@ -32,7 +32,7 @@ EXPORTS = (
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
-    "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_thumbnail_rgb_box", "ke_reduce_rgb", "ke_jpeg_decode_scaled", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode",
+    "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_thumbnail_rgb_box", "ke_reduce_rgb", "ke_jpeg_decode_scaled", "ke_jpeg_last_split", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode",
     "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash", "ke_sad_pairs", "ke_synth_rgb", "ke_synth_rgb_indexed",
     "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches", "ke_last_scan_path",
 ) + tuple(f"ke_{kind}_{call}" for kind in KINDS for call in ("probe", "decode", "caveats"))
@@ -138,6 +138,7 @@ def load_library() -> C.CDLL:
         lib.ke_thumbnail_rgb_box.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp]
         lib.ke_reduce_rgb.argtypes = [vp, vp, i32, i32, i32, i32, vp]
         lib.ke_jpeg_decode_scaled.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp]
+        lib.ke_jpeg_last_split.argtypes = [vp, vp, vp]
         lib.ke_band_pairs_after_size.argtypes = [vp, vp, vp, i64, i32, i32, dbl, i64, vp]
         lib.ke_hamming_scan.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, dbl, i64, vp, i64,
                                         C.POINTER(i64), vp]
@@ -392,6 +393,14 @@ class Context:
     def last_decode_sub_batches(self) -> int:
         """Sub-batches of the last decode call that ran the shared sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa, webpn)."""
         return int(self._lib.ke_last_decode_sub_batches(self._h))
+
+    def jpeg_last_split(self) -> tuple:
+        """(files, lanes) of the last JPEG decode call on this context: the files whose restart intervals were decoded on lanes of
+        their own (KE_JPEG_SPLIT_RESTARTS=1; the rule is in include/keyes.h) and the lanes launched for them.  (0, 0) with the
+        variable unset."""
+        files, lanes = C.c_int64(), C.c_int64()
+        self._check(self._lib.ke_jpeg_last_split(self._h, C.byref(files), C.byref(lanes)), "ke_jpeg_last_split")
+        return int(files.value), int(lanes.value)
 
     def last_scan_path(self) -> int:
         """Path the last hamming_scan with n >= 2 took, chosen on the device: 0 = all-pairs tiles, 1 = band buckets."""

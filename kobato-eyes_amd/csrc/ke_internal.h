@@ -148,6 +148,7 @@ struct ke_ctx {
     bool ssim_exact = false;         // ke_ssim_set_mode: false = integer-sum kernel (default), true = fp64-carry kernel
     float *margin_cur = nullptr;     // device array the hash kernels of the CURRENT call write tie margins to (slot = hash slot)
     int64_t decode_sub_batches = 0;  // sub-batches the last ke_decode_sub_batches worked its images off in (ke_last_decode_sub_batches)
+    int64_t jpeg_files_split = 0, jpeg_split_lanes = 0;   // of the last JPEG decode call: files decoded interval-wise, their lanes (ke_jpeg_last_split)
     bool dct_tables_ready = false;   // __constant__ tables are per device: uploaded once per context
 };
 

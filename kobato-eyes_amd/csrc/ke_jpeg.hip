@@ -8,6 +8,8 @@
 //                     scan; the parallelism is across the batch -- a 16 384-image batch is one wave per CU, 100 000 images
 //                     fill the chip) and writes every block's coefficients (int16) whole;
 //   ke_jpeg_entropy_prog : the same for progressive files, scan after scan into a zeroed coefficient array;
+//   ke_jpeg_find_restarts + ke_jpeg_entropy_rst : opt-in (KE_JPEG_SPLIT_RESTARTS), for sequential files with restart intervals:
+//                     one thread per group of intervals instead of one per image (ke_jpeg_restarts.h);
 //   ke_jpeg_idct    : one thread per 8x8 block: dequantise, jpeg_idct_islow, samples into padded component planes;
 //   ke_jpeg_colour  : one thread per 4 output pixels: fancy upsampling + YCbCr -> RGB (or the luma plane as it is), packed
 //                     8-bit pixels where ke_hash_images / ke_ssim_pairs expect them.
@@ -22,6 +24,7 @@
 
 #include "ke_decode_batch.h"
 #include "ke_jpeg_parse.h"
+#include "ke_jpeg_restarts.h"
 
 namespace {
 
@@ -200,6 +203,84 @@ __global__ __launch_bounds__(64) void ke_jpeg_find_end(KeJpegDev *__restrict__ i
     }
 }
 
+// ---- restart intervals on separate lanes (KE_JPEG_SPLIT_RESTARTS; ke_jpeg_restarts.h has the plan, the rule and the argument
+// why the answers are the walk's).  A file the host found worth splitting (sequential, DRI, a plan of two lanes or more):
+struct KeRstFile {
+    uint32_t img;                  // its record in the sub-batch
+    uint32_t lane_base;            // its first lane among the sub-batch's (a prefix sum of n_lanes); also its slice of the marker table
+    KeRstPlan plan;
+};
+
+// How a split file is kept from ke_jpeg_entropy without touching that kernel: ke_jpeg_find_restarts sets the DEVICE record's
+// info.progressive to kTakenByLanes, and the walk takes files with progressive == 0 only (nothing else on the device reads the
+// field: the progressive kernel gets its files as a list from the host).  A flag array as one more parameter of the walk was
+// tried first: the same registers and an MCU loop instruction for instruction the parent's, behind 15 more instructions of
+// prologue -- and 3.5 % slower on every row with the variable unset, in turns with the parent's build.
+constexpr int32_t kTakenByLanes = 2;
+
+// One wave per such file, behind ke_jpeg_find_end (scan_end is known): ke_rst_index a wave wide.  16 bytes per lane and step,
+// dword reads as in ke_jpeg_find_end; a lane's markers are counted, the counts' prefix over the wave comes from one __ballot
+// per bit of the count, and a running base carries the ordinal from step to step.  marks[lane_base + j] = position of marker
+// j * g - 1 (the one lane j starts behind); split[img] = 1 only if the rule holds.
+__global__ __launch_bounds__(64) void ke_jpeg_find_restarts(KeJpegDev *__restrict__ imgs, const KeRstFile *__restrict__ rfiles, int64_t n_files,
+                                                            const uint8_t *__restrict__ files, const int32_t *__restrict__ status,
+                                                            uint32_t *__restrict__ marks, int32_t *__restrict__ split) {
+    const int64_t f = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (f >= n_files) return;
+    const KeRstFile rf = rfiles[f];
+    if (status[rf.img] != KE_JPEG_OK) return;                       // (split[] was zeroed) turned down by ke_jpeg_find_end
+    KeJpegDev &d = imgs[rf.img];
+    const uint8_t *p = files + d.file_off;
+    const int64_t from = d.info.scan_offset, to = (int64_t)d.info.scan_end - 1;      // markers lie in [from, to)
+    const uintptr_t a0 = (uintptr_t)(p + from) & ~(uintptr_t)3;
+    const int64_t pos0 = (int64_t)(a0 - (uintptr_t)p);
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t *my_marks = marks + rf.lane_base;
+    uint32_t seen = 0;                                              // markers in front of this step (the same in every lane)
+    bool bad = false;
+    for (int64_t base = pos0; base < to; base += 64 * 16) {
+        const int64_t q = base + (int64_t)lane * 16;
+        uint32_t v[5] = {0, 0, 0, 0, 0};
+        uint32_t hits = 0;                                          // bit k: a marker at q + k
+        if (q < to) {                                               // reads q .. q + 19 < scan_end + 19: inside the buffer's 256 bytes of slack
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(p + q);
+#pragma unroll
+            for (int k = 0; k < 5; ++k) v[k] = w[k];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint32_t b0 = (v[k >> 2] >> (8 * (k & 3))) & 0xFFu, b1 = (v[(k + 1) >> 2] >> (8 * ((k + 1) & 3))) & 0xFFu;
+                const int64_t e = q + k;
+                if (b0 == 0xFFu && b1 != 0u && e >= from && e < to) hits |= 1u << k;
+            }
+        }
+        if (__ballot(hits != 0) == 0) continue;
+        const uint32_t mine = (uint32_t)__builtin_popcount(hits);  // 0 .. 8 (two bytes each)
+        uint32_t before = 0, step_total = 0;
+#pragma unroll
+        for (int bit = 0; bit < 4; ++bit) {
+            const uint64_t m = __ballot((mine >> bit) & 1u);
+            before += (uint32_t)__builtin_popcountll(m & below) << bit;
+            step_total += (uint32_t)__builtin_popcountll(m) << bit;
+        }
+        uint32_t ord = seen + before;
+        while (hits) {
+            const int k = __builtin_ctz(hits);
+            hits &= hits - 1;
+            if (p[q + k + 1] != 0xD0u + (ord & 7u)) bad = true;   // (markers are rare: a byte load, no indexing of v by a variable)
+            const uint32_t j = (ord + 1) / rf.plan.g;
+            if ((ord + 1) % rf.plan.g == 0 && j >= 1 && j < rf.plan.n_lanes) my_marks[j] = (uint32_t)(q + k);
+            ++ord;
+        }
+        seen += step_total;
+    }
+    const bool any_bad = __ballot(bad) != 0;
+    if (lane == 0 && !any_bad && seen == rf.plan.n_int - 1) {
+        split[rf.img] = 1;
+        d.info.progressive = kTakenByLanes;                         // ke_jpeg_entropy walks files with progressive == 0 only
+    }
+}
+
 __global__ __launch_bounds__(64) void ke_jpeg_entropy(const KeJpegDev *__restrict__ imgs, int64_t n, const uint8_t *__restrict__ files,
                                                       const KeHuffTable *__restrict__ tables, int16_t *__restrict__ coefs,
                                                       int32_t *__restrict__ status, int lanes) {
@@ -311,6 +392,135 @@ __global__ __launch_bounds__(64) void ke_jpeg_entropy(const KeJpegDev *__restric
     }
     if (rc == KE_JPEG_OK && ke_bits_ran_dry(bits)) rc = KE_JPEG_CORRUPT;    // used bits beyond the data: truncated or damaged
     status[i] = rc;
+}
+
+// One thread per (file, lane j of its plan): global lane L of the sub-batch's n_lanes_total belongs to the file whose
+// [lane_base, lane_base + n_lanes) holds it (binary search: consecutive lanes are mostly one file's, so a wave's lanes share
+// their Huffman tables in LDS).  The machinery is ke_jpeg_entropy's -- stream window, block in LDS, tables in LDS, `lanes` per
+// wave -- and so is the MCU loop, as a second copy: here it runs over a range of MCUs behind a start that is not the scan's,
+// and the walk's loop is left as it stands (DESIGN 5 has the register counts).  Only a failing lane writes the file's status,
+// and all of them write the same value.
+__global__ __launch_bounds__(64) void ke_jpeg_entropy_rst(const KeJpegDev *__restrict__ imgs, const KeRstFile *__restrict__ rfiles, int64_t n_files,
+                                                          int64_t n_lanes_total, const uint8_t *__restrict__ files,
+                                                          const KeHuffTable *__restrict__ tables, int16_t *__restrict__ coefs,
+                                                          int32_t *__restrict__ status, int lanes, const uint32_t *__restrict__ marks,
+                                                          const int32_t *__restrict__ split) {
+    __shared__ KeHuffTable s_tab[kLdsTables];
+    __shared__ int s_ids[kLdsTables];
+    __shared__ int s_count, s_all;
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[64 * kWinPitch];
+    __shared__ __attribute__((aligned(16))) uint8_t s_blk[64 * kBlkPitch];
+    const int lane = threadIdx.x;
+    const int64_t L = (int64_t)blockIdx.x * lanes + lane;
+    const int64_t Lc = L < n_lanes_total ? L : n_lanes_total - 1;
+    int64_t lo = 0, hi = n_files - 1;                                     // the last file whose lane_base <= Lc
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if ((int64_t)rfiles[mid].lane_base <= Lc) lo = mid; else hi = mid - 1;
+    }
+    const KeRstFile rf = rfiles[lo];
+    const KeJpegDev &d = imgs[rf.img];
+    const KeJpegInfo &in = d.info;
+    const uint32_t j = (uint32_t)(Lc - rf.lane_base);
+    const bool live = lane < lanes && L < n_lanes_total && j < rf.plan.n_lanes && split[rf.img] != 0;
+    if (lane == 0) { s_count = 0; s_all = 1; }
+    __syncthreads();
+    int my_dc[3], my_ac[3];
+    for (int c = 0; c < 3; ++c) { my_dc[c] = in.huff_dc[c < in.ncomp ? c : 0]; my_ac[c] = in.huff_ac[c < in.ncomp ? c : 0]; }
+    for (int turn = 0; turn < 64; ++turn) {                               // lanes register their ids one after the other
+        if (lane == turn && live) {
+            for (int c = 0; c < in.ncomp; ++c)
+                for (int id : {my_dc[c], my_ac[c]}) {
+                    bool found = false;
+                    for (int k = 0; k < s_count; ++k) found |= s_ids[k] == id;
+                    if (!found) {
+                        if (s_count < kLdsTables) s_ids[s_count++] = id; else s_all = 0;
+                    }
+                }
+        }
+        __syncthreads();
+    }
+    const int n_tab = s_count;
+    const bool in_lds = s_all != 0;
+    if (in_lds) {
+        for (int k = 0; k < n_tab; ++k) {
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(&tables[s_ids[k]]);
+            uint32_t *dst = reinterpret_cast<uint32_t *>(&s_tab[k]);
+            for (int w = lane; w < (int)(sizeof(KeHuffTable) / 4); w += 64) dst[w] = src[w];
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    auto slot_of = [&](int id) { int k = 0; while (k < n_tab - 1 && s_ids[k] != id) ++k; return k; };
+    int dc_slot[3], ac_slot[3];
+    for (int c = 0; c < 3; ++c) { dc_slot[c] = in_lds ? slot_of(my_dc[c]) : 0; ac_slot[c] = in_lds ? slot_of(my_ac[c]) : 0; }
+
+    const int ncomp = in.ncomp, mcus_x = in.mcus_x, restart_interval = in.restart_interval;
+    const KeRstLane ln = ke_rst_lane(rf.plan, (uint32_t)(in.mcus_x * in.mcus_y), (uint32_t)restart_interval, j);
+    // the lane's bytes: from 2 behind the marker in front of its first interval to the marker that closes its last
+    const uint32_t start = j == 0 ? in.scan_offset : marks[rf.lane_base + j] + 2;
+    const uint32_t end = j + 1 == rf.plan.n_lanes ? in.scan_end : marks[rf.lane_base + j + 1];
+    KeBits bits;
+    ke_bits_init(bits, files + d.file_off, start, end);
+    bits.next_rst = (int32_t)ln.next_rst;
+    Stream st;
+    st.file = files + d.file_off;
+    st.win = s_win + lane * kWinPitch;
+    st.end = end;
+    stream_load(st, start);
+    int16_t *lblk = reinterpret_cast<int16_t *>(s_blk + lane * kBlkPitch);
+    int hs[3], vs[3], bpr[3], bbase[3];
+    for (int c = 0; c < 3; ++c) { hs[c] = in.hs[c]; vs[c] = in.vs[c]; bpr[c] = in.plane_w[c] >> 3; bbase[c] = d.block_base[c]; }
+    int pred[3] = {0, 0, 0};
+    int restart_left = restart_interval;
+    int rc = KE_JPEG_OK;
+    int16_t *base = coefs + d.coef_off;
+    int my = (int)(ln.mcu_first / (uint32_t)mcus_x), mx = (int)(ln.mcu_first - (uint32_t)my * (uint32_t)mcus_x);
+    for (uint32_t m = ln.mcu_first; m < ln.mcu_last && rc == KE_JPEG_OK; ++m) {
+        if (restart_left == 0) {
+            if (ke_bits_restart(bits) != KE_JPEG_OK) { rc = KE_JPEG_CORRUPT; break; }
+            pred[0] = pred[1] = pred[2] = 0;
+            restart_left = restart_interval;
+        }
+        for (int c = 0; c < ncomp && rc == KE_JPEG_OK; ++c) {
+            const KeHuffTable *gdc = &tables[my_dc[c]], *gac = &tables[my_ac[c]];
+            const KeHuffTable *ldc = &s_tab[dc_slot[c]], *lac = &s_tab[ac_slot[c]];
+            for (int by = 0; by < vs[c] && rc == KE_JPEG_OK; ++by) {
+                for (int bx = 0; bx < hs[c]; ++bx) {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) reinterpret_cast<uint4 *>(lblk)[k] = uint4{0u, 0u, 0u, 0u};
+                    int s = in_lds ? huff_decode(bits, st, ldc) : huff_decode(bits, st, gdc);
+                    if (s < 0 || s > 11) { rc = KE_JPEG_CORRUPT; break; }
+                    pred[c] += receive_extend(bits, st, s);
+                    lblk[0] = (int16_t)pred[c];
+                    for (int k = 1; k < 64;) {
+                        const int rs = in_lds ? huff_decode(bits, st, lac) : huff_decode(bits, st, gac);
+                        if (rs < 0) { rc = KE_JPEG_CORRUPT; break; }
+                        const int r = rs >> 4;
+                        s = rs & 15;
+                        if (s == 0) {
+                            if (r != 15) break;
+                            k += 16;
+                            continue;
+                        }
+                        k += r;
+                        if (k > 63) { rc = KE_JPEG_CORRUPT; break; }
+                        lblk[k] = (int16_t)receive_extend(bits, st, s);         // zigzag order in memory, as ke_jpeg_entropy leaves it
+                        ++k;
+                    }
+                    if (rc != KE_JPEG_OK) break;
+                    uint4 *dst = reinterpret_cast<uint4 *>(base + ((size_t)bbase[c] + (size_t)(my * vs[c] + by) * bpr[c] + (mx * hs[c] + bx)) * 64);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) dst[k] = reinterpret_cast<const uint4 *>(lblk)[k];
+                }
+            }
+        }
+        --restart_left;
+        if (++mx == mcus_x) { mx = 0; ++my; }
+    }
+    // the walk's check at the restart behind this lane's last interval (or at the end of the scan): bits beyond the lane's data
+    if (rc == KE_JPEG_OK && ke_bits_ran_dry(bits)) rc = KE_JPEG_CORRUPT;
+    if (rc != KE_JPEG_OK) status[rf.img] = rc;
 }
 
 // ---- progressive files.  One thread per image again, scan after scan into the image's coefficient array (zeroed before).
@@ -881,6 +1091,7 @@ KE_API int ke_jpeg_caveats(const uint8_t *files, const uint64_t *offsets, const 
 static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
                              const int32_t *denoms, uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
     KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "compressed files are parsed"));
+    ctx->jpeg_files_split = ctx->jpeg_split_lanes = 0;
     if (n == 0) return KE_OK;
     const bool trace = std::getenv("KE_TRACE") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
@@ -913,6 +1124,7 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
     KeJpegTables tables;                              // one pool for the batch: every part's tables interned again
     std::vector<KeJpegScan> scans;                    // of the progressive files, image after image
     std::vector<int32_t> prog_list;
+    std::vector<KeRstFile> rst_files;                 // of a sub-batch: the files whose restart intervals go to lanes of their own
     std::vector<KeJpegScaled> geo;                    // with denoms: the reduced geometry, in device order as devs
     KeStreamGuard guard;                                          // after the host vectors it waits for
     void *d_files;
@@ -920,6 +1132,15 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
     std::unique_ptr<KeJpegDev[]> all(new KeJpegDev[(size_t)n]);           // record i <-> file i; status != OK = not decodable
     std::vector<Part> parts(16);
     const bool on_device_end = !std::getenv("KE_JPEG_HOST_END");      // 1: walk every file's entropy data on the host, as before
+    // KE_JPEG_SPLIT_RESTARTS=1: sequential files with restart intervals are decoded interval-wise (ke_jpeg_restarts.h);
+    // KE_JPEG_SPLIT_MIN_MCUS: the MCUs a lane should at least have (tuning, and the tests' way to lanes in tiny files)
+    const char *split_env = std::getenv("KE_JPEG_SPLIT_RESTARTS");
+    const bool split_on = split_env && *split_env && std::strcmp(split_env, "0") != 0;
+    uint32_t split_min_mcus = KE_RST_MIN_MCUS;
+    if (const char *e = std::getenv("KE_JPEG_SPLIT_MIN_MCUS")) {
+        const long v = std::atol(e);
+        if (v >= 1) split_min_mcus = (uint32_t)std::min<long>(v, 1l << 30);
+    }
     const int nparts = ke_parallel_ranges(n, [&](int64_t first, int64_t last, int t) {
         Part &p = parts[(size_t)t];
         p.first = first; p.last = last;
@@ -969,7 +1190,7 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
         std::sort(order.begin(), order.end(), [](const Key &x, const Key &y) { return x.a != y.a ? x.a < y.a : x.b != y.b ? x.b < y.b : x.i < y.i; });
     lap("merge tables + order");
     const int64_t total = (int64_t)order.size();
-    const size_t meta_bytes = (size_t)total * sizeof(KeJpegDev) + (size_t)total * 4 + 64;
+    const size_t meta_bytes = (size_t)total * sizeof(KeJpegDev) + (size_t)total * 4 + 64 + (split_on ? (size_t)total * 4 : 0);
     if (ctx->h_meta_bytes < meta_bytes) {
         if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
         ctx->h_meta = nullptr;
@@ -979,6 +1200,7 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
     }
     KeJpegDev *devs = (KeJpegDev *)ctx->h_meta;                          // page-locked, device order
     int32_t *h_st = (int32_t *)((uint8_t *)ctx->h_meta + (size_t)total * sizeof(KeJpegDev));
+    int32_t *h_split = h_st + total;                                     // (split_on only) the split flags, read back with the statuses
     auto part_index = [&](int64_t i) { int t = 0; while (t + 1 < nparts && i >= parts[(size_t)t].last) ++t; return t; };
     ke_parallel_ranges(total, [&](int64_t first, int64_t last, int) {
         for (int64_t k = first; k < last; ++k) {
@@ -1058,6 +1280,29 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
         KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)coef_units * 2 + 64, &d_coef));
         KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)plane_bytes + 64, &d_planes));
         KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)m * 4, &d_status));
+        // the files whose plan has two lanes or more, and the prefix of their lanes; none: nothing new is reserved or launched
+        rst_files.clear();
+        uint64_t rst_lanes = 0;
+        if (split_on)
+            for (int64_t k = 0; k < m; ++k) {
+                const KeJpegInfo &in = devs[first + k].info;
+                if (in.progressive || in.restart_interval <= 0) continue;
+                const KeRstPlan plan = ke_rst_plan((uint32_t)in.mcus_x * (uint32_t)in.mcus_y, (uint32_t)in.restart_interval, split_min_mcus, KE_RST_LANE_CAP);
+                if (!ke_rst_plan_splits(plan) || rst_lanes + plan.n_lanes > (1ull << 31)) continue;     // (lane indices stay below 2^31)
+                rst_files.push_back(KeRstFile{(uint32_t)k, (uint32_t)rst_lanes, plan});
+                rst_lanes += plan.n_lanes;
+            }
+        KeRstFile *d_rfiles = nullptr;
+        uint32_t *d_marks = nullptr;
+        int32_t *d_split = nullptr;
+        if (!rst_files.empty()) {                                        // one buffer: [records | marker table | split flags]
+            const size_t rec_bytes = (rst_files.size() * sizeof(KeRstFile) + 15) & ~(size_t)15;
+            void *d_rst;
+            KE_TRY(ke_reserve(ctx, KE_BUF_TILE32, rec_bytes + (size_t)rst_lanes * 4 + (size_t)m * 4, &d_rst));
+            d_rfiles = (KeRstFile *)d_rst;
+            d_marks = (uint32_t *)((uint8_t *)d_rst + rec_bytes);
+            d_split = (int32_t *)(d_marks + rst_lanes);
+        }
         lap("layout + reserve");
         KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs + first, (size_t)m * sizeof(KeJpegDev), hipMemcpyHostToDevice, ctx->stream));
         // sequential files: no clearing of the coefficient array, every block of an image that decodes is written whole (a
@@ -1075,10 +1320,26 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
         };
         hipLaunchKernelGGL(ke_jpeg_find_end, dim3((unsigned)m), dim3(64), 0, ctx->stream, (KeJpegDev *)d_imgs, m, (const uint8_t *)d_files,
                            (int32_t *)d_status);
+        if (!rst_files.empty()) {
+            KE_HIP(ctx, hipMemcpyAsync(d_rfiles, rst_files.data(), rst_files.size() * sizeof(KeRstFile), hipMemcpyHostToDevice, ctx->stream));
+            KE_HIP(ctx, hipMemsetAsync(d_split, 0, (size_t)m * 4, ctx->stream));
+            hipLaunchKernelGGL(ke_jpeg_find_restarts, dim3((unsigned)rst_files.size()), dim3(64), 0, ctx->stream, (KeJpegDev *)d_imgs,
+                               (const KeRstFile *)d_rfiles, (int64_t)rst_files.size(), (const uint8_t *)d_files, (const int32_t *)d_status, d_marks,
+                               d_split);
+            lap("find restarts (enqueue)");
+        }
         if ((int64_t)prog_list.size() < m) {
             const int lanes = lanes_for(m, (int64_t)ctx->cu_count * 8);
             hipLaunchKernelGGL(ke_jpeg_entropy, dim3((unsigned)((m + lanes - 1) / lanes)), dim3(64), 0, ctx->stream, (const KeJpegDev *)d_imgs, m,
                                (const uint8_t *)d_files, (const KeHuffTable *)d_tables, (int16_t *)d_coef, (int32_t *)d_status, lanes);
+        }
+        if (!rst_files.empty()) {
+            const int lanes = lanes_for((int64_t)rst_lanes, (int64_t)ctx->cu_count * 8);
+            hipLaunchKernelGGL(ke_jpeg_entropy_rst, dim3((unsigned)((rst_lanes + lanes - 1) / lanes)), dim3(64), 0, ctx->stream,
+                               (const KeJpegDev *)d_imgs, (const KeRstFile *)d_rfiles, (int64_t)rst_files.size(), (int64_t)rst_lanes,
+                               (const uint8_t *)d_files, (const KeHuffTable *)d_tables, (int16_t *)d_coef, (int32_t *)d_status, lanes,
+                               (const uint32_t *)d_marks, (const int32_t *)d_split);
+            lap("restart lanes (enqueue)");
         }
         if (!prog_list.empty()) {
             void *d_list;
@@ -1118,10 +1379,13 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
         }
         KE_HIP(ctx, hipGetLastError());
         KE_HIP(ctx, hipMemcpyAsync(h_st + first, d_status, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (!rst_files.empty()) KE_HIP(ctx, hipMemcpyAsync(h_split + first, d_split, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
         lap("enqueue");
         KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // prog_list is a host vector; the scratch is reused
         lap("wait for the stream");
         for (int64_t k = 0; k < m; ++k) status_out[order[(size_t)(first + k)].i] = h_st[first + k];
+        for (const KeRstFile &rf : rst_files)
+            if (h_split[first + rf.img]) { ++ctx->jpeg_files_split; ctx->jpeg_split_lanes += rf.plan.n_lanes; }
         first = last;
     }
     ke_time_end(ctx, KE_T_JPEG);
@@ -1143,4 +1407,11 @@ KE_API int ke_jpeg_decode_scaled(ke_ctx *ctx, const uint8_t *files, const uint64
             return ke_fail(ctx, KE_EINVAL, "file %lld: scale 1/%d (1, 2, 4 or 8)", (long long)i, denoms[i]);
     if (n == 0) denoms = nullptr;
     return jpeg_decode_batch(ctx, files, offsets, sizes, n, denoms, pixels_out, out_offsets, status_out);
+}
+
+KE_API int ke_jpeg_last_split(ke_ctx *ctx, int64_t *files_split, int64_t *lanes) {
+    if (!ctx) return KE_EINVAL;
+    if (files_split) *files_split = ctx->jpeg_files_split;
+    if (lanes) *lanes = ctx->jpeg_split_lanes;
+    return KE_OK;
 }
