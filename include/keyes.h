@@ -647,6 +647,23 @@ int64_t ke_last_decode_sub_batches(ke_ctx *ctx);
  * sorted copy of the table: 12 bytes per hash and band). */
 int32_t ke_last_scan_path(ke_ctx *ctx);
 
+/* ---- for the tests of the general resampler (the pixels do not depend on the plan): what the last group of images that
+ * ke_resize_luma_uniform, ke_fit_luma_uniform, ke_ssim_pairs' fit step, ke_thumbnail_rgb or ke_thumbnail_rgb_box resampled on
+ * this context was launched as.  A call that works its images off in several groups reports the last one.  The hash calls
+ * do not update it: their fallback tiles run the same two resamplers, but not through this entry.
+ *   [0] 0 = generic passes (one thread per output, Pillow's two passes), 1 = banded (horizontal taps per row band, vertical
+ *       taps from the transposed columns)
+ *   [1] chunks each output's horizontal tap window is cut into (1, 2, 4, 8, 16 or 32)
+ *   [2] dwords per chunk (8, 16, 24 or 32)
+ *   [3] horizontal launches (the outputs are split when their chunks exceed the 256 lanes of a workgroup)
+ *   [4] row bands per image
+ *   [5] 1 = rows read through the funnel-shift loader (width no multiple of 4), 0 = whole dwords
+ *   [6] 1 = vertical taps on the matrix cores, 0 = on the VALU (more than 128 output rows, or KE_VTILE_VALU set)
+ *   [7] 1 = vertical pass first (generic only: Pillow's rule for sources over 100 times taller than wide)
+ * Entries that do not apply to the path taken are -1 ([1]..[6] for generic, [7] for banded); all are -1 before any such
+ * call.  KE_EINVAL for a NULL context or a NULL plan_out. */
+int ke_last_resize_plan(ke_ctx *ctx, int32_t plan_out[8]);
+
 #ifdef __cplusplus
 }
 #endif

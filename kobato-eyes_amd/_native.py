@@ -34,7 +34,7 @@ EXPORTS = (
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
     "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_thumbnail_rgb_box", "ke_reduce_rgb", "ke_jpeg_decode_scaled", "ke_jpeg_last_split", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode",
     "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash", "ke_sad_pairs", "ke_synth_rgb", "ke_synth_rgb_indexed",
-    "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches", "ke_last_scan_path",
+    "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches", "ke_last_scan_path", "ke_last_resize_plan",
 ) + tuple(f"ke_{kind}_{call}" for kind in KINDS for call in ("probe", "decode", "caveats"))
 
 _lib: Optional[C.CDLL] = None
@@ -161,6 +161,7 @@ def load_library() -> C.CDLL:
         lib.ke_last_decode_sub_batches.restype = C.c_int64
         lib.ke_last_scan_path.argtypes = [vp]
         lib.ke_last_scan_path.restype = i32
+        lib.ke_last_resize_plan.argtypes = [vp, vp]
         _lib = lib
         return lib
 
@@ -405,6 +406,15 @@ class Context:
     def last_scan_path(self) -> int:
         """Path the last hamming_scan with n >= 2 took, chosen on the device: 0 = all-pairs tiles, 1 = band buckets."""
         return int(self._lib.ke_last_scan_path(self._h))
+
+    def last_resize_plan(self) -> tuple:
+        """What the last group of the general resampler (resize_luma_uniform, fit_luma_uniform, the fit step of ssim_pairs, the
+        thumbnail calls) was launched as: (banded, chunks per output, dwords per chunk, horizontal launches, bands per image,
+        funnel-shift loader, vertical taps on the matrix cores, vertical pass first); -1 where an entry does not apply and
+        before any call (include/keyes.h: ke_last_resize_plan)."""
+        plan = np.empty(8, np.int32)
+        self._check(self._lib.ke_last_resize_plan(self._h, _addr(plan)), "ke_last_resize_plan")
+        return tuple(int(v) for v in plan)
 
     # -- hashing ----------------------------------------------------------------------------
     def hash_uniform(self, pixels, n: int, width: int, height: int, channels: int, *, want_phash=True,

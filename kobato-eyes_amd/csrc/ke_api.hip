@@ -362,6 +362,14 @@ KE_API int64_t ke_last_decode_sub_batches(ke_ctx *ctx) { return ctx ? ctx->decod
 
 KE_API int32_t ke_last_scan_path(ke_ctx *ctx) { return ctx ? ctx->scan_path : -1; }
 
+static_assert(KE_RP_COUNT == 8, "ke_last_resize_plan reports eight entries");
+KE_API int ke_last_resize_plan(ke_ctx *ctx, int32_t plan_out[8]) {
+    if (!ctx) return KE_EINVAL;
+    if (!plan_out) return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    std::memcpy(plan_out, ctx->resize_plan, sizeof ctx->resize_plan);
+    return KE_OK;
+}
+
 // ---- hashing -------------------------------------------------------------------------------
 namespace {
 

@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "ke_internal.h"
+#include "ke_coeffs.h"
 
 namespace {
 

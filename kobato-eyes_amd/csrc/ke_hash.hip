@@ -1019,12 +1019,14 @@ int launch_hband_ndwc(ke_ctx *ctx, const KeBandArgs &a, int64_t n, size_t lds, i
     }
 }
 
-int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles);
+int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles,
+                 int32_t *plan = nullptr);
 
 // Banded target: src images -> (oh x ow) u8 tiles.  Returns KE_EUNSUPPORTED for shapes it does not take
 // (Pillow's vertical-first rule, images under 4 pixels, windows beyond 8 chunks of 32 dwords).
+// plan (nullable): the KE_RP_* record of what is launched.
 int resample_banded(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles, int filter = KE_FILTER_LANCZOS,
-                    const float *box = nullptr) {
+                    const float *box = nullptr, int32_t *plan = nullptr) {
     if ((int64_t)g.h > (int64_t)g.w * 100 && oh < g.h) return KE_EUNSUPPORTED;
     if ((int64_t)g.w * g.h < 4 || g.w > 16384 || g.h > 65536 || (int64_t)g.w * g.h * g.channels >= (1LL << 31)) return KE_EUNSUPPORTED;
     const KeAxisCoeffs *chz = box ? ke_get_coeffs(ctx, g.w, ow, filter, box[0], box[2]) : ke_get_coeffs(ctx, g.w, ow, filter);
@@ -1043,6 +1045,7 @@ int resample_banded(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *
     if (best_log2 < 0) return KE_EUNSUPPORTED;
     const KeChunkTable *tc = ke_get_chunks(ctx, chz, 1 << best_log2, 8);
     if (!tc) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+    if (plan) { plan[KE_RP_CPO] = tc->cpo; plan[KE_RP_NDWC] = tc->ndwc; }
     KeBandArgs a;
     std::memset(&a, 0, sizeof a);
     a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.w = g.w; a.h = g.h;
@@ -1066,6 +1069,7 @@ int resample_banded(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *
     const int64_t rows = std::min<int64_t>(cap_rows, (((g.h + want_bands - 1) / want_bands + unit - 1) / unit) * unit);
     a.band_rows = (int)rows;
     a.bands = (g.h + a.band_rows - 1) / a.band_rows;
+    if (plan) plan[KE_RP_BANDS] = a.bands;
     a.bp = ((a.band_rows + 3) & ~3) + 4;
     a.nout_total = ow; a.cpo_log2 = best_log2;
     a.cpacked = tc->d_cpacked; a.cstart = tc->d_cstart; a.cxor = tc->d_cxor; a.bias = chz->d_bias;
@@ -1082,6 +1086,7 @@ int resample_banded(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *
     // dword boundary, so a quad is DW whole dwords and the last quad of the image ends with the image.  Other widths, and
     // ragged batches in which some image starts off a dword boundary, take the funnel-shift loader.
     const bool aligned = g.w % 4 == 0 && !g.misaligned;
+    if (plan) { plan[KE_RP_BANDED] = 1; plan[KE_RP_FUNNEL] = aligned ? 0 : 1; plan[KE_RP_LAUNCHES] = 0; }
     for (int first = 0; first < ow; first += per_launch) {
         a.out_first = first;
         a.nout = std::min(per_launch, ow - first);
@@ -1093,8 +1098,9 @@ int resample_banded(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *
         else if (g.channels == 1) rc = aligned ? launch_hband_ndwc<1, true>(ctx, a, g.n, lds, tc->ndwc) : launch_hband_ndwc<1, false>(ctx, a, g.n, lds, tc->ndwc);
         else rc = aligned ? launch_hband_ndwc<4, true>(ctx, a, g.n, lds, tc->ndwc) : launch_hband_ndwc<4, false>(ctx, a, g.n, lds, tc->ndwc);
         if (rc != KE_OK) return rc;
+        if (plan) ++plan[KE_RP_LAUNCHES];
     }
-    return launch_vtile(ctx, a.hs, a.hp, g.n, ow, oh, cvt, d_tiles);
+    return launch_vtile(ctx, a.hs, a.hp, g.n, ow, oh, cvt, d_tiles, plan);
 }
 
 // Vertical taps of the banded paths on the matrix cores: T[yy][col] = sum_y k[yy][y] * hs[col][y] is the product of the tap
@@ -1142,8 +1148,10 @@ __global__ __launch_bounds__(256) void ke_vtile_mx(const KeVtileMxArgs a) {
 }
 
 // vertical taps of the banded paths: hs[img][ow][hp] signed bytes -> (oh x ow) u8 tiles
-int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles) {
-    if (oh <= 128 && !getenv("KE_VTILE_VALU")) {
+int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles, int32_t *plan) {
+    const bool on_mx = oh <= 128 && !getenv("KE_VTILE_VALU");
+    if (plan) plan[KE_RP_VMX] = on_mx ? 1 : 0;
+    if (on_mx) {
         const KeMxTable *mx = ke_get_mx(ctx, cvt);
         if (!mx) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
         KeVtileMxArgs m;
@@ -1329,7 +1337,7 @@ __global__ __launch_bounds__(1024) void ke_hstrips(const KeStripArgs a) {
     }
 }
 
-int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles);
+int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles, int32_t *plan);
 
 // (32 x 32) or (8 x 9) tile of packed RGB images 2816..5300 pixels wide, large groups only
 int resample_strips(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles) {
@@ -1397,12 +1405,16 @@ int resample_strips(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *
 
 // Generic target: src images -> (oh x ow) u8 tiles, two single-axis passes in Pillow's order.
 int resample_generic(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles, int filter = KE_FILTER_LANCZOS,
-                     const float *box = nullptr) {
+                     const float *box = nullptr, int32_t *plan = nullptr) {
     const KeAxisCoeffs *chz = box ? ke_get_coeffs(ctx, g.w, ow, filter, box[0], box[2]) : ke_get_coeffs(ctx, g.w, ow, filter);
     const KeAxisCoeffs *cvt = box ? ke_get_coeffs(ctx, g.h, oh, filter, box[1], box[3]) : ke_get_coeffs(ctx, g.h, oh, filter);
     if (!chz || !cvt) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
     // Pillow's Image.resize shrinks very tall, narrow images vertically first (PIL/Image.py).
     const bool vertical_first = (int64_t)g.h > (int64_t)g.w * 100 && oh < g.h;
+    if (plan) {   // whatever the banded path wrote before it declined goes
+        for (int k = 0; k < KE_RP_COUNT; ++k) plan[k] = -1;
+        plan[KE_RP_BANDED] = 0; plan[KE_RP_VFIRST] = vertical_first ? 1 : 0;
+    }
     const int mid_w = vertical_first ? g.w : ow, mid_h = vertical_first ? oh : g.h;
     const size_t mid_bytes = (size_t)mid_w * mid_h;
     const int64_t max_n = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20) / mid_bytes));
@@ -1411,7 +1423,7 @@ int resample_generic(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t 
             KeHashGroup s = g;
             s.n = std::min(max_n, g.n - f);
             if (g.offsets) s.offsets = g.offsets + f; else s.pixels = g.pixels + (size_t)f * g.stride;
-            KE_TRY(resample_generic(ctx, s, ow, oh, d_tiles + (size_t)f * ow * oh, filter, box));
+            KE_TRY(resample_generic(ctx, s, ow, oh, d_tiles + (size_t)f * ow * oh, filter, box, plan));
         }
         return KE_OK;
     }
@@ -1662,8 +1674,9 @@ int ke_launch_resize_group(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, in
         s.n = std::min(chunk, g.n - f);
         if (g.offsets) s.offsets = g.offsets + f; else s.pixels = g.pixels + (size_t)f * g.stride;
         uint8_t *dst = d_tiles + (size_t)f * ow * oh;
-        int rc = resample_banded(ctx, s, ow, oh, dst, filter, box);
-        if (rc == KE_EUNSUPPORTED) rc = resample_generic(ctx, s, ow, oh, dst, filter, box);
+        for (int k = 0; k < KE_RP_COUNT; ++k) ctx->resize_plan[k] = -1;
+        int rc = resample_banded(ctx, s, ow, oh, dst, filter, box, ctx->resize_plan);
+        if (rc == KE_EUNSUPPORTED) rc = resample_generic(ctx, s, ow, oh, dst, filter, box, ctx->resize_plan);
         KE_TRY(rc);
     }
     return KE_OK;

@@ -13,64 +13,9 @@
 #include <vector>
 
 #include "../../include/keyes.h"
+#include "ke_coeffs.h"
 
 #define KE_API extern "C" __attribute__((visibility("default")))
-
-// ---------------------------------------------------------------------------------------
-// Lanczos coefficient tables (host side: ke_coeffs.cpp).
-// plain  : Pillow's own layout, bounds[o] = (first tap, tap count), kk[o][ksize] 22-bit ints.
-// packed : the layout the fused kernel eats.  For output o the window starts at byte
-//          start[o] (multiple of 8) and spans 4*ndw bytes; tap weight k is split into three
-//          balanced signed bytes k = b0 + 256*b1 + 65536*b2, stored per window dword as three
-//          packed i8x4 words (one per byte plane) so a v_dot4_i32_i8 against four signed luma
-//          bytes (L-128) accumulates each plane; bias[o] = 128*sum(k) + 2^21.
-// ---------------------------------------------------------------------------------------
-struct KeAxisCoeffs {
-    int in_size = 0, out_size = 0;
-    int ksize = 0;
-    std::vector<int32_t> bounds;  // 2*out
-    std::vector<int32_t> kk;      // out*ksize
-    int ndw = 0;                  // window dwords (multiple of 4)
-    int span = 0;                 // max(start[o] + 4*ndw)
-    std::vector<int32_t> start;   // out
-    std::vector<int32_t> bias;    // out
-    std::vector<int32_t> packed;  // out*ndw*3
-    // device copies
-    int32_t *d_bounds = nullptr, *d_kk = nullptr, *d_start = nullptr, *d_bias = nullptr, *d_packed = nullptr;
-    // chunked byte-plane layouts, by chunks-per-output (see KeChunkTable)
-    std::map<int, struct KeChunkTable *> chunked;
-    // matrix-core operand layouts of the same byte planes (see KeMxTable), built on first use, by (min_ks, align64)
-    std::map<int, struct KeMxTable *> mx;
-};
-
-// The tap matrix as B operands of v_mfma_i32_16x16x64_i8: the resample of one axis is the banded product
-// out[row][o] = sum_x luma[row][x] * k[o][x]; outputs are taken 16 at a time (tile j = o / 16), the taps of a tile
-// live in x in [base[j], base[j] + 64*ks), and step s of tile j, byte plane p is one 64x16 operand whose lane l
-// holds the 16 bytes k_p[o = 16j + (l & 15)][x = base[j] + 64s + 16(l >> 4) + 0..15] (zero outside the window
-// and for o >= out_size).  frag index: (((j*ks + s)*3 + p)*64 + l)*4 dwords.
-struct KeMxTable {
-    int tiles = 0, ks = 0;
-    std::vector<int32_t> base;   // tiles, multiples of 16
-    std::vector<int32_t> frag;
-    int32_t *d_frag = nullptr;
-};
-
-// Chunked byte-plane layout for long windows: every output's packed window is cut into `cpo` chunks of
-// `ndwc` dwords; virtual column v = o*cpo + c starts at cstart[v] and owns cpacked[v][ndwc][3]; the
-// chunks' plane sums are added before bias[o] and the clip.
-struct KeChunkTable {
-    int cpo = 0, ndwc = 0, cspan = 0;
-    std::vector<int32_t> cstart, cpacked;
-    // cxor[v] in 0..3: lane v visits window dword pair p at physical pair p ^ cxor[v], chosen on the host so
-    // that the 32 lanes of a half-wave hit distinct LDS banks with ds_read_b64 (needs ndwc % 8 == 0)
-    std::vector<int32_t> cxor;
-    int32_t *d_cstart = nullptr, *d_cpacked = nullptr, *d_cxor = nullptr;
-};
-
-
-void ke_build_axis_coeffs(int in_size, int out_size, KeAxisCoeffs &out, int filter, float in0, float in1);
-void ke_build_chunked(const KeAxisCoeffs &c, int cpo, KeChunkTable &out, int ndwc_multiple = 4);
-void ke_build_mx(const KeAxisCoeffs &c, KeMxTable &out, int min_ks = 0, bool align64 = false);
 
 struct KeDevBuf {
     void *ptr = nullptr;
@@ -145,6 +90,7 @@ struct ke_ctx {
     void *h_meta = nullptr;          // page-locked per-image records of a decode batch on their way to the device, and the statuses back
     size_t h_meta_bytes = 0;
     int scan_path = -1;              // path of the last ke_hamming_scan: 0 tiles, 1 buckets (ke_last_scan_path)
+    int32_t resize_plan[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // of the last group of ke_launch_resize_group (ke_last_resize_plan)
     bool ssim_exact = false;         // ke_ssim_set_mode: false = integer-sum kernel (default), true = fp64-carry kernel
     float *margin_cur = nullptr;     // device array the hash kernels of the CURRENT call write tie margins to (slot = hash slot)
     int64_t decode_sub_batches = 0;  // sub-batches the last ke_decode_sub_batches worked its images off in (ke_last_decode_sub_batches)
@@ -198,6 +144,8 @@ int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, u
                          uint8_t *d_tile32_out, uint8_t *d_tile98_out, hipStream_t fused_stream = nullptr);
 // luma + resize of a group to (oh x ow) u8 tiles with the given filter (banded path, generic fallback)
 // box = {x0, y0, x1, y1} source rectangle (Pillow's resize box), NULL = the whole image
+// ctx->resize_plan holds what was launched for the last group, written where each value is decided (ke_last_resize_plan):
+enum { KE_RP_BANDED = 0, KE_RP_CPO, KE_RP_NDWC, KE_RP_LAUNCHES, KE_RP_BANDS, KE_RP_FUNNEL, KE_RP_VMX, KE_RP_VFIRST, KE_RP_COUNT };
 int ke_launch_resize_group(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, int filter, uint8_t *d_tiles,
                            const float *box = nullptr);
 int ke_launch_tile_ahash(ke_ctx *ctx, const uint8_t *d_tiles, int64_t n, int grid, int tile, uint64_t *d_bits);
