@@ -636,7 +636,7 @@ double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind);
 
 /* ---- for the tests of the scratch budgets (KE_<KIND>_SCRATCH_BYTES; results do not depend on them, so nothing else shows
  * that one was honoured): the number of sub-batches in which the last decode call on this context that runs the shared
- * sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa, webpn; the other kinds keep loops of their own or need none) worked
+ * sub-batch loop (jpeg, png, bmpx, gif, tiffc, tiffz, webp, webpl, webpa, webpn; bmp and tiff have no scratch and need none) worked
  * off the images it accepted.  0 before any such call; -1 for a NULL context. */
 int64_t ke_last_decode_sub_batches(ke_ctx *ctx);
 

@@ -392,7 +392,7 @@ class Context:
         return float(self._lib.ke_last_kernel_ms(self._h, kind))
 
     def last_decode_sub_batches(self) -> int:
-        """Sub-batches of the last decode call that ran the shared sub-batch loop (bmpx, gif, tiffc, tiffz, webp, webpl, webpa, webpn)."""
+        """Sub-batches of the last decode call that ran the shared sub-batch loop (every kind but bmp and tiff, which have no scratch)."""
         return int(self._lib.ke_last_decode_sub_batches(self._h))
 
     def jpeg_last_split(self) -> tuple:

@@ -1,7 +1,7 @@
-// ke_decode_batch.h -- the host side that the nine ke_<kind>_{probe,caveats,decode} entry points share (keyes.h, "arguments and
+// ke_decode_batch.h -- the host side that the twelve ke_<kind>_{probe,caveats,decode} entry points share (keyes.h, "arguments and
 // conventions" at ke_jpeg_decode): the argument checks, the per-file loops of probe and caveats, the upload of the files, the
-// scratch budget, the row-tile geometry and the loop over sub-batches.  No kernels; a format supplies its parser, its records,
-// what an image costs and what is launched for a sub-batch.
+// scratch budget, the row-tile geometry and the loop over sub-batches (ten of them run it: uncompressed BMP and TIFF have no
+// scratch).  No kernels; a format supplies its parser, its records, what an image costs and what is launched for a sub-batch.
 #pragma once
 
 #include <algorithm>

@@ -87,7 +87,7 @@ struct ke_ctx {
     int64_t edge_slots = 1024;       // edges carried by one record of ke_allgather_edges (follows the largest list seen)
     void *h_comm = nullptr;          // pinned landing zone of the gathered edge records
     size_t h_comm_bytes = 0;
-    void *h_meta = nullptr;          // page-locked per-image records of a decode batch on their way to the device, and the statuses back
+    void *h_meta = nullptr;          // page-locked per-image records of a decode batch on their way to the device
     size_t h_meta_bytes = 0;
     int scan_path = -1;              // path of the last ke_hamming_scan: 0 tiles, 1 buckets (ke_last_scan_path)
     int32_t resize_plan[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // of the last group of ke_launch_resize_group (ke_last_resize_plan)

@@ -1086,61 +1086,73 @@ KE_API int ke_jpeg_caveats(const uint8_t *files, const uint64_t *offsets, const 
     });
 }
 
-// The decode call.  denoms = NULL: ke_jpeg_decode, exactly as before.  Otherwise file i is decoded at 1 / denoms[i]
-// (ke_jpeg_decode_scaled): the same parse, order, entropy kernels and scratch, the IDCT and colour kernels of the reduced sizes.
-static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
-                             const int32_t *denoms, uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
-    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "compressed files are parsed"));
-    ctx->jpeg_files_split = ctx->jpeg_split_lanes = 0;
-    if (n == 0) return KE_OK;
-    const bool trace = std::getenv("KE_TRACE") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
+// ---- the decode call in steps: the switches, prepare (parse, merge, order, gather, geometry) and, per sub-batch of
+// ke_decode_sub_batches, the record layout (take), the restart-lane plan, the entropy stage and the pixel stage (launch)
+
+struct JpegSwitches {                  // the environment, read once per call; and KE_TRACE's clock
+    bool trace = std::getenv("KE_TRACE") != nullptr;
+    bool device_end = !std::getenv("KE_JPEG_HOST_END");              // 1: walk every file's entropy data on the host, as before
+    bool keep_order = std::getenv("KE_JPEG_KEEP_ORDER") != nullptr;
+    // KE_JPEG_SPLIT_RESTARTS=1: sequential files with restart intervals are decoded interval-wise (ke_jpeg_restarts.h);
+    // KE_JPEG_SPLIT_MIN_MCUS: the MCUs a lane should at least have (tuning, and the tests' way to lanes in tiny files)
+    bool split = false;
+    uint32_t split_min_mcus = KE_RST_MIN_MCUS;
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+    JpegSwitches() {
+        const char *e = std::getenv("KE_JPEG_SPLIT_RESTARTS");
+        split = e && *e && std::strcmp(e, "0") != 0;
+        const long v = (e = std::getenv("KE_JPEG_SPLIT_MIN_MCUS")) ? std::atol(e) : 0;
+        if (v >= 1) split_min_mcus = (uint32_t)std::min<long>(v, 1l << 30);
+    }
+    void lap(const char *what) {
         if (!trace) return;
         const auto now = std::chrono::steady_clock::now();
         std::fprintf(stderr, "[ke_jpeg_decode] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
-    };
-    // ---- host: headers, Huffman tables, geometry -- on the host's threads (a header costs a few microseconds; 65 536 of them on
-    // one thread are more than the kernels take).  A record is 700 bytes (three quantisation tables), so records are written
-    // once, where they are parsed, and move once more: in device order into the page-locked block they are uploaded from.
-    // (Before: per-thread vectors merged into one, copied again by the sort, uploaded from pageable memory -- 50 ms of a
-    // 65 536-file call, as long as the entropy kernel.)
+    }
+};
+
+// What prepare makes of the caller's files, and the call's device arrays.  Copies are queued from tables.pool, scans and geo:
+// a call declares its JpegBatch (and its JpegSubBatch) before its KeStreamGuard.
+struct JpegBatch {
+    struct Key { uint64_t a, b; uint32_t i; };
+    std::vector<Key> order;            // the accepted files in device order: order[k].i is the caller's index
+    KeJpegDev *devs = nullptr;         // their records in that order, page-locked (ctx->h_meta)
+    KeJpegTables tables;               // one pool for the batch: every part's tables interned again
+    std::vector<KeJpegScan> scans;     // of the progressive files, image after image
+    std::vector<KeJpegScaled> geo;     // with denoms: the reduced geometry, in device order as devs
+    void *d_files = nullptr, *d_tables = nullptr, *d_scans = nullptr;
+};
+
+// ctx->h_meta, grown to hold `count` records.
+static int jpeg_page_locked_records(ke_ctx *ctx, size_t count, KeJpegDev **devs) {
+    const size_t bytes = count * sizeof(KeJpegDev);
+    if (ctx->h_meta_bytes < bytes) {
+        if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
+        ctx->h_meta = nullptr, ctx->h_meta_bytes = 0;
+        KE_HIP(ctx, hipHostMalloc(&ctx->h_meta, bytes + bytes / 4, hipHostMallocDefault));
+        ctx->h_meta_bytes = bytes + bytes / 4;
+    }
+    *devs = (KeJpegDev *)ctx->h_meta;
+    return KE_OK;
+}
+
+// host: headers, Huffman tables, geometry -- on the host's threads (a header costs a few microseconds; 65 536 of them on one
+// thread are more than the kernels take).  A record is 700 bytes (three quantisation tables), so records are written once,
+// where they are parsed, and move once more: in device order into the page-locked block they are uploaded from.  (Before:
+// per-thread vectors merged into one, copied again by the sort, uploaded from pageable memory -- 50 ms of a 65 536-file call,
+// as long as the entropy kernel.)  status_out[i] is the parser's; b.order stays empty when it accepts no file.
+static int jpeg_prepare(ke_ctx *ctx, JpegSwitches &sw, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                        const int32_t *denoms, const uint64_t *out_offsets, int32_t *status_out, JpegBatch &b) {
     struct Part {
         KeJpegTables tables;
         std::vector<KeJpegScan> scans;
         int64_t first = 0, last = 0;
+        std::vector<int> remap;        // its table numbers -> the batch's
+        uint32_t scan_base = 0;        // its first scan among the batch's
     };
-    // the compressed bytes set off for the device before anything is parsed: one contiguous range of the caller's buffer (the
-    // files the decoder will turn down travel along -- they are the few), 17 ms for the 970 MB of 65 536 files, hidden behind
-    // the parsing below
-    uint64_t lo = ~0ull, hi = 0;
-    for (int64_t i = 0; i < n; ++i)
-        if (sizes[i]) { lo = std::min(lo, offsets[i]); hi = std::max(hi, offsets[i] + sizes[i]); }
-    if (hi <= lo) {
-        for (int64_t i = 0; i < n; ++i) status_out[i] = KE_JPEG_CORRUPT;
-        return KE_OK;
-    }
-    KeJpegTables tables;                              // one pool for the batch: every part's tables interned again
-    std::vector<KeJpegScan> scans;                    // of the progressive files, image after image
-    std::vector<int32_t> prog_list;
-    std::vector<KeRstFile> rst_files;                 // of a sub-batch: the files whose restart intervals go to lanes of their own
-    std::vector<KeJpegScaled> geo;                    // with denoms: the reduced geometry, in device order as devs
-    KeStreamGuard guard;                                          // after the host vectors it waits for
-    void *d_files;
-    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));   // the stream windows read up to 64 bytes past a file
     std::unique_ptr<KeJpegDev[]> all(new KeJpegDev[(size_t)n]);           // record i <-> file i; status != OK = not decodable
     std::vector<Part> parts(16);
-    const bool on_device_end = !std::getenv("KE_JPEG_HOST_END");      // 1: walk every file's entropy data on the host, as before
-    // KE_JPEG_SPLIT_RESTARTS=1: sequential files with restart intervals are decoded interval-wise (ke_jpeg_restarts.h);
-    // KE_JPEG_SPLIT_MIN_MCUS: the MCUs a lane should at least have (tuning, and the tests' way to lanes in tiny files)
-    const char *split_env = std::getenv("KE_JPEG_SPLIT_RESTARTS");
-    const bool split_on = split_env && *split_env && std::strcmp(split_env, "0") != 0;
-    uint32_t split_min_mcus = KE_RST_MIN_MCUS;
-    if (const char *e = std::getenv("KE_JPEG_SPLIT_MIN_MCUS")) {
-        const long v = std::atol(e);
-        if (v >= 1) split_min_mcus = (uint32_t)std::min<long>(v, 1l << 30);
-    }
     const int nparts = ke_parallel_ranges(n, [&](int64_t first, int64_t last, int t) {
         Part &p = parts[(size_t)t];
         p.first = first; p.last = last;
@@ -1148,7 +1160,7 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
         for (int64_t i = first; i < last; ++i) {
             KeJpegDev &d = all[(size_t)i];
             bool defer = false;
-            ke_parse_jpeg(files + offsets[i], (size_t)sizes[i], p.tables, d.info, true, &p.scans, on_device_end ? &defer : nullptr);
+            ke_parse_jpeg(files + offsets[i], (size_t)sizes[i], p.tables, d.info, true, &p.scans, sw.device_end ? &defer : nullptr);
             status_out[i] = d.info.status;
             if (d.info.status != KE_JPEG_OK) continue;
             d.end_on_device = defer ? 1 : 0;
@@ -1157,238 +1169,274 @@ static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *
             d.out_off = out_offsets[i];
         }
     });
-    lap("parse (threads)");
-    std::vector<std::vector<int>> remaps((size_t)nparts);
-    std::vector<uint32_t> scan_base((size_t)nparts);
+    sw.lap("parse (threads)");
     for (int t = 0; t < nparts; ++t) {
         Part &p = parts[(size_t)t];
-        scan_base[(size_t)t] = (uint32_t)scans.size();
-        scans.insert(scans.end(), p.scans.begin(), p.scans.end());
-        std::vector<int> &remap = remaps[(size_t)t];
-        remap.resize(p.tables.keys.size());
-        for (size_t k = 0; k < remap.size(); ++k) {
-            const std::vector<uint8_t> &key = p.tables.keys[k];
-            remap[k] = tables.intern(key.data(), key.data() + 16, (int)key.size() - 16);
-        }
+        p.scan_base = (uint32_t)b.scans.size();
+        b.scans.insert(b.scans.end(), p.scans.begin(), p.scans.end());
+        for (const std::vector<uint8_t> &key : p.tables.keys) p.remap.push_back(b.tables.intern(key.data(), key.data() + 16, (int)key.size() - 16));
     }
     // The 64 lanes of a wave step through their images block by block and finish together at best: neighbours in the device
     // order should be images of like geometry and like compressed size (like amounts of work per block).  The order is a sort
     // of (key, file) pairs; the records themselves are gathered afterwards.
-    struct Key { uint64_t a, b; uint32_t i; };
-    std::vector<Key> order;
-    order.reserve((size_t)n);
-    const bool keep_order = std::getenv("KE_JPEG_KEEP_ORDER") != nullptr;
+    using Key = JpegBatch::Key;
+    b.order.reserve((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         const KeJpegDev &d = all[(size_t)i];
         if (d.info.status != KE_JPEG_OK) continue;
         const KeJpegInfo &in = d.info;
         const uint64_t work = (uint64_t)in.mcus_x * in.mcus_y * in.ncomp, bytes = (d.end_on_device ? d.file_size : in.scan_end) - in.scan_offset;
-        order.push_back(keep_order ? Key{0, 0, (uint32_t)i} : Key{((uint64_t)(in.progressive ? 1 : 0) << 63) | (~work & 0x7FFFFFFFFFFFFFFFull), ~bytes, (uint32_t)i});
+        b.order.push_back(sw.keep_order ? Key{0, 0, (uint32_t)i} : Key{((uint64_t)(in.progressive ? 1 : 0) << 63) | (~work & 0x7FFFFFFFFFFFFFFFull), ~bytes, (uint32_t)i});
     }
-    if (order.empty()) return KE_OK;                           // (the guard waits: the caller's buffer is still being read)
-    if (!keep_order)
-        std::sort(order.begin(), order.end(), [](const Key &x, const Key &y) { return x.a != y.a ? x.a < y.a : x.b != y.b ? x.b < y.b : x.i < y.i; });
-    lap("merge tables + order");
-    const int64_t total = (int64_t)order.size();
-    const size_t meta_bytes = (size_t)total * sizeof(KeJpegDev) + (size_t)total * 4 + 64 + (split_on ? (size_t)total * 4 : 0);
-    if (ctx->h_meta_bytes < meta_bytes) {
-        if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
-        ctx->h_meta = nullptr;
-        ctx->h_meta_bytes = 0;
-        KE_HIP(ctx, hipHostMalloc(&ctx->h_meta, meta_bytes + meta_bytes / 4, hipHostMallocDefault));
-        ctx->h_meta_bytes = meta_bytes + meta_bytes / 4;
-    }
-    KeJpegDev *devs = (KeJpegDev *)ctx->h_meta;                          // page-locked, device order
-    int32_t *h_st = (int32_t *)((uint8_t *)ctx->h_meta + (size_t)total * sizeof(KeJpegDev));
-    int32_t *h_split = h_st + total;                                     // (split_on only) the split flags, read back with the statuses
+    if (b.order.empty()) return KE_OK;
+    if (!sw.keep_order)
+        std::sort(b.order.begin(), b.order.end(), [](const Key &x, const Key &y) { return x.a != y.a ? x.a < y.a : x.b != y.b ? x.b < y.b : x.i < y.i; });
+    sw.lap("merge tables + order");
+    const int64_t total = (int64_t)b.order.size();
+    KE_TRY(jpeg_page_locked_records(ctx, (size_t)total, &b.devs));
     auto part_index = [&](int64_t i) { int t = 0; while (t + 1 < nparts && i >= parts[(size_t)t].last) ++t; return t; };
     ke_parallel_ranges(total, [&](int64_t first, int64_t last, int) {
         for (int64_t k = first; k < last; ++k) {
-            const int64_t i = order[(size_t)k].i;
-            KeJpegDev &d = devs[k];
+            const int64_t i = b.order[(size_t)k].i;
+            KeJpegDev &d = b.devs[k];
             d = all[(size_t)i];
-            const int t = part_index(i);
+            const Part &p = parts[(size_t)part_index(i)];
             if (d.info.progressive) {
-                d.info.first_scan += scan_base[(size_t)t];
+                d.info.first_scan += p.scan_base;
             } else {
                 for (int c = 0; c < d.info.ncomp; ++c) {
-                    d.info.huff_dc[c] = remaps[(size_t)t][(size_t)d.info.huff_dc[c]];
-                    d.info.huff_ac[c] = remaps[(size_t)t][(size_t)d.info.huff_ac[c]];
+                    d.info.huff_dc[c] = p.remap[(size_t)d.info.huff_dc[c]];
+                    d.info.huff_ac[c] = p.remap[(size_t)d.info.huff_ac[c]];
                 }
             }
         }
     });
-    all.reset();
     if (denoms) {
-        geo.resize((size_t)total);
-        for (int64_t k = 0; k < total; ++k) ke_jpeg_scaled_geometry(devs[k].info, denoms[order[(size_t)k].i], geo[(size_t)k]);
+        b.geo.resize((size_t)total);
+        for (int64_t k = 0; k < total; ++k) ke_jpeg_scaled_geometry(b.devs[k].info, denoms[b.order[(size_t)k].i], b.geo[(size_t)k]);
     }
-    lap("records into device order");
-    void *d_tables;
-    KE_TRY(ke_reserve(ctx, KE_BUF_JPEG_TABLES, tables.pool.size() * sizeof(KeHuffTable), &d_tables));
-    KE_HIP(ctx, hipMemcpyAsync(d_tables, tables.pool.data(), tables.pool.size() * sizeof(KeHuffTable), hipMemcpyHostToDevice, ctx->stream));
-    void *d_scans = nullptr;
-    if (!scans.empty()) {
-        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, scans.size() * sizeof(KeJpegScan), &d_scans));
-        KE_HIP(ctx, hipMemcpyAsync(d_scans, scans.data(), scans.size() * sizeof(KeJpegScan), hipMemcpyHostToDevice, ctx->stream));
+    sw.lap("records into device order");
+    return KE_OK;
+}
+
+// A sub-batch: what take lays out, and what launch reserves and works off.  Copies are queued from prog_list and rst_files.
+struct JpegSubBatch {
+    size_t first = 0;                  // its first image in the device order
+    uint64_t coef_units = 0, plane_bytes = 0;
+    int max_blocks = 0, max_w = 0, max_h = 0, progressive = 0;
+    std::vector<int32_t> prog_list;    // its progressive files
+    std::vector<KeRstFile> rst_files;  // the files whose restart intervals go to lanes of their own, and the lanes of them all
+    uint64_t rst_lanes = 0;
+    void *d_imgs = nullptr, *d_coef = nullptr, *d_planes = nullptr;
+    int32_t *d_status = nullptr, *d_split = nullptr;     // KE_BUF_OUT0: m status words; behind them m split flags where files are split
+    KeRstFile *d_rfiles = nullptr;                       // KE_BUF_TILE32: [records | marker table]
+    uint32_t *d_marks = nullptr;
+};
+
+// Image k's record laid out in the sub-batch's scratch: coefficients (2 B per sample) + planes (1 B per sample).  One thread
+// per image: the larger the sub-batch the better the chip is filled (65 536 images are one wave per SIMD).
+static bool jpeg_take(JpegBatch &b, JpegSubBatch &sub, uint64_t lo, uint64_t budget, size_t k, bool fresh) {
+    if (fresh) {
+        sub.first = k;
+        sub.coef_units = sub.plane_bytes = 0;
+        sub.max_blocks = sub.max_w = sub.max_h = sub.progressive = 0;
     }
-    // sub-batches bounded by scratch: coefficients (2 B per sample) + planes (1 B per sample)
-    // one thread per image: the larger the sub-batch the better the chip is filled (65 536 images are one wave per SIMD) -- the
+    KeJpegDev &d = b.devs[k];
+    // the image index is a pair of grid dimensions (65 535 x 65 535).  Progressive files: at most two waves of them per CU in one
+    // launch (measured: a third wave per CU slows all three by more than it adds -- 65 536 files 458 ms in one launch, 417 in two)
+    if (k - sub.first >= (1u << 20) || (d.info.progressive && sub.progressive >= 32768)) return false;
+    uint64_t blocks = 0, pl = 0;
+    for (int c = 0; c < d.info.ncomp; ++c) {
+        blocks += (uint64_t)(d.info.plane_w[c] >> 3) * (d.info.plane_h[c] >> 3);
+        pl += (uint64_t)d.info.plane_w[c] * d.info.plane_h[c];
+    }
+    if (!fresh && (sub.coef_units + blocks * 64) * 2 + sub.plane_bytes + pl > budget) return false;
+    sub.progressive += d.info.progressive ? 1 : 0;
+    d.file_off -= lo;
+    d.coef_off = sub.coef_units;
+    uint64_t at = 0;
+    for (int c = 0; c < 3; ++c) {
+        d.block_base[c] = (int32_t)at;
+        d.plane_off[c] = sub.plane_bytes;
+        if (c < d.info.ncomp) {
+            at += (uint64_t)(d.info.plane_w[c] >> 3) * (d.info.plane_h[c] >> 3);
+            sub.plane_bytes += ((uint64_t)d.info.plane_w[c] * d.info.plane_h[c] + 15) & ~15ull;
+        }
+    }
+    d.blocks_total = (int32_t)blocks;
+    sub.coef_units += blocks * 64;
+    sub.max_blocks = std::max(sub.max_blocks, (int)blocks);
+    sub.max_w = std::max(sub.max_w, b.geo.empty() ? d.info.width : b.geo[k].out_w);
+    sub.max_h = std::max(sub.max_h, b.geo.empty() ? d.info.height : b.geo[k].out_h);
+    return true;
+}
+
+// The restart-lane plan of a sub-batch: the files whose plan has two lanes or more, with the prefix of their lanes.
+static uint64_t jpeg_restart_lanes(const KeJpegDev *devs, int64_t m, uint32_t min_mcus, std::vector<KeRstFile> &rst_files) {
+    uint64_t rst_lanes = 0;
+    for (int64_t k = 0; k < m; ++k) {
+        const KeJpegInfo &in = devs[k].info;
+        if (in.progressive || in.restart_interval <= 0) continue;
+        const KeRstPlan plan = ke_rst_plan((uint32_t)in.mcus_x * (uint32_t)in.mcus_y, (uint32_t)in.restart_interval, min_mcus, KE_RST_LANE_CAP);
+        if (!ke_rst_plan_splits(plan) || rst_lanes + plan.n_lanes > (1ull << 31)) continue;     // (lane indices stay below 2^31)
+        rst_files.push_back(KeRstFile{(uint32_t)k, (uint32_t)rst_lanes, plan});
+        rst_lanes += plan.n_lanes;
+    }
+    return rst_lanes;
+}
+
+// images per wave: 64 once that makes two waves for every SIMD, fewer (down to 8) below that (measured: 65 536 files 90.1 ms
+// at 64 per wave, 86.4 at 32, 103 at 16; 16 384 files 38.3 at 16, 34.5 at 8)
+static int jpeg_lanes_for(int64_t images, int64_t waves_wanted) {
+    int lanes = 64;
+    while (lanes > 8 && (images + lanes / 2 - 1) / (lanes / 2) <= waves_wanted) lanes /= 2;
+    return lanes;
+}
+
+// The entropy stage of a sub-batch of m images (devs: its records on the host): the ends of the entropy-coded segments, the
+// restart markers of the files to split, the one-lane walk, the restart lanes, the progressive files.
+static int jpeg_enqueue_entropy(ke_ctx *ctx, JpegSwitches &sw, const JpegBatch &b, JpegSubBatch &s, const KeJpegDev *devs, int64_t m) {
+    const KeJpegDev *d_imgs = (const KeJpegDev *)s.d_imgs;
+    const uint8_t *d_files = (const uint8_t *)b.d_files;
+    const int64_t nrf = (int64_t)s.rst_files.size(), rst_lanes = (int64_t)s.rst_lanes, waves = (int64_t)ctx->cu_count * 8;
+    hipLaunchKernelGGL(ke_jpeg_find_end, dim3((unsigned)m), dim3(64), 0, ctx->stream, (KeJpegDev *)s.d_imgs, m, d_files, s.d_status);
+    if (nrf) {
+        KE_HIP(ctx, hipMemcpyAsync(s.d_rfiles, s.rst_files.data(), (size_t)nrf * sizeof(KeRstFile), hipMemcpyHostToDevice, ctx->stream));
+        KE_HIP(ctx, hipMemsetAsync(s.d_split, 0, (size_t)m * 4, ctx->stream));
+        hipLaunchKernelGGL(ke_jpeg_find_restarts, dim3((unsigned)nrf), dim3(64), 0, ctx->stream, (KeJpegDev *)s.d_imgs, (const KeRstFile *)s.d_rfiles, nrf,
+                           d_files, (const int32_t *)s.d_status, s.d_marks, s.d_split);
+        sw.lap("find restarts (enqueue)");
+    }
+    // sequential files: no clearing of the coefficient array, every block of an image that decodes is written whole (a
+    // damaged image's remaining blocks hold whatever was there, and its pixels are discarded with its status);
+    // progressive files build their coefficients up scan by scan, from zero
+    s.prog_list.clear();
+    for (int64_t k = 0; k < m; ++k)
+        if (devs[k].info.progressive) s.prog_list.push_back((int32_t)k);
+    const int64_t np = (int64_t)s.prog_list.size();
+    if (np < m) {
+        const int lanes = jpeg_lanes_for(m, waves);
+        hipLaunchKernelGGL(ke_jpeg_entropy, dim3((unsigned)((m + lanes - 1) / lanes)), dim3(64), 0, ctx->stream, d_imgs, m, d_files,
+                           (const KeHuffTable *)b.d_tables, (int16_t *)s.d_coef, s.d_status, lanes);
+    }
+    if (nrf) {
+        const int lanes = jpeg_lanes_for(rst_lanes, waves);
+        hipLaunchKernelGGL(ke_jpeg_entropy_rst, dim3((unsigned)((rst_lanes + lanes - 1) / lanes)), dim3(64), 0, ctx->stream, d_imgs,
+                           (const KeRstFile *)s.d_rfiles, nrf, rst_lanes, d_files, (const KeHuffTable *)b.d_tables, (int16_t *)s.d_coef, s.d_status, lanes,
+                           (const uint32_t *)s.d_marks, (const int32_t *)s.d_split);
+        sw.lap("restart lanes (enqueue)");
+    }
+    if (np) {
+        void *d_list;
+        KE_TRY(ke_reserve(ctx, KE_BUF_OUT1, (size_t)np * 4, &d_list));
+        KE_HIP(ctx, hipMemcpyAsync(d_list, s.prog_list.data(), (size_t)np * 4, hipMemcpyHostToDevice, ctx->stream));
+        for (size_t run0 = 0, run1; run0 < (size_t)np; run0 = run1 + 1) {      // their coefficients to zero, one memset per run of neighbours in the batch
+            for (run1 = run0; run1 + 1 < (size_t)np && s.prog_list[run1 + 1] == s.prog_list[run1] + 1;) ++run1;
+            const KeJpegDev &from = devs[s.prog_list[run0]], &to = devs[s.prog_list[run1]];
+            const uint64_t units = to.coef_off + (uint64_t)to.blocks_total * 64 - from.coef_off;
+            KE_HIP(ctx, hipMemsetAsync((int16_t *)s.d_coef + from.coef_off, 0, (size_t)units * 2, ctx->stream));
+        }
+        const int lanes = jpeg_lanes_for(np, (int64_t)ctx->cu_count * 2);      // two waves of these per CU (see jpeg_take)
+        hipLaunchKernelGGL(ke_jpeg_entropy_prog, dim3((unsigned)((np + lanes - 1) / lanes)), dim3(64), 0, ctx->stream, d_imgs, (const int32_t *)d_list, np,
+                           d_files, (const KeJpegScan *)b.d_scans, (int16_t *)s.d_coef, s.d_status, lanes);
+    }
+    return KE_OK;
+}
+
+// The pixel stage: IDCT into the planes, then upsampling and colour into the caller's buffer -- at the files' own sizes, or
+// (geo: the sub-batch's reduced geometry) at the scaled ones.
+static int jpeg_enqueue_pixels(ke_ctx *ctx, const JpegSubBatch &s, int64_t m, const KeJpegScaled *geo, uint8_t *pixels_out) {
+    const KeJpegDev *d_imgs = (const KeJpegDev *)s.d_imgs;
+    const dim3 idct((unsigned)((s.max_blocks + 255) / 256), (unsigned)std::min<int64_t>(m, 65535), (unsigned)((m + 65534) / 65535));
+    const int xblocks = (s.max_w + 255) / 256, yblocks = (s.max_h + kColourRows - 1) / kColourRows;
+    const dim3 colour((unsigned)(xblocks * yblocks), idct.y, idct.z);
+    if (!geo) {
+        hipLaunchKernelGGL(ke_jpeg_idct, idct, dim3(256), 0, ctx->stream, d_imgs, m, (const int16_t *)s.d_coef, (uint8_t *)s.d_planes, s.d_status);
+        hipLaunchKernelGGL(ke_jpeg_colour, colour, dim3(256), 0, ctx->stream, d_imgs, m, xblocks, (const uint8_t *)s.d_planes, pixels_out);
+        return KE_OK;
+    }
+    void *d_geo;
+    KE_TRY(ke_reserve(ctx, KE_BUF_OUT2, (size_t)m * sizeof(KeJpegScaled), &d_geo));
+    KE_HIP(ctx, hipMemcpyAsync(d_geo, geo, (size_t)m * sizeof(KeJpegScaled), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(ke_jpeg_idct_scaled, idct, dim3(256), 0, ctx->stream, d_imgs, (const KeJpegScaled *)d_geo, m, (const int16_t *)s.d_coef,
+                       (uint8_t *)s.d_planes, s.d_status);
+    hipLaunchKernelGGL(ke_jpeg_colour_scaled, colour, dim3(256), 0, ctx->stream, d_imgs, (const KeJpegScaled *)d_geo, m, xblocks,
+                       (const uint8_t *)s.d_planes, pixels_out);
+    return KE_OK;
+}
+
+// The sub-batch that take packed: its plan, the reserves, the records' copy and the two stages.  Names m status words, or 2 m
+// with the split flags behind them.  No file with a plan of two lanes or more: nothing new is reserved or launched.
+static int jpeg_launch(ke_ctx *ctx, JpegSwitches &sw, const JpegBatch &b, JpegSubBatch &s, int64_t m, uint8_t *pixels_out, const int32_t **status,
+                       size_t *words) {
+    const KeJpegDev *devs = b.devs + s.first;
+    s.rst_files.clear();
+    s.rst_lanes = sw.split ? jpeg_restart_lanes(devs, m, sw.split_min_mcus, s.rst_files) : 0;
+    const bool split = !s.rst_files.empty();
+    KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)m * sizeof(KeJpegDev), &s.d_imgs));
+    KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)s.coef_units * 2 + 64, &s.d_coef));
+    KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)s.plane_bytes + 64, &s.d_planes));
+    KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)m * (split ? 8 : 4), (void **)&s.d_status));
+    s.d_split = split ? s.d_status + m : nullptr;
+    if (split) {
+        const size_t rec_bytes = (s.rst_files.size() * sizeof(KeRstFile) + 15) & ~(size_t)15;
+        KE_TRY(ke_reserve(ctx, KE_BUF_TILE32, rec_bytes + (size_t)s.rst_lanes * 4, (void **)&s.d_rfiles));
+        s.d_marks = (uint32_t *)((uint8_t *)s.d_rfiles + rec_bytes);
+    }
+    sw.lap("layout + reserve");
+    KE_HIP(ctx, hipMemcpyAsync(s.d_imgs, devs, (size_t)m * sizeof(KeJpegDev), hipMemcpyHostToDevice, ctx->stream));
+    KE_TRY(jpeg_enqueue_entropy(ctx, sw, b, s, devs, m));
+    KE_TRY(jpeg_enqueue_pixels(ctx, s, m, b.geo.empty() ? nullptr : b.geo.data() + s.first, pixels_out));
+    *status = s.d_status;
+    *words = (size_t)m * (split ? 2 : 1);
+    sw.lap("enqueue");
+    return KE_OK;
+}
+
+// The decode call.  denoms = NULL: ke_jpeg_decode, exactly as before.  Otherwise file i is decoded at 1 / denoms[i]
+// (ke_jpeg_decode_scaled): the same parse, order, entropy kernels and scratch, the IDCT and colour kernels of the reduced sizes.
+static int jpeg_decode_batch(ke_ctx *ctx, const uint8_t *files, const uint64_t *offsets, const uint64_t *sizes, int64_t n,
+                             const int32_t *denoms, uint8_t *pixels_out, const uint64_t *out_offsets, int32_t *status_out) {
+    KE_TRY(ke_decode_check_args(ctx, files, offsets, sizes, n, pixels_out, out_offsets, status_out, "compressed files are parsed"));
+    ctx->jpeg_files_split = ctx->jpeg_split_lanes = 0;
+    if (n == 0) return KE_OK;
+    JpegSwitches sw;
+    // the compressed bytes set off for the device before anything is parsed: one contiguous range of the caller's buffer (the
+    // files the decoder will turn down travel along -- they are the few), 17 ms for the 970 MB of 65 536 files, hidden behind
+    // the parsing
+    uint64_t lo = ~0ull, hi = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (sizes[i]) { lo = std::min(lo, offsets[i]); hi = std::max(hi, offsets[i] + sizes[i]); }
+    if (hi <= lo) {
+        for (int64_t i = 0; i < n; ++i) status_out[i] = KE_JPEG_CORRUPT;
+        return KE_OK;
+    }
+    JpegBatch batch;
+    JpegSubBatch sub;
+    KeStreamGuard guard;                                          // after the host vectors it waits for
+    KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &batch.d_files));   // the stream windows read up to 64 bytes past a file
+    KE_TRY(jpeg_prepare(ctx, sw, files, offsets, sizes, n, denoms, out_offsets, status_out, batch));
+    if (batch.order.empty()) return KE_OK;                     // (the guard waits: the caller's buffer is still being read)
+    KE_TRY(ke_reserve(ctx, KE_BUF_JPEG_TABLES, batch.tables.pool.size() * sizeof(KeHuffTable), &batch.d_tables));
+    KE_HIP(ctx, hipMemcpyAsync(batch.d_tables, batch.tables.pool.data(), batch.tables.pool.size() * sizeof(KeHuffTable), hipMemcpyHostToDevice, ctx->stream));
+    if (!batch.scans.empty()) {
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, batch.scans.size() * sizeof(KeJpegScan), &batch.d_scans));
+        KE_HIP(ctx, hipMemcpyAsync(batch.d_scans, batch.scans.data(), batch.scans.size() * sizeof(KeJpegScan), hipMemcpyHostToDevice, ctx->stream));
+    }
     // half of what this context's scratch and the free HBM come to together (a sum that does not move when the scratch is
     // regrown, so that consecutive calls cut their batches alike and keep their buffers), up to 160 GB
     uint64_t budget;
-    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_TMP, KE_BUF_SSIM_IN}, (uint64_t)2 << 30, (uint64_t)160 << 30, nullptr, KE_BUDGET_ENV_LOWERS, &budget));
-    int64_t first = 0;
-    ke_time_begin(ctx, KE_T_JPEG);
-    while (first < total) {
-        uint64_t coef_units = 0, plane_bytes = 0;
-        int64_t last = first;
-        int max_blocks = 0, max_w = 0, max_h = 0;
-        int64_t progressive_here = 0;
-        while (last < total && last - first < (1 << 20)) {       // (the image index is a pair of grid dimensions: 65 535 x 65 535)
-            KeJpegDev &d = devs[last];
-            // progressive files: at most two waves of them per CU in one launch (measured: a third wave per CU slows all three
-            // by more than it adds -- 65 536 files 458 ms in one launch, 417 in two)
-            if (d.info.progressive && ++progressive_here > 32768) break;
-            uint64_t blocks = 0, pl = 0;
-            for (int c = 0; c < d.info.ncomp; ++c) {
-                blocks += (uint64_t)(d.info.plane_w[c] >> 3) * (d.info.plane_h[c] >> 3);
-                pl += (uint64_t)d.info.plane_w[c] * d.info.plane_h[c];
-            }
-            if (last > first && (coef_units + blocks * 64) * 2 + plane_bytes + pl > budget) break;
-            d.file_off -= lo;
-            d.coef_off = coef_units;
-            uint64_t b = 0;
-            for (int c = 0; c < 3; ++c) {
-                d.block_base[c] = (int32_t)b;
-                d.plane_off[c] = plane_bytes;
-                if (c < d.info.ncomp) {
-                    b += (uint64_t)(d.info.plane_w[c] >> 3) * (d.info.plane_h[c] >> 3);
-                    plane_bytes += ((uint64_t)d.info.plane_w[c] * d.info.plane_h[c] + 15) & ~15ull;
-                }
-            }
-            d.blocks_total = (int32_t)blocks;
-            coef_units += blocks * 64;
-            max_blocks = std::max(max_blocks, (int)blocks);
-            max_w = std::max(max_w, denoms ? geo[(size_t)last].out_w : d.info.width);
-            max_h = std::max(max_h, denoms ? geo[(size_t)last].out_h : d.info.height);
-            ++last;
-        }
-        const int64_t m = last - first;
-        void *d_imgs, *d_coef, *d_planes, *d_status;
-        KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)m * sizeof(KeJpegDev), &d_imgs));
-        KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)coef_units * 2 + 64, &d_coef));
-        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)plane_bytes + 64, &d_planes));
-        KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)m * 4, &d_status));
-        // the files whose plan has two lanes or more, and the prefix of their lanes; none: nothing new is reserved or launched
-        rst_files.clear();
-        uint64_t rst_lanes = 0;
-        if (split_on)
-            for (int64_t k = 0; k < m; ++k) {
-                const KeJpegInfo &in = devs[first + k].info;
-                if (in.progressive || in.restart_interval <= 0) continue;
-                const KeRstPlan plan = ke_rst_plan((uint32_t)in.mcus_x * (uint32_t)in.mcus_y, (uint32_t)in.restart_interval, split_min_mcus, KE_RST_LANE_CAP);
-                if (!ke_rst_plan_splits(plan) || rst_lanes + plan.n_lanes > (1ull << 31)) continue;     // (lane indices stay below 2^31)
-                rst_files.push_back(KeRstFile{(uint32_t)k, (uint32_t)rst_lanes, plan});
-                rst_lanes += plan.n_lanes;
-            }
-        KeRstFile *d_rfiles = nullptr;
-        uint32_t *d_marks = nullptr;
-        int32_t *d_split = nullptr;
-        if (!rst_files.empty()) {                                        // one buffer: [records | marker table | split flags]
-            const size_t rec_bytes = (rst_files.size() * sizeof(KeRstFile) + 15) & ~(size_t)15;
-            void *d_rst;
-            KE_TRY(ke_reserve(ctx, KE_BUF_TILE32, rec_bytes + (size_t)rst_lanes * 4 + (size_t)m * 4, &d_rst));
-            d_rfiles = (KeRstFile *)d_rst;
-            d_marks = (uint32_t *)((uint8_t *)d_rst + rec_bytes);
-            d_split = (int32_t *)(d_marks + rst_lanes);
-        }
-        lap("layout + reserve");
-        KE_HIP(ctx, hipMemcpyAsync(d_imgs, devs + first, (size_t)m * sizeof(KeJpegDev), hipMemcpyHostToDevice, ctx->stream));
-        // sequential files: no clearing of the coefficient array, every block of an image that decodes is written whole (a
-        // damaged image's remaining blocks hold whatever was there, and its pixels are discarded with its status);
-        // progressive files build their coefficients up scan by scan, from zero
-        prog_list.clear();
-        for (int64_t k = 0; k < m; ++k)
-            if (devs[first + k].info.progressive) prog_list.push_back((int32_t)k);
-        // images per wave: 64 once that makes two waves for every SIMD, fewer (down to 8) below that (measured: 65 536 files
-        // 90.1 ms at 64 per wave, 86.4 at 32, 103 at 16; 16 384 files 38.3 at 16, 34.5 at 8)
-        auto lanes_for = [&](int64_t images, int64_t waves_wanted) {
-            int lanes = 64;
-            while (lanes > 8 && (images + lanes / 2 - 1) / (lanes / 2) <= waves_wanted) lanes /= 2;
-            return lanes;
-        };
-        hipLaunchKernelGGL(ke_jpeg_find_end, dim3((unsigned)m), dim3(64), 0, ctx->stream, (KeJpegDev *)d_imgs, m, (const uint8_t *)d_files,
-                           (int32_t *)d_status);
-        if (!rst_files.empty()) {
-            KE_HIP(ctx, hipMemcpyAsync(d_rfiles, rst_files.data(), rst_files.size() * sizeof(KeRstFile), hipMemcpyHostToDevice, ctx->stream));
-            KE_HIP(ctx, hipMemsetAsync(d_split, 0, (size_t)m * 4, ctx->stream));
-            hipLaunchKernelGGL(ke_jpeg_find_restarts, dim3((unsigned)rst_files.size()), dim3(64), 0, ctx->stream, (KeJpegDev *)d_imgs,
-                               (const KeRstFile *)d_rfiles, (int64_t)rst_files.size(), (const uint8_t *)d_files, (const int32_t *)d_status, d_marks,
-                               d_split);
-            lap("find restarts (enqueue)");
-        }
-        if ((int64_t)prog_list.size() < m) {
-            const int lanes = lanes_for(m, (int64_t)ctx->cu_count * 8);
-            hipLaunchKernelGGL(ke_jpeg_entropy, dim3((unsigned)((m + lanes - 1) / lanes)), dim3(64), 0, ctx->stream, (const KeJpegDev *)d_imgs, m,
-                               (const uint8_t *)d_files, (const KeHuffTable *)d_tables, (int16_t *)d_coef, (int32_t *)d_status, lanes);
-        }
-        if (!rst_files.empty()) {
-            const int lanes = lanes_for((int64_t)rst_lanes, (int64_t)ctx->cu_count * 8);
-            hipLaunchKernelGGL(ke_jpeg_entropy_rst, dim3((unsigned)((rst_lanes + lanes - 1) / lanes)), dim3(64), 0, ctx->stream,
-                               (const KeJpegDev *)d_imgs, (const KeRstFile *)d_rfiles, (int64_t)rst_files.size(), (int64_t)rst_lanes,
-                               (const uint8_t *)d_files, (const KeHuffTable *)d_tables, (int16_t *)d_coef, (int32_t *)d_status, lanes,
-                               (const uint32_t *)d_marks, (const int32_t *)d_split);
-            lap("restart lanes (enqueue)");
-        }
-        if (!prog_list.empty()) {
-            void *d_list;
-            KE_TRY(ke_reserve(ctx, KE_BUF_OUT1, prog_list.size() * 4, &d_list));
-            KE_HIP(ctx, hipMemcpyAsync(d_list, prog_list.data(), prog_list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            size_t run0 = 0;                           // their coefficients to zero, one memset per run of neighbours in the batch
-            while (run0 < prog_list.size()) {
-                size_t run1 = run0;
-                while (run1 + 1 < prog_list.size() && prog_list[run1 + 1] == prog_list[run1] + 1) ++run1;
-                const KeJpegDev &a = devs[first + prog_list[run0]], &b = devs[first + prog_list[run1]];
-                const uint64_t from = a.coef_off, to = b.coef_off + (uint64_t)b.blocks_total * 64;
-                KE_HIP(ctx, hipMemsetAsync((int16_t *)d_coef + from, 0, (size_t)(to - from) * 2, ctx->stream));
-                run0 = run1 + 1;
-            }
-            const int64_t np = (int64_t)prog_list.size();
-            const int lanes = lanes_for(np, (int64_t)ctx->cu_count * 2);      // two waves of these per CU (see above)
-            hipLaunchKernelGGL(ke_jpeg_entropy_prog, dim3((unsigned)((np + lanes - 1) / lanes)), dim3(64), 0, ctx->stream, (const KeJpegDev *)d_imgs,
-                               (const int32_t *)d_list, np, (const uint8_t *)d_files, (const KeJpegScan *)d_scans, (int16_t *)d_coef,
-                               (int32_t *)d_status, lanes);
-        }
-        const unsigned gy = (unsigned)std::min<int64_t>(m, 65535), gz = (unsigned)((m + 65534) / 65535);
-        const int xblocks = (max_w + 255) / 256, yblocks = (max_h + kColourRows - 1) / kColourRows;
-        if (!denoms) {
-            hipLaunchKernelGGL(ke_jpeg_idct, dim3((unsigned)((max_blocks + 255) / 256), gy, gz), dim3(256), 0, ctx->stream,
-                               (const KeJpegDev *)d_imgs, m, (const int16_t *)d_coef, (uint8_t *)d_planes, (int32_t *)d_status);
-            hipLaunchKernelGGL(ke_jpeg_colour, dim3((unsigned)(xblocks * yblocks), gy, gz), dim3(256), 0, ctx->stream,
-                               (const KeJpegDev *)d_imgs, m, xblocks, (const uint8_t *)d_planes, pixels_out);
-        } else {
-            void *d_geo;
-            KE_TRY(ke_reserve(ctx, KE_BUF_OUT2, (size_t)m * sizeof(KeJpegScaled), &d_geo));
-            KE_HIP(ctx, hipMemcpyAsync(d_geo, geo.data() + first, (size_t)m * sizeof(KeJpegScaled), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(ke_jpeg_idct_scaled, dim3((unsigned)((max_blocks + 255) / 256), gy, gz), dim3(256), 0, ctx->stream,
-                               (const KeJpegDev *)d_imgs, (const KeJpegScaled *)d_geo, m, (const int16_t *)d_coef, (uint8_t *)d_planes,
-                               (int32_t *)d_status);
-            hipLaunchKernelGGL(ke_jpeg_colour_scaled, dim3((unsigned)(xblocks * yblocks), gy, gz), dim3(256), 0, ctx->stream,
-                               (const KeJpegDev *)d_imgs, (const KeJpegScaled *)d_geo, m, xblocks, (const uint8_t *)d_planes, pixels_out);
-        }
-        KE_HIP(ctx, hipGetLastError());
-        KE_HIP(ctx, hipMemcpyAsync(h_st + first, d_status, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (!rst_files.empty()) KE_HIP(ctx, hipMemcpyAsync(h_split + first, d_split, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        lap("enqueue");
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // prog_list is a host vector; the scratch is reused
-        lap("wait for the stream");
-        for (int64_t k = 0; k < m; ++k) status_out[order[(size_t)(first + k)].i] = h_st[first + k];
-        for (const KeRstFile &rf : rst_files)
-            if (h_split[first + rf.img]) { ++ctx->jpeg_files_split; ctx->jpeg_split_lanes += rf.plan.n_lanes; }
-        first = last;
-    }
-    ke_time_end(ctx, KE_T_JPEG);
+    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_TMP, KE_BUF_SSIM_IN}, (uint64_t)2 << 30, (uint64_t)160 << 30, "KE_JPEG_SCRATCH_BYTES", KE_BUDGET_ENV_LOWERS, &budget));
+    KE_TRY(ke_decode_sub_batches(
+        ctx, batch.order.size(), [&](size_t k, bool fresh) { return jpeg_take(batch, sub, lo, budget, k, fresh); },
+        [&](size_t m, const int32_t **status, size_t *words) { return jpeg_launch(ctx, sw, batch, sub, (int64_t)m, pixels_out, status, words); },
+        [&](size_t at, size_t k, size_t m, const int32_t *st) {
+            if (k == 0) sw.lap("wait for the stream");
+            status_out[batch.order[at].i] = st[k];
+            if (k + 1 == m)                                    // the sub-batch's last: what of its plan the device took
+                for (const KeRstFile &rf : sub.rst_files)
+                    if (st[m + rf.img]) { ++ctx->jpeg_files_split; ctx->jpeg_split_lanes += rf.plan.n_lanes; }
+        }));
     guard.disarm();
     return KE_OK;
 }

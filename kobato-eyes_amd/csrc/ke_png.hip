@@ -441,47 +441,47 @@ KE_API int ke_png_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offs
     // the compressed files (one contiguous range of the caller's buffer) -> device
     std::vector<KePngDev> devs;
     std::vector<KePngPiece> pieces;
-    std::vector<int32_t> st;
     KeStreamGuard guard;                                           // after the host vectors it waits for
     void *d_files;
     KE_TRY(ke_upload_files(ctx, guard, files, lo, hi, KE_BUF_PIXELS, 256, &d_files));
     // sub-batches bounded by scratch (streams + filtered scanlines + copy records)
     uint64_t budget;
-    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_SSIM_IN, KE_BUF_TMP, KE_BUF_SSIM_AUX}, (uint64_t)2 << 30, (uint64_t)160 << 30, nullptr,
+    KE_TRY(ke_scratch_budget(ctx, {KE_BUF_SSIM_IN, KE_BUF_TMP, KE_BUF_SSIM_AUX}, (uint64_t)2 << 30, (uint64_t)160 << 30, "KE_PNG_SCRATCH_BYTES",
                              KE_BUDGET_ENV_LOWERS, &budget));
-    size_t first = 0;
-    ke_time_begin(ctx, KE_T_JPEG);
-    while (first < items.size()) {
-        uint64_t zbytes = 0, raw_bytes = 0, nrecs = 0;
-        int max_groups = 0;
-        size_t last = first;
-        devs.clear();
-        pieces.clear();
-        while (last < items.size()) {
-            Item &it = items[last];
-            const uint64_t zl = ((uint64_t)it.d.info.zlen + 15) & ~15ull;
-            const uint64_t want = it.d.info.raw_len;
-            const uint64_t rw = (want + 32 + 15) & ~15ull, rc = want / 3 + 2;      // a copy covers at least 3 bytes
-            if (last > first && zbytes + zl + raw_bytes + rw + (nrecs + rc) * 8 > budget) break;
-            it.d.info.zoff = 0;
-            it.d.z_off = zbytes;
-            it.d.raw_off = raw_bytes;
-            it.d.rec_off = nrecs;
-            nrecs += rc;
-            uint64_t at = zbytes;
-            for (size_t s = it.seg0; s < it.seg1; ++s)
-                for (uint32_t o = 0; o < segs[s].len; o += kPieceBytes) {
-                    const uint32_t len = std::min(kPieceBytes, segs[s].len - o);
-                    pieces.push_back(KePngPiece{segs[s].off - lo + o, at, len, 0});
-                    at += len;
-                }
-            zbytes += zl;
-            raw_bytes += rw;
-            max_groups = std::max(max_groups, (it.d.info.row_bytes / (it.d.info.mapped ? 1 : it.d.info.fbpp) + 3) >> 2);
-            devs.push_back(it.d);
-            ++last;
+    uint64_t zbytes = 0, raw_bytes = 0, nrecs = 0;
+    int max_groups = 0;
+    auto take = [&](size_t k, bool fresh) {
+        if (fresh) {
+            zbytes = raw_bytes = nrecs = 0;
+            max_groups = 0;
+            devs.clear();
+            pieces.clear();
         }
-        const int64_t m = (int64_t)devs.size();
+        Item &it = items[k];
+        const uint64_t zl = ((uint64_t)it.d.info.zlen + 15) & ~15ull;
+        const uint64_t want = it.d.info.raw_len;
+        const uint64_t rw = (want + 32 + 15) & ~15ull, rc = want / 3 + 2;      // a copy covers at least 3 bytes
+        if (!fresh && zbytes + zl + raw_bytes + rw + (nrecs + rc) * 8 > budget) return false;
+        it.d.info.zoff = 0;
+        it.d.z_off = zbytes;
+        it.d.raw_off = raw_bytes;
+        it.d.rec_off = nrecs;
+        nrecs += rc;
+        uint64_t at = zbytes;
+        for (size_t s = it.seg0; s < it.seg1; ++s)
+            for (uint32_t o = 0; o < segs[s].len; o += kPieceBytes) {
+                const uint32_t len = std::min(kPieceBytes, segs[s].len - o);
+                pieces.push_back(KePngPiece{segs[s].off - lo + o, at, len, 0});
+                at += len;
+            }
+        zbytes += zl;
+        raw_bytes += rw;
+        max_groups = std::max(max_groups, (it.d.info.row_bytes / (it.d.info.mapped ? 1 : it.d.info.fbpp) + 3) >> 2);
+        devs.push_back(it.d);
+        return true;
+    };
+    auto launch = [&](size_t count, const int32_t **status, size_t *words) {
+        const int64_t m = (int64_t)count;
         void *d_streams, *d_imgs, *d_pieces, *d_raw, *d_work, *d_status, *d_adler, *d_rec, *d_nrec;
         KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, (size_t)nrecs * 8, &d_rec));
         KE_TRY(ke_reserve(ctx, KE_BUF_TILE32, (size_t)m * 4, &d_nrec));
@@ -529,14 +529,12 @@ KE_API int ke_png_decode(ke_ctx *ctx, const uint8_t *files, const uint64_t *offs
         KE_UNFILTER_KINDS(15, true, true);
 #undef KE_UNFILTER_KINDS
 #undef KE_UNFILTER
-        KE_HIP(ctx, hipGetLastError());
-        st.resize((size_t)m);
-        KE_HIP(ctx, hipMemcpyAsync(st.data(), d_status, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // devs / pieces / st are host vectors; scratch is reused
-        for (int64_t k = 0; k < m; ++k) status_out[items[first + (size_t)k].which] = st[(size_t)k];
-        first = last;
-    }
-    ke_time_end(ctx, KE_T_JPEG);
+        *status = (const int32_t *)d_status;
+        *words = count;
+        return (int)KE_OK;
+    };
+    KE_TRY(ke_decode_sub_batches(ctx, items.size(), take, launch,
+                                 [&](size_t at, size_t k, size_t, const int32_t *st) { status_out[items[at].which] = st[k]; }));
     guard.disarm();
     return KE_OK;
 }
