@@ -125,6 +125,27 @@ int ke_hash_images_ex(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offset
                       const int32_t *heights, int32_t channels, int64_t n, uint64_t *phash_out,
                       uint64_t *dhash_out, int32_t *status_out, float *margin_out);
 
+/* ---- turned pHashes: the pHash of all eight orientations of an image, from its one 32x32 tile.  A capability of this
+ * library only: the reference has no such feature and no reference line is replaced.
+ * Orientation k in 0..7 of a 2-D array a (NumPy notation):
+ *     t = a.T if k & 4 else a;   if k & 1: t = t[:, ::-1] (mirror, left <-> right);   if k & 2: t = t[::-1] (flip, top <-> bottom)
+ * k = 0 identity, 1 mirror, 2 flip, 3 turn by 180 degrees, 4 transpose, 5 quarter turn clockwise, 6 quarter turn
+ * counter-clockwise, 7 transverse; 5 and 6 are each other's inverse, every other k is its own.
+ * Turned pHash k of an image is the reference's pHash arithmetic (src/sig/phash.py:38-45: DCT, the 8x8 corner, the float32
+ * mean of flat[1:], the bits) applied to orientation k of the image's 32x32 LANCZOS luma tile -- the tile
+ * ke_luma_tiles_uniform returns.  Column 0 is the image's pHash, bit for bit.  Columns 1..3 equal the pHash of the really
+ * turned image on the images measured (the resize passes commute with a flip); for k >= 4 the two resize passes swap
+ * order in the turned file, and its pHash lay at most 2 bits away.
+ *
+ * ke_tiles_turned       : tile32 = n tiles of 1024 bytes (host or device); turned_out = n * 8 hashes (host or device),
+ *                         turned_out[i * 8 + k].
+ * ke_hash_images_turned : the arguments of ke_hash_images with turned_out (n * 8, host or device) in place of the two
+ *                         hash outputs; grouped and dispatched by the same code, the tiles made by the same kernels.
+ *                         A failed image (status_out[i] != 0) has eight zeros. */
+int ke_tiles_turned(ke_ctx *ctx, const uint8_t *tile32, int64_t n, uint64_t *turned_out);
+int ke_hash_images_turned(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths,
+                          const int32_t *heights, int32_t channels, int64_t n, uint64_t *turned_out, int32_t *status_out);
+
 /* ---- pinned staging: the batch boundary of core.fastsig (src/core/fastsig.py:24-37, 65-99: decode in workers, hash,
  * collect in order) as a two-stage pipeline -- north-star step (1), "decodes batches of images to a pinned staging buffer".
  *
@@ -521,6 +542,24 @@ int ke_hamming_scan_from(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids
                          int64_t first_new, int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
                          int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
                          int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out);
+
+/* The same scan between a library and a table of queries, without comparing the queries with each other.  The table is
+ * [library | queries]: positions first_new .. n-1 are queries.  The edge set is exactly
+ * { e of ke_hamming_scan(same arguments) : e.a < first_new <= e.b }, each edge with the h and bands it has there --
+ * first_new * (n - first_new) pairs through a rectangle of the same tiles or the same buckets (KE_SCAN_MODE applies; auto
+ * uses the rule of ke_hamming_scan_from against the rectangle's pairs).  The reference has no such scan: this call
+ * replaces no reference line, it serves ke_hash_images_turned's eight hashes per file.
+ * What depends on the whole table stays whole-table: the bucket sizes bucket_pair_cap is held against and counters_out[3].
+ * counters_out: [0] pairs i < first_new <= j this shard stands for, counted per tile and checked against the host's closed
+ * form as above; over all shards first_new * (n - first_new).  [1], [2] over the emitted edges.  [3] as above.
+ * first_new = 0 or n gives no edge and counters_out[0] = 0; outside [0, n] is KE_EINVAL.  KE_EUNSUPPORTED where the tile
+ * kernel is the only path (KE_SCAN_MODE=tiles, bands wider than the bucket tables) and this shard's part of the rectangle
+ * has more than 8 388 607 tiles of 1024 x 1024, which one launch does not hold.
+ * part_index / part_count, capacity and *n_edges_out behave as above. */
+int ke_hamming_scan_cross(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
+                          int64_t first_new, int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
+                          int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
+                          int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out);
 
 /* The reference's "size=" funnel counter (src/dup/scanner.py:268-270 with _passes_size_ratio, :358-370): over every band
  * and band value whose bucket the reference walks (>= 2 members, under the pair cap), the member pairs that pass the size

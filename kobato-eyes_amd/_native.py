@@ -28,7 +28,7 @@ EXPORTS = (
     "ke_abi_version", "ke_create", "ke_create_error", "ke_destroy", "ke_last_error", "ke_set_stream",
     "ke_get_stream", "ke_synchronize", "ke_device_info", "ke_malloc", "ke_free", "ke_memcpy",
     "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan",
-    "ke_hamming_scan_from", "ke_band_pairs_after_size",
+    "ke_hamming_scan_from", "ke_hamming_scan_cross", "ke_tiles_turned", "ke_hash_images_turned", "ke_band_pairs_after_size",
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
@@ -144,6 +144,9 @@ def load_library() -> C.CDLL:
                                         C.POINTER(i64), vp]
         lib.ke_hamming_scan_from.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, dbl, i64, vp, i64,
                                              C.POINTER(i64), vp]
+        lib.ke_hamming_scan_cross.argtypes = lib.ke_hamming_scan_from.argtypes
+        lib.ke_tiles_turned.argtypes = [vp, vp, i64, vp]
+        lib.ke_hash_images_turned.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp]
         lib.ke_cluster_labels.argtypes = [vp, i64, i64, vp]
         lib.ke_ssim_pairs_uniform.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
         lib.ke_ssim_set_mode.argtypes = [vp, i32]
@@ -462,6 +465,33 @@ class Context:
             self._check(self._lib.ke_hash_images_ex(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n,
                                                     _addr(ph), _addr(dh), _addr(status), _addr(margin)), "ke_hash_images_ex")
         return (ph, dh, status, margin) if want_margin else (ph, dh, status)
+
+    def tiles_turned(self, tiles, n: Optional[int] = None):
+        """The eight turned pHashes (include/keyes.h, ke_tiles_turned) of n 32x32 uint8 tiles: u64[n, 8], column k =
+        the pHash arithmetic on orientation k of the tile.  ``tiles``: a host array or, with ``n``, a device pointer."""
+        if isinstance(tiles, np.ndarray):
+            tiles = np.ascontiguousarray(tiles, dtype=np.uint8)
+            if tiles.size % 1024:
+                raise ValueError("tiles must be 32 x 32 bytes each")
+            n = tiles.size // 1024
+        out = np.zeros((int(n), 8), np.uint64)
+        with self._lock:
+            self._check(self._lib.ke_tiles_turned(self._h, _addr(tiles), int(n), _addr(out)), "ke_tiles_turned")
+        return out
+
+    def hash_images_turned(self, images: Sequence[np.ndarray]):
+        """``hash_images`` with the eight turned pHashes in place of the two hashes: (turned u64[n, 8], status).  Column 0
+        is the image's pHash; a failed image has eight zeros."""
+        n = len(images)
+        if n == 0:
+            return np.empty((0, 8), np.uint64), np.empty(0, np.int32)
+        flat, offsets, widths, heights, ch = _pack_images(images)
+        turned = np.zeros((n, 8), np.uint64)
+        status = np.empty(n, np.int32)
+        with self._lock:
+            self._check(self._lib.ke_hash_images_turned(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n,
+                                                        _addr(turned), _addr(status)), "ke_hash_images_turned")
+        return turned, status
 
     # -- pinned staging ---------------------------------------------------------------------
     def stage_create(self, bytes_per_buffer: int, max_images: int, n_buffers: int = 2) -> None:
@@ -858,6 +888,16 @@ class Context:
         Returns (phash u64[n], dhash u64[n] | None, status int32[n]); status != 0 = not handled here (decode the file with
         Pillow).  The files come as bytes (``blobs``), as ``paths`` the library reads, or as ``ahead = (FilesAhead, lo, hi)``:
         files lo..hi of a batch read beforehand.  ``skip``: a mask of files to leave alone (status 1)."""
+        return self._hash_chain(blobs, want_dhash, kind, paths, ahead, skip, turned=False)
+
+    def hash_turned(self, blobs, *, kind: str, paths=None):
+        """``hash``'s chain with ke_hash_images_turned behind the decode: (turned u64[n, 8], status int32[n]); status != 0 =
+        not handled here, eight zeros."""
+        turned, _, st = self._hash_chain(blobs, False, kind, paths, None, None, turned=True)
+        return turned, st
+
+    def _hash_chain(self, blobs, want_dhash, kind, paths, ahead, skip, *, turned: bool):
+        shape = (0, 8) if turned else (0,)
         if ahead is not None:                            # where the files come from is settled here, once
             n = ahead[2] - ahead[1]
             take = lambda lo, hi: ahead[0].part(ahead[1] + lo, ahead[1] + hi)
@@ -868,24 +908,28 @@ class Context:
             n = len(blobs)
             take = lambda lo, hi: self._packed(blobs[lo:hi])
         if n == 0:
-            return np.zeros(0, np.uint64), (np.zeros(0, np.uint64) if want_dhash else None), np.zeros(0, np.int32)
+            return np.zeros(shape, np.uint64), (np.zeros(0, np.uint64) if want_dhash else None), np.zeros(0, np.int32)
         skip = None if skip is None else np.asarray(skip, bool)
 
         def run(lo: int, hi: int):
-            ph = np.zeros(hi - lo, np.uint64)
+            ph = np.zeros((hi - lo,) + shape[1:], np.uint64)
             dh = np.zeros(hi - lo, np.uint64) if want_dhash else None
             dev, out_off, w, h, c, st, _ = self._decode_packed(take(lo, hi), kind, skip=None if skip is None else skip[lo:hi])
             for ch in (1, 3, 4):
                 idx = np.nonzero((st == 0) & (c == ch))[0]
                 if len(idx) == 0:
                     continue
-                p = np.zeros(len(idx), np.uint64)
+                p = np.zeros((len(idx),) + shape[1:], np.uint64)
                 d = np.zeros(len(idx), np.uint64) if want_dhash else None
                 status = np.zeros(len(idx), np.int32)
                 offs = np.ascontiguousarray(out_off[idx])
                 ws, hs = np.ascontiguousarray(w[idx]), np.ascontiguousarray(h[idx])
-                self._check(self._lib.ke_hash_images(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p), _addr(d),
-                                                     _addr(status)), "ke_hash_images")
+                if turned:
+                    self._check(self._lib.ke_hash_images_turned(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p),
+                                                                _addr(status)), "ke_hash_images_turned")
+                else:
+                    self._check(self._lib.ke_hash_images(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p), _addr(d),
+                                                         _addr(status)), "ke_hash_images")
                 ph[idx] = p
                 if want_dhash:
                     dh[idx] = d
@@ -900,10 +944,16 @@ class Context:
     # -- scan -------------------------------------------------------------------------------
     def hamming_scan(self, hashes, n: int, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4,
                      size_ratio: float = 0.0, bucket_pair_cap: int = 0, part_index=0, part_count=1,
-                     capacity: Optional[int] = None, first_new: int = 0):
+                     capacity: Optional[int] = None, first_new: Optional[int] = None, cross: bool = False):
         """Returns (edges[EDGE_DTYPE] on the host, counters u64[4]).  hashes/ids/sizes: host arrays or device ptrs.
         first_new > 0: only the edges whose later position is at least first_new (ke_hamming_scan_from); counters[0] is
-        then the region's pair count, [1] and [2] are over those edges, [3] stays the whole table's."""
+        then the region's pair count, [1] and [2] are over those edges, [3] stays the whole table's.
+        cross=True (needs first_new): the table is [library | queries] and only the edges a < first_new <= b come back
+        (ke_hamming_scan_cross); counters[0] is first_new * (n - first_new) over the shards."""
+        if cross and first_new is None:
+            raise ValueError("cross=True needs first_new")
+        first_new = int(first_new or 0)
+
         def host(a, dt):
             return np.ascontiguousarray(a, dtype=dt) if isinstance(a, (np.ndarray, list, tuple)) else a
 
@@ -914,7 +964,12 @@ class Context:
         while True:
             edges = np.empty(cap, EDGE_DTYPE)
             with self._lock:
-                if first_new:
+                if cross:
+                    self._check(self._lib.ke_hamming_scan_cross(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, first_new,
+                                                                part_index, part_count, threshold, band_bits, band_count,
+                                                                float(size_ratio), int(bucket_pair_cap), _addr(edges), cap,
+                                                                C.byref(n_edges), _addr(counters)), "ke_hamming_scan_cross")
+                elif first_new:
                     self._check(self._lib.ke_hamming_scan_from(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, int(first_new),
                                                                part_index, part_count, threshold, band_bits, band_count,
                                                                float(size_ratio), int(bucket_pair_cap), _addr(edges), cap,

@@ -154,6 +154,42 @@ def find_new_duplicates(library: Iterable, added: Iterable, *, previous: Optiona
     return [c for c in clusters if any(e.file.file_id in new_ids for e in c.files)]
 
 
+def _turned_scan(files: Iterable, *, hamming_threshold, size_ratio, band_bits, band_count, device):
+    """find_turned_duplicates' work: (clusters, matches, the (id, id) keys of the plain candidate edges)."""
+    from . import turned as _turned
+    from .scanner import DuplicateEdge, assemble_clusters
+
+    candidates = [f for f in _parse_files(files) if f.phash is not None]
+    if len(candidates) < 2:
+        return [], [], set()
+    config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
+                                 band_count=band_count)
+    scanner = DuplicateScanner(config, device=device)
+    hashes, ok = _turned.turned_signatures([f.path for f in candidates], device=device)
+    plain = scanner.candidate_edges(candidates)
+    matches = scanner.turned_edges(candidates, hashes, ok)
+    edges = list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
+    return (assemble_clusters(candidates, edges) if edges else []), matches, set(plain)
+
+
+def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, band_bits: int = 16,
+                           band_count: int = 4, device: Optional[int] = None) -> tuple:
+    """(clusters, matches): near-duplicates including mirrored, flipped and rotated copies.
+
+    ``files``: as for ``find_duplicates``, each with a readable ``path``: the files are read and the pHashes of their
+    eight orientations made from the 32x32 tile the hash kernels form (``turned.turned_signatures``; nothing is stored).
+    ``matches``: the ``scanner.TurnedMatch`` list of ``DuplicateScanner.turned_edges`` -- file a, file b, the orientation
+    that turns b's picture into a's, the hamming distance.  ``clusters``: ``assemble_clusters`` over the plain candidate
+    edges of the stored hashes together with the matches as edges.  A file whose turned hashes could not be made (Pillow
+    cannot open it) takes part with its stored pHash only.
+
+    Out of scope here: an SSIM re-check of turned pairs (``ke_normalise_rgb`` could turn one member first: a follow-up),
+    persisting turned hashes, ``devices=[...]`` (one process, one GPU) and dHash."""
+    clusters, matches, _ = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
+                                        band_count=band_count, device=0 if device is None else int(device))
+    return clusters, matches
+
+
 def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None, config: Optional[DuplicateScanConfig] = None,
                        progress: Optional[Callable[[str, int, int], None]] = None,
                        cancel_fn: Optional[Callable[[], bool]] = None, device: Optional[int] = None,
@@ -194,4 +230,5 @@ def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None
     return DuplicateScanner(config or DuplicateScanConfig(), device=device).build_clusters(files)
 
 
-__all__ = ["DedupSettings", "compute_signature", "find_duplicates", "find_new_duplicates", "run_duplicate_scan", "ClusterBuilder"]
+__all__ = ["DedupSettings", "compute_signature", "find_duplicates", "find_new_duplicates", "find_turned_duplicates", "run_duplicate_scan",
+           "ClusterBuilder"]

@@ -2,7 +2,7 @@
 
     python -m kobato_eyes_amd.cli scan-dups --db kobato.db --hamming 8 [--like '%/photos/%'] [--size-ratio 0.5]
                                             [--added-like '%/incoming/%'] [--refine] [--csv out.csv] [--device 0]
-                                            [--devices 0,1,2]
+                                            [--devices 0,1,2] [--turned]
 
 Reproduces the call sequence of DuplicateScanRunnable.run (src/ui/dup_workers.py:148-239) without Qt: rows in
 the shape of db.repository.iter_files_for_dup (src/db/repository.py:416-454), missing signatures filled and
@@ -45,26 +45,65 @@ def iter_files_for_dup(conn: sqlite3.Connection, path_like: Optional[str], added
         yield item
 
 
-def export_duplicate_clusters_csv(clusters: Sequence, file_path) -> None:
+def export_duplicate_clusters_csv(clusters: Sequence, file_path, orientations: Optional[dict] = None) -> None:
+    """``orientations`` (scan-dups --turned): {file_id: orientation}; the CSV then has a ninth column ``orientation``,
+    filled for the files that are linked to their group's keeper only through a turn (``orientations_to_keeper``)."""
     with open(file_path, "w", encoding="utf-8", newline="") as handle:
         writer = csv.writer(handle)
-        writer.writerow(CSV_HEADER)
+        writer.writerow(CSV_HEADER + (["orientation"] if orientations is not None else []))
         for group, cluster in enumerate(clusters, start=1):
             for entry in cluster.files:
                 f = entry.file
-                writer.writerow([group, f.file_id, f.path.as_posix(), f.size or 0, f.width or 0, f.height or 0,
-                                 1 if f.file_id == cluster.keeper_id else 0,
-                                 entry.best_hamming if entry.best_hamming is not None else ""])
+                row = [group, f.file_id, f.path.as_posix(), f.size or 0, f.width or 0, f.height or 0,
+                       1 if f.file_id == cluster.keeper_id else 0,
+                       entry.best_hamming if entry.best_hamming is not None else ""]
+                if orientations is not None:
+                    row.append(orientations.get(f.file_id, ""))
+                writer.writerow(row)
+
+
+def orientations_to_keeper(clusters: Sequence, matches: Sequence, plain_keys) -> dict:
+    """{file_id: orientation} for the files that are linked to their group's keeper only through a turn: the orientation
+    (turned.ORIENTATIONS) that brings the file's picture to the keeper's.  Worked out group by group from the keeper
+    outwards: a plain candidate edge (``plain_keys``: their (id, id) keys) carries the identity, a turned match its
+    orientation or the inverse, plain edges first; files that come out with the identity are left out."""
+    from .turned import COMPOSE, INVERSE
+
+    links: dict = {}
+    for a, b in plain_keys:
+        links.setdefault(a, []).append((b, 0))
+        links.setdefault(b, []).append((a, 0))
+    for m in matches:                                   # orientation turns b's picture into a's
+        links.setdefault(m.file_id_a, []).append((m.file_id_b, m.orientation))
+        links.setdefault(m.file_id_b, []).append((m.file_id_a, INVERSE[m.orientation]))
+    out: dict = {}
+    for cluster in clusters:
+        to_keeper = {cluster.keeper_id: 0}
+        queue = [cluster.keeper_id]
+        while queue:
+            f = queue.pop(0)
+            for g, t in sorted(links.get(f, ()), key=lambda link: (link[1] != 0, link[0])):   # t turns g's picture into f's
+                if g not in to_keeper:
+                    to_keeper[g] = COMPOSE[t][to_keeper[f]]
+                    queue.append(g)
+        out.update({f: k for f, k in to_keeper.items() if k})
+    return out
 
 
 def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, path_like: Optional[str] = None,
                   refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
-                  devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None) -> list:
+                  devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None, turned: bool = False,
+                  orientations_out: Optional[dict] = None) -> list:
     """``devices``: the missing signatures are computed by one worker process per entry; the scan and the tile-aHash / MAE
     refine stay in this process, on ``device`` (default ``devices[0]``, else 0).  ``added_like``: the files of the
     selection whose path matches this LIKE pattern are the added set, the rest the library; only the pairs that touch an
     added file are scanned and only the clusters with an added member come back (``find_new_duplicates`` without
-    ``previous``: a link between two library files is absent)."""
+    ``previous``: a link between two library files is absent).  ``turned``: the files of the selection are read and
+    mirrored, flipped and rotated copies are linked as well (``find_turned_duplicates``; not together with
+    ``added_like`` or ``refine``); ``orientations_out`` then receives ``orientations_to_keeper`` of the result."""
+    if turned and (added_like or refine):
+        # the refine pipeline compares pixels as they lie and would cut every link that exists through a turn
+        raise ValueError("--turned cannot be combined with --added-like or --refine")
     from . import DuplicateFile, DuplicateScanConfig, DuplicateScanner, fast_fill_missing_signatures
     from .refine_parallel import refine_by_pixels_parallel, refine_by_tilehash_parallel
 
@@ -100,7 +139,14 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
         except ValueError:
             continue                                   # rows still without a hash are skipped, as the reference does
     tick("Clustering duplicates", 0, len(files))
-    if added_like:
+    if turned:
+        from .api import _turned_scan
+
+        clusters, matches, plain_keys = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio,
+                                                     band_bits=16, band_count=4, device=device)
+        if orientations_out is not None:
+            orientations_out.update(orientations_to_keeper(clusters, matches, plain_keys))
+    elif added_like:
         from .api import find_new_duplicates
 
         added_ids = {r["file_id"] for r in rows if r["added"]}
@@ -128,6 +174,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("--added-like", default=None,
                     help="SQL LIKE pattern: the matching files of the selection are newly added, the rest is the library; only "
                          "pairs with an added file are scanned and only groups with an added file are reported")
+    sp.add_argument("--turned", action="store_true",
+                    help="read the files of the selection and link mirrored, flipped and rotated copies as well; the CSV gains an "
+                         "orientation column: the turn that brings a file's picture to its group's keeper's")
     sp.add_argument("--refine", action="store_true", help="run the tile-aHash + pixel-MAE refine pipeline on the clusters")
     sp.add_argument("--tile-max-bits", type=int, default=32)
     sp.add_argument("--mae-thr", type=float, default=0.004)
@@ -138,11 +187,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARNING)
+    orientations = {} if args.turned else None
     clusters = scan_database(args.db, hamming_threshold=args.hamming, size_ratio=args.size_ratio, path_like=args.like,
                              refine=args.refine, tile_max_bits=args.tile_max_bits, mae_thr=args.mae_thr, device=args.device,
-                             devices=args.devices, added_like=args.added_like)
+                             devices=args.devices, added_like=args.added_like, turned=args.turned, orientations_out=orientations)
     if args.csv:
-        export_duplicate_clusters_csv(clusters, args.csv)
+        export_duplicate_clusters_csv(clusters, args.csv, orientations)
     members = sum(len(c.files) for c in clusters)
     print(f"{len(clusters)} duplicate group(s), {members} file(s)" + (f" -> {args.csv}" if args.csv else ""))
     return 0

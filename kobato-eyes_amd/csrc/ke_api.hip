@@ -469,7 +469,10 @@ static KeHashGroup hash_group(const KeShapeGroup &sg, const uint8_t *d_px, const
 
 static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths,
                             const int32_t *heights, int32_t channels, int64_t n, uint64_t *phash_out,
-                            uint64_t *dhash_out, int32_t *status_out, float *margin_out) {
+                            uint64_t *dhash_out, int32_t *status_out, float *margin_out, uint64_t *turned_out = nullptr) {
+    // turned_out (ke_hash_images_turned; phash_out, dhash_out and margin_out are NULL then): every size group runs with a
+    // piece of one tile scratch as its tile output and no hash output, and ke_tiles_to_phash_turned makes the eight hashes
+    // of each tile -- the scratch is indexed by position in the group, the kernel scatters by the group's output slots.
     if (!ctx) return KE_EINVAL;
     if (margin_out && !phash_out) return ke_fail(ctx, KE_EINVAL, "margin_out needs phash_out");
     if (n < 0 || (n > 0 && (!pixels || !widths || !heights)))
@@ -510,6 +513,23 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
         else { KE_TRY(ke_reserve(ctx, KE_BUF_OUT1, (size_t)n * 8, &tmp)); d_dh = (uint64_t *)tmp; }
         KE_HIP(ctx, hipMemsetAsync(d_dh, 0, (size_t)n * 8, ctx->stream));
     }
+    uint64_t *d_tn = nullptr;
+    uint8_t *d_tiles = nullptr;
+    const bool t_dev = turned_out && ke_is_device_ptr(turned_out);
+    if (turned_out) {
+        if (t_dev) d_tn = turned_out;
+        else { KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)n * 64, &tmp)); d_tn = (uint64_t *)tmp; }
+        KE_HIP(ctx, hipMemsetAsync(d_tn, 0, (size_t)n * 64, ctx->stream));
+        // device-resident pixels: all groups' tiles at once; host pixels: one staged chunk of a group at a time
+        size_t most = 0, all = 0;
+        for (const KeShapeGroup &sg : groups) {
+            const size_t img_bytes = (size_t)sg.w * sg.h * channels;
+            most = std::max(most, std::min((size_t)sg.n, std::max<size_t>(1, kStageBytes / img_bytes)));
+            all += (size_t)sg.n;
+        }
+        KE_TRY(ke_reserve(ctx, KE_BUF_TURN_TILES, (in_dev ? all : most) * 1024, &tmp));
+        d_tiles = (uint8_t *)tmp;
+    }
     const bool m_dev = margin_out && ke_is_device_ptr(margin_out);
     MarginScope margin_scope{ctx};
     if (margin_out) {
@@ -542,8 +562,12 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
             for (int k = 0; k < 2; ++k) KE_HIP(ctx, hipStreamWaitEvent(ctx->side[k], ctx->side_fork, 0));
         }
         int rc_groups = KE_OK;
-        for (size_t gi = 0; gi < groups.size() && rc_groups == KE_OK; ++gi)
-            rc_groups = ke_launch_hash_group(ctx, hash_group(groups[gi], pixels, (const uint64_t *)meta), d_ph, d_dh, nullptr, nullptr, overlap ? ctx->side[gi & 1] : nullptr);
+        size_t tile_at = 0;                                                     // turned: the group's first tile in the scratch
+        for (size_t gi = 0; gi < groups.size() && rc_groups == KE_OK; ++gi) {
+            rc_groups = ke_launch_hash_group(ctx, hash_group(groups[gi], pixels, (const uint64_t *)meta), d_ph, d_dh,
+                                             d_tiles ? d_tiles + tile_at * 1024 : nullptr, nullptr, overlap ? ctx->side[gi & 1] : nullptr);
+            tile_at += (size_t)groups[gi].n;
+        }
         if (overlap) {                                                          // join, also on the error path
             for (int k = 0; k < 2; ++k) {
                 KE_HIP(ctx, hipEventRecord(ctx->side_join[k], ctx->side[k]));
@@ -551,6 +575,14 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
             }
         }
         KE_TRY(rc_groups);
+        if (d_tiles) {                                                          // behind the join: every group's tiles are there
+            tile_at = 0;
+            for (const KeShapeGroup &sg : groups) {
+                const KeHashGroup g = hash_group(sg, pixels, (const uint64_t *)meta);
+                KE_TRY(ke_launch_tiles_turned(ctx, d_tiles + tile_at * 1024, g.out_idx, g.n, d_tn));
+                tile_at += (size_t)sg.n;
+            }
+        }
     } else {
         for (const KeShapeGroup &sg : groups) {
             const size_t img_bytes = (size_t)sg.w * sg.h * channels;
@@ -574,7 +606,8 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
                                            hipMemcpyHostToDevice, ctx->stream));
                 KeHashGroup g{(const uint8_t *)tmp, (const uint64_t *)meta, img_bytes,
                               (const int64_t *)((uint8_t *)meta + (size_t)m * 8), m, sg.w, sg.h, channels};
-                KE_TRY(ke_launch_hash_group(ctx, g, d_ph, d_dh, nullptr, nullptr));
+                KE_TRY(ke_launch_hash_group(ctx, g, d_ph, d_dh, d_tiles, nullptr));
+                if (d_tiles) KE_TRY(ke_launch_tiles_turned(ctx, d_tiles, g.out_idx, m, d_tn));
                 KE_HIP(ctx, hipStreamSynchronize(ctx->stream));  // goff/gidx and the staging buffers are reused
             }
         }
@@ -586,6 +619,8 @@ static int hash_images_impl(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *
         KE_HIP(ctx, hipMemcpyAsync(dhash_out, d_dh, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (margin_out && !m_dev)
         KE_HIP(ctx, hipMemcpyAsync(margin_out, ctx->margin_cur, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (turned_out && !t_dev)
+        KE_HIP(ctx, hipMemcpyAsync(turned_out, d_tn, (size_t)n * 64, hipMemcpyDeviceToHost, ctx->stream));
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KE_OK;
 }
@@ -600,6 +635,32 @@ KE_API int ke_hash_images_ex(ke_ctx *ctx, const uint8_t *pixels, const uint64_t 
                              const int32_t *heights, int32_t channels, int64_t n, uint64_t *phash_out,
                              uint64_t *dhash_out, int32_t *status_out, float *margin_out) {
     return hash_images_impl(ctx, pixels, offsets, widths, heights, channels, n, phash_out, dhash_out, status_out, margin_out);
+}
+
+KE_API int ke_hash_images_turned(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths,
+                                 const int32_t *heights, int32_t channels, int64_t n, uint64_t *turned_out, int32_t *status_out) {
+    if (!ctx) return KE_EINVAL;
+    if (n > 0 && !turned_out) return ke_fail(ctx, KE_EINVAL, "turned_out is NULL");
+    return hash_images_impl(ctx, pixels, offsets, widths, heights, channels, n, nullptr, nullptr, status_out, nullptr, turned_out);
+}
+
+KE_API int ke_tiles_turned(ke_ctx *ctx, const uint8_t *tile32, int64_t n, uint64_t *turned_out) {
+    if (!ctx) return KE_EINVAL;
+    if (n < 0 || (n > 0 && (!tile32 || !turned_out))) return ke_fail(ctx, KE_EINVAL, "tile32/turned_out must be non-NULL");
+    if (n == 0) return KE_OK;
+    KE_HIP(ctx, hipSetDevice(ctx->device));
+    const void *d_t = nullptr;
+    KE_TRY(ke_to_device(ctx, tile32, (size_t)n * 1024, KE_BUF_TURN_TILES, &d_t));
+    const bool out_dev = ke_is_device_ptr(turned_out);
+    uint64_t *d_out = turned_out;
+    void *tmp;
+    if (!out_dev) { KE_TRY(ke_reserve(ctx, KE_BUF_OUT0, (size_t)n * 64, &tmp)); d_out = (uint64_t *)tmp; }
+    ke_time_begin(ctx, KE_T_HASH);
+    KE_TRY(ke_launch_tiles_turned(ctx, (const uint8_t *)d_t, nullptr, n, d_out));
+    ke_time_end(ctx, KE_T_HASH);
+    if (!out_dev) KE_HIP(ctx, hipMemcpyAsync(turned_out, d_out, (size_t)n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KE_OK;
 }
 
 // ---- pinned staging ---------------------------------------------------------------------------
@@ -772,11 +833,11 @@ KE_API int ke_stage_submit_hash(ke_ctx *ctx, int32_t slot, const uint64_t *offse
 }
 
 // ---- scan ------------------------------------------------------------------------------------
-// ke_hamming_scan (first_new = 0) and ke_hamming_scan_from: one body, the region is ke_launch_scan's business
+// ke_hamming_scan (first_new = 0), ke_hamming_scan_from and ke_hamming_scan_cross: one body, the region is ke_launch_scan's business
 static int hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n, int64_t first_new,
                         int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
                         int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
-                        int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
+                        int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out, bool cross = false) {
     if (!ctx) return KE_EINVAL;
     if (n < 0 || (n > 0 && !hashes)) return ke_fail(ctx, KE_EINVAL, "hashes is NULL");
     if (first_new < 0 || first_new > n) return ke_fail(ctx, KE_EINVAL, "first_new %lld outside [0, %lld]", (long long)first_new, (long long)n);
@@ -823,7 +884,7 @@ static int hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids,
     unsigned long long *d_cnt = nullptr, pairs = 0;
     KE_TRY(ke_launch_scan(ctx, (const uint64_t *)d_h, (const int64_t *)d_ids, (const int64_t *)d_sizes, n, part_index,
                           part_count, threshold, band_bits, band_count, size_ratio, bucket_pair_cap, d_edges, capacity,
-                          &d_cnt, &pairs, counters_out != nullptr, first_new));
+                          &d_cnt, &pairs, counters_out != nullptr, first_new, cross));
     unsigned long long h_cnt[KE_SCAN_STATE_WORDS];
     KE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, ctx->stream));
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -857,6 +918,14 @@ KE_API int ke_hamming_scan_from(ke_ctx *ctx, const uint64_t *hashes, const int64
                                 int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
     return hamming_scan(ctx, hashes, ids, sizes, n, first_new, part_index, part_count, threshold, band_bits, band_count, size_ratio,
                         bucket_pair_cap, edges_out, capacity, n_edges_out, counters_out);
+}
+
+KE_API int ke_hamming_scan_cross(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
+                                 int64_t first_new, int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
+                                 int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
+                                 int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
+    return hamming_scan(ctx, hashes, ids, sizes, n, first_new, part_index, part_count, threshold, band_bits, band_count, size_ratio,
+                        bucket_pair_cap, edges_out, capacity, n_edges_out, counters_out, true);
 }
 
 KE_API int ke_band_pairs_after_size(ke_ctx *ctx, const uint64_t *hashes, const int64_t *sizes, int64_t n, int32_t band_bits,

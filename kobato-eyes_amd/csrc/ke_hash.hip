@@ -191,6 +191,77 @@ __global__ __launch_bounds__(256) void ke_tiles_to_hashes(const uint8_t *__restr
     }
 }
 
+// The eight turned pHashes of a tile (include/keyes.h, ke_tiles_turned): orientation k of a 2-D array a is
+//   t = a.T if k & 4 else a;  if k & 1: t = t[:, ::-1];  if k & 2: t = t[::-1]
+// and turned hash k is what tile32_to_phash gives for orientation k of the tile.
+// The first two steps of tile32_to_phash -- rows, then columns, the 8 x 8 corner as float32 in cf -- for the tile or, with
+// kTransposed, for its transpose.  All 256 threads call this; cf is complete behind the closing barrier.
+template <bool kTransposed>
+__device__ __forceinline__ void tile32_coeffs(const uint8_t *tile, double *Td, float *cf, int tid) {
+    {
+        const int y = tid >> 3, kx = tid & 7;
+        double x[32];
+#pragma unroll
+        for (int n = 0; n < 32; ++n) x[n] = (double)tile[kTransposed ? n * 32 + y : y * 32 + n];
+        Td[y * 8 + kx] = dct32_one(x, kx);
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int ky = tid >> 3, kx = tid & 7;
+        double x[32];
+#pragma unroll
+        for (int n = 0; n < 32; ++n) x[n] = Td[n * 8 + kx];
+        const double s = (ky == 0 && kx == 0) ? KE_SCALE00 : ((ky == 0 || kx == 0) ? KE_SCALE0K : KE_SCALEKK);
+        cf[tid] = (float)(dct32_one(x, ky) * s);
+    }
+    __syncthreads();
+}
+
+// One workgroup per tile, two coefficient sets for eight hashes.  Mirroring a row negates dct32_one's odd outputs exactly --
+// they are fma chains over x[n] - x[31-n], and fma(-a, c, -acc) = -fma(a, c, acc) -- and leaves its even outputs as they are
+// (sums of x[n] + x[31-n]); a negated input negates every output exactly, through the float32 conversion too.  So the
+// coefficients of the mirrored tile are those of the tile with the sign of the odd columns turned, of the flipped tile with
+// the sign of the odd rows turned, and the four orientations of the transpose (k & 4) come the same way from the
+// transposed tile's own set -- which is computed, not read off the tile's: there the two passes swap order and the float32
+// values can differ.  A zero may come out as -0 where the turned tile would give +0; no sum and no comparison below can
+// tell.  Each of the eight then gets its own float32 mean over its own flat[1:], in NumPy's pairwise order as in
+// tile32_to_phash, and its own ballot: wave w makes orientations w and w + 4.  Tile img of the array goes to slot
+// out_idx[img] (img without out_idx); turned[slot * 8 + k].
+__global__ __launch_bounds__(256) void ke_tiles_to_phash_turned(const uint8_t *__restrict__ tile32, const int64_t *__restrict__ out_idx,
+                                                                 uint64_t *__restrict__ turned) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_tile[1024];
+    __shared__ double s_T[256];
+    __shared__ float s_cf[2][64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t img = blockIdx.x;
+    const int64_t slot = out_idx ? out_idx[img] : img;
+    reinterpret_cast<uint32_t *>(s_tile)[tid] = reinterpret_cast<const uint32_t *>(tile32 + (size_t)img * 1024)[tid];
+    __syncthreads();
+    tile32_coeffs<false>(s_tile, s_T, s_cf[0], tid);
+    tile32_coeffs<true>(s_tile, s_T, s_cf[1], tid);
+    for (int k = wv; k < 8; k += 4) {
+        const float *base = s_cf[k >> 2];
+        // flat[i], i = ky * 8 + kx, of orientation k
+        auto coef = [&](int i) {
+            const bool neg = ((k & 1) && (i & 1)) != ((k & 2) && ((i >> 3) & 1));
+            return neg ? -base[i] : base[i];
+        };
+        float r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = coef(1 + j);
+#pragma unroll
+        for (int i = 8; i < 56; i += 8)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] = r[j] + coef(1 + i + j);
+        float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+#pragma unroll
+        for (int i = 56; i < 63; ++i) res = res + coef(1 + i);
+        const float mean = res / 63.0f;
+        const unsigned long long m = __ballot(coef(lane) > mean);   // lane i <-> flat[i]
+        if (lane == 0) turned[slot * 8 + k] = __brevll(m);          // flat[0] is the MSB
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // Pieces shared by the fused kernel and the banded path: luma of four packed RGB pixels, the byte-plane
 // recombination, the kernel arguments and the part of the chain behind the row loop.
@@ -1660,6 +1731,15 @@ int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, u
             }
         }
     }
+    return KE_OK;
+}
+
+int ke_launch_tiles_turned(ke_ctx *ctx, const uint8_t *d_tile32, const int64_t *d_out_idx, int64_t n, uint64_t *d_turned) {
+    if (n <= 0) return KE_OK;
+    if (n > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
+    KE_TRY(upload_dct_tables(ctx));
+    hipLaunchKernelGGL(ke_tiles_to_phash_turned, dim3((unsigned)n), dim3(256), 0, ctx->stream, d_tile32, d_out_idx, d_turned);
+    KE_HIP(ctx, hipGetLastError());
     return KE_OK;
 }
 

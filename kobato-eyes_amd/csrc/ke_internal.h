@@ -44,6 +44,7 @@ enum {
     KE_BUF_COMM,         // gathered hash shards before they are put back into corpus order
     KE_BUF_COMM_EDGES,   // edge records: [send | world x recv]
     KE_BUF_JPEG_TABLES,  // Huffman tables of a JPEG batch
+    KE_BUF_TURN_TILES,   // ke_hash_images_turned: the 32x32 tiles of a call's images, group after group
     KE_BUF_COUNT
 };
 
@@ -142,6 +143,8 @@ struct KeHashGroup {
 // fused_stream (nullable): where the scratch-free one-workgroup-per-image kernel of the group may run instead of ctx->stream
 int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, uint64_t *d_dhash,
                          uint8_t *d_tile32_out, uint8_t *d_tile98_out, hipStream_t fused_stream = nullptr);
+// the eight turned pHashes of n 32x32 tiles (device): tile k -> d_turned[(d_out_idx ? d_out_idx[k] : k) * 8 + 0..7]
+int ke_launch_tiles_turned(ke_ctx *ctx, const uint8_t *d_tile32, const int64_t *d_out_idx, int64_t n, uint64_t *d_turned);
 // luma + resize of a group to (oh x ow) u8 tiles with the given filter (banded path, generic fallback)
 // box = {x0, y0, x1, y1} source rectangle (Pillow's resize box), NULL = the whole image
 // ctx->resize_plan holds what was launched for the last group, written where each value is decided (ke_last_resize_plan):
@@ -156,7 +159,7 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
 int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
                    int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
                    int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
-                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new);
+                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross = false);
 constexpr int KE_SCAN_STATE_WORDS = 5;   // what ke_hamming_scan reads back: counters [0..3] and the path word
 int ke_launch_ssim(ke_ctx *ctx, const uint8_t *d_images, int w, int h, int channels, const int64_t *d_pa,
                    const int64_t *d_pb, int64_t n_pairs, double *d_out);

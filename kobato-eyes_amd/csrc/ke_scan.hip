@@ -148,8 +148,15 @@ __global__ __launch_bounds__(256) void ke_scan_expand(const uint64_t *__restrict
 // (region, ke_scan_region.h) and the columns below first_new are left out -- whole chunks and 16-column blocks by where
 // the loops start (wave-uniform), the lanes of the block first_new lies in at the rare path.  Every kFrom branch is
 // compile-time, region is not read without it.
-template <bool kFrom>
+// kMode = kScanCross is ke_scan_tiles_cross, the pairs i < first_new <= j of a table [library | queries]: the region is the
+// rectangle of row blocks that hold a row below first_new against the chunks from first_new's on (ke_cross_region), the
+// columns are cut as for kFrom, and the rows at or beyond first_new are left out -- a wave whose 128 rows all lie there
+// walks no block but still meets the others at every barrier of the chunk loop, a single such row is dropped per lane at
+// the rare path.  Every kCross branch is compile-time too.
+constexpr int kScanAll = 0, kScanFrom = 1, kScanCross = 2;
+template <int kMode>
 __device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRegion region) {
+    constexpr bool kCross = kMode == kScanCross, kFrom = kMode != kScanAll;   // kFrom: the columns start at first_new
     __shared__ ke_v4i s_b[2][kChunk / 16 * 64];      // two chunks of 16 operand tiles
     if (a.counters[kPathWord]) return;               // the bucket kernels do this call's scan
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -166,7 +173,9 @@ __device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRe
     // Tiles of the upper triangle, row-major: row block rb owns column chunks kCPR*rb .. ncc-1, so
     // offset(rb) = rb*ncc - kCPR*rb*(rb-1)/2.  Invert with a float estimate and an exact fix-up.
     int64_t rb, cc;
-    if constexpr (kFrom) {
+    if constexpr (kCross) {
+        ke_cross_tile(region, t, &rb, &cc);
+    } else if constexpr (kFrom) {
         ke_region_tile(region, t, &rb, &cc);         // the same inversion behind the region's rectangle (ke_scan_region.h)
     } else {
         const double hc = 0.5 * kCPR, bq = (double)a.ncc + hc;
@@ -179,7 +188,10 @@ __device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRe
     }
     const int64_t row0 = rb * kTile, col0 = cc * kCols;
     const int64_t wrow0 = row0 + (int64_t)wv * (kRT * 16);          // this wave's 128 rows
-    if constexpr (kFrom) {
+    if constexpr (kCross) {
+        // pairs i < first_new <= j of this tile: over the shards first_new (n - first_new)
+        if (tid == 0) atomicAdd(&a.counters[0], (unsigned long long)ke_cross_tile_pairs(region, rb, cc));
+    } else if constexpr (kFrom) {
         // pairs i < j, j >= first_new of this tile: over the shards n (n - 1) / 2 - f (f - 1) / 2
         if (tid == 0) atomicAdd(&a.counters[0], (unsigned long long)ke_region_tile_pairs(region, rb, cc));
     } else if (tid == 0) {
@@ -232,6 +244,9 @@ __device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRe
             const int64_t before = region.first_new - (col0 + (int64_t)c * kChunk);
             if (before > 0) ct0 = max(ct0, (int)min((int64_t)(kChunk / 16), before / 16));
         }
+        if constexpr (kCross) {  // a wave whose rows are all queries has no block to walk (wave-uniform); it stays for the barriers
+            if (wrow0 >= region.first_new) ct0 = kChunk / 16;
+        }
         for (int ct = ct0; ct < kChunk / 16; ++ct) {
             const ke_v4i bv = bt[ct * 64 + lane];
             const ke_v8i b = {bv[0], bv[1], bv[2], bv[3], 0, 0, 0, 0};
@@ -261,7 +276,9 @@ __device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRe
                     const int k = __ffs(hits) - 1;
                     hits &= hits - 1;
                     const int64_t gi = wrow0 + (k >> 2) * 16 + 4 * (lane >> 4) + (k & 3);
-                    if (gi < gj) {
+                    bool take = gi < gj;
+                    if constexpr (kCross) take = take && gi < region.first_new;
+                    if (take) {
                         const uint64_t x = a.hashes[gi];
                         consider_pair(a, gi, gj, x, y, __popcll(x ^ y));
                     }
@@ -274,10 +291,14 @@ __device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRe
     }
 }
 
-__global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) { scan_tiles_body<false>(a, KeScanRegion{}); }
+__global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) { scan_tiles_body<kScanAll>(a, KeScanRegion{}); }
 
 __global__ __launch_bounds__(kThreads) void ke_scan_tiles_from(const ScanArgs a, const KeScanRegion region) {
-    scan_tiles_body<true>(a, region);
+    scan_tiles_body<kScanFrom>(a, region);
+}
+
+__global__ __launch_bounds__(kThreads) void ke_scan_tiles_cross(const ScanArgs a, const KeScanRegion region) {
+    scan_tiles_body<kScanCross>(a, region);
 }
 
 __global__ void ke_band_hist(const uint64_t *__restrict__ hashes, int64_t n, int band_bits, int band_count,
@@ -428,8 +449,8 @@ __global__ void ke_bucket_scatter(const uint64_t *__restrict__ hashes, int64_t n
 constexpr int kPairSlots = 1024, kPairStage = 256;
 
 // kFrom (ke_bucket_pairs_from): a pair is kept only when its later position is at least first_new; its shard stays
-// (lo + hi) mod part_count.
-template <bool kFrom>
+// (lo + hi) mod part_count.  kScanCross (ke_bucket_pairs_cross): only when lo < first_new <= hi as well.
+template <int kMode>
 __device__ __forceinline__ void bucket_pairs_body(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
                                                   const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
                                                   int64_t first_new) {
@@ -461,7 +482,8 @@ __device__ __forceinline__ void bucket_pairs_body(const ScanArgs a, const uint64
             const int64_t pj = pos[k];
             const int64_t lo = pi < pj ? pi : pj, hi = pi < pj ? pj : pi;
             if (hi >= a.n || (lo + hi) % part_count != part_index) continue;
-            if constexpr (kFrom) { if (hi < first_new) continue; }
+            if constexpr (kMode != kScanAll) { if (hi < first_new) continue; }
+            if constexpr (kMode == kScanCross) { if (lo >= first_new) continue; }
             const uint64_t xl = pi < pj ? x : y, xh = pi < pj ? y : x;
             int bands, shared;
             if (!pair_is_edge(a, lo, hi, xl, xh, b, &bands, &shared)) continue;
@@ -490,13 +512,19 @@ __device__ __forceinline__ void bucket_pairs_body(const ScanArgs a, const uint64
 
 __global__ __launch_bounds__(256) void ke_bucket_pairs(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
                                                         const uint32_t *__restrict__ sorted_pos, int part_index, int part_count) {
-    bucket_pairs_body<false>(a, sorted_hash, sorted_pos, part_index, part_count, 0);
+    bucket_pairs_body<kScanAll>(a, sorted_hash, sorted_pos, part_index, part_count, 0);
 }
 
 __global__ __launch_bounds__(256) void ke_bucket_pairs_from(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
                                                              const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
                                                              int64_t first_new) {
-    bucket_pairs_body<true>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
+    bucket_pairs_body<kScanFrom>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
+}
+
+__global__ __launch_bounds__(256) void ke_bucket_pairs_cross(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
+                                                              const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
+                                                              int64_t first_new) {
+    bucket_pairs_body<kScanCross>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
 }
 
 // Wide bands (2^band_bits bins do not fit a table): the band values are sorted together with their positions and the
@@ -633,11 +661,12 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
 int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
                    int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
                    int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
-                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new) {
+                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross) {
     // first_new > 0: only the pairs i < j with j >= first_new (ke_hamming_scan_from), through kernels of their own;
-    // first_new == 0 launches what it always did
-    const bool from = first_new > 0;
-    const KeScanRegion region = ke_scan_region(n, first_new);
+    // first_new == 0 launches what it always did.  cross: only the pairs i < first_new <= j (ke_hamming_scan_cross), again
+    // through kernels of its own, for every first_new in [0, n] (0 and n: an empty region, no tile kernel).
+    const bool from = cross || first_new > 0;
+    const KeScanRegion region = cross ? ke_cross_region(n, first_new) : ke_scan_region(n, first_new);
     ScanArgs a;
     a.hashes = d_hashes; a.ids = d_ids; a.sizes = (size_ratio > 0.0) ? d_sizes : nullptr;
     a.n = n;
@@ -652,7 +681,8 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
     a.cap = bucket_pair_cap > 0 ? (unsigned long long)bucket_pair_cap : 0ull;
     a.edges = d_edges; a.capacity = capacity;
     // pairs of the region this shard stands for (host, O(row blocks); first_new = 0: the pairs i < j < n)
-    const unsigned long long pairs = ke_region_shard_pairs(region, part_index, part_count);
+    const unsigned long long pairs = cross ? ke_cross_shard_pairs(region, part_index, part_count)
+                                           : ke_region_shard_pairs(region, part_index, part_count);
     *pairs_evaluated = pairs;
     // KE_SCAN_MODE=auto|tiles|buckets, read once: auto lets the device choose per call; the other two force a path
     // (buckets still means tiles where the bucket path is not built).  Must be the same on every rank of a sharded scan.
@@ -700,8 +730,10 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
         if (bucket_path) {
             const unsigned blocks = (unsigned)((bins + kBinsPerBlock - 1) / kBinsPerBlock);
             // the rule's yardstick is what the tile kernel would have to visit: the region's pairs
-            const unsigned long long all_pairs = (unsigned long long)n * (unsigned long long)(n - 1) / 2 -
-                                                 (unsigned long long)first_new * (unsigned long long)(first_new > 0 ? first_new - 1 : 0) / 2;
+            const unsigned long long all_pairs =
+                cross ? (unsigned long long)first_new * (unsigned long long)(n - first_new)
+                      : (unsigned long long)n * (unsigned long long)(n - 1) / 2 -
+                            (unsigned long long)first_new * (unsigned long long)(first_new > 0 ? first_new - 1 : 0) / 2;
             hipLaunchKernelGGL(ke_bucket_stats, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins, a.cap, block_sums,
                                state);
             hipLaunchKernelGGL(ke_bucket_offsets, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins,
@@ -709,7 +741,10 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
             hipLaunchKernelGGL(ke_bucket_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, band_bits,
                                band_count, offsets, sorted_hash, sorted_pos, (const unsigned long long *)state);
             const dim3 pair_grid((unsigned)((n + kPairSlots - 1) / kPairSlots), (unsigned)band_count);
-            if (from)
+            if (cross)
+                hipLaunchKernelGGL(ke_bucket_pairs_cross, pair_grid, dim3(256), 0, ctx->stream, a, (const uint64_t *)sorted_hash,
+                                   (const uint32_t *)sorted_pos, part_index, part_count, first_new);
+            else if (from)
                 hipLaunchKernelGGL(ke_bucket_pairs_from, pair_grid, dim3(256), 0, ctx->stream, a, (const uint64_t *)sorted_hash,
                                    (const uint32_t *)sorted_pos, part_index, part_count, first_new);
             else
@@ -750,13 +785,20 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
         hipLaunchKernelGGL(ke_scan_expand, dim3((unsigned)((n_pad * 4 + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, n_pad,
                            (ke_v4i *)exp, (const unsigned long long *)(state + kPathWord));
         if (my_tiles > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
+        // A launch holds fewer than 2^32 threads; beyond that only a part of the grid runs and the call ends at the caller's
+        // pair count check with a count that is short (so it does for the two older scans, from about 4 million hashes on).
+        // The cross scan says so here where the tile kernel is its only path.
+        if (cross && !bucket_path && my_tiles > 0xffffffffLL / kThreads)
+            return ke_fail(ctx, KE_EUNSUPPORTED, "%lld tiles of %d threads do not fit one launch", (long long)my_tiles, kThreads);
         static const int xcd = [] { const char *e = std::getenv("KE_SCAN_XCD"); return e ? std::atoi(e) : 0; }();
         a.xcd_remap = xcd;
         // with the remap the grid is padded to a multiple of 8 so that every slot exists on some workgroup
         const int64_t grid = xcd ? (my_tiles + 7) / 8 * 8 : my_tiles;
         // one workgroup per tile on either kernel: splitting a thin region's tiles over 2 or 4 workgroups was measured and
         // did not pay
-        if (from)
+        if (cross)
+            hipLaunchKernelGGL(ke_scan_tiles_cross, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
+        else if (from)
             hipLaunchKernelGGL(ke_scan_tiles_from, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
         else
             hipLaunchKernelGGL(ke_scan_tiles, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a);

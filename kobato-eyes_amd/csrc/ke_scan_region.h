@@ -1,6 +1,7 @@
 // The pair scan's tiling and the part of it that a scan "from first_new" covers: which tiles exist, which workgroup
 // ordinal is which tile, how many pairs a tile and a shard stand for.  Plain integer arithmetic without HIP types, for
-// the kernel (ke_scan.hip), for the host's closed form beside it and for a host-only program (tests/_scan_region_cpu.cpp).
+// the kernel (ke_scan.hip), for the host's closed form beside it and for the host-only programs (tests/_scan_region_cpu.cpp,
+// tests/_scan_cross_cpu.cpp).  The cross region of ke_hamming_scan_cross has its functions at the end of the file.
 //
 // The table is [library | added]: positions first_new .. n-1 are new, and the region is the pairs i < j with
 // j >= first_new.  Over the 1024 x 1024 tiling of the upper triangle that is a trapezoid: with cc0 = first_new / kKeScanCols,
@@ -121,6 +122,62 @@ KE_REGION_FN uint64_t ke_region_shard_pairs(const KeScanRegion &r, int part_inde
             }
             if (t % part_count == part_index) pairs += (uint64_t)ke_region_tile_pairs(r, rb, cc);
         }
+    }
+    return pairs;
+}
+
+// ---- the cross region: the table is [library | queries] and only the pairs i < first_new <= j are wanted, the queries are
+// not compared with each other.  Over the same tiling that is the rectangle of row blocks 0 .. ceil(first_new / kKeScanTile) - 1
+// against the column chunks cc0 .. ncc-1, row-major; nothing of the triangle below it.  first_new = 0 or n: no tile.
+KE_REGION_FN KeScanRegion ke_cross_region(int64_t n, int64_t first_new) {
+    KeScanRegion r;
+    r.n = n; r.first_new = first_new;
+    r.nb = (n + kKeScanTile - 1) / kKeScanTile;
+    r.ncc = (n + kKeScanCols - 1) / kKeScanCols;
+    r.cc0 = first_new / kKeScanCols;
+    r.tri_base = 0;
+    if (first_new <= 0 || first_new >= n) {
+        r.rect = r.width = r.rect_tiles = r.n_tiles = 0;
+        return r;
+    }
+    r.rect = (first_new + kKeScanTile - 1) / kKeScanTile;
+    r.width = r.ncc - r.cc0;
+    r.rect_tiles = r.n_tiles = r.rect * r.width;
+    return r;
+}
+
+// Tile ordinal t in [0, n_tiles) of the cross region -> (rb, cc)
+KE_REGION_FN void ke_cross_tile(const KeScanRegion &r, int64_t t, int64_t *rb_out, int64_t *cc_out) {
+    *rb_out = t / r.width;
+    *cc_out = r.cc0 + t % r.width;
+}
+
+// pairs i < first_new <= j that tile (rb, cc) of the cross region stands for: its rows below first_new times its columns
+// from first_new on (every such pair has i < j)
+KE_REGION_FN int64_t ke_cross_tile_pairs(const KeScanRegion &r, int64_t rb, int64_t cc) {
+    const int64_t row0 = rb * kKeScanTile, col0 = cc * kKeScanCols;
+    const int64_t rows = (row0 + kKeScanTile < r.first_new ? row0 + kKeScanTile : r.first_new) - row0;
+    const int64_t jlo = col0 > r.first_new ? col0 : r.first_new;
+    const int64_t jhi = col0 + kKeScanCols < r.n ? col0 + kKeScanCols : r.n;
+    if (rows <= 0 || jhi <= jlo) return 0;
+    return rows * (jhi - jlo);
+}
+
+// Pairs of the cross region that shard part_index of part_count stands for (tile t goes to shard t mod part_count), in
+// O(row blocks): of a row block's tiles only the one first_new lies in and the last one have fewer than kKeScanCols columns.
+KE_REGION_FN uint64_t ke_cross_shard_pairs(const KeScanRegion &r, int part_index, int part_count) {
+    uint64_t pairs = 0;
+    for (int64_t rb = 0; rb < r.rect && r.n_tiles > 0; ++rb) {
+        const int64_t off = rb * r.width;
+        const int64_t t_last = off + r.width - 1;
+        if (off % part_count == part_index) pairs += (uint64_t)ke_cross_tile_pairs(r, rb, r.cc0);
+        if (r.width < 2) continue;
+        if (t_last % part_count == part_index) pairs += (uint64_t)ke_cross_tile_pairs(r, rb, r.ncc - 1);
+        // chunks cc0+1 .. ncc-2 are whole: ordinals [off + 1, t_last)
+        const int64_t t = off + 1;
+        const int64_t below_last = t_last <= part_index ? 0 : (t_last - part_index + part_count - 1) / part_count;
+        const int64_t below_t = t <= part_index ? 0 : (t - part_index + part_count - 1) / part_count;
+        pairs += (uint64_t)(below_last - below_t) * (uint64_t)ke_cross_tile_pairs(r, rb, r.cc0 + 1);
     }
     return pairs;
 }

@@ -71,6 +71,18 @@ def phash_dhash(image, *, device: int = 0) -> tuple[int, int]:
     return _to_signed(int(ph[0])), _to_signed(int(dh[0]))
 
 
+def phash_turned(image, *, device: int = 0) -> tuple:
+    """The pHashes of the eight orientations of an image (turned.ORIENTATIONS), each made from orientation k of the image's
+    32x32 LANCZOS luma tile: a tuple of 8 signed ints, the first one ``phash(image)``."""
+    arr = image_to_array(image)
+    if arr.shape[0] == 0 or arr.shape[1] == 0:
+        raise ValueError("cannot hash an empty image")
+    turned, status = _native.get_context(device).hash_images_turned([arr])
+    if status[0] != 0:
+        raise ValueError(f"the image was not hashed (status {int(status[0])})")
+    return tuple(_to_signed(int(v)) for v in turned[0])
+
+
 def hash_batch(images: Sequence, *, want_dhash: bool = True, device: int = 0):
     """Ragged batch of PIL images / arrays -> (phash u64[n], dhash u64[n] | None, ok bool[n]).
     Images are grouped by channel count; each group is one ke_hash_images call."""
@@ -98,4 +110,4 @@ def hamming64(a: int, b: int) -> int:
     return ((int(a) ^ int(b)) & _MASK64).bit_count() if hasattr(int, "bit_count") else bin((int(a) ^ int(b)) & _MASK64).count("1")
 
 
-__all__ = ["phash", "dhash", "phash_dhash", "hash_batch", "hamming64"]
+__all__ = ["phash", "dhash", "phash_dhash", "phash_turned", "hash_batch", "hamming64"]

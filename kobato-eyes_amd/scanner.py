@@ -151,6 +151,17 @@ class DuplicateEdge:
     hamming: Optional[int]
 
 
+@dataclass(frozen=True)
+class TurnedMatch:
+    """Two files of which one looks like a turned copy of the other: orientation ``orientation`` (turned.ORIENTATIONS) of
+    file_id_b's picture is file_id_a's picture, to within ``hamming`` bits of the pHash.  file_id_a < file_id_b."""
+
+    file_id_a: int
+    file_id_b: int
+    orientation: int
+    hamming: int
+
+
 def _safe_positive_int(value: Optional[str]) -> Optional[int]:
     if value is None or not value.strip():
         return None
@@ -211,6 +222,52 @@ class DuplicateScanner:
             band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
             part_index=self._part[0], part_count=self._part[1], **({"first_new": int(first_new)} if first_new else {}))
         return self._edges_from_raw(candidates, hashes, ids, raw, counters, sizes=sizes, ratio=ratio, cap=cap)
+
+    def turned_edges(self, candidates: Sequence[DuplicateFile], turned, ok=None) -> list:
+        """[TurnedMatch]: the pairs of files of which one looks like a mirrored, flipped or rotated copy of the other.
+
+        ``turned``: u64[n, 8], row i the eight turned pHashes of candidates[i] (turned.turned_signatures; column 0 is not
+        used, the stored pHash stands for the file as it is).  ``ok``: a mask of the rows that hold hashes; a file without
+        takes part with its stored pHash only.  The table is [pHash of the n candidates | turned[i, 1:8] of the files
+        with hashes, file by file], a turned entry carrying its source file's id and size -- the scan's own ``ids[i] !=
+        ids[j]`` therefore drops a symmetric picture matching itself -- and the scan is a cross scan with first_new = n
+        (``ke_hamming_scan_cross``): the 7 n turned entries are not compared with each other.  An edge (a, b) is file a
+        against orientation k = (b - n) % 7 + 1 of the ((b - n) // 7)-th file with hashes.  One match is kept per unordered
+        pair of files: the smallest hamming, then the smallest orientation.  A match found from the file with the larger id
+        has its orientation mapped through turned.INVERSE, so that ``orientation`` always turns b's picture into a's.
+        size_ratio, the band config, KE_DUP_BUCKET_PAIR_CAP and this scanner's part_index / part_count apply as in
+        ``candidate_edges``; the funnel counters are not touched."""
+        from .turned import INVERSE
+
+        cfg = self._config
+        n = len(candidates)
+        turned = np.asarray(turned, dtype=np.uint64).reshape(n, 8)
+        src = np.arange(n) if ok is None else np.nonzero(np.asarray(ok, bool))[0]
+        if n == 0 or len(src) == 0:
+            return []
+        base_h = np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=n)
+        base_ids = np.fromiter((f.file_id for f in candidates), dtype=np.int64, count=n)
+        base_sizes = np.fromiter(((f.size or 0) for f in candidates), dtype=np.int64, count=n)
+        hashes = np.concatenate([base_h, turned[src, 1:8].reshape(-1)])
+        ids = np.concatenate([base_ids, np.repeat(base_ids[src], 7)])
+        sizes = np.concatenate([base_sizes, np.repeat(base_sizes[src], 7)])
+        cap = _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
+        ratio = cfg.size_ratio if (cfg.size_ratio is not None and cfg.size_ratio > 0) else 0.0
+        ctx = _native.get_context(self._device)
+        raw, _ = ctx.hamming_scan(
+            hashes, len(hashes), ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
+            band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
+            part_index=self._part[0], part_count=self._part[1], first_new=n, cross=True)
+        best: dict[tuple[int, int], tuple[int, int]] = {}
+        for a, b, h in zip(raw["a"].tolist(), raw["b"].tolist(), raw["h"].tolist()):
+            k = (b - n) % 7 + 1
+            id_a, id_b = int(base_ids[a]), int(base_ids[src[(b - n) // 7]])
+            if id_a > id_b:                      # found from the other side: what turns a's picture into b's
+                id_a, id_b, k = id_b, id_a, INVERSE[k]
+            found = (int(h), k)
+            if (id_a, id_b) not in best or found < best[(id_a, id_b)]:
+                best[(id_a, id_b)] = found
+        return [TurnedMatch(a, b, k, h) for (a, b), (h, k) in sorted(best.items())]
 
     # -- the reference's funnel counters (src/dup/scanner.py:258-299) ---------------------------------------------
     def _band_values(self, hashes: np.ndarray, band: int) -> np.ndarray:
