@@ -26,6 +26,7 @@
 #include "ke_internal.h"
 #include "dct_table.h"
 #include "ke_hash_select.h"
+#include "ke_resample_plan.h"
 
 namespace {
 
@@ -476,7 +477,7 @@ int upload_dct_tables(ke_ctx *ctx) {
 // the bottom.  The last tile is peeled: it has nothing to prefetch (a guarded prefetch would make hipcc wait
 // for the loads right after issuing them, an unguarded one would fetch 1/ntiles more bytes from HBM).
 // ---------------------------------------------------------------------------------------
-constexpr int kRTM = 32;
+constexpr int kRTM = kKeTileRowsMx;
 typedef int ke_v4i __attribute__((ext_vector_type(4)));
 
 // dHash leg (DH): the 9-output axis is one more 16-column operand tile whose taps span the whole row,
@@ -657,13 +658,6 @@ __global__ __launch_bounds__(256, 2) void ke_phash_fused_mx(const KeFusedArgs a)
     fused_tail<(DH ? 1 : 0)>(a, Lt, HT, HTd, tid, img);
 }
 
-// Band mode of the single-pass kernels (see KeFusedArgs::bands): how a group is cut, and where the columns go.
-struct KeBandPlan {
-    int bands, band_rows;
-    uint8_t *hs, *hsd;
-    int hs_hp, hsd_hp;
-};
-
 // ---------------------------------------------------------------------------------------
 // Wide rows (up to 2048 pixels): the same chain with the work cut differently.  A 32-row tile of such a row
 // no longer fits LDS twice and one wave cannot hold the operands of a whole output tile, so: 16-row tiles,
@@ -673,7 +667,7 @@ struct KeBandPlan {
 // the transposed column one tile later -- the exchange of the dHash leg above, four ways.  With DH the eight waves
 // also take an eighth each of the dHash axis' operand steps (KDW per wave) and meet in wave 0 the same way.
 // ---------------------------------------------------------------------------------------
-constexpr int kRTW = 16;
+constexpr int kRTW = kKeTileRowsWide;
 
 template <int KSH, int QPT, bool DH, int KDW, int C, bool UNAL>
 __global__ __launch_bounds__(512, 1) void ke_phash_fused_wide(const KeFusedArgs a) {
@@ -1072,107 +1066,13 @@ __global__ __launch_bounds__(256) void ke_vtile(const KeVtileArgs a) {
     }
 }
 
-template <int NDWC, int C, bool ALIGNED>
-int launch_hband_one(ke_ctx *ctx, const KeBandArgs &a, int64_t n, size_t lds) {
-    hipLaunchKernelGGL((ke_hband<NDWC, C, ALIGNED>), dim3((unsigned)(n * a.bands)), dim3(256), lds, ctx->stream, a);
-    KE_HIP(ctx, hipGetLastError());
-    return KE_OK;
-}
-
-template <int C, bool ALIGNED>
-int launch_hband_ndwc(ke_ctx *ctx, const KeBandArgs &a, int64_t n, size_t lds, int ndwc) {
-    switch (ndwc) {
-        case 8: return launch_hband_one<8, C, ALIGNED>(ctx, a, n, lds);
-        case 16: return launch_hband_one<16, C, ALIGNED>(ctx, a, n, lds);
-        case 24: return launch_hband_one<24, C, ALIGNED>(ctx, a, n, lds);
-        case 32: return launch_hband_one<32, C, ALIGNED>(ctx, a, n, lds);
-        default: return KE_EUNSUPPORTED;
-    }
-}
-
-int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles,
-                 int32_t *plan = nullptr);
-
-// Banded target: src images -> (oh x ow) u8 tiles.  Returns KE_EUNSUPPORTED for shapes it does not take
-// (Pillow's vertical-first rule, images under 4 pixels, windows beyond 8 chunks of 32 dwords).
-// plan (nullable): the KE_RP_* record of what is launched.
-int resample_banded(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles, int filter = KE_FILTER_LANCZOS,
-                    const float *box = nullptr, int32_t *plan = nullptr) {
-    if ((int64_t)g.h > (int64_t)g.w * 100 && oh < g.h) return KE_EUNSUPPORTED;
-    if ((int64_t)g.w * g.h < 4 || g.w > 16384 || g.h > 65536 || (int64_t)g.w * g.h * g.channels >= (1LL << 31)) return KE_EUNSUPPORTED;
-    const KeAxisCoeffs *chz = box ? ke_get_coeffs(ctx, g.w, ow, filter, box[0], box[2]) : ke_get_coeffs(ctx, g.w, ow, filter);
-    const KeAxisCoeffs *cvt = box ? ke_get_coeffs(ctx, g.h, oh, filter, box[1], box[3]) : ke_get_coeffs(ctx, g.h, oh, filter);
-    if (!chz || !cvt) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    // chunks per output: the power of two that wastes the fewest padded dwords, chunk <= 32 dwords; when the
-    // virtual columns of all outputs do not fit the 256 lanes, the outputs are split over several launches
-    int best_log2 = -1, best_waste = 1 << 30;
-    for (int l = 0; l <= 5; ++l) {
-        const int cpo = 1 << l, ndwc = (((chz->ndw + cpo - 1) / cpo) + 7) & ~7;
-        if (ndwc > 32) continue;
-        const int launches = (ow * cpo + 255) / 256;
-        const int waste = cpo * ndwc - chz->ndw + (ndwc > 24 ? 8 : 0) + 1000 * (launches - 1);   // mild preference for <= 24 (3 waves/SIMD)
-        if (waste < best_waste) { best_waste = waste; best_log2 = l; }
-    }
-    if (best_log2 < 0) return KE_EUNSUPPORTED;
-    const KeChunkTable *tc = ke_get_chunks(ctx, chz, 1 << best_log2, 8);
-    if (!tc) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    if (plan) { plan[KE_RP_CPO] = tc->cpo; plan[KE_RP_NDWC] = tc->ndwc; }
-    KeBandArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.w = g.w; a.h = g.h;
-    a.qr = (g.w + 3) / 4;
-    if (a.qr > 2048) return KE_EUNSUPPORTED;
-    a.lp = (4 * a.qr + 7) & ~7;
-    a.rt = std::max(1, std::min(2048 / a.qr, g.h));
-    // Rows per workgroup.  Upper bounds: about 2 MB of pixels (amortises the tap-plane loads of a workgroup; measured
-    // 4-6 % over 512 KB bands), 480 rows and 24 KB of LDS for the band's staged output bytes.  The image is then cut
-    // into EQUAL bands (a short last band leaves its CU idle at the end), each a whole number of 4-tile groups so that
-    // bands start on a multiple of 4 rows.
-    const int unit = 4 * a.rt;
-    const int per_launch = std::min(ow, 256 >> best_log2);   // outputs whose virtual columns fit 256 lanes
-    int64_t cap_rows = std::max<int64_t>(unit, ((int64_t)(2048 << 10) / ((int64_t)g.w * g.channels)) / unit * unit);
-    cap_rows = std::min<int64_t>(cap_rows, std::max(unit, 480 / unit * unit));
-    cap_rows = std::min<int64_t>(cap_rows, std::max<int64_t>(unit, ((24 * 1024) / per_launch - 8) / unit * unit));
-    // small groups still have to fill the chip: aim for at least ~3000 workgroups per launch (4 per SIMD slot)
-    const int64_t min_bands = std::min<int64_t>((3072 + g.n - 1) / g.n, (g.h + unit - 1) / unit);
-    if (min_bands > 1) cap_rows = std::min<int64_t>(cap_rows, std::max<int64_t>(unit, ((g.h + min_bands - 1) / min_bands + unit - 1) / unit * unit));
-    const int64_t want_bands = (g.h + cap_rows - 1) / cap_rows;
-    const int64_t rows = std::min<int64_t>(cap_rows, (((g.h + want_bands - 1) / want_bands + unit - 1) / unit) * unit);
-    a.band_rows = (int)rows;
-    a.bands = (g.h + a.band_rows - 1) / a.band_rows;
-    if (plan) plan[KE_RP_BANDS] = a.bands;
-    a.bp = ((a.band_rows + 3) & ~3) + 4;
-    a.nout_total = ow; a.cpo_log2 = best_log2;
-    a.cpacked = tc->d_cpacked; a.cstart = tc->d_cstart; a.cxor = tc->d_cxor; a.bias = chz->d_bias;
-    const int tile_bytes = a.rt * a.lp + std::max(0, tc->cspan - a.lp) + 16;
-    a.lt_half = (tile_bytes + 15) & ~15;
-    const size_t lds = 2 * (size_t)a.lt_half + (size_t)per_launch * a.bp;
-    if (lds > 64 * 1024) return KE_EUNSUPPORTED;
-    a.hp = ((std::max(cvt->span, g.h + 4) + 7) & ~7) + 8;
-    void *hs;
-    KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)g.n * ow * a.hp + 8192, &hs));     // + slack: ke_vtile_mx reads whole steps
-    a.hs = (uint8_t *)hs;
-    if ((int64_t)g.n * a.bands > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch");
-    // "aligned" = every row starts on a quad boundary of the packed stream (w % 4 == 0) and every image starts on a
-    // dword boundary, so a quad is DW whole dwords and the last quad of the image ends with the image.  Other widths, and
-    // ragged batches in which some image starts off a dword boundary, take the funnel-shift loader.
-    const bool aligned = g.w % 4 == 0 && !g.misaligned;
-    if (plan) { plan[KE_RP_BANDED] = 1; plan[KE_RP_FUNNEL] = aligned ? 0 : 1; plan[KE_RP_LAUNCHES] = 0; }
-    for (int first = 0; first < ow; first += per_launch) {
-        a.out_first = first;
-        a.nout = std::min(per_launch, ow - first);
-        int vcp = 1, vl = 0;
-        while (vcp < (a.nout << best_log2)) { vcp <<= 1; ++vl; }
-        a.vcp_log2 = vl;
-        int rc;
-        if (g.channels == 3) rc = aligned ? launch_hband_ndwc<3, true>(ctx, a, g.n, lds, tc->ndwc) : launch_hband_ndwc<3, false>(ctx, a, g.n, lds, tc->ndwc);
-        else if (g.channels == 1) rc = aligned ? launch_hband_ndwc<1, true>(ctx, a, g.n, lds, tc->ndwc) : launch_hband_ndwc<1, false>(ctx, a, g.n, lds, tc->ndwc);
-        else rc = aligned ? launch_hband_ndwc<4, true>(ctx, a, g.n, lds, tc->ndwc) : launch_hband_ndwc<4, false>(ctx, a, g.n, lds, tc->ndwc);
-        if (rc != KE_OK) return rc;
-        if (plan) ++plan[KE_RP_LAUNCHES];
-    }
-    return launch_vtile(ctx, a.hs, a.hp, g.n, ow, oh, cvt, d_tiles, plan);
-}
+// every instantiation of ke_hband: [bytes per pixel 3 / 1 / 4][dword or funnel-shift loader][chunk dwords / 8 - 1]
+using KeHbandKernel = void (*)(KeBandArgs);
+#define KE_HBAND_ROW(C, A) {ke_hband<8, C, A>, ke_hband<16, C, A>, ke_hband<24, C, A>, ke_hband<32, C, A>}
+const KeHbandKernel kHbandKernels[3][2][4] = {{KE_HBAND_ROW(3, true), KE_HBAND_ROW(3, false)},
+                                              {KE_HBAND_ROW(1, true), KE_HBAND_ROW(1, false)},
+                                              {KE_HBAND_ROW(4, true), KE_HBAND_ROW(4, false)}};
+#undef KE_HBAND_ROW
 
 // Vertical taps of the banded paths on the matrix cores: T[yy][col] = sum_y k[yy][y] * hs[col][y] is the product of the tap
 // matrix (A: 16 outputs x 64 rows per step, the KeMxTable image of the vertical axis) with the transposed columns, which
@@ -1218,33 +1118,58 @@ __global__ __launch_bounds__(256) void ke_vtile_mx(const KeVtileMxArgs a) {
     }
 }
 
-// vertical taps of the banded paths: hs[img][ow][hp] signed bytes -> (oh x ow) u8 tiles
-int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles, int32_t *plan) {
-    const bool on_mx = oh <= 128 && !getenv("KE_VTILE_VALU");
-    if (plan) plan[KE_RP_VMX] = on_mx ? 1 : 0;
-    if (on_mx) {
-        const KeMxTable *mx = ke_get_mx(ctx, cvt);
-        if (!mx) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+// Every reason a plan declines for is KE_EUNSUPPORTED to the caller; one of them comes with a message.
+int declined(ke_ctx *ctx, KeDecline why) {
+    return why == KE_DECLINE_ONE_LAUNCH ? ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch") : KE_EUNSUPPORTED;
+}
+
+KePlanShape shape_of(const KeHashGroup &g) {
+    return {g.w, g.h, g.channels, g.n, g.misaligned, (uintptr_t)g.pixels % 4 == 0, g.stride % 4 == 0, g.offsets != nullptr};
+}
+
+// The one place this file reads the environment: once per ke_launch_hash_group / ke_launch_resize_group call.
+KeHashSwitches read_switches() {
+    KeHashSwitches sw;
+    if (const char *e = getenv("KE_FUSED_MIN_IMAGES")) { sw.fused_min_set = true; sw.fused_min_images = atoll(e); }
+    sw.vtile_valu = getenv("KE_VTILE_VALU") != nullptr;
+    return sw;
+}
+
+// the taps of both axes of a resize; box (nullable) = {x0, y0, x1, y1}
+struct KeAxes {
+    const KeAxisCoeffs *hz, *vt;
+};
+int fetch_axes(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, int filter, const float *box, KeAxes *ax) {
+    ax->hz = box ? ke_get_coeffs(ctx, g.w, ow, filter, box[0], box[2]) : ke_get_coeffs(ctx, g.w, ow, filter);
+    ax->vt = box ? ke_get_coeffs(ctx, g.h, oh, filter, box[1], box[3]) : ke_get_coeffs(ctx, g.h, oh, filter);
+    return ax->hz && ax->vt ? KE_OK : ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+}
+
+// vertical taps of the banded paths: hs[img][ow][hp] signed bytes -> (oh x ow) u8 tiles.  ran (nullable): the plan that ran.
+int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles,
+                 const KeHashSwitches &sw, KeVtilePlan *ran = nullptr) {
+    const KeMxTable *mx = nullptr;
+    if (ke_vtile_on_mx(oh, sw) && !(mx = ke_get_mx(ctx, cvt))) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+    const KeVtilePlan p = ke_plan_vtile(ow, oh, hp, n, sw, mx ? mx->tiles : 0);
+    if (p.why) return declined(ctx, p.why);
+    if (ran) *ran = p;
+    if (p.on_mx) {
         KeVtileMxArgs m;
         std::memset(&m, 0, sizeof m);
         m.hs = hs; m.hp = hp; m.ow = ow; m.oh = oh;
-        m.frag = mx->d_frag; m.ks = mx->ks; m.mt = mx->tiles; m.nt = (ow + 15) / 16;
+        m.frag = mx->d_frag; m.ks = mx->ks; m.mt = mx->tiles; m.nt = p.nt;
         for (int j = 0; j < mx->tiles; ++j) m.base[j] = mx->base[j];
         m.bias = cvt->d_bias; m.tiles = d_tiles;
-        m.items = n * m.mt * m.nt;
-        const int64_t blocks = (m.items + 3) / 4;
-        if (blocks > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch");
-        hipLaunchKernelGGL(ke_vtile_mx, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, m);
-        KE_HIP(ctx, hipGetLastError());
-        return KE_OK;
+        m.items = p.items;
+        hipLaunchKernelGGL(ke_vtile_mx, dim3((unsigned)p.blocks), dim3(256), 0, ctx->stream, m);
+    } else {
+        KeVtileArgs v;
+        v.hs = hs; v.hp = hp; v.ow = ow; v.oh = oh;
+        v.packed = cvt->d_packed; v.start = cvt->d_start; v.bias = cvt->d_bias; v.ndw = cvt->ndw;
+        v.cg = p.cg;
+        v.tiles = d_tiles;
+        hipLaunchKernelGGL(ke_vtile, dim3((unsigned)n), dim3(256), p.lds, ctx->stream, v);
     }
-    KeVtileArgs v;
-    v.hs = hs; v.hp = hp; v.ow = ow; v.oh = oh;
-    v.packed = cvt->d_packed; v.start = cvt->d_start; v.bias = cvt->d_bias; v.ndw = cvt->ndw;
-    v.cg = std::max(1, std::min(ow, (48 * 1024) / hp));
-    v.tiles = d_tiles;
-    if ((size_t)v.cg * hp > 64 * 1024) return KE_EUNSUPPORTED;
-    hipLaunchKernelGGL(ke_vtile, dim3((unsigned)n), dim3(256), (size_t)v.cg * hp, ctx->stream, v);
     KE_HIP(ctx, hipGetLastError());
     return KE_OK;
 }
@@ -1277,8 +1202,7 @@ struct KeStripArgs {
     int hp;
 };
 
-constexpr int kSW = 2048;                 // strip width in pixels: 16 rows of it are one LDS buffer
-constexpr int kSLP = kSW + 16;            // LDS pitch of a strip row (129 x 16 B: conflict-free operand rows)
+constexpr int kSW = kKeStripWidth, kSLP = kKeStripPitch;   // the strip geometry (ke_resample_plan.h)
 
 // The strip geometry is compile-time on purpose: a run-time strip width (equal strips, no nearly empty last one)
 // costs row/column registers per load slot, spills at 1024 threads x 128 registers and ran 25 % slower.
@@ -1408,115 +1332,125 @@ __global__ __launch_bounds__(1024) void ke_hstrips(const KeStripArgs a) {
     }
 }
 
-int launch_vtile(ke_ctx *ctx, const uint8_t *hs, int hp, int64_t n, int ow, int oh, const KeAxisCoeffs *cvt, uint8_t *d_tiles, int32_t *plan);
+// What resample_to_tiles ran for a group: the plans ke_last_resize_plan is written from.
+struct KeRanPlan {
+    bool banded;
+    int ndwc;               // banded: chunk dwords of the horizontal pass
+    KeHbandPlan hband;
+    KeVtilePlan vtile;
+    KeGenericPlan generic;  // !banded
+};
+
+// Banded target: src images -> (oh x ow) u8 tiles.  Returns KE_EUNSUPPORTED for shapes it does not take
+// (Pillow's vertical-first rule, images under 4 pixels, windows beyond 32 chunks of 32 dwords).
+int resample_banded(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles, const KeHashSwitches &sw, int filter,
+                    const float *box, KeRanPlan *ran) {
+    KeAxes ax;
+    KE_TRY(fetch_axes(ctx, g, ow, oh, filter, box, &ax));
+    const KePlanShape shape = shape_of(g);
+    const KeHbandChunks chunks = ke_plan_hband_chunks(shape, ow, oh, ax.hz->ndw);
+    if (chunks.why) return declined(ctx, chunks.why);
+    const KeChunkTable *tc = ke_get_chunks(ctx, ax.hz, 1 << chunks.best_log2, 8);
+    if (!tc) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+    const KeHbandPlan p = ke_plan_hband(shape, ow, chunks.best_log2, tc->cspan, ax.vt->span);
+    if (p.why) return declined(ctx, p.why);
+    if (tc->ndwc < 8 || tc->ndwc > 32 || tc->ndwc % 8) return KE_EUNSUPPORTED;
+    void *hs;
+    KE_TRY(ke_reserve(ctx, KE_BUF_TMP, p.scratch_bytes, &hs));
+    KeBandArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.w = g.w; a.h = g.h;
+    a.qr = p.qr; a.lp = p.lp; a.rt = p.rt; a.band_rows = p.band_rows; a.bands = p.bands; a.bp = p.bp;
+    a.nout_total = ow; a.cpo_log2 = p.best_log2;
+    a.cpacked = tc->d_cpacked; a.cstart = tc->d_cstart; a.cxor = tc->d_cxor; a.bias = ax.hz->d_bias;
+    a.lt_half = p.lt_half;
+    a.hs = (uint8_t *)hs; a.hp = p.hp;
+    const KeHbandKernel kernel = kHbandKernels[g.channels == 3 ? 0 : g.channels == 1 ? 1 : 2][p.aligned ? 0 : 1][tc->ndwc / 8 - 1];
+    for (int i = 0; i < p.launches; ++i) {
+        const KeHbandLaunch l = ke_hband_launch(p, ow, i);
+        a.out_first = l.out_first; a.nout = l.nout; a.vcp_log2 = l.vcp_log2;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(g.n * p.bands)), dim3(256), p.lds, ctx->stream, a);
+        KE_HIP(ctx, hipGetLastError());
+    }
+    KeVtilePlan vtile;
+    KE_TRY(launch_vtile(ctx, a.hs, a.hp, g.n, ow, oh, ax.vt, d_tiles, sw, &vtile));
+    if (ran) { ran->banded = true; ran->ndwc = tc->ndwc; ran->hband = p; ran->vtile = vtile; }
+    return KE_OK;
+}
+
+// every instantiation of ke_hstrips: [32 or 9 output columns][operand steps per wave - 3]
+using KeStripKernel = void (*)(KeStripArgs);
+const KeStripKernel kStripKernels[2][4] = {{ke_hstrips<3, 2>, ke_hstrips<4, 2>, ke_hstrips<5, 2>, ke_hstrips<6, 2>},
+                                           {ke_hstrips<3, 1>, ke_hstrips<4, 1>, ke_hstrips<5, 1>, ke_hstrips<6, 1>}};
 
 // (32 x 32) or (8 x 9) tile of packed RGB images 2816..5300 pixels wide, large groups only
-int resample_strips(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles) {
-    if (!((ow == 32 && oh == 32) || (ow == 9 && oh == 8))) return KE_EUNSUPPORTED;
-    if (g.misaligned || g.channels != 3 || g.w % 4 || g.w <= 2048 || (int64_t)g.h > (int64_t)g.w * 100 || g.h == oh) return KE_EUNSUPPORTED;
-    if ((int64_t)g.w * g.h * 3 >= (1LL << 31) || (uintptr_t)g.pixels % 4 || !(g.offsets || g.stride % 4 == 0)) return KE_EUNSUPPORTED;
-    const KeAxisCoeffs *chz = ke_get_coeffs(ctx, g.w, ow);
-    const KeAxisCoeffs *cvt = ke_get_coeffs(ctx, g.h, oh);
-    if (!chz || !cvt) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    const int nt = (ow + 15) / 16, parts = 16 / nt;
-    // natural step count with 64-aligned bases decides the instantiation
-    int ks = 0;
-    for (int j = 0; j < nt; ++j) {
-        int lo = g.w, hi = 0;
-        for (int o = 16 * j; o < std::min(16 * j + 16, ow); ++o) { lo = std::min(lo, chz->bounds[2 * o]); hi = std::max(hi, chz->bounds[2 * o] + chz->bounds[2 * o + 1]); }
-        ks = std::max(ks, (hi - (lo & ~63) + 63) / 64);
-    }
-    const int ksh = std::max((ks + parts - 1) / parts, 3);
-    if (ksh > 6) return KE_EUNSUPPORTED;
-    const KeMxTable *mx = ke_get_mx(ctx, chz, parts * ksh, true);
+int resample_strips(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles, const KeHashSwitches &sw) {
+    KeAxes ax;
+    KE_TRY(fetch_axes(ctx, g, ow, oh, KE_FILTER_LANCZOS, nullptr, &ax));
+    const KePlanShape shape = shape_of(g);
+    const KeStripSteps steps = ke_plan_strips_steps(shape, ow, oh, ax.hz->bounds.data());
+    if (steps.why) return declined(ctx, steps.why);
+    const KeMxTable *mx = ke_get_mx(ctx, ax.hz, steps.parts * steps.ksh, true);
     if (!mx) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    if (mx->tiles != nt || mx->ks != parts * ksh || mx->base[0] % 64 || (nt == 2 && mx->base[1] % 64)) return KE_EUNSUPPORTED;
+    const KeStripPlan p = ke_plan_strips(shape, ow, steps, *mx, ax.vt->span, ctx->cu_count, sw);
+    if (p.why) return declined(ctx, p.why);
+    void *hs;
+    KE_TRY(ke_reserve(ctx, KE_BUF_TMP, p.scratch_bytes, &hs));
     KeStripArgs a;
     std::memset(&a, 0, sizeof a);
     a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.w = g.w; a.h = g.h;
-    a.nstrips = (g.w + kSW - 1) / kSW;
-    // a nearly empty last strip costs a full strip of load slots: rows that leave less than 3/8 of one stay banded
-    if (g.w - (a.nstrips - 1) * kSW < 768) return KE_EUNSUPPORTED;
-    // bands of up to 256 rows, equal, multiples of 16; only worth it when the bands fill the chip
-    const int64_t want_bands = (g.h + 255) / 256;
-    a.band_rows = (int)((((g.h + want_bands - 1) / want_bands) + 15) / 16 * 16);
-    a.bands = (g.h + a.band_rows - 1) / a.band_rows;
-    // few workgroups cannot fill the chip: such groups keep the banded kernel (smaller bands, up to 3072 workgroups);
-    // KE_FUSED_MIN_IMAGES, when set, decides instead (as for the single-pass kernels)
-    if (const char *e = getenv("KE_FUSED_MIN_IMAGES")) {
-        if (g.n < atoll(e)) return KE_EUNSUPPORTED;
-    } else if (g.n * a.bands < 2 * (int64_t)ctx->cu_count) {
-        return KE_EUNSUPPORTED;
-    }
-    a.mx_frag = mx->d_frag; a.base0 = mx->base[0]; a.base1 = nt == 2 ? mx->base[1] : 0;
-    a.bias = chz->d_bias;
+    a.nstrips = p.nstrips; a.band_rows = p.band_rows; a.bands = p.bands;
+    a.mx_frag = mx->d_frag; a.base0 = p.base0; a.base1 = p.base1;
+    a.bias = ax.hz->d_bias;
     a.ncols = ow;
-    a.bp = a.band_rows + 4;
-    size_t lds = 2 * (size_t)16 * kSLP;
-    a.x_off = (int)lds; lds += (size_t)2 * nt * (parts - 1) * 1024;
-    a.hb_off = (int)lds; lds += (size_t)ow * a.bp;
-    a.hp = ((std::max(cvt->span, g.h + 4) + 7) & ~7) + 8;
-    void *hs;
-    KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)g.n * ow * a.hp + 8192, &hs));
-    a.hs = (uint8_t *)hs;
-    if ((int64_t)g.n * a.bands > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch");
-    const dim3 grid((unsigned)(g.n * a.bands)), blk(1024);
-#define KE_STRIPS(K, T) do { \
-        KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&ke_hstrips<K, T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((ke_hstrips<K, T>), grid, blk, lds, ctx->stream, a); } while (0)
-    if (nt == 2) {
-        switch (ksh) { case 3: KE_STRIPS(3, 2); break; case 4: KE_STRIPS(4, 2); break; case 5: KE_STRIPS(5, 2); break; default: KE_STRIPS(6, 2); break; }
-    } else {
-        switch (ksh) { case 3: KE_STRIPS(3, 1); break; case 4: KE_STRIPS(4, 1); break; case 5: KE_STRIPS(5, 1); break; default: KE_STRIPS(6, 1); break; }
-    }
-#undef KE_STRIPS
+    a.bp = p.bp; a.x_off = p.x_off; a.hb_off = p.hb_off;
+    a.hs = (uint8_t *)hs; a.hp = p.hp;
+    const KeStripKernel kernel = kStripKernels[steps.nt == 2 ? 0 : 1][steps.ksh - 3];
+    KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(g.n * p.bands)), dim3(1024), p.lds, ctx->stream, a);
     KE_HIP(ctx, hipGetLastError());
-    return launch_vtile(ctx, a.hs, a.hp, g.n, ow, oh, cvt, d_tiles);
+    return launch_vtile(ctx, a.hs, a.hp, g.n, ow, oh, ax.vt, d_tiles, sw);
 }
 
 // Generic target: src images -> (oh x ow) u8 tiles, two single-axis passes in Pillow's order.
-int resample_generic(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles, int filter = KE_FILTER_LANCZOS,
-                     const float *box = nullptr, int32_t *plan = nullptr) {
-    const KeAxisCoeffs *chz = box ? ke_get_coeffs(ctx, g.w, ow, filter, box[0], box[2]) : ke_get_coeffs(ctx, g.w, ow, filter);
-    const KeAxisCoeffs *cvt = box ? ke_get_coeffs(ctx, g.h, oh, filter, box[1], box[3]) : ke_get_coeffs(ctx, g.h, oh, filter);
-    if (!chz || !cvt) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    // Pillow's Image.resize shrinks very tall, narrow images vertically first (PIL/Image.py).
-    const bool vertical_first = (int64_t)g.h > (int64_t)g.w * 100 && oh < g.h;
-    if (plan) {   // whatever the banded path wrote before it declined goes
-        for (int k = 0; k < KE_RP_COUNT; ++k) plan[k] = -1;
-        plan[KE_RP_BANDED] = 0; plan[KE_RP_VFIRST] = vertical_first ? 1 : 0;
-    }
-    const int mid_w = vertical_first ? g.w : ow, mid_h = vertical_first ? oh : g.h;
-    const size_t mid_bytes = (size_t)mid_w * mid_h;
-    const int64_t max_n = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20) / mid_bytes));
-    if (g.n > max_n) {   // bound the first-pass scratch: split the group
-        for (int64_t f = 0; f < g.n; f += max_n) {
-            KeHashGroup s = g;
-            s.n = std::min(max_n, g.n - f);
-            if (g.offsets) s.offsets = g.offsets + f; else s.pixels = g.pixels + (size_t)f * g.stride;
-            KE_TRY(resample_generic(ctx, s, ow, oh, d_tiles + (size_t)f * ow * oh, filter, box, plan));
+int resample_generic(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles, int filter, const float *box, KeRanPlan *ran) {
+    KeAxes ax;
+    KE_TRY(fetch_axes(ctx, g, ow, oh, filter, box, &ax));
+    const KeAxisCoeffs *chz = ax.hz, *cvt = ax.vt;
+    const KeGenericPlan p = ke_plan_generic(g.w, g.h, ow, oh);
+    if (ran) { ran->banded = false; ran->generic = p; }
+    for (int64_t f = 0; f < g.n; f += p.max_n) {   // bound the first-pass scratch: split the group
+        const KeHashGroup s = ke_sub_group(g, f, std::min(p.max_n, g.n - f));
+        uint8_t *dst = d_tiles + (size_t)f * ow * oh;
+        void *tmp;
+        KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)s.n * p.mid_bytes, &tmp));
+        if (!ke_fits_one_launch(s.n * p.b0)) return declined(ctx, KE_DECLINE_ONE_LAUNCH);
+        if (!p.vertical_first) {
+            hipLaunchKernelGGL(ke_resample_pass<0>, dim3((unsigned)(s.n * p.b0)), dim3(256), 0, ctx->stream, s.pixels, s.offsets,
+                               s.stride, s.channels, s.w, s.h, chz->d_bounds, chz->d_kk, chz->ksize, ow, (uint8_t *)tmp, p.b0);
+            hipLaunchKernelGGL(ke_resample_pass<1>, dim3((unsigned)(s.n * p.b1)), dim3(256), 0, ctx->stream, (const uint8_t *)tmp,
+                               (const uint64_t *)nullptr, (uint64_t)p.mid_bytes, 1, p.mid_w, p.mid_h, cvt->d_bounds, cvt->d_kk,
+                               cvt->ksize, oh, dst, p.b1);
+        } else {
+            hipLaunchKernelGGL(ke_resample_pass<1>, dim3((unsigned)(s.n * p.b0)), dim3(256), 0, ctx->stream, s.pixels, s.offsets,
+                               s.stride, s.channels, s.w, s.h, cvt->d_bounds, cvt->d_kk, cvt->ksize, oh, (uint8_t *)tmp, p.b0);
+            hipLaunchKernelGGL(ke_resample_pass<0>, dim3((unsigned)(s.n * p.b1)), dim3(256), 0, ctx->stream, (const uint8_t *)tmp,
+                               (const uint64_t *)nullptr, (uint64_t)p.mid_bytes, 1, p.mid_w, p.mid_h, chz->d_bounds, chz->d_kk,
+                               chz->ksize, ow, dst, p.b1);
         }
-        return KE_OK;
+        KE_HIP(ctx, hipGetLastError());
     }
-    void *tmp;
-    KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)g.n * mid_bytes, &tmp));
-    const int b0 = (int)((mid_bytes + 255) / 256), b1 = (ow * oh + 255) / 256;
-    if ((int64_t)g.n * b0 > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch");
-    if (!vertical_first) {
-        hipLaunchKernelGGL(ke_resample_pass<0>, dim3((unsigned)(g.n * b0)), dim3(256), 0, ctx->stream, g.pixels, g.offsets,
-                           g.stride, g.channels, g.w, g.h, chz->d_bounds, chz->d_kk, chz->ksize, ow, (uint8_t *)tmp, b0);
-        hipLaunchKernelGGL(ke_resample_pass<1>, dim3((unsigned)(g.n * b1)), dim3(256), 0, ctx->stream, (const uint8_t *)tmp,
-                           (const uint64_t *)nullptr, (uint64_t)mid_bytes, 1, mid_w, mid_h, cvt->d_bounds, cvt->d_kk,
-                           cvt->ksize, oh, d_tiles, b1);
-    } else {
-        hipLaunchKernelGGL(ke_resample_pass<1>, dim3((unsigned)(g.n * b0)), dim3(256), 0, ctx->stream, g.pixels, g.offsets,
-                           g.stride, g.channels, g.w, g.h, cvt->d_bounds, cvt->d_kk, cvt->ksize, oh, (uint8_t *)tmp, b0);
-        hipLaunchKernelGGL(ke_resample_pass<0>, dim3((unsigned)(g.n * b1)), dim3(256), 0, ctx->stream, (const uint8_t *)tmp,
-                           (const uint64_t *)nullptr, (uint64_t)mid_bytes, 1, mid_w, mid_h, chz->d_bounds, chz->d_kk,
-                           chz->ksize, ow, d_tiles, b1);
-    }
-    KE_HIP(ctx, hipGetLastError());
     return KE_OK;
+}
+
+// The fall-back chain behind every tile: the strip kernel where the caller tries it (the resize entry does not), the
+// banded path, the generic passes.  ran (nullable): the plans of the path that ran.
+int resample_to_tiles(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, uint8_t *d_tiles, const KeHashSwitches &sw, bool try_strips,
+                      int filter = KE_FILTER_LANCZOS, const float *box = nullptr, KeRanPlan *ran = nullptr) {
+    int rc = try_strips ? resample_strips(ctx, g, ow, oh, d_tiles, sw) : KE_EUNSUPPORTED;
+    if (rc == KE_EUNSUPPORTED) rc = resample_banded(ctx, g, ow, oh, d_tiles, sw, filter, box, ran);
+    if (rc == KE_EUNSUPPORTED) rc = resample_generic(ctx, g, ow, oh, d_tiles, filter, box, ran);
+    return rc;
 }
 
 // The single-pass kernels behind the rows of ke_hash_select.h: the same list expanded a second time, for the pointers alone.
@@ -1526,23 +1460,33 @@ const KeFusedKernel kSpKernels[] = {KE_SINGLE_PASS_ROWS(KE_SP_KERNEL)};
 #undef KE_SP_KERNEL
 static_assert(sizeof(kSpKernels) / sizeof(kSpKernels[0]) == kKeSpRowCount, "one kernel per row");
 
+// Band mode of the single-pass kernels (see KeFusedArgs::bands): how a group is cut, and where the columns go.
+struct KeBandTarget {
+    const KeSpBandPlan *plan;
+    uint8_t *hs, *hsd;
+};
+
 // Launches row r of the table on a group, or declines (KE_EUNSUPPORTED) where the row's tables or its LDS needs do not
 // fit.  Both families take the same KeFusedArgs; they differ in the tile (32 rows by 256 threads, 16 by 512), in how
 // the operand steps are counted, and in the exchange area behind the columns.
 int launch_fused(ke_ctx *ctx, int r, const KeHashGroup &g, const KeAxisCoeffs *ch, const KeAxisCoeffs *cv, uint64_t *d_phash,
-                 uint8_t *d_tile32, uint64_t *d_dhash, uint8_t *d_tile98, const KeBandPlan *plan) {
-    const KeSpRow &row = kKeSpRows[r];
-    const bool wide = row.family == KE_SP_WIDE, DH = row.dh();
-    const int W = g.w, C = row.channels();
-    const int rt = wide ? kRTW : kRTM, threads = wide ? 512 : 256;
-    const int ks = wide ? 4 * row.t[0] : row.t[1];                     // operand steps per output tile: a quarter per wave, or KS
-    // dHash steps: the whole row in eight parts of KDW steps, or in two halves of KD = ceil(W64 / 2) steps
-    const int ksd = wide ? 8 * row.t[3] : 2 * ((row.t[0] + 1) / 2);
-    const bool exact = !wide && !row.t[3];                             // compile-time row length
-    if ((W % 4 != 0) != row.unal() || (wide ? kRTW * ((W + 3) / 4) > 512 * row.t[1] : W < row.w_lo || W > row.w_hi)) return KE_EUNSUPPORTED;
-    const KeMxTable *mx = ke_get_mx(ctx, ch, ks);     // at least ks steps per tile (zero-padded)
+                 uint8_t *d_tile32, uint64_t *d_dhash, uint8_t *d_tile98, const KeBandTarget *bands) {
+    const bool DH = kKeSpRows[r].dh();
+    const KeFusedSteps steps = ke_plan_fused_steps(r, g.w);
+    if (steps.why) return declined(ctx, steps.why);
+    const KeMxTable *mx = ke_get_mx(ctx, ch, steps.ks);     // at least ks steps per tile (zero-padded)
     if (!mx) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    if (mx->tiles != 2 || mx->ks != ks) return KE_EUNSUPPORTED;
+    const KeAxisCoeffs *chd = nullptr, *cvd = nullptr;
+    const KeMxTable *mxd = nullptr;
+    const KeChunkTable *tv = nullptr;
+    if (DH) {
+        chd = ke_get_coeffs(ctx, g.w, 9); cvd = ke_get_coeffs(ctx, g.h, 8);
+        if (!chd || !cvd) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+        mxd = ke_get_mx(ctx, chd, steps.ksd); tv = ke_get_chunks(ctx, cvd, 3);
+        if (!mxd || !tv) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+    }
+    const KeFusedPlan p = ke_plan_fused(r, g.w, g.h, g.n, steps, *mx, cv->span, mxd, tv, bands ? bands->plan : nullptr);
+    if (p.why) return declined(ctx, p.why);
     KeFusedArgs a;
     std::memset(&a, 0, sizeof a);
     a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.out_idx = g.out_idx; a.h = g.h;
@@ -1550,68 +1494,37 @@ int launch_fused(ke_ctx *ctx, int r, const KeHashGroup &g, const KeAxisCoeffs *c
     a.v_packed = cv->d_packed; a.v_start = cv->d_start; a.v_bias = cv->d_bias;
     a.ndwv = cv->ndw;
     a.mx_frag = mx->d_frag; a.mx_base0 = mx->base[0]; a.mx_base1 = mx->base[1];
-    const int rows_padded = plan ? plan->band_rows : ((g.h + rt - 1) / rt) * rt;
-    if (plan) { a.bands = plan->bands; a.band_rows = plan->band_rows; a.hs = plan->hs; a.hsd = plan->hsd; a.hs_hp = plan->hs_hp; a.hsd_hp = plan->hsd_hp; }
-    // one tile buffer: rt padded rows + the part of the last row's operand window that overhangs the row
-    const int overhang = std::max(0, std::max(std::max(mx->base[0], mx->base[1]) + 64 * ks, DH ? 64 * ksd : 0) - W);
-    a.qw = (W + 3) / 4;
-    a.w = W; a.row_bytes = W * C;
-    a.qw_inv = (int)(uint32_t)((0x100000000ull + (uint64_t)a.qw - 1) / (uint64_t)a.qw);
-    // row pitch: an odd number of 16-byte units, so the 16 rows of an operand land in distinct bank groups
-    a.lp = exact ? W + 16 : (((W + 15) / 16 + 1) | 1) * 16;
-    a.lt_half = (rt * a.lp + overhang + 15) & ~15;
-    a.lt_bytes = 2 * a.lt_half;
-    a.hp = ((std::max(plan ? 0 : cv->span, rows_padded) + 7) & ~7) + 8;
-    a.hpd = 8;
+    if (bands) { a.bands = bands->plan->bands; a.band_rows = bands->plan->band_rows; a.hs = bands->hs; a.hsd = bands->hsd; a.hs_hp = bands->plan->hs_hp; a.hsd_hp = bands->plan->hsd_hp; }
+    a.qw = p.qw; a.qw_inv = p.qw_inv; a.lp = p.lp;
+    a.w = g.w; a.row_bytes = p.row_bytes;
+    a.lt_half = p.lt_half; a.lt_bytes = 2 * p.lt_half;
+    a.hp = p.hp; a.hpd = p.hpd; a.x_off = p.x_off;
     a.phash = d_phash; a.tile32_out = d_tile32; a.margin = ctx->margin_cur;
-    size_t lds = (size_t)a.lt_bytes + (size_t)32 * a.hp;
-    if (!wide) lds = std::max<size_t>(lds, 4096);
     if (DH) {
-        const KeAxisCoeffs *chd = ke_get_coeffs(ctx, g.w, 9), *cvd = ke_get_coeffs(ctx, g.h, 8);
-        if (!chd || !cvd) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-        const KeMxTable *mxd = ke_get_mx(ctx, chd, ksd);
-        const KeChunkTable *tv = ke_get_chunks(ctx, cvd, 3);
-        if (!mxd || !tv) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-        if (mxd->tiles != 1 || mxd->base[0] != 0 || mxd->ks != ksd) return KE_EUNSUPPORTED;
         a.mxd_frag = mxd->d_frag;
         a.hd_bias = chd->d_bias;
         a.vd_cpacked = tv->d_cpacked; a.vd_cstart = tv->d_cstart; a.vd_bias = cvd->d_bias;
         a.ndwcv = tv->ndwc;
-        a.hpd = ((std::max(plan ? 0 : tv->cspan, rows_padded) + 7) & ~7) + 8;
         a.dhash = d_dhash; a.tile98_out = d_tile98;
-        lds += (size_t)9 * a.hpd;
     }
-    // the exchange area X behind the columns: the wide kernel's waves always meet there (12 KB, and 14 KB more for the
-    // dHash leg), the narrow kernel's only for its dHash leg (4 KB)
-    if (wide || DH) {
-        lds = (lds + 15) & ~(size_t)15;
-        a.x_off = (int)lds;
-        lds += wide ? 2 * 2 * 3 * 1024 + (DH ? 2 * 7 * 1024 : 0) : 4096;
-    }
-    // up to 80 KB two workgroups share a CU.  A tall image (its 32 x H transposed columns) would need more and run one
-    // per CU; if cutting it into bands brings the columns back under that line, decline: the caller then runs this
-    // kernel per band (measured 5.4-6.0 TB/s against 3.9-4.9 for one workgroup per CU)
-    if (lds > 150 * 1024) return KE_EUNSUPPORTED;
-    if (!plan && lds > 80 * 1024 && lds - (size_t)(32 * (a.hp - 136)) - (DH ? (size_t)(9 * (a.hpd - 136)) : 0) <= 80 * 1024) return KE_EUNSUPPORTED;
-    if (lds > 64 * 1024)
-        KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kSpKernels[r]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (g.n * (plan ? plan->bands : 1) > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "group too large for one launch");
-    hipLaunchKernelGGL(kSpKernels[r], dim3((unsigned)(g.n * (plan ? plan->bands : 1))), dim3(threads), lds, ctx->stream, a);
+    if (p.raise_lds_limit)
+        KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kSpKernels[r]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+    hipLaunchKernelGGL(kSpKernels[r], dim3((unsigned)p.workgroups), dim3(p.threads), p.lds, ctx->stream, a);
     KE_HIP(ctx, hipGetLastError());
     return KE_OK;
 }
 
 // Picks the single-pass kernel for a group (row length, bytes per pixel, one or both hashes) and launches it: the rows
 // ke_single_pass_candidates lists, in its order, until one does not decline.
-// plan == NULL: one workgroup per image, hashes (and optional tiles) written directly.  plan != NULL: band mode, the
-// transposed columns go to plan->hs / plan->hsd and the caller finishes with ke_vtile.  *did_d: dHash was covered too.
+// bands == NULL: one workgroup per image, hashes (and optional tiles) written directly.  bands != NULL: band mode, the
+// transposed columns go to bands->hs / bands->hsd and the caller finishes with ke_vtile.  *did_d: dHash was covered too.
 // Returns KE_EUNSUPPORTED when no single-pass kernel takes the shape (or its LDS needs exceed the CU).
 int dispatch_single_pass(ke_ctx *ctx, const KeHashGroup &g, bool want_d, uint64_t *d_phash, uint8_t *d_t32, uint64_t *d_dhash,
-                         uint8_t *d_t98, const KeBandPlan *plan, bool *did_d) {
+                         uint8_t *d_t98, const KeBandTarget *bands, bool *did_d) {
     *did_d = false;
     // ragged groups: ke_hash_images checks every offset and sets g.misaligned when one is not a multiple of 4
     const KeSpShape shape{g.w, g.h, g.channels, g.misaligned, (uintptr_t)g.pixels % 4 == 0, g.offsets || g.stride % 4 == 0,
-                          want_d, plan != nullptr};
+                          want_d, bands != nullptr};
     int rows[kKeSpMaxCandidates];
     const int n = ke_single_pass_candidates(shape, rows);
     if (!n) return KE_EUNSUPPORTED;
@@ -1620,7 +1533,7 @@ int dispatch_single_pass(ke_ctx *ctx, const KeHashGroup &g, bool want_d, uint64_
     if (!ch || !cv) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
     for (int k = 0; k < n; ++k) {
         const bool dh = kKeSpRows[rows[k]].dh();
-        const int rc = launch_fused(ctx, rows[k], g, ch, cv, d_phash, d_t32, dh ? d_dhash : nullptr, dh ? d_t98 : nullptr, plan);
+        const int rc = launch_fused(ctx, rows[k], g, ch, cv, d_phash, d_t32, dh ? d_dhash : nullptr, dh ? d_t98 : nullptr, bands);
         if (rc != KE_EUNSUPPORTED) { *did_d = dh && rc == KE_OK; return rc; }
     }
     return KE_EUNSUPPORTED;
@@ -1628,34 +1541,19 @@ int dispatch_single_pass(ke_ctx *ctx, const KeHashGroup &g, bool want_d, uint64_
 
 // The single-pass kernels per band of rows: for images whose transposed columns do not fit LDS, and for groups too
 // small to fill the GPU with one workgroup per image.  Tiles come out of ke_vtile as for every banded image.
-int resample_single_pass_banded(ke_ctx *ctx, const KeHashGroup &g, uint8_t *d_t32, uint8_t *d_t98, bool *did_d) {
+int resample_single_pass_banded(ke_ctx *ctx, const KeHashGroup &g, uint8_t *d_t32, uint8_t *d_t98, const KeHashSwitches &sw, bool *did_d) {
     *did_d = false;
-    if ((int64_t)g.h > (int64_t)g.w * 100 || g.h < 16) return KE_EUNSUPPORTED;
     const KeAxisCoeffs *cvt = ke_get_coeffs(ctx, g.h, 32);
     const KeAxisCoeffs *cvd = d_t98 ? ke_get_coeffs(ctx, g.h, 8) : nullptr;
     if (!cvt || (d_t98 && !cvd)) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
-    KeBandPlan plan;
-    // bands: at most 1024 rows (32 KB of columns in LDS), and enough of them that the launch has ~4 workgroups per CU
-    const int64_t fill = (4 * (int64_t)ctx->cu_count + g.n - 1) / g.n;
-    // ... and short enough that two workgroups share a CU (80 KB each) where the kernel's fixed LDS allows it
-    const bool both = d_t98 != nullptr && g.channels == 3;
-    const int64_t fixed = (g.w <= 768 && !(both && g.w > 512)) ? 64 * (int64_t)(g.w + 32) + (both ? 4096 : 0)
-                                                               : 32 * (int64_t)(g.w + 32) + 12288 + (both ? 14336 : 0);
-    int64_t max_rows = (80 * 1024 - fixed) / (both ? 41 : 32) / 32 * 32 - 32;
-    if (max_rows < 128) max_rows = 1024;
-    max_rows = std::min<int64_t>(max_rows, 1024);
-    int64_t bands = std::max<int64_t>((g.h + max_rows - 1) / max_rows, std::min<int64_t>(fill, (g.h + 63) / 64));
-    plan.band_rows = (int)(((g.h + bands - 1) / bands + 31) / 32 * 32);
-    plan.bands = (g.h + plan.band_rows - 1) / plan.band_rows;
-    plan.hs_hp = ((std::max(cvt->span, g.h + 4) + 7) & ~7) + 8;
-    plan.hsd_hp = cvd ? ((std::max(cvd->span, g.h + 4) + 7) & ~7) + 8 : 8;
+    const KeSpBandPlan p = ke_plan_sp_bands(shape_of(g), d_t98 != nullptr, cvt->span, cvd ? cvd->span : 0, ctx->cu_count);
+    if (p.why) return declined(ctx, p.why);
     void *hs;
-    KE_TRY(ke_reserve(ctx, KE_BUF_TMP, (size_t)g.n * (32 * (size_t)plan.hs_hp + (cvd ? 9 * (size_t)plan.hsd_hp : 0)) + 8192, &hs));
-    plan.hs = (uint8_t *)hs;
-    plan.hsd = cvd ? plan.hs + (size_t)g.n * 32 * plan.hs_hp : nullptr;
-    KE_TRY(dispatch_single_pass(ctx, g, d_t98 != nullptr, nullptr, nullptr, nullptr, nullptr, &plan, did_d));
-    KE_TRY(launch_vtile(ctx, plan.hs, plan.hs_hp, g.n, 32, 32, cvt, d_t32));
-    if (*did_d) KE_TRY(launch_vtile(ctx, plan.hsd, plan.hsd_hp, g.n, 9, 8, cvd, d_t98));
+    KE_TRY(ke_reserve(ctx, KE_BUF_TMP, p.scratch_bytes, &hs));
+    const KeBandTarget bands{&p, (uint8_t *)hs, cvd ? (uint8_t *)hs + (size_t)g.n * 32 * p.hs_hp : nullptr};
+    KE_TRY(dispatch_single_pass(ctx, g, d_t98 != nullptr, nullptr, nullptr, nullptr, nullptr, &bands, did_d));
+    KE_TRY(launch_vtile(ctx, bands.hs, p.hs_hp, g.n, 32, 32, cvt, d_t32, sw));
+    if (*did_d) KE_TRY(launch_vtile(ctx, bands.hsd, p.hsd_hp, g.n, 9, 8, cvd, d_t98, sw));
     return KE_OK;
 }
 
@@ -1664,17 +1562,11 @@ int resample_single_pass_banded(ke_ctx *ctx, const KeHashGroup &g, uint8_t *d_t3
 int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, uint64_t *d_dhash, uint8_t *d_tile32_out,
                          uint8_t *d_tile98_out, hipStream_t fused_stream) {
     KE_TRY(upload_dct_tables(ctx));
+    const KeHashSwitches sw = read_switches();
     const bool want_p = d_phash || d_tile32_out, want_d = d_dhash || d_tile98_out;
     bool p_done = false, d_done = false;
-    // The single-pass kernels give one workgroup a whole image, so a small group of large images cannot fill the chip
-    // that way; such a group runs the same kernels per band of rows (a single image is spread over the whole GPU).
-    // Measured crossover on MI355X: about 200 images at 512x512 and 1024^2, 500-700 at 2048^2, none below ~400 KB per
-    // image.  KE_FUSED_MIN_IMAGES overrides the threshold (tests set it to 1 to reach the one-workgroup-per-image form
-    // with a few images).
-    const int64_t image_bytes = (int64_t)g.w * g.h * g.channels;
-    int64_t fused_min = image_bytes < 400 * 1024 ? 1 : image_bytes < (8 << 20) ? 192 : 512;
-    if (const char *e = getenv("KE_FUSED_MIN_IMAGES")) fused_min = atoll(e);
-    if (want_p && g.n >= fused_min) {
+    // a group large enough for it (ke_fused_min_images) runs the single-pass kernels with one workgroup per image
+    if (want_p && g.n >= ke_fused_min_images((int64_t)g.w * g.h * g.channels, sw)) {
         bool did_d = false;
         // one workgroup per image: no scratch buffers, so the caller may put it on a side stream where it overlaps the
         // neighbouring size groups' kernels (what follows below uses the context's scratch and stays on the context's stream)
@@ -1685,22 +1577,14 @@ int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, u
         if (rc == KE_OK) { p_done = true; d_done = did_d; }
         else if (rc != KE_EUNSUPPORTED) return rc;
     }
-    // ---- generic path, chunked so the first-pass scratch stays bounded
+    // ---- tiles first, chunked so the first-pass scratch stays bounded
     if ((want_p && !p_done) || (want_d && !d_done)) {
-        // the banded path needs 32*H bytes of scratch per image, the generic passes up to W*H: size chunks for
-        // the former (the generic fallback re-chunks itself below)
-        const size_t per_img = (size_t)40 * (std::max(g.h, 32) + 1024);
-        const int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20) / per_img));
+        const int64_t chunk = ke_chunk_images(ke_hash_scratch_per_image(g.h));
         for (int64_t f = 0; f < g.n; f += chunk) {
-            KeHashGroup s = g;
-            s.n = std::min(chunk, g.n - f);
-            uint64_t sub_off = 0;
-            if (g.offsets) s.offsets = g.offsets + f; else sub_off = (uint64_t)f * g.stride;
-            if (!g.offsets) s.pixels = g.pixels + sub_off;
+            const KeHashGroup s = ke_sub_group(g, f, std::min(chunk, g.n - f));
             // out_idx == NULL means "slot = position in this group": keep that true for the sub-chunk
             // by offsetting the output pointers instead.
             const int64_t slot0 = g.out_idx ? 0 : f;
-            if (g.out_idx) s.out_idx = g.out_idx + f;
             void *t32 = nullptr, *t98 = nullptr;
             bool d_here = false;
             if (want_d && !d_done) {
@@ -1710,18 +1594,11 @@ int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, u
             if (want_p && !p_done) {
                 if (d_tile32_out) t32 = d_tile32_out + (size_t)f * 1024;
                 else KE_TRY(ke_reserve(ctx, KE_BUF_TILE32, (size_t)s.n * 1024, &t32));
-                int rb = resample_single_pass_banded(ctx, s, (uint8_t *)t32, (uint8_t *)t98, &d_here);
-                if (rb == KE_EUNSUPPORTED) rb = resample_strips(ctx, s, 32, 32, (uint8_t *)t32);
-                if (rb == KE_EUNSUPPORTED) rb = resample_banded(ctx, s, 32, 32, (uint8_t *)t32);
-                if (rb == KE_EUNSUPPORTED) rb = resample_generic(ctx, s, 32, 32, (uint8_t *)t32);
+                int rb = resample_single_pass_banded(ctx, s, (uint8_t *)t32, (uint8_t *)t98, sw, &d_here);
+                if (rb == KE_EUNSUPPORTED) rb = resample_to_tiles(ctx, s, 32, 32, (uint8_t *)t32, sw, true);
                 KE_TRY(rb);
             }
-            if (want_d && !d_done && !d_here) {
-                int rb = resample_strips(ctx, s, 9, 8, (uint8_t *)t98);
-                if (rb == KE_EUNSUPPORTED) rb = resample_banded(ctx, s, 9, 8, (uint8_t *)t98);
-                if (rb == KE_EUNSUPPORTED) rb = resample_generic(ctx, s, 9, 8, (uint8_t *)t98);
-                KE_TRY(rb);
-            }
+            if (want_d && !d_done && !d_here) KE_TRY(resample_to_tiles(ctx, s, 9, 8, (uint8_t *)t98, sw, true));
             uint64_t *ph = (d_phash && !p_done) ? d_phash + slot0 : nullptr;
             uint64_t *dh = (d_dhash && !d_done) ? d_dhash + slot0 : nullptr;
             if (ph || dh) {
@@ -1736,7 +1613,7 @@ int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, u
 
 int ke_launch_tiles_turned(ke_ctx *ctx, const uint8_t *d_tile32, const int64_t *d_out_idx, int64_t n, uint64_t *d_turned) {
     if (n <= 0) return KE_OK;
-    if (n > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
+    if (!ke_fits_one_launch(n)) return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
     KE_TRY(upload_dct_tables(ctx));
     hipLaunchKernelGGL(ke_tiles_to_phash_turned, dim3((unsigned)n), dim3(256), 0, ctx->stream, d_tile32, d_out_idx, d_turned);
     KE_HIP(ctx, hipGetLastError());
@@ -1747,17 +1624,21 @@ int ke_launch_tiles_turned(ke_ctx *ctx, const uint8_t *d_tile32, const int64_t *
 // the shipped refine stage does for its 32x32 / 128x128 thumbnails (BILINEAR).
 int ke_launch_resize_group(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, int filter, uint8_t *d_tiles, const float *box) {
     if (ow <= 0 || oh <= 0 || ow > 4096 || oh > 4096) return ke_fail(ctx, KE_EINVAL, "bad output size %dx%d", ow, oh);
-    const size_t per_img = (size_t)(ow + 8) * (std::max(g.h, oh) + 1024);
-    const int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)512 << 20) / per_img));
+    const KeHashSwitches sw = read_switches();
+    const int64_t chunk = ke_chunk_images(ke_resize_scratch_per_image(ow, oh, g.h));
     for (int64_t f = 0; f < g.n; f += chunk) {
-        KeHashGroup s = g;
-        s.n = std::min(chunk, g.n - f);
-        if (g.offsets) s.offsets = g.offsets + f; else s.pixels = g.pixels + (size_t)f * g.stride;
-        uint8_t *dst = d_tiles + (size_t)f * ow * oh;
-        for (int k = 0; k < KE_RP_COUNT; ++k) ctx->resize_plan[k] = -1;
-        int rc = resample_banded(ctx, s, ow, oh, dst, filter, box, ctx->resize_plan);
-        if (rc == KE_EUNSUPPORTED) rc = resample_generic(ctx, s, ow, oh, dst, filter, box, ctx->resize_plan);
-        KE_TRY(rc);
+        KeRanPlan ran;
+        KE_TRY(resample_to_tiles(ctx, ke_sub_group(g, f, std::min(chunk, g.n - f)), ow, oh, d_tiles + (size_t)f * ow * oh, sw, false, filter, box, &ran));
+        // ke_last_resize_plan: what ran for the last group, all -1 but what the path decides
+        int32_t *rp = ctx->resize_plan;
+        for (int k = 0; k < KE_RP_COUNT; ++k) rp[k] = -1;
+        rp[KE_RP_BANDED] = ran.banded ? 1 : 0;
+        if (ran.banded) {
+            rp[KE_RP_CPO] = 1 << ran.hband.best_log2; rp[KE_RP_NDWC] = ran.ndwc; rp[KE_RP_LAUNCHES] = ran.hband.launches;
+            rp[KE_RP_BANDS] = ran.hband.bands; rp[KE_RP_FUNNEL] = ran.hband.aligned ? 0 : 1; rp[KE_RP_VMX] = ran.vtile.on_mx ? 1 : 0;
+        } else {
+            rp[KE_RP_VFIRST] = ran.generic.vertical_first ? 1 : 0;
+        }
     }
     return KE_OK;
 }

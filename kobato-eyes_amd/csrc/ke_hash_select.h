@@ -73,6 +73,9 @@ struct KeSpShape {
 
 constexpr int kKeSpMaxCandidates = 4;
 
+// Taller than 100 widths: from there Pillow's Image.resize shrinks vertically first, where the target is shorter
+inline bool ke_taller_than_100_widths(int w, int h) { return (int64_t)h > (int64_t)w * 100; }
+
 // The rows (indices into kKeSpRows) to try for a shape, in order; 0 when no single-pass kernel takes it.  The caller
 // launches the first row that does not decline (KE_EUNSUPPORTED: coefficient tables or LDS needs beyond the row).  A
 // row with DH covers both hashes; the others leave dHash to the caller.
@@ -81,7 +84,7 @@ inline int ke_single_pass_candidates(const KeSpShape &s, int out[kKeSpMaxCandida
     const bool unal = w % 4 != 0;                  // rows that do not end on a 4-pixel boundary: RGB, pHash leg only
     if (s.misaligned) return 0;                    // the banded funnel-shift loader takes such a group
     if (w <= 64 || w > (unal ? 1024 : c == 3 ? 2816 : 2048) || h == 32 || h < 16 || (unal && c != 3) ||
-        (!s.band_plan && h > 4096) || (int64_t)h > (int64_t)w * 100 || (!unal && (!s.base_dword || !s.stride_dword)) ||
+        (!s.band_plan && h > 4096) || ke_taller_than_100_widths(w, h) || (!unal && (!s.base_dword || !s.stride_dword)) ||
         (int64_t)w * h * c >= (1LL << 31))
         return 0;
     const bool both = s.want_d && h != 8 && c == 3 && !unal;

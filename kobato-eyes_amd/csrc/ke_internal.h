@@ -140,6 +140,15 @@ struct KeHashGroup {
     int w, h, channels;
     bool misaligned = false;   // some image of the group starts at an address that is not a multiple of 4
 };
+// Images [first, first + count) of a group.  With out_idx == NULL a slot is the position in the group: the caller keeps
+// that true for the part by offsetting its output pointers.
+inline KeHashGroup ke_sub_group(const KeHashGroup &g, int64_t first, int64_t count) {
+    KeHashGroup s = g;
+    s.n = count;
+    if (g.offsets) s.offsets = g.offsets + first; else s.pixels = g.pixels + (size_t)first * g.stride;
+    if (g.out_idx) s.out_idx = g.out_idx + first;
+    return s;
+}
 // fused_stream (nullable): where the scratch-free one-workgroup-per-image kernel of the group may run instead of ctx->stream
 int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, uint64_t *d_dhash,
                          uint8_t *d_tile32_out, uint8_t *d_tile98_out, hipStream_t fused_stream = nullptr);
@@ -147,7 +156,7 @@ int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, u
 int ke_launch_tiles_turned(ke_ctx *ctx, const uint8_t *d_tile32, const int64_t *d_out_idx, int64_t n, uint64_t *d_turned);
 // luma + resize of a group to (oh x ow) u8 tiles with the given filter (banded path, generic fallback)
 // box = {x0, y0, x1, y1} source rectangle (Pillow's resize box), NULL = the whole image
-// ctx->resize_plan holds what was launched for the last group, written where each value is decided (ke_last_resize_plan):
+// ctx->resize_plan holds what was launched for the last group, written from the plans of the path that ran (ke_last_resize_plan):
 enum { KE_RP_BANDED = 0, KE_RP_CPO, KE_RP_NDWC, KE_RP_LAUNCHES, KE_RP_BANDS, KE_RP_FUNNEL, KE_RP_VMX, KE_RP_VFIRST, KE_RP_COUNT };
 int ke_launch_resize_group(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, int filter, uint8_t *d_tiles,
                            const float *box = nullptr);
