@@ -630,6 +630,24 @@ int ke_ssim_pairs(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, c
                   int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
                   double *ssim_out, int32_t *status_out);
 
+/* A capability of this library only (the reference has no turned duplicates): the luma plane of one of the eight orientations
+ * of a picture.  Orientation k in 0..7 as python's turned.ORIENTATIONS: transposed if k & 4, then mirrored (left <-> right) if
+ * k & 1, then flipped (top <-> bottom) if k & 2; 0 is a plain luma copy.  Image i (widths[i] x heights[i], channels[i] = 1, 3 or 4,
+ * the fourth ignored, at src + src_offsets[i]) -> the convert("L") luma of orientation orientations[i] of it, 1 byte per pixel,
+ * rows packed, at dst + dst_offsets[i]: heights[i] x widths[i] for k & 4.  Luma is per pixel, so the plane is byte for byte the
+ * luma of the turned picture.  src, dst: device; the arrays: host.  Blocks. */
+int ke_turn_luma(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offsets, const int32_t *widths, const int32_t *heights,
+                 const int32_t *channels, const int32_t *orientations, int64_t n, uint8_t *dst, const uint64_t *dst_offsets);
+
+/* ke_ssim_pairs with one more array: pair k is image pair_a[k] against orientation orient_b[k] (0..7, as ke_turn_luma) of
+ * image pair_b[k].  The common size is taken from b's turned size (swapped for k & 4); the fit, the SSIM and the statuses are
+ * ke_ssim_pairs'.  Every distinct (image, orientation != 0) of a call is turned once, by one ke_turn_luma launch into scratch
+ * of 1 byte per pixel, and enters the fit as a one-channel source.  orient_b NULL or all zeros: ke_ssim_pairs' answers, bit for
+ * bit.  An orientation outside 0..7: KE_EINVAL, nothing launched. */
+int ke_ssim_pairs_turned(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                         int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *orient_b,
+                         int64_t n_pairs, double *ssim_out, int32_t *status_out);
+
 /* ---- shipped refine stage ("next" row of SURVEY 8f): replaces the per-file work of
  * ui.dup_refine_parallel -- tile_ahash_bits (src/ui/dup_refine_parallel.py:59-83), _load_small_gray
  * (:203-207) and _mae01 (:208-210).

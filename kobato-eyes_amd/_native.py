@@ -32,7 +32,7 @@ EXPORTS = (
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
-    "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_thumbnail_rgb_box", "ke_reduce_rgb", "ke_jpeg_decode_scaled", "ke_jpeg_last_split", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_set_mode",
+    "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_thumbnail_rgb_box", "ke_reduce_rgb", "ke_jpeg_decode_scaled", "ke_jpeg_last_split", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_pairs_turned", "ke_turn_luma", "ke_ssim_set_mode",
     "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash", "ke_sad_pairs", "ke_synth_rgb", "ke_synth_rgb_indexed",
     "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches", "ke_last_scan_path", "ke_last_resize_plan",
 ) + tuple(f"ke_{kind}_{call}" for kind in KINDS for call in ("probe", "decode", "caveats"))
@@ -151,6 +151,8 @@ def load_library() -> C.CDLL:
         lib.ke_ssim_pairs_uniform.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
         lib.ke_ssim_set_mode.argtypes = [vp, i32]
         lib.ke_ssim_pairs.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp, i64, vp, vp]
+        lib.ke_ssim_pairs_turned.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, i64, vp, vp]
+        lib.ke_turn_luma.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
         lib.ke_resize_luma_uniform.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]
         lib.ke_fit_luma_uniform.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]
         lib.ke_tile_ahash.argtypes = [vp, vp, i64, i32, i32, vp]
@@ -1042,6 +1044,52 @@ class Context:
             self._check(self._lib.ke_ssim_pairs(self._h, base, _addr(offsets), _addr(widths), _addr(heights), channels, len(ptrs), _addr(pa),
                                                 _addr(pb), len(pa), _addr(out), _addr(status)), "ke_ssim_pairs")
         return out, status
+
+    def ssim_pairs_turned(self, images: Sequence[np.ndarray], pair_a, pair_b, orient_b):
+        """ssim_pairs with image ``pair_b[k]`` under orientation ``orient_b[k]`` (0..7, turned.ORIENTATIONS; None: all 0)."""
+        n = len(images)
+        flat, offsets, widths, heights, ch = _pack_images(images)
+        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
+        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
+        ob = None if orient_b is None else np.ascontiguousarray(orient_b, dtype=np.int32)
+        out = np.empty(len(pa), np.float64)
+        status = np.empty(len(pa), np.int32)
+        with self._lock:
+            self._check(self._lib.ke_ssim_pairs_turned(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n, _addr(pa),
+                                                       _addr(pb), _addr(ob), len(pa), _addr(out), _addr(status)), "ke_ssim_pairs_turned")
+        return out, status
+
+    def ssim_pairs_turned_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b, orient_b):
+        """ssim_pairs_on_device with image ``pair_b[k]`` under orientation ``orient_b[k]`` (0..7, turned.ORIENTATIONS): each
+        distinct (image, orientation != 0) is turned once on the device (ke_turn_luma) before the fit."""
+        ptrs = np.asarray(pointers, np.uint64)
+        base = int(ptrs.min())
+        offsets = np.ascontiguousarray(ptrs - np.uint64(base))
+        widths = np.ascontiguousarray(widths, np.int32)
+        heights = np.ascontiguousarray(heights, np.int32)
+        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
+        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
+        ob = np.ascontiguousarray(orient_b, dtype=np.int32)
+        out = np.empty(len(pa), np.float64)
+        status = np.empty(len(pa), np.int32)
+        with self._lock:
+            self._check(self._lib.ke_ssim_pairs_turned(self._h, base, _addr(offsets), _addr(widths), _addr(heights), channels, len(ptrs),
+                                                       _addr(pa), _addr(pb), _addr(ob), len(pa), _addr(out), _addr(status)),
+                        "ke_ssim_pairs_turned")
+        return out, status
+
+    def turn_luma(self, src: int, src_offsets, widths, heights, channels, orientations, dst: int, dst_offsets) -> None:
+        """Images on the device (``widths[i]`` x ``heights[i]``, 1, 3 or 4 channels, at ``src + src_offsets[i]``) -> the luma plane
+        of orientation ``orientations[i]`` (0..7, turned.ORIENTATIONS) of each, one byte per pixel, rows packed, at
+        ``dst + dst_offsets[i]`` of the caller's device buffer (ke_turn_luma): ``heights[i]`` x ``widths[i]`` for k & 4."""
+        so, do = np.ascontiguousarray(src_offsets, dtype=np.uint64), np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        w, h = np.ascontiguousarray(widths, dtype=np.int32), np.ascontiguousarray(heights, dtype=np.int32)
+        c, o = np.ascontiguousarray(channels, dtype=np.int32), np.ascontiguousarray(orientations, dtype=np.int32)
+        if not len(so) == len(do) == len(w) == len(h) == len(c) == len(o):
+            raise ValueError("turn_luma: the arrays differ in length")
+        with self._lock:
+            self._check(self._lib.ke_turn_luma(self._h, src, _addr(so), _addr(w), _addr(h), _addr(c), _addr(o), len(so), dst, _addr(do)),
+                        "ke_turn_luma")
 
     # -- shipped refine stage -------------------------------------------------------------------
     def resize_luma_uniform(self, pixels, n: int, width: int, height: int, channels: int, out_w: int, out_h: int,

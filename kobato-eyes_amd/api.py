@@ -154,8 +154,9 @@ def find_new_duplicates(library: Iterable, added: Iterable, *, previous: Optiona
     return [c for c in clusters if any(e.file.file_id in new_ids for e in c.files)]
 
 
-def _turned_scan(files: Iterable, *, hamming_threshold, size_ratio, band_bits, band_count, device):
-    """find_turned_duplicates' work: (clusters, matches, the (id, id) keys of the plain candidate edges)."""
+def _turned_scan(files: Iterable, *, hamming_threshold, size_ratio, band_bits, band_count, device, ssim_threshold=None):
+    """find_turned_duplicates' work: (clusters, matches, the (id, id) keys of the plain candidate edges).  With
+    ``ssim_threshold`` the matches and the keys are the ones that passed the re-check."""
     from . import turned as _turned
     from .scanner import DuplicateEdge, assemble_clusters
 
@@ -168,12 +169,31 @@ def _turned_scan(files: Iterable, *, hamming_threshold, size_ratio, band_bits, b
     hashes, ok = _turned.turned_signatures([f.path for f in candidates], device=device)
     plain = scanner.candidate_edges(candidates)
     matches = scanner.turned_edges(candidates, hashes, ok)
+    if ssim_threshold is not None and (plain or matches):
+        plain, matches = _turned_ssim_kept(plain, matches, candidates, ssim_threshold, device)
     edges = list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
     return (assemble_clusters(candidates, edges) if edges else []), matches, set(plain)
 
 
+def _turned_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, device: int) -> tuple:
+    """The plain candidate edges and the turned matches that pass the SSIM re-check, from one refine_turned_pairs call: a
+    plain edge is scored as the pixels lie (orientation 0), a match as file a against its orientation of file b.  A
+    surviving match carries its score; a pair whose files cannot be read is dropped, as _ssim_kept drops it."""
+    from dataclasses import replace
+
+    by_id = {f.file_id: f for f in candidates}
+    keys = list(plain)
+    rows = [(plain[k].file_id_a, plain[k].file_id_b, by_id[plain[k].file_id_a].path, by_id[plain[k].file_id_b].path, 0) for k in keys]
+    rows += [(m.file_id_a, m.file_id_b, by_id[m.file_id_a].path, by_id[m.file_id_b].path, m.orientation) for m in matches]
+    refined = _refine.refine_turned_pairs(rows, thresholds=_refine.RefinementThresholds(ssim=ssim_threshold), device=device)
+    passed = [r is not None and r.is_duplicate for r in refined]
+    kept_plain = {k: plain[k] for k, yes in zip(keys, passed) if yes}
+    kept_matches = [replace(m, ssim=r.ssim) for m, r, yes in zip(matches, refined[len(keys):], passed[len(keys):]) if yes]
+    return kept_plain, kept_matches
+
+
 def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, band_bits: int = 16,
-                           band_count: int = 4, device: Optional[int] = None) -> tuple:
+                           band_count: int = 4, device: Optional[int] = None, ssim_threshold: Optional[float] = None) -> tuple:
     """(clusters, matches): near-duplicates including mirrored, flipped and rotated copies.
 
     ``files``: as for ``find_duplicates``, each with a readable ``path``: the files are read and the pHashes of their
@@ -183,10 +203,15 @@ def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_
     edges of the stored hashes together with the matches as edges.  A file whose turned hashes could not be made (Pillow
     cannot open it) takes part with its stored pHash only.
 
-    Out of scope here: an SSIM re-check of turned pairs (``ke_normalise_rgb`` could turn one member first: a follow-up),
-    persisting turned hashes, ``devices=[...]`` (one process, one GPU) and dHash."""
+    With ``ssim_threshold`` set, every plain candidate edge and every match is re-checked on the files' pixels, a match as
+    file a against its orientation of file b, turned on the device (``refine.refine_turned_pairs``, one call for all).
+    Only edges with ``ssim >= ssim_threshold`` reach the clusters, and ``matches`` holds the surviving matches, each with
+    its ``ssim``.  A pair that is both a plain edge and a match stays linked if either passes; a pair with an unreadable
+    file is dropped.  Unset: no pixels are compared and ``ssim`` is None.
+
+    Out of scope here: persisting turned hashes, ``devices=[...]`` (one process, one GPU) and dHash."""
     clusters, matches, _ = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
-                                        band_count=band_count, device=0 if device is None else int(device))
+                                        band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)
     return clusters, matches
 
 

@@ -2,7 +2,7 @@
 
     python -m kobato_eyes_amd.cli scan-dups --db kobato.db --hamming 8 [--like '%/photos/%'] [--size-ratio 0.5]
                                             [--added-like '%/incoming/%'] [--refine] [--csv out.csv] [--device 0]
-                                            [--devices 0,1,2] [--turned]
+                                            [--devices 0,1,2] [--turned [--turned-ssim 0.9]]
 
 Reproduces the call sequence of DuplicateScanRunnable.run (src/ui/dup_workers.py:148-239) without Qt: rows in
 the shape of db.repository.iter_files_for_dup (src/db/repository.py:416-454), missing signatures filled and
@@ -93,14 +93,19 @@ def orientations_to_keeper(clusters: Sequence, matches: Sequence, plain_keys) ->
 def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, path_like: Optional[str] = None,
                   refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
                   devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None, turned: bool = False,
-                  orientations_out: Optional[dict] = None) -> list:
+                  orientations_out: Optional[dict] = None, turned_ssim: Optional[float] = None) -> list:
     """``devices``: the missing signatures are computed by one worker process per entry; the scan and the tile-aHash / MAE
     refine stay in this process, on ``device`` (default ``devices[0]``, else 0).  ``added_like``: the files of the
     selection whose path matches this LIKE pattern are the added set, the rest the library; only the pairs that touch an
     added file are scanned and only the clusters with an added member come back (``find_new_duplicates`` without
     ``previous``: a link between two library files is absent).  ``turned``: the files of the selection are read and
     mirrored, flipped and rotated copies are linked as well (``find_turned_duplicates``; not together with
-    ``added_like`` or ``refine``); ``orientations_out`` then receives ``orientations_to_keeper`` of the result."""
+    ``added_like`` or ``refine``); ``orientations_out`` then receives ``orientations_to_keeper`` of the result.
+    ``turned_ssim`` (only with ``turned``): the candidate edges and the turned matches are re-checked with SSIM, a match with
+    one file turned on the device, and only those at or above this score link files (``find_turned_duplicates``'
+    ``ssim_threshold``); the orientations are then worked out from the survivors."""
+    if turned_ssim is not None and not turned:
+        raise ValueError("--turned-ssim needs --turned")
     if turned and (added_like or refine):
         # the refine pipeline compares pixels as they lie and would cut every link that exists through a turn
         raise ValueError("--turned cannot be combined with --added-like or --refine")
@@ -143,7 +148,7 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
         from .api import _turned_scan
 
         clusters, matches, plain_keys = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio,
-                                                     band_bits=16, band_count=4, device=device)
+                                                     band_bits=16, band_count=4, device=device, ssim_threshold=turned_ssim)
         if orientations_out is not None:
             orientations_out.update(orientations_to_keeper(clusters, matches, plain_keys))
     elif added_like:
@@ -177,6 +182,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("--turned", action="store_true",
                     help="read the files of the selection and link mirrored, flipped and rotated copies as well; the CSV gains an "
                          "orientation column: the turn that brings a file's picture to its group's keeper's")
+    sp.add_argument("--turned-ssim", type=float, default=None,
+                    help="with --turned: re-check every candidate edge and turned match with SSIM on the pixels (one file turned on "
+                         "the device for a match) and link only those at or above this score, e.g. 0.9")
     sp.add_argument("--refine", action="store_true", help="run the tile-aHash + pixel-MAE refine pipeline on the clusters")
     sp.add_argument("--tile-max-bits", type=int, default=32)
     sp.add_argument("--mae-thr", type=float, default=0.004)
@@ -190,7 +198,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     orientations = {} if args.turned else None
     clusters = scan_database(args.db, hamming_threshold=args.hamming, size_ratio=args.size_ratio, path_like=args.like,
                              refine=args.refine, tile_max_bits=args.tile_max_bits, mae_thr=args.mae_thr, device=args.device,
-                             devices=args.devices, added_like=args.added_like, turned=args.turned, orientations_out=orientations)
+                             devices=args.devices, added_like=args.added_like, turned=args.turned, orientations_out=orientations,
+                             turned_ssim=args.turned_ssim)
     if args.csv:
         export_duplicate_clusters_csv(clusters, args.csv, orientations)
     members = sum(len(c.files) for c in clusters)

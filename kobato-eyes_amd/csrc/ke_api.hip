@@ -1122,6 +1122,129 @@ KE_API int ke_ssim_pairs(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *off
     return KE_OK;
 }
 
+// ke_ssim_pairs with image b of pair k under orientation orient_b[k].  A "plane source" is what the fit step reads: an image
+// as it lies in `pixels` (orientation 0), or the turned luma plane of an (image, orientation) in KE_BUF_TURN_LUMA, one
+// channel, of the turned size.  Everything from the fit on is ke_ssim_pairs' sequence over plane sources instead of images.
+KE_API int ke_ssim_pairs_turned(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                                int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *orient_b,
+                                int64_t n_pairs, double *ssim_out, int32_t *status_out) {
+    if (!ctx) return KE_EINVAL;
+    if (n_pairs < 0 || n_images < 0) return ke_fail(ctx, KE_EINVAL, "negative count");
+    if (n_pairs == 0) return KE_OK;
+    if (!pixels || !widths || !heights || !pair_a || !pair_b || !ssim_out) return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    if (channels != 1 && channels != 3 && channels != 4) return ke_fail(ctx, KE_EINVAL, "channels must be 1, 3 or 4");
+    for (const void *p : {(const void *)offsets, (const void *)widths, (const void *)heights, (const void *)pair_a, (const void *)pair_b,
+                          (const void *)orient_b, (const void *)ssim_out, (const void *)status_out})
+        if (p && ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/widths/heights/pairs/orientations/outputs are host arrays");
+    if (orient_b)
+        for (int64_t k = 0; k < n_pairs; ++k)
+            if (orient_b[k] < 0 || orient_b[k] > 7) return ke_fail(ctx, KE_EINVAL, "pair %lld: orientation %d outside 0..7", (long long)k, orient_b[k]);
+    KE_HIP(ctx, hipSetDevice(ctx->device));
+    trim_coeff_cache(ctx);
+    const double nan = std::nan("");
+    std::vector<uint64_t> off((size_t)n_images);
+    uint64_t run = 0;
+    for (int64_t i = 0; i < n_images; ++i) {
+        off[i] = offsets ? offsets[i] : run;
+        if (widths[i] > 0 && heights[i] > 0) run += (uint64_t)widths[i] * heights[i] * channels;
+    }
+    uint64_t total_bytes = 0;
+    for (int64_t i = 0; i < n_images; ++i)
+        if (widths[i] > 0 && heights[i] > 0) total_bytes = std::max<uint64_t>(total_bytes, off[i] + (uint64_t)widths[i] * heights[i] * channels);
+    using Src = std::pair<int64_t, int>;                                // (image, orientation)
+    auto src_b = [&](int64_t k) { return Src{pair_b[k], orient_b ? orient_b[k] : 0}; };
+    auto src_w = [&](Src s) { return (s.second & 4) ? heights[s.first] : widths[s.first]; };
+    auto src_h = [&](Src s) { return (s.second & 4) ? widths[s.first] : heights[s.first]; };
+    std::map<std::pair<int, int>, std::vector<int64_t>> by_size;        // common (w, h) -> pairs
+    std::map<Src, uint64_t> turned_at;                                  // (image, orientation != 0) -> bytes into KE_BUF_TURN_LUMA
+    std::vector<KeTurnJob> jobs;
+    uint64_t turned_bytes = 0;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        ssim_out[k] = nan;
+        const int64_t ia = pair_a[k], ib = pair_b[k];
+        const bool ok = ia >= 0 && ia < n_images && ib >= 0 && ib < n_images && widths[ia] > 0 && heights[ia] > 0 && widths[ib] > 0 &&
+                        heights[ib] > 0;
+        if (!ok) { if (status_out) status_out[k] = KE_PAIR_BAD_IMAGE; continue; }
+        const Src b = src_b(k);
+        const int w = std::min(widths[ia], src_w(b)), h = std::min(heights[ia], src_h(b));   // src/dup/refine.py:45-47, b as it lies turned
+        if (w < 7 || h < 7) { if (status_out) status_out[k] = KE_PAIR_TOO_SMALL; continue; }
+        if (status_out) status_out[k] = KE_PAIR_OK;
+        by_size[{w, h}].push_back(k);
+        if (b.second != 0 && !turned_at.count(b)) {
+            turned_at[b] = turned_bytes;
+            jobs.push_back(KeTurnJob{off[ib], turned_bytes, widths[ib], heights[ib], channels, b.second});
+            turned_bytes += ((uint64_t)widths[ib] * heights[ib] + 255) & ~(uint64_t)255;      // every plane starts on a dword
+        }
+    }
+    if (by_size.empty()) return KE_OK;
+    const void *d_px;
+    KE_TRY(ke_to_device(ctx, pixels, (size_t)total_bytes, KE_BUF_PIXELS, &d_px));
+    ke_time_begin(ctx, KE_T_SSIM);
+    void *d_turned = nullptr;
+    if (!jobs.empty()) {
+        KE_TRY(ke_reserve(ctx, KE_BUF_TURN_LUMA, (size_t)turned_bytes, &d_turned));
+        KE_TRY(ke_launch_turn_luma(ctx, (const uint8_t *)d_px, jobs.data(), (int64_t)jobs.size(), (uint8_t *)d_turned));
+    }
+    for (auto &kv : by_size) {
+        const int w = kv.first.first, h = kv.first.second;
+        const std::vector<int64_t> &ks = kv.second;
+        // a fit launch reads one buffer at one channel count, so a group is (source w, source h, turned or not)
+        using Key = std::tuple<int, int, int>;
+        auto key_of = [&](Src s) { return Key{src_w(s), src_h(s), s.second != 0}; };
+        std::map<Key, std::vector<Src>> groups;                          // first use order inside a group
+        std::map<Src, int64_t> slot;                                     // plane source -> position inside its group
+        for (int64_t k : ks)
+            for (Src s : {Src{pair_a[k], 0}, src_b(k)})
+                if (!slot.count(s)) {
+                    auto &g = groups[key_of(s)];
+                    slot[s] = (int64_t)g.size();
+                    g.push_back(s);
+                }
+        int64_t base = 0;
+        std::map<Key, int64_t> group_base;
+        for (auto &g : groups) { group_base[g.first] = base; base += (int64_t)g.second.size(); }
+        const size_t plane = (size_t)w * h;
+        void *planes, *meta, *aux;
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)base * plane, &planes));
+        KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)base * 8, &meta));
+        std::vector<uint64_t> meta_h((size_t)base);
+        for (auto &g : groups)
+            for (size_t j = 0; j < g.second.size(); ++j)
+                meta_h[(size_t)group_base[g.first] + j] = g.second[j].second ? turned_at[g.second[j]] : off[g.second[j].first];
+        KE_HIP(ctx, hipMemcpyAsync(meta, meta_h.data(), (size_t)base * 8, hipMemcpyHostToDevice, ctx->stream));
+        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // meta_h is a local
+        for (auto &g : groups) {
+            const int sw = std::get<0>(g.first), sh = std::get<1>(g.first);
+            const bool turned = std::get<2>(g.first) != 0;
+            const int ch = turned ? 1 : channels;
+            const uint8_t *from = turned ? (const uint8_t *)d_turned : (const uint8_t *)d_px;
+            const int64_t gb = group_base[g.first], m = (int64_t)g.second.size();
+            KeHashGroup hg{from, (const uint64_t *)meta + gb, (uint64_t)sw * sh * ch, nullptr, m, sw, sh, ch};
+            hg.misaligned = ke_any_misaligned((uintptr_t)from, meta_h.data() + gb, m);
+            float box[4];
+            if (fit_box(sw, sh, w, h, box) != KE_OK) return ke_fail(ctx, KE_EINVAL, "crop box outside the image");
+            KE_TRY(ke_launch_resize_group(ctx, hg, w, h, KE_FILTER_BICUBIC, (uint8_t *)planes + (size_t)gb * plane, box));
+        }
+        const int64_t np = (int64_t)ks.size();
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, (size_t)np * 24, &aux));
+        std::vector<int64_t> idx((size_t)2 * np);
+        for (int64_t j = 0; j < np; ++j) {
+            const Src a{pair_a[ks[j]], 0}, b = src_b(ks[j]);
+            idx[j] = group_base[key_of(a)] + slot[a];
+            idx[np + j] = group_base[key_of(b)] + slot[b];
+        }
+        KE_HIP(ctx, hipMemcpyAsync(aux, idx.data(), (size_t)2 * np * 8, hipMemcpyHostToDevice, ctx->stream));
+        double *d_out = (double *)((uint8_t *)aux + (size_t)2 * np * 8);
+        KE_TRY(ke_launch_ssim(ctx, (const uint8_t *)planes, w, h, 1, (const int64_t *)aux, (const int64_t *)aux + np, np, d_out));
+        std::vector<double> scores((size_t)np);
+        KE_HIP(ctx, hipMemcpyAsync(scores.data(), d_out, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int64_t j = 0; j < np; ++j) ssim_out[ks[j]] = scores[j];
+    }
+    ke_time_end(ctx, KE_T_SSIM);
+    return KE_OK;
+}
+
 // ---- shipped refine stage: thumbnails, tile aHash, pixel MAE --------------------------------------
 static int resize_luma_common(ke_ctx *ctx, const uint8_t *pixels, int64_t n, int32_t width, int32_t height, int32_t channels,
                               int32_t out_w, int32_t out_h, int32_t filter, const float *box, uint8_t *tiles_out);

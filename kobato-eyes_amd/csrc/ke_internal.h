@@ -45,6 +45,7 @@ enum {
     KE_BUF_COMM_EDGES,   // edge records: [send | world x recv]
     KE_BUF_JPEG_TABLES,  // Huffman tables of a JPEG batch
     KE_BUF_TURN_TILES,   // ke_hash_images_turned: the 32x32 tiles of a call's images, group after group
+    KE_BUF_TURN_LUMA,    // ke_ssim_pairs_turned: the turned luma planes of a call, 1 B/px per distinct (image, orientation)
     KE_BUF_COUNT
 };
 
@@ -160,6 +161,13 @@ int ke_launch_tiles_turned(ke_ctx *ctx, const uint8_t *d_tile32, const int64_t *
 enum { KE_RP_BANDED = 0, KE_RP_CPO, KE_RP_NDWC, KE_RP_LAUNCHES, KE_RP_BANDS, KE_RP_FUNNEL, KE_RP_VMX, KE_RP_VFIRST, KE_RP_COUNT };
 int ke_launch_resize_group(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, int filter, uint8_t *d_tiles,
                            const float *box = nullptr);
+// the luma plane of orientation `orientation` (0..7, turned.ORIENTATIONS) of each image, rows packed (ke_turn.hip); the
+// job table goes through KE_BUF_META and the stream is drained before the call returns
+struct KeTurnJob {
+    uint64_t src_off, dst_off;   // bytes from d_src / d_dst
+    int32_t w, h, channels, orientation;
+};
+int ke_launch_turn_luma(ke_ctx *ctx, const uint8_t *d_src, const KeTurnJob *jobs, int64_t n, uint8_t *d_dst);
 int ke_launch_tile_ahash(ke_ctx *ctx, const uint8_t *d_tiles, int64_t n, int grid, int tile, uint64_t *d_bits);
 int ke_launch_sad_pairs(ke_ctx *ctx, const uint8_t *d_thumbs, int64_t pixels, const int64_t *d_pa, const int64_t *d_pb,
                         int64_t n_pairs, uint64_t *d_out);

@@ -173,12 +173,14 @@ def _upload(ctx, arrays: dict, placed: dict, buffers: list) -> None:
     ctx.memcpy(dev, flat, len(flat))
 
 
-def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, count: dict, cfg: RefinementThresholds) -> None:
+def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, count: dict, cfg: RefinementThresholds,
+           turned: bool = False) -> None:
     """One ``ke_ssim_pairs`` call for the pairs of this run (the library groups them: one fit launch per (source size,
-    common size), one SSIM launch per common size)."""
+    common size), one SSIM launch per common size).  ``turned``: a pair carries an orientation as its fifth item and the
+    call is ``ke_ssim_pairs_turned``, which scores a against that orientation of b."""
     live = []
     for k in chunk:
-        fid_a, fid_b, pa, pb = pairs[k]
+        pa, pb = pairs[k][2], pairs[k][3]
         if str(pa) not in placed or str(pb) not in placed:
             out[k] = None                                      # unreadable file: src/dup/refine.py:82-85
         else:
@@ -187,20 +189,27 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
         return
     paths = list(placed)
     index = {p: i for i, p in enumerate(paths)}
-    scores, status = ctx.ssim_pairs_on_device([placed[p][0] for p in paths], [placed[p][1] for p in paths], [placed[p][2] for p in paths],
-                                              3, [index[str(pairs[k][2])] for k in live], [index[str(pairs[k][3])] for k in live])
+    where = ([placed[p][0] for p in paths], [placed[p][1] for p in paths], [placed[p][2] for p in paths], 3,
+             [index[str(pairs[k][2])] for k in live], [index[str(pairs[k][3])] for k in live])
+    if turned:
+        scores, status = ctx.ssim_pairs_turned_on_device(*where, [int(pairs[k][4]) for k in live])
+    else:
+        scores, status = ctx.ssim_pairs_on_device(*where)
     common, fits = set(), set()
     for k, sc, st in zip(live, scores.tolist(), status.tolist()):
-        fid_a, fid_b, pa, pb = pairs[k]
+        fid_a, fid_b, pa, pb = pairs[k][:4]
         if st != 0:                                            # skimage raises for images smaller than its window
             logger.warning("SSIM refinement failed for %s and %s: win_size exceeds image extent", pa, pb)
             out[k] = _decide(fid_a, fid_b, None, ["ssim unavailable"], cfg)
             continue
         out[k] = _decide(fid_a, fid_b, float(sc), [], cfg)
         (_, wa, ha), (_, wb, hb) = placed[str(pa)], placed[str(pb)]
+        o = int(pairs[k][4]) if turned else 0
+        if o & 4:
+            wb, hb = hb, wb
         size = (min(wa, wb), min(ha, hb))
         common.add(size)
-        fits.update({((ha, wa), size), ((hb, wb), size)})
+        fits.update({((ha, wa), False, size), ((hb, wb), o != 0, size)})    # a turned plane is a source of its own
     count["fit_launches"] += len(fits)
     count["ssim_launches"] += len(common)
 
@@ -231,6 +240,13 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
 
         return ranks.refine_pairs(pairs, devices, thresholds=thresholds, io_workers=io_workers,
                                   max_decoded_bytes=max_decoded_bytes, stats=stats, max_side=max_side)
+    return _refine_runs(pairs, False, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, _after_run)
+
+
+def _refine_runs(pairs: Sequence[tuple], turned: bool, thresholds, device: int, io_workers: int, max_decoded_bytes: int,
+                 stats: Optional[dict], max_side: int, _after_run=None) -> list:
+    """The run loop of refine_pairs and refine_turned_pairs: decode what a run of pairs needs, once per file and within
+    the budget, score the run with one library call, free, go on."""
     from concurrent.futures import ThreadPoolExecutor
 
     cfg = thresholds or RefinementThresholds()
@@ -257,7 +273,7 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
                 arrays = dict(zip(rest, pool.map(lambda p: _load(p, max_side), rest)))
                 count["decodes"] += len(need)
                 _upload(ctx, arrays, placed, buffers)
-                _score(ctx, pairs, range(start, stop), placed, out, count, cfg)
+                _score(ctx, pairs, range(start, stop), placed, out, count, cfg, turned)
             finally:
                 for dev in buffers:
                     ctx.free(dev)
@@ -267,6 +283,27 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
     if stats is not None:
         stats.update(count)
     return out
+
+
+def refine_turned_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThresholds] = None, device: int = 0,
+                        io_workers: int = 8, max_decoded_bytes: int = 1 << 30, stats: Optional[dict] = None,
+                        max_side: int = MAX_SIDE) -> list:
+    """``refine_pairs`` for a list of ``(file_id_a, file_id_b, path_a, path_b, orientation)``: file a is scored against
+    orientation ``orientation`` (0..7, ``turned.ORIENTATIONS``) of file b, as ``refine_pairs`` would score a against a file
+    that holds b turned that way.  A capability of this library only: the reference has no turned duplicates.
+
+    Both files are decoded as they lie (the same decode runs, budget and loader fallback as ``refine_pairs``, the same
+    ``stats``); b is turned on the device, luma only, once per distinct (file, orientation) of a run (``ke_turn_luma`` inside
+    ``ke_ssim_pairs_turned``).  Luma commutes with the turn and the resampler is bit-exact with Pillow on every source, so the
+    score is the one the turned file would get, bit for bit.  Returns a ``RefinedMatch`` or ``None`` (unreadable file) per
+    pair, in input order.
+
+    There is no ``devices=``: ``ranks.refine_pairs`` ships 4-tuples to its workers.  An orientation outside 0..7 is a
+    ``ValueError`` before anything is decoded."""
+    for pair in pairs:
+        if not 0 <= int(pair[4]) < 8:
+            raise ValueError(f"orientation {pair[4]} outside 0..7")
+    return _refine_runs(pairs, True, thresholds, device, io_workers, max_decoded_bytes, stats, max_side)
 
 
 def refine_pair(file_id_a: int, file_id_b: int, path_a, path_b, *, thresholds: Optional[RefinementThresholds] = None,
@@ -285,4 +322,4 @@ def refine_pair(file_id_a: int, file_id_b: int, path_a, path_b, *, thresholds: O
     return _decide(file_id_a, file_id_b, ssim_value, errors, cfg)
 
 
-__all__ = ["RefinementThresholds", "RefinedMatch", "refine_pair", "refine_pairs", "compute_ssim", "ssim_pairs"]
+__all__ = ["RefinementThresholds", "RefinedMatch", "refine_pair", "refine_pairs", "refine_turned_pairs", "compute_ssim", "ssim_pairs"]

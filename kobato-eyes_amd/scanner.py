@@ -154,12 +154,15 @@ class DuplicateEdge:
 @dataclass(frozen=True)
 class TurnedMatch:
     """Two files of which one looks like a turned copy of the other: orientation ``orientation`` (turned.ORIENTATIONS) of
-    file_id_b's picture is file_id_a's picture, to within ``hamming`` bits of the pHash.  file_id_a < file_id_b."""
+    file_id_b's picture is file_id_a's picture, to within ``hamming`` bits of the pHash.  file_id_a < file_id_b.  ``ssim``: the
+    score of file a against that orientation of file b where the pair went through the SSIM re-check
+    (api.find_turned_duplicates with ``ssim_threshold``), else None."""
 
     file_id_a: int
     file_id_b: int
     orientation: int
     hamming: int
+    ssim: Optional[float] = None
 
 
 def _safe_positive_int(value: Optional[str]) -> Optional[int]:
