@@ -648,6 +648,40 @@ int ke_ssim_pairs_turned(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *off
                          int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *orient_b,
                          int64_t n_pairs, double *ssim_out, int32_t *status_out);
 
+/* ---- bordered copies.  A capability of this library only (the reference has no such feature): the CONTENT BOX of an image
+ * and the pHash of the image cut to it, for finding a letterboxed, pillarboxed, framed or white-margined copy of a picture.
+ *
+ * Image i: heights[i] rows of widths[i] * channels bytes at pixels + offsets[i] (offsets NULL: packed back to back), any byte
+ * offset legal; channels 1, 3 or 4, the fourth byte ignored as the hashes ignore it.
+ *   ref[c] = pixel (0, 0), channel c.  A pixel DIFFERS when max over c of |p[c] - ref[c]| > tolerance (0..255).
+ *   No pixel differs: the image has no box, four zeros.  Otherwise the box is (x0, y0, x1, y1): the smallest x and y of a
+ *   differing pixel and the largest plus one -- Pillow's getbbox convention.  In Pillow (RGBA first through convert("RGB")):
+ *       bg   = Image.new(im.mode, im.size, im.getpixel((0, 0)))
+ *       mask = ImageChops.difference(im, bg).point(lambda v: 255 if v > tol else 0)
+ *       box  = mask.getbbox()
+ *   A box QUALIFIES for a trimmed hash when it exists, both its sides are >= 8, and it cuts at least 2 % off one axis:
+ *   (w - bw) * 50 >= w or (h - bh) * 50 >= h.  (A one-pixel trim would only double the plain hash's edges.)
+ *   The TRIMMED pHash of an image with a qualifying box is ke_hash_images' pHash of the box's pixels (im.crop(box)).
+ *
+ * ke_content_boxes: boxes_out[4 i .. 4 i + 3] = the box of image i, four zeros for an image without one or with a status other
+ *   than KE_IMG_OK (status_out nullable).  One pass over the pixels, which are never read outside
+ *   [pixels + offsets[i], + w * h * channels).  pixels: host or device; everything else host arrays.
+ * ke_crop_pack: rows [y0, y1) x columns [x0, x1) of image i (boxes[4 i ..], inside the image and not empty, else KE_EINVAL) ->
+ *   dst + dst_offsets[i], rows packed, (x1 - x0) * channels bytes each; nothing outside those bytes is written.  src, dst:
+ *   device; the arrays: host.
+ * ke_hash_images_trimmed: the boxes, the qualifying rule on the host, ke_crop_pack of the qualifying images into scratch of at
+ *   most 1 GiB a chunk (or one crop, if larger), ke_hash_images on the crops.  has_out[i] = 1 and phash_out[i] = the trimmed
+ *   pHash where the box qualifies; otherwise has_out[i] = 0 and phash_out[i] = 0, and boxes_out still holds the box.  A failed
+ *   image has status != KE_IMG_OK and zeros.  pixels: host (staged in chunks of at most 1 GiB) or device; the rest host arrays.
+ * All three block.  ke_last_kernel_ms kind 5 times the box kernel, kind 6 the crop kernel (of the last chunk). */
+int ke_content_boxes(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                     int32_t channels, int64_t n, int32_t tolerance, int32_t *boxes_out, int32_t *status_out);
+int ke_crop_pack(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offsets, const int32_t *widths, const int32_t *heights,
+                 int32_t channels, const int32_t *boxes, int64_t n, uint8_t *dst, const uint64_t *dst_offsets);
+int ke_hash_images_trimmed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                           int32_t channels, int64_t n, int32_t tolerance, uint64_t *phash_out, int32_t *boxes_out, uint8_t *has_out,
+                           int32_t *status_out);
+
 /* ---- shipped refine stage ("next" row of SURVEY 8f): replaces the per-file work of
  * ui.dup_refine_parallel -- tile_ahash_bits (src/ui/dup_refine_parallel.py:59-83), _load_small_gray
  * (:203-207) and _mae01 (:208-210).
@@ -687,7 +721,8 @@ int ke_synth_hashes(ke_ctx *ctx, uint64_t seed, int64_t n, uint64_t *hashes_out)
 
 /* ---- timing hook for bench.py: wall time of the kernels enqueued by the LAST call of the
  * named kind on this context, measured with hipEvents on the context's stream.
- * kind: 0 = hash kernel(s), 1 = scan kernel, 2 = ssim kernel, 3 = synth kernel, 4 = JPEG / PNG decode kernels.
+ * kind: 0 = hash kernel(s), 1 = scan kernel, 2 = ssim kernel, 3 = synth kernel, 4 = JPEG / PNG decode kernels,
+ * 5 = content-box kernel, 6 = crop kernel.
  * Returns milliseconds, or a negative value if nothing was recorded.  Blocks until done. */
 double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind);
 

@@ -29,6 +29,7 @@ EXPORTS = (
     "ke_get_stream", "ke_synchronize", "ke_device_info", "ke_malloc", "ke_free", "ke_memcpy",
     "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan",
     "ke_hamming_scan_from", "ke_hamming_scan_cross", "ke_tiles_turned", "ke_hash_images_turned", "ke_band_pairs_after_size",
+    "ke_content_boxes", "ke_crop_pack", "ke_hash_images_trimmed",
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
@@ -147,6 +148,9 @@ def load_library() -> C.CDLL:
         lib.ke_hamming_scan_cross.argtypes = lib.ke_hamming_scan_from.argtypes
         lib.ke_tiles_turned.argtypes = [vp, vp, i64, vp]
         lib.ke_hash_images_turned.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp]
+        lib.ke_content_boxes.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp]
+        lib.ke_crop_pack.argtypes = [vp, vp, vp, vp, vp, i32, vp, i64, vp, vp]
+        lib.ke_hash_images_trimmed.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp]
         lib.ke_cluster_labels.argtypes = [vp, i64, i64, vp]
         lib.ke_ssim_pairs_uniform.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
         lib.ke_ssim_set_mode.argtypes = [vp, i32]
@@ -494,6 +498,60 @@ class Context:
             self._check(self._lib.ke_hash_images_turned(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n,
                                                         _addr(turned), _addr(status)), "ke_hash_images_turned")
         return turned, status
+
+    def content_boxes(self, images: Sequence[np.ndarray], tolerance: int):
+        """The content boxes (include/keyes.h, ke_content_boxes) of host images sharing one channel count:
+        (boxes int32[n, 4] as (x0, y0, x1, y1), four zeros for an image without a box; status int32[n])."""
+        n = len(images)
+        if n == 0:
+            return np.zeros((0, 4), np.int32), np.zeros(0, np.int32)
+        flat, offsets, widths, heights, ch = _pack_images(images)
+        boxes = np.zeros((n, 4), np.int32)
+        status = np.zeros(n, np.int32)
+        with self._lock:
+            self._check(self._lib.ke_content_boxes(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n, int(tolerance),
+                                                   _addr(boxes), _addr(status)), "ke_content_boxes")
+        return boxes, status
+
+    def content_boxes_at(self, pixels, offsets, widths, heights, channels: int, tolerance: int):
+        """``content_boxes`` of images that lie in one buffer already -- a host array or a device pointer -- at any byte
+        offsets: (boxes int32[n, 4], status int32[n])."""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        widths, heights = np.ascontiguousarray(widths, np.int32), np.ascontiguousarray(heights, np.int32)
+        n = len(offsets)
+        boxes = np.zeros((n, 4), np.int32)
+        status = np.zeros(n, np.int32)
+        with self._lock:
+            self._check(self._lib.ke_content_boxes(self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights), int(channels), n,
+                                                   int(tolerance), _addr(boxes), _addr(status)), "ke_content_boxes")
+        return boxes, status
+
+    def crop_pack(self, src: int, src_offsets, widths, heights, channels: int, boxes, dst: int, dst_offsets) -> None:
+        """Rows [y0, y1) x columns [x0, x1) of image i of a device buffer (``boxes[i]``) -> ``dst + dst_offsets[i]`` of the
+        caller's device buffer, rows packed (ke_crop_pack)."""
+        so, do = np.ascontiguousarray(src_offsets, np.uint64), np.ascontiguousarray(dst_offsets, np.uint64)
+        w, h = np.ascontiguousarray(widths, np.int32), np.ascontiguousarray(heights, np.int32)
+        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        if not len(so) == len(do) == len(w) == len(h) == len(b):
+            raise ValueError("crop_pack: the arrays differ in length")
+        with self._lock:
+            self._check(self._lib.ke_crop_pack(self._h, src, _addr(so), _addr(w), _addr(h), int(channels), _addr(b), len(so), dst, _addr(do)),
+                        "ke_crop_pack")
+
+    def hash_images_trimmed(self, images: Sequence[np.ndarray], tolerance: int):
+        """``hash_images`` with the trimmed pHash (include/keyes.h, ke_hash_images_trimmed): (phash u64[n], boxes int32[n, 4],
+        has bool[n], status int32[n]).  An image without a qualifying box has has = False and hash 0; its box is still there."""
+        n = len(images)
+        if n == 0:
+            return np.zeros(0, np.uint64), np.zeros((0, 4), np.int32), np.zeros(0, bool), np.zeros(0, np.int32)
+        flat, offsets, widths, heights, ch = _pack_images(images)
+        ph, boxes = np.zeros(n, np.uint64), np.zeros((n, 4), np.int32)
+        has, status = np.zeros(n, np.uint8), np.zeros(n, np.int32)
+        with self._lock:
+            self._check(self._lib.ke_hash_images_trimmed(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n,
+                                                         int(tolerance), _addr(ph), _addr(boxes), _addr(has), _addr(status)),
+                        "ke_hash_images_trimmed")
+        return ph, boxes, has.astype(bool), status
 
     # -- pinned staging ---------------------------------------------------------------------
     def stage_create(self, bytes_per_buffer: int, max_images: int, n_buffers: int = 2) -> None:
@@ -890,15 +948,24 @@ class Context:
         Returns (phash u64[n], dhash u64[n] | None, status int32[n]); status != 0 = not handled here (decode the file with
         Pillow).  The files come as bytes (``blobs``), as ``paths`` the library reads, or as ``ahead = (FilesAhead, lo, hi)``:
         files lo..hi of a batch read beforehand.  ``skip``: a mask of files to leave alone (status 1)."""
-        return self._hash_chain(blobs, want_dhash, kind, paths, ahead, skip, turned=False)
+        return self._hash_chain(blobs, want_dhash, kind, paths, ahead, skip, mode="plain")[:3]
 
     def hash_turned(self, blobs, *, kind: str, paths=None):
         """``hash``'s chain with ke_hash_images_turned behind the decode: (turned u64[n, 8], status int32[n]); status != 0 =
         not handled here, eight zeros."""
-        turned, _, st = self._hash_chain(blobs, False, kind, paths, None, None, turned=True)
+        turned, _, st, _ = self._hash_chain(blobs, False, kind, paths, None, None, mode="turned")
         return turned, st
 
-    def _hash_chain(self, blobs, want_dhash, kind, paths, ahead, skip, *, turned: bool):
+    def hash_trimmed(self, blobs, *, kind: str, paths=None, tolerance: int = 48):
+        """``hash``'s chain with ke_hash_images_trimmed behind the decode: (phash u64[n], boxes int32[n, 4], has bool[n],
+        status int32[n]); status != 0 = not handled here, zeros."""
+        ph, _, st, (boxes, has) = self._hash_chain(blobs, False, kind, paths, None, None, mode="trimmed", tolerance=tolerance)
+        return ph, boxes, has, st
+
+    def _hash_chain(self, blobs, want_dhash, kind, paths, ahead, skip, *, mode: str, tolerance: int = 0):
+        """(phash, dhash | None, status, extra) of one of the three calls behind the decode: "plain" ke_hash_images, "turned"
+        ke_hash_images_turned (phash is u64[n, 8]), "trimmed" ke_hash_images_trimmed (extra = (boxes, has), else None)."""
+        turned, trimmed = mode == "turned", mode == "trimmed"
         shape = (0, 8) if turned else (0,)
         if ahead is not None:                            # where the files come from is settled here, once
             n = ahead[2] - ahead[1]
@@ -910,11 +977,13 @@ class Context:
             n = len(blobs)
             take = lambda lo, hi: self._packed(blobs[lo:hi])
         if n == 0:
-            return np.zeros(shape, np.uint64), (np.zeros(0, np.uint64) if want_dhash else None), np.zeros(0, np.int32)
+            return (np.zeros(shape, np.uint64), (np.zeros(0, np.uint64) if want_dhash else None), np.zeros(0, np.int32),
+                    (np.zeros((0, 4), np.int32), np.zeros(0, bool)) if trimmed else None)
         skip = None if skip is None else np.asarray(skip, bool)
 
         def run(lo: int, hi: int):
             ph = np.zeros((hi - lo,) + shape[1:], np.uint64)
+            boxes, has = (np.zeros((hi - lo, 4), np.int32), np.zeros(hi - lo, bool)) if trimmed else (None, None)
             dh = np.zeros(hi - lo, np.uint64) if want_dhash else None
             dev, out_off, w, h, c, st, _ = self._decode_packed(take(lo, hi), kind, skip=None if skip is None else skip[lo:hi])
             for ch in (1, 3, 4):
@@ -929,6 +998,11 @@ class Context:
                 if turned:
                     self._check(self._lib.ke_hash_images_turned(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p),
                                                                 _addr(status)), "ke_hash_images_turned")
+                elif trimmed:
+                    b, t = np.zeros((len(idx), 4), np.int32), np.zeros(len(idx), np.uint8)
+                    self._check(self._lib.ke_hash_images_trimmed(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), int(tolerance),
+                                                                 _addr(p), _addr(b), _addr(t), _addr(status)), "ke_hash_images_trimmed")
+                    boxes[idx], has[idx] = b, t.astype(bool)
                 else:
                     self._check(self._lib.ke_hash_images(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p), _addr(d),
                                                          _addr(status)), "ke_hash_images")
@@ -936,12 +1010,13 @@ class Context:
                 if want_dhash:
                     dh[idx] = d
                 st[idx[status != 0]] = 2
-            return ph, dh, st
+            return ph, dh, st, boxes, has
 
         with self._lock:                                 # the decode buffer is this call's until the pixels are hashed
             parts = _in_halves(run, 0, n)
         return (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]) if want_dhash else None,
-                np.concatenate([p[2] for p in parts]))
+                np.concatenate([p[2] for p in parts]),
+                (np.concatenate([p[3] for p in parts]), np.concatenate([p[4] for p in parts])) if trimmed else None)
 
     # -- scan -------------------------------------------------------------------------------
     def hamming_scan(self, hashes, n: int, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4,

@@ -215,6 +215,43 @@ def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_
     return clusters, matches
 
 
+def _trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, band_bits, band_count, device):
+    """find_trimmed_duplicates' work: (clusters, matches)."""
+    from . import trimmed as _trimmed
+    from .scanner import DuplicateEdge, assemble_clusters
+
+    candidates = [f for f in _parse_files(files) if f.phash is not None]
+    if len(candidates) < 2:
+        return [], []
+    config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
+                                 band_count=band_count)
+    scanner = DuplicateScanner(config, device=device)
+    hashes, boxes, has, ok = _trimmed.trimmed_signatures([f.path for f in candidates], tolerance=tolerance, device=device)
+    plain = scanner.candidate_edges(candidates)
+    matches = scanner.trimmed_edges(candidates, hashes, has & ok, boxes)
+    edges = list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
+    return (assemble_clusters(candidates, edges) if edges else []), matches
+
+
+def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tolerance: int = 48, size_ratio: Optional[float] = None,
+                            band_bits: int = 16, band_count: int = 4, device: Optional[int] = None) -> tuple:
+    """(clusters, matches): near-duplicates including copies with a margin round them -- letterboxed, pillarboxed, framed,
+    on a white page, on a larger canvas.
+
+    ``files``: as for ``find_duplicates``, each with a readable ``path``: the files are read, their content boxes found on
+    the device (include/keyes.h, ``ke_content_boxes``: the pixels farther than ``tolerance`` from the corner pixel) and the
+    pHash of every qualifying box made (``trimmed.trimmed_signatures``; nothing is stored).  ``matches``: the
+    ``scanner.TrimmedMatch`` list of ``DuplicateScanner.trimmed_edges`` -- file a, file b, which side was cut, the hamming
+    distance, the boxes.  ``clusters``: ``assemble_clusters`` over the plain candidate edges of the stored hashes together
+    with the matches as edges.  A file without a qualifying box, or one that cannot be opened, takes part with its stored
+    pHash only.
+
+    Out of scope here: an SSIM or MAE re-check on the crop, ``devices=[...]`` (one process, one GPU), persisting trimmed
+    hashes, borders of two colours or gradients, trimmed and turned together, and dHash."""
+    return _trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio, band_bits=band_bits,
+                         band_count=band_count, device=0 if device is None else int(device))
+
+
 def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None, config: Optional[DuplicateScanConfig] = None,
                        progress: Optional[Callable[[str, int, int], None]] = None,
                        cancel_fn: Optional[Callable[[], bool]] = None, device: Optional[int] = None,
@@ -255,5 +292,5 @@ def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None
     return DuplicateScanner(config or DuplicateScanConfig(), device=device).build_clusters(files)
 
 
-__all__ = ["DedupSettings", "compute_signature", "find_duplicates", "find_new_duplicates", "find_turned_duplicates", "run_duplicate_scan",
-           "ClusterBuilder"]
+__all__ = ["DedupSettings", "compute_signature", "find_duplicates", "find_new_duplicates", "find_turned_duplicates", "find_trimmed_duplicates",
+           "run_duplicate_scan", "ClusterBuilder"]

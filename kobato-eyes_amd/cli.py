@@ -3,6 +3,7 @@
     python -m kobato_eyes_amd.cli scan-dups --db kobato.db --hamming 8 [--like '%/photos/%'] [--size-ratio 0.5]
                                             [--added-like '%/incoming/%'] [--refine] [--csv out.csv] [--device 0]
                                             [--devices 0,1,2] [--turned [--turned-ssim 0.9]]
+                                            [--trimmed [--trim-tolerance 48]]
 
 Reproduces the call sequence of DuplicateScanRunnable.run (src/ui/dup_workers.py:148-239) without Qt: rows in
 the shape of db.repository.iter_files_for_dup (src/db/repository.py:416-454), missing signatures filled and
@@ -45,12 +46,14 @@ def iter_files_for_dup(conn: sqlite3.Connection, path_like: Optional[str], added
         yield item
 
 
-def export_duplicate_clusters_csv(clusters: Sequence, file_path, orientations: Optional[dict] = None) -> None:
+def export_duplicate_clusters_csv(clusters: Sequence, file_path, orientations: Optional[dict] = None, boxes: Optional[dict] = None) -> None:
     """``orientations`` (scan-dups --turned): {file_id: orientation}; the CSV then has a ninth column ``orientation``,
-    filled for the files that are linked to their group's keeper only through a turn (``orientations_to_keeper``)."""
+    filled for the files that are linked to their group's keeper only through a turn (``orientations_to_keeper``).
+    ``boxes`` (scan-dups --trimmed): {file_id: (x0, y0, x1, y1)}; the ninth column is then ``box``, ``x0 y0 x1 y1`` for a file
+    that is linked through its content box (``boxes_of_matches``) and empty for a file linked as it is."""
     with open(file_path, "w", encoding="utf-8", newline="") as handle:
         writer = csv.writer(handle)
-        writer.writerow(CSV_HEADER + (["orientation"] if orientations is not None else []))
+        writer.writerow(CSV_HEADER + (["orientation"] if orientations is not None else []) + (["box"] if boxes is not None else []))
         for group, cluster in enumerate(clusters, start=1):
             for entry in cluster.files:
                 f = entry.file
@@ -59,7 +62,20 @@ def export_duplicate_clusters_csv(clusters: Sequence, file_path, orientations: O
                        entry.best_hamming if entry.best_hamming is not None else ""]
                 if orientations is not None:
                     row.append(orientations.get(f.file_id, ""))
+                if boxes is not None:
+                    row.append(" ".join(str(v) for v in boxes[f.file_id]) if f.file_id in boxes else "")
                 writer.writerow(row)
+
+
+def boxes_of_matches(matches: Sequence) -> dict:
+    """{file_id: box} for the files that some ``scanner.TrimmedMatch`` links through their content box."""
+    out: dict = {}
+    for m in matches:
+        if m.trimmed_a and m.box_a is not None:
+            out[m.file_id_a] = m.box_a
+        if m.trimmed_b and m.box_b is not None:
+            out[m.file_id_b] = m.box_b
+    return out
 
 
 def orientations_to_keeper(clusters: Sequence, matches: Sequence, plain_keys) -> dict:
@@ -93,7 +109,8 @@ def orientations_to_keeper(clusters: Sequence, matches: Sequence, plain_keys) ->
 def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, path_like: Optional[str] = None,
                   refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
                   devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None, turned: bool = False,
-                  orientations_out: Optional[dict] = None, turned_ssim: Optional[float] = None) -> list:
+                  orientations_out: Optional[dict] = None, turned_ssim: Optional[float] = None, trimmed: bool = False,
+                  trim_tolerance: int = 48, boxes_out: Optional[dict] = None) -> list:
     """``devices``: the missing signatures are computed by one worker process per entry; the scan and the tile-aHash / MAE
     refine stay in this process, on ``device`` (default ``devices[0]``, else 0).  ``added_like``: the files of the
     selection whose path matches this LIKE pattern are the added set, the rest the library; only the pairs that touch an
@@ -103,9 +120,15 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
     ``added_like`` or ``refine``); ``orientations_out`` then receives ``orientations_to_keeper`` of the result.
     ``turned_ssim`` (only with ``turned``): the candidate edges and the turned matches are re-checked with SSIM, a match with
     one file turned on the device, and only those at or above this score link files (``find_turned_duplicates``'
-    ``ssim_threshold``); the orientations are then worked out from the survivors."""
+    ``ssim_threshold``); the orientations are then worked out from the survivors.  ``trimmed``: the files of the selection
+    are read and copies with a margin round them are linked as well (``find_trimmed_duplicates`` with ``trim_tolerance``;
+    not together with ``turned``, ``added_like`` or ``refine``); ``boxes_out`` then receives ``boxes_of_matches`` of the
+    result."""
     if turned_ssim is not None and not turned:
         raise ValueError("--turned-ssim needs --turned")
+    if trimmed and (turned or added_like or refine):
+        # the refine pipeline compares whole pictures and would cut every link that exists through a crop
+        raise ValueError("--trimmed cannot be combined with --turned, --added-like or --refine")
     if turned and (added_like or refine):
         # the refine pipeline compares pixels as they lie and would cut every link that exists through a turn
         raise ValueError("--turned cannot be combined with --added-like or --refine")
@@ -151,6 +174,13 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
                                                      band_bits=16, band_count=4, device=device, ssim_threshold=turned_ssim)
         if orientations_out is not None:
             orientations_out.update(orientations_to_keeper(clusters, matches, plain_keys))
+    elif trimmed:
+        from .api import _trimmed_scan
+
+        clusters, matches = _trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=trim_tolerance, size_ratio=size_ratio,
+                                          band_bits=16, band_count=4, device=device)
+        if boxes_out is not None:
+            boxes_out.update(boxes_of_matches(matches))
     elif added_like:
         from .api import find_new_duplicates
 
@@ -185,6 +215,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("--turned-ssim", type=float, default=None,
                     help="with --turned: re-check every candidate edge and turned match with SSIM on the pixels (one file turned on "
                          "the device for a match) and link only those at or above this score, e.g. 0.9")
+    sp.add_argument("--trimmed", action="store_true",
+                    help="read the files of the selection and link copies with a margin round them as well (letterbox, pillarbox, "
+                         "frame, white page); the CSV gains a box column: x0 y0 x1 y1 of a file linked through its content box")
+    sp.add_argument("--trim-tolerance", type=int, default=48,
+                    help="with --trimmed: a pixel belongs to the content when a channel lies farther than this from the corner pixel")
     sp.add_argument("--refine", action="store_true", help="run the tile-aHash + pixel-MAE refine pipeline on the clusters")
     sp.add_argument("--tile-max-bits", type=int, default=32)
     sp.add_argument("--mae-thr", type=float, default=0.004)
@@ -196,12 +231,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARNING)
     orientations = {} if args.turned else None
+    boxes = {} if args.trimmed else None
     clusters = scan_database(args.db, hamming_threshold=args.hamming, size_ratio=args.size_ratio, path_like=args.like,
                              refine=args.refine, tile_max_bits=args.tile_max_bits, mae_thr=args.mae_thr, device=args.device,
                              devices=args.devices, added_like=args.added_like, turned=args.turned, orientations_out=orientations,
-                             turned_ssim=args.turned_ssim)
+                             turned_ssim=args.turned_ssim, trimmed=args.trimmed, trim_tolerance=args.trim_tolerance, boxes_out=boxes)
     if args.csv:
-        export_duplicate_clusters_csv(clusters, args.csv, orientations)
+        export_duplicate_clusters_csv(clusters, args.csv, orientations, boxes)
     members = sum(len(c.files) for c in clusters)
     print(f"{len(clusters)} duplicate group(s), {members} file(s)" + (f" -> {args.csv}" if args.csv else ""))
     return 0

@@ -22,7 +22,7 @@ struct KeDevBuf {
     size_t bytes = 0;
 };
 
-enum { KE_T_HASH = 0, KE_T_SCAN = 1, KE_T_SSIM = 2, KE_T_SYNTH = 3, KE_T_JPEG = 4, KE_T_COUNT = 5 };
+enum { KE_T_HASH = 0, KE_T_SCAN = 1, KE_T_SSIM = 2, KE_T_SYNTH = 3, KE_T_JPEG = 4, KE_T_TRIM_BOX = 5, KE_T_TRIM_CROP = 6, KE_T_COUNT = 7 };
 enum {
     KE_BUF_PIXELS = 0,   // staged input images
     KE_BUF_TMP,          // first-pass output of the generic resampler
@@ -46,6 +46,8 @@ enum {
     KE_BUF_JPEG_TABLES,  // Huffman tables of a JPEG batch
     KE_BUF_TURN_TILES,   // ke_hash_images_turned: the 32x32 tiles of a call's images, group after group
     KE_BUF_TURN_LUMA,    // ke_ssim_pairs_turned: the turned luma planes of a call, 1 B/px per distinct (image, orientation)
+    KE_BUF_TRIM_BOXES,   // ke_content_boxes: the boxes of a call's images, 16 B each
+    KE_BUF_TRIM_CROPS,   // ke_hash_images_trimmed: the packed crops of one chunk of qualifying images
     KE_BUF_COUNT
 };
 

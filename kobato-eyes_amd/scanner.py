@@ -165,6 +165,21 @@ class TurnedMatch:
     ssim: Optional[float] = None
 
 
+@dataclass(frozen=True)
+class TrimmedMatch:
+    """Two files of which one looks like the other with a margin round it, to within ``hamming`` bits of the pHash.
+    ``trimmed_a`` / ``trimmed_b``: whether that side entered the comparison cut to its content box; ``box_a`` / ``box_b``: that
+    box as (x0, y0, x1, y1), None where the side is the file as it is.  file_id_a < file_id_b."""
+
+    file_id_a: int
+    file_id_b: int
+    trimmed_a: bool
+    trimmed_b: bool
+    hamming: int
+    box_a: Optional[tuple] = None
+    box_b: Optional[tuple] = None
+
+
 def _safe_positive_int(value: Optional[str]) -> Optional[int]:
     if value is None or not value.strip():
         return None
@@ -271,6 +286,55 @@ class DuplicateScanner:
             if (id_a, id_b) not in best or found < best[(id_a, id_b)]:
                 best[(id_a, id_b)] = found
         return [TurnedMatch(a, b, k, h) for (a, b), (h, k) in sorted(best.items())]
+
+    def trimmed_edges(self, candidates: Sequence[DuplicateFile], hashes, has, boxes=None) -> list:
+        """[TrimmedMatch]: the pairs of files of which one looks like the other with a margin round it.
+
+        ``hashes``: u64[n], entry i the trimmed pHash of candidates[i]; ``has``: the mask of the files that have one
+        (trimmed.trimmed_signatures); ``boxes``: int32[n, 4], the boxes the matches carry (None: a trimmed side carries no
+        box either).  The table is [stored pHash of the n candidates | trimmed hash of the files with one], a trimmed entry
+        carrying its file's id and size -- the scan's own ``ids[i] != ids[j]`` therefore drops a file against its own crop --
+        and the scan is the scan from first_new = n (``ke_hamming_scan_from``), NOT the cross scan: two copies of a picture
+        with different margins meet in trimmed x trimmed.  One match is kept per unordered pair of files: the smallest
+        hamming, then (trimmed_a, trimmed_b) in order.  size_ratio, the band config, KE_DUP_BUCKET_PAIR_CAP and this scanner's
+        part_index / part_count apply as in ``candidate_edges``; the funnel counters are not touched."""
+        cfg = self._config
+        n = len(candidates)
+        hashes = np.asarray(hashes, dtype=np.uint64).reshape(n)
+        src = np.nonzero(np.asarray(has, bool).reshape(n))[0]
+        if n == 0 or len(src) == 0:
+            return []
+        base_h = np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=n)
+        base_ids = np.fromiter((f.file_id for f in candidates), dtype=np.int64, count=n)
+        base_sizes = np.fromiter(((f.size or 0) for f in candidates), dtype=np.int64, count=n)
+        table = np.concatenate([base_h, hashes[src]])
+        ids = np.concatenate([base_ids, base_ids[src]])
+        sizes = np.concatenate([base_sizes, base_sizes[src]])
+        cap = _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
+        ratio = cfg.size_ratio if (cfg.size_ratio is not None and cfg.size_ratio > 0) else 0.0
+        ctx = _native.get_context(self._device)
+        raw, _ = ctx.hamming_scan(
+            table, len(table), ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
+            band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
+            part_index=self._part[0], part_count=self._part[1], first_new=n, cross=False)
+
+        def side(pos: int) -> tuple:           # table position -> (candidate, trimmed)
+            return (int(src[pos - n]), True) if pos >= n else (pos, False)
+
+        best: dict[tuple[int, int], tuple] = {}
+        for a, b, h in zip(raw["a"].tolist(), raw["b"].tolist(), raw["h"].tolist()):
+            (ca, ta), (cb, tb) = side(a), side(b)
+            if base_ids[ca] > base_ids[cb]:
+                ca, ta, cb, tb = cb, tb, ca, ta
+            key = (int(base_ids[ca]), int(base_ids[cb]))
+            found = (int(h), ta, tb, ca, cb)
+            if key not in best or found[:3] < best[key][:3]:
+                best[key] = found
+
+        def box(c: int, trimmed: bool) -> Optional[tuple]:
+            return tuple(int(v) for v in np.asarray(boxes)[c]) if trimmed and boxes is not None else None
+
+        return [TrimmedMatch(a, b, ta, tb, h, box(ca, ta), box(cb, tb)) for (a, b), (h, ta, tb, ca, cb) in sorted(best.items())]
 
     # -- the reference's funnel counters (src/dup/scanner.py:258-299) ---------------------------------------------
     def _band_values(self, hashes: np.ndarray, band: int) -> np.ndarray:
