@@ -673,7 +673,13 @@ int ke_ssim_pairs_turned(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *off
  *   most 1 GiB a chunk (or one crop, if larger), ke_hash_images on the crops.  has_out[i] = 1 and phash_out[i] = the trimmed
  *   pHash where the box qualifies; otherwise has_out[i] = 0 and phash_out[i] = 0, and boxes_out still holds the box.  A failed
  *   image has status != KE_IMG_OK and zeros.  pixels: host (staged in chunks of at most 1 GiB) or device; the rest host arrays.
- * All three block.  ke_last_kernel_ms kind 5 times the box kernel, kind 6 the crop kernel (of the last chunk). */
+ * ke_crop_luma: the same rows and columns of image i (channels[i] = 1, 3 or 4, the fourth byte ignored; any other count, an
+ *   empty box or one not inside its image: KE_EINVAL, nothing launched) -> their convert("L") luma (ke_turn_luma's, orientation
+ *   0), 1 byte per pixel, rows packed, at dst + dst_offsets[i]; any byte offset is legal on both sides, nothing is read outside
+ *   [src + src_offsets[i], + w * h * channels[i]) and nothing written outside the plane.  One streaming pass: no LDS, a wave a
+ *   box row, aligned dwords on both sides.  src, dst: device; the arrays: host.
+ * All four block.  ke_last_kernel_ms kind 5 times the box kernel, kind 6 the crop kernel (of the last chunk), kind 7 the
+ * luma-crop kernel. */
 int ke_content_boxes(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
                      int32_t channels, int64_t n, int32_t tolerance, int32_t *boxes_out, int32_t *status_out);
 int ke_crop_pack(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offsets, const int32_t *widths, const int32_t *heights,
@@ -681,6 +687,22 @@ int ke_crop_pack(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offsets, c
 int ke_hash_images_trimmed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
                            int32_t channels, int64_t n, int32_t tolerance, uint64_t *phash_out, int32_t *boxes_out, uint8_t *has_out,
                            int32_t *status_out);
+int ke_crop_luma(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offsets, const int32_t *widths, const int32_t *heights,
+                 const int32_t *channels, const int32_t *boxes, int64_t n, uint8_t *dst, const uint64_t *dst_offsets);
+
+/* ke_ssim_pairs with two more arrays, for re-checking a bordered copy on its content box: pair k is box box_a[4 k ..] of image
+ * pair_a[k] against box box_b[4 k ..] of image pair_b[k], boxes as (x0, y0, x1, y1).  A NULL array, a box of four zeros and the
+ * box (0, 0, w, h) mean the image as it lies: that side enters the fit straight from `pixels`, as in ke_ssim_pairs.  Any other
+ * box must be non-empty and inside its image, else KE_EINVAL naming the pair, nothing launched.  The common size is the minimum
+ * of the two VIEW sizes; the fit, the SSIM and the statuses are ke_ssim_pairs'.  Every distinct (image, box) of a call is cut
+ * out once, by one ke_crop_luma launch into scratch of 1 byte per pixel, and enters the fit as a one-channel source of the
+ * box's size; fit groups are (view w, view h, cropped or not).
+ * CROP, THEN FIT.  The box is not folded into the fit's resample box: Pillow's resampler clips its taps to the image it is given,
+ * not to the box, so the margin would bleed into the crop's edge.  As it is, the answer is bit-equal to ke_ssim_pairs on images
+ * that hold the crops (a.crop(box_a), b.crop(box_b)): luma is per pixel and the resampler is bit-exact. */
+int ke_ssim_pairs_boxed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                        int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *box_a,
+                        const int32_t *box_b, int64_t n_pairs, double *ssim_out, int32_t *status_out);
 
 /* ---- shipped refine stage ("next" row of SURVEY 8f): replaces the per-file work of
  * ui.dup_refine_parallel -- tile_ahash_bits (src/ui/dup_refine_parallel.py:59-83), _load_small_gray
@@ -722,7 +744,7 @@ int ke_synth_hashes(ke_ctx *ctx, uint64_t seed, int64_t n, uint64_t *hashes_out)
 /* ---- timing hook for bench.py: wall time of the kernels enqueued by the LAST call of the
  * named kind on this context, measured with hipEvents on the context's stream.
  * kind: 0 = hash kernel(s), 1 = scan kernel, 2 = ssim kernel, 3 = synth kernel, 4 = JPEG / PNG decode kernels,
- * 5 = content-box kernel, 6 = crop kernel.
+ * 5 = content-box kernel, 6 = crop kernel, 7 = luma-crop kernel.
  * Returns milliseconds, or a negative value if nothing was recorded.  Blocks until done. */
 double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind);
 

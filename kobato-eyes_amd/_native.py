@@ -29,7 +29,7 @@ EXPORTS = (
     "ke_get_stream", "ke_synchronize", "ke_device_info", "ke_malloc", "ke_free", "ke_memcpy",
     "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan",
     "ke_hamming_scan_from", "ke_hamming_scan_cross", "ke_tiles_turned", "ke_hash_images_turned", "ke_band_pairs_after_size",
-    "ke_content_boxes", "ke_crop_pack", "ke_hash_images_trimmed",
+    "ke_content_boxes", "ke_crop_pack", "ke_hash_images_trimmed", "ke_crop_luma", "ke_ssim_pairs_boxed",
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
@@ -151,6 +151,8 @@ def load_library() -> C.CDLL:
         lib.ke_content_boxes.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp]
         lib.ke_crop_pack.argtypes = [vp, vp, vp, vp, vp, i32, vp, i64, vp, vp]
         lib.ke_hash_images_trimmed.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp]
+        lib.ke_crop_luma.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+        lib.ke_ssim_pairs_boxed.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp]
         lib.ke_cluster_labels.argtypes = [vp, i64, i64, vp]
         lib.ke_ssim_pairs_uniform.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
         lib.ke_ssim_set_mode.argtypes = [vp, i32]
@@ -537,6 +539,29 @@ class Context:
         with self._lock:
             self._check(self._lib.ke_crop_pack(self._h, src, _addr(so), _addr(w), _addr(h), int(channels), _addr(b), len(so), dst, _addr(do)),
                         "ke_crop_pack")
+
+    def content_boxes_on_device(self, pointers, widths, heights, channels: int, tolerance: int):
+        """``content_boxes`` of images that already lie in device memory, each at its own address (decoded there, or
+        uploaded), as ``ssim_pairs_on_device`` takes them: (boxes int32[n, 4], status int32[n])."""
+        ptrs = np.asarray(pointers, np.uint64)
+        if len(ptrs) == 0:
+            return np.zeros((0, 4), np.int32), np.zeros(0, np.int32)
+        base = int(ptrs.min())
+        return self.content_boxes_at(base, ptrs - np.uint64(base), widths, heights, channels, tolerance)
+
+    def crop_luma(self, src: int, src_offsets, widths, heights, channels, boxes, dst: int, dst_offsets) -> None:
+        """The ``convert("L")`` luma of rows [y0, y1) x columns [x0, x1) of image i of a device buffer (``boxes[i]``;
+        ``channels[i]`` = 1, 3 or 4) -> ``dst + dst_offsets[i]`` of the caller's device buffer, one byte per pixel, rows packed
+        (ke_crop_luma)."""
+        so, do = np.ascontiguousarray(src_offsets, np.uint64), np.ascontiguousarray(dst_offsets, np.uint64)
+        w, h = np.ascontiguousarray(widths, np.int32), np.ascontiguousarray(heights, np.int32)
+        c = np.ascontiguousarray(channels, np.int32)
+        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        if not len(so) == len(do) == len(w) == len(h) == len(c) == len(b):
+            raise ValueError("crop_luma: the arrays differ in length")
+        with self._lock:
+            self._check(self._lib.ke_crop_luma(self._h, src, _addr(so), _addr(w), _addr(h), _addr(c), _addr(b), len(so), dst, _addr(do)),
+                        "ke_crop_luma")
 
     def hash_images_trimmed(self, images: Sequence[np.ndarray], tolerance: int):
         """``hash_images`` with the trimmed pHash (include/keyes.h, ke_hash_images_trimmed): (phash u64[n], boxes int32[n, 4],
@@ -1152,6 +1177,42 @@ class Context:
                                                        _addr(pa), _addr(pb), _addr(ob), len(pa), _addr(out), _addr(status)),
                         "ke_ssim_pairs_turned")
         return out, status
+
+    def _ssim_pairs_boxed(self, pixels, offsets, widths, heights, channels: int, n: int, pair_a, pair_b, box_a, box_b):
+        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
+        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
+        boxes = []
+        for b in (box_a, box_b):
+            b = None if b is None else np.ascontiguousarray(b, dtype=np.int32).reshape(-1, 4)
+            if b is not None and len(b) != len(pa):
+                raise ValueError("ssim_pairs_boxed: a box array holds one box per pair")
+            boxes.append(b)
+        if len(pb) != len(pa):
+            raise ValueError("ssim_pairs_boxed: the pair arrays differ in length")
+        out = np.empty(len(pa), np.float64)
+        status = np.empty(len(pa), np.int32)
+        with self._lock:
+            self._check(self._lib.ke_ssim_pairs_boxed(self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights), int(channels), n,
+                                                      _addr(pa), _addr(pb), _addr(boxes[0]), _addr(boxes[1]), len(pa), _addr(out),
+                                                      _addr(status)), "ke_ssim_pairs_boxed")
+        return out, status
+
+    def ssim_pairs_boxed(self, images: Sequence[np.ndarray], pair_a, pair_b, box_a, box_b):
+        """ssim_pairs on boxes of the images (ke_ssim_pairs_boxed): pair k is box ``box_a[k]`` of image ``pair_a[k]`` against box
+        ``box_b[k]`` of image ``pair_b[k]``, boxes as (x0, y0, x1, y1).  ``None``, four zeros and (0, 0, w, h) mean the image as it
+        lies.  The scores are those of ``ssim_pairs`` on images that hold the crops, bit for bit."""
+        flat, offsets, widths, heights, ch = _pack_images(images)
+        return self._ssim_pairs_boxed(flat, offsets, widths, heights, ch, len(images), pair_a, pair_b, box_a, box_b)
+
+    def ssim_pairs_boxed_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b, box_a, box_b):
+        """ssim_pairs_on_device on boxes of the images: each distinct (image, box) is cut out once on the device, luma only
+        (ke_crop_luma), before the fit."""
+        ptrs = np.asarray(pointers, np.uint64)
+        base = int(ptrs.min())
+        offsets = np.ascontiguousarray(ptrs - np.uint64(base))
+        widths = np.ascontiguousarray(widths, np.int32)
+        heights = np.ascontiguousarray(heights, np.int32)
+        return self._ssim_pairs_boxed(base, offsets, widths, heights, channels, len(ptrs), pair_a, pair_b, box_a, box_b)
 
     def turn_luma(self, src: int, src_offsets, widths, heights, channels, orientations, dst: int, dst_offsets) -> None:
         """Images on the device (``widths[i]`` x ``heights[i]``, 1, 3 or 4 channels, at ``src + src_offsets[i]``) -> the luma plane

@@ -215,8 +215,29 @@ def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_
     return clusters, matches
 
 
-def _trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, band_bits, band_count, device):
-    """find_trimmed_duplicates' work: (clusters, matches)."""
+def _trimmed_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, tolerance: int,
+                       device: int) -> tuple:
+    """The plain candidate edges and the trimmed matches that pass the SSIM re-check, from one refine_trimmed_pairs call: a
+    plain edge is scored as the pixels lie (neither side trimmed), a match with its ``trimmed_a`` / ``trimmed_b``.  A
+    surviving match carries its score; a pair whose files cannot be read is dropped, as _ssim_kept drops it."""
+    from dataclasses import replace
+
+    by_id = {f.file_id: f for f in candidates}
+    keys = list(plain)
+    rows = [(plain[k].file_id_a, plain[k].file_id_b, by_id[plain[k].file_id_a].path, by_id[plain[k].file_id_b].path, False, False)
+            for k in keys]
+    rows += [(m.file_id_a, m.file_id_b, by_id[m.file_id_a].path, by_id[m.file_id_b].path, m.trimmed_a, m.trimmed_b) for m in matches]
+    refined = _refine.refine_trimmed_pairs(rows, tolerance=tolerance, thresholds=_refine.RefinementThresholds(ssim=ssim_threshold),
+                                           device=device)
+    passed = [r is not None and r.is_duplicate for r in refined]
+    kept_plain = {k: plain[k] for k, yes in zip(keys, passed) if yes}
+    kept_matches = [replace(m, ssim=r.ssim) for m, r, yes in zip(matches, refined[len(keys):], passed[len(keys):]) if yes]
+    return kept_plain, kept_matches
+
+
+def _trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, band_bits, band_count, device, ssim_threshold=None):
+    """find_trimmed_duplicates' work: (clusters, matches).  With ``ssim_threshold`` the matches, and the plain edges among the
+    clusters' links, are the ones that passed the re-check."""
     from . import trimmed as _trimmed
     from .scanner import DuplicateEdge, assemble_clusters
 
@@ -229,12 +250,15 @@ def _trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, 
     hashes, boxes, has, ok = _trimmed.trimmed_signatures([f.path for f in candidates], tolerance=tolerance, device=device)
     plain = scanner.candidate_edges(candidates)
     matches = scanner.trimmed_edges(candidates, hashes, has & ok, boxes)
-    edges = list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
+    if ssim_threshold is not None and (plain or matches):
+        plain, matches = _trimmed_ssim_kept(plain, matches, candidates, ssim_threshold, tolerance, device)
+    edges =list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
     return (assemble_clusters(candidates, edges) if edges else []), matches
 
 
 def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tolerance: int = 48, size_ratio: Optional[float] = None,
-                            band_bits: int = 16, band_count: int = 4, device: Optional[int] = None) -> tuple:
+                            band_bits: int = 16, band_count: int = 4, device: Optional[int] = None,
+                            ssim_threshold: Optional[float] = None) -> tuple:
     """(clusters, matches): near-duplicates including copies with a margin round them -- letterboxed, pillarboxed, framed,
     on a white page, on a larger canvas.
 
@@ -246,10 +270,16 @@ def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tole
     with the matches as edges.  A file without a qualifying box, or one that cannot be opened, takes part with its stored
     pHash only.
 
-    Out of scope here: an SSIM or MAE re-check on the crop, ``devices=[...]`` (one process, one GPU), persisting trimmed
+    With ``ssim_threshold`` set, every plain candidate edge and every match is re-checked on the files' pixels, a match with
+    each trimmed side cut to its content box on the device -- the box of the pixels as the refine seam decodes them, found
+    there (``refine.refine_trimmed_pairs``, one call for all).  Only edges with ``ssim >= ssim_threshold`` reach the clusters,
+    and ``matches`` holds the surviving matches, each with its ``ssim``.  A pair that is both a plain edge and a match stays
+    linked if either passes; a pair with an unreadable file is dropped.  Unset: no pixels are compared and ``ssim`` is None.
+
+    Out of scope here: an MAE re-check on the crop, ``devices=[...]`` (one process, one GPU), persisting trimmed
     hashes, borders of two colours or gradients, trimmed and turned together, and dHash."""
     return _trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio, band_bits=band_bits,
-                         band_count=band_count, device=0 if device is None else int(device))
+                         band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)
 
 
 def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None, config: Optional[DuplicateScanConfig] = None,

@@ -3,7 +3,7 @@
     python -m kobato_eyes_amd.cli scan-dups --db kobato.db --hamming 8 [--like '%/photos/%'] [--size-ratio 0.5]
                                             [--added-like '%/incoming/%'] [--refine] [--csv out.csv] [--device 0]
                                             [--devices 0,1,2] [--turned [--turned-ssim 0.9]]
-                                            [--trimmed [--trim-tolerance 48]]
+                                            [--trimmed [--trim-tolerance 48] [--trimmed-ssim 0.9]]
 
 Reproduces the call sequence of DuplicateScanRunnable.run (src/ui/dup_workers.py:148-239) without Qt: rows in
 the shape of db.repository.iter_files_for_dup (src/db/repository.py:416-454), missing signatures filled and
@@ -110,7 +110,7 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
                   refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
                   devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None, turned: bool = False,
                   orientations_out: Optional[dict] = None, turned_ssim: Optional[float] = None, trimmed: bool = False,
-                  trim_tolerance: int = 48, boxes_out: Optional[dict] = None) -> list:
+                  trim_tolerance: int = 48, boxes_out: Optional[dict] = None, trimmed_ssim: Optional[float] = None) -> list:
     """``devices``: the missing signatures are computed by one worker process per entry; the scan and the tile-aHash / MAE
     refine stay in this process, on ``device`` (default ``devices[0]``, else 0).  ``added_like``: the files of the
     selection whose path matches this LIKE pattern are the added set, the rest the library; only the pairs that touch an
@@ -123,9 +123,13 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
     ``ssim_threshold``); the orientations are then worked out from the survivors.  ``trimmed``: the files of the selection
     are read and copies with a margin round them are linked as well (``find_trimmed_duplicates`` with ``trim_tolerance``;
     not together with ``turned``, ``added_like`` or ``refine``); ``boxes_out`` then receives ``boxes_of_matches`` of the
-    result."""
+    result.  ``trimmed_ssim`` (only with ``trimmed``): the candidate edges and the trimmed matches are re-checked with SSIM, a
+    match with its trimmed sides cut to their content boxes on the device, and only those at or above this score link files
+    (``find_trimmed_duplicates``' ``ssim_threshold``); the boxes are then those of the survivors."""
     if turned_ssim is not None and not turned:
         raise ValueError("--turned-ssim needs --turned")
+    if trimmed_ssim is not None and not trimmed:
+        raise ValueError("--trimmed-ssim needs --trimmed")
     if trimmed and (turned or added_like or refine):
         # the refine pipeline compares whole pictures and would cut every link that exists through a crop
         raise ValueError("--trimmed cannot be combined with --turned, --added-like or --refine")
@@ -178,7 +182,7 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
         from .api import _trimmed_scan
 
         clusters, matches = _trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=trim_tolerance, size_ratio=size_ratio,
-                                          band_bits=16, band_count=4, device=device)
+                                          band_bits=16, band_count=4, device=device, ssim_threshold=trimmed_ssim)
         if boxes_out is not None:
             boxes_out.update(boxes_of_matches(matches))
     elif added_like:
@@ -220,6 +224,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                          "frame, white page); the CSV gains a box column: x0 y0 x1 y1 of a file linked through its content box")
     sp.add_argument("--trim-tolerance", type=int, default=48,
                     help="with --trimmed: a pixel belongs to the content when a channel lies farther than this from the corner pixel")
+    sp.add_argument("--trimmed-ssim", type=float, default=None,
+                    help="with --trimmed: re-check every candidate edge and trimmed match with SSIM on the pixels (a trimmed side cut "
+                         "to its content box on the device) and link only those at or above this score, e.g. 0.9")
     sp.add_argument("--refine", action="store_true", help="run the tile-aHash + pixel-MAE refine pipeline on the clusters")
     sp.add_argument("--tile-max-bits", type=int, default=32)
     sp.add_argument("--mae-thr", type=float, default=0.004)
@@ -235,7 +242,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     clusters = scan_database(args.db, hamming_threshold=args.hamming, size_ratio=args.size_ratio, path_like=args.like,
                              refine=args.refine, tile_max_bits=args.tile_max_bits, mae_thr=args.mae_thr, device=args.device,
                              devices=args.devices, added_like=args.added_like, turned=args.turned, orientations_out=orientations,
-                             turned_ssim=args.turned_ssim, trimmed=args.trimmed, trim_tolerance=args.trim_tolerance, boxes_out=boxes)
+                             turned_ssim=args.turned_ssim, trimmed=args.trimmed, trim_tolerance=args.trim_tolerance, boxes_out=boxes,
+                             trimmed_ssim=args.trimmed_ssim)
     if args.csv:
         export_duplicate_clusters_csv(clusters, args.csv, orientations, boxes)
     members = sum(len(c.files) for c in clusters)

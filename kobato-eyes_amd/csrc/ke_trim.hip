@@ -1,6 +1,7 @@
 // ke_trim.hip -- bordered copies: the content box of every image of a batch (ke_content_boxes), the boxes' rows copied out
-// packed (ke_crop_pack), and the pHash of the qualifying crops through the existing hash dispatch (ke_hash_images_trimmed).
-// The definition is in include/keyes.h, the arithmetic in ke_trim_core.h.
+// packed (ke_crop_pack), the pHash of the qualifying crops through the existing hash dispatch (ke_hash_images_trimmed), and the
+// luma plane of a box (ke_crop_luma, the crop of ke_ssim_pairs_boxed in ke_api.hip).
+// The definition is in include/keyes.h, the arithmetic in ke_trim_core.h, the luma in ke_turn_core.h.
 //
 // ke_content_boxes_kernel: one read of every pixel.  A work item is (image, band of KE_TRIM_BAND_ROWS rows); a workgroup of
 // 256 threads takes a run of the item list.  A wave takes a row, its lanes the row's aligned 16-byte vectors: the row starts on
@@ -19,10 +20,14 @@
 // at any alignment, so they are cut from two aligned source dwords with a funnel shift (ke_turn.hip's step C), and a row's
 // first and last <= 3 bytes are byte stores.  A source dword that reaches outside the image's bytes is put together from
 // byte loads.
+//
+// ke_crop_luma_kernel: the same, for the luma plane of the box (ke_ssim_pairs_boxed's crops): a destination dword is four pixels,
+// so 4, 12 or 16 source bytes, and what is written is 1 byte per pixel instead of the box's rows as they are.
 #include <algorithm>
 
 #include "ke_internal.h"
 #include "ke_trim_core.h"
+#include "ke_turn_core.h"
 
 namespace {
 
@@ -179,6 +184,59 @@ __global__ __launch_bounds__(256) void ke_crop_pack_kernel(const uint8_t *__rest
     }
 }
 
+// ke_crop_luma_kernel: ke_crop_pack_kernel's shape with the luma between the load and the store.  A destination dword is four
+// pixels, so its source is 4 * CH bytes at any alignment: CH aligned dwords and, unless the bytes start on one, one more, cut
+// with funnel shifts into CH dwords that start at the first pixel.  The alignment is the same for every dword of a row.
+template <int CH>
+__device__ __forceinline__ void crop_luma_rows(const uint8_t *__restrict__ s, const uint8_t *s_end, uint8_t *__restrict__ d,
+                                               const KeCropLumaJob &job, int lane, int wave) {
+    for (int r = blockIdx.x * 4 + wave; r < job.bh; r += gridDim.x * 4) {
+        const uint8_t *srow = s + ((size_t)(job.y0 + r) * job.w + job.x0) * CH;
+        uint8_t *g = d + (size_t)r * job.bw;
+        int head = (int)((4 - ((uintptr_t)g & 3)) & 3);
+        if (head > job.bw) head = job.bw;
+        const int nd = (job.bw - head) >> 2, done = head + 4 * nd;
+        const int sh = (int)((uintptr_t)(srow + head * CH) & 3);
+        const uint8_t *a0 = srow + head * CH - sh;
+        for (int j = lane; j < nd; j += 64) {
+            const uint8_t *a = a0 + (size_t)j * (4 * CH);
+            uint32_t t[CH + 1];
+#pragma unroll
+            for (int k = 0; k < CH; ++k) t[k] = load_dword_inside(a + 4 * k, s, s_end);
+            if (sh) {
+                t[CH] = load_dword_inside(a + 4 * CH, s, s_end);
+#pragma unroll
+                for (int k = 0; k < CH; ++k) t[k] = __funnelshift_r(t[k], t[k + 1], 8 * sh);
+            }
+            uint32_t v = 0;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                uint8_t px[CH];
+#pragma unroll
+                for (int c = 0; c < CH; ++c) px[c] = (uint8_t)(t[(p * CH + c) >> 2] >> (8 * ((p * CH + c) & 3)));
+                v |= (uint32_t)ke_turn_luma_px(px, CH) << (8 * p);
+            }
+            *(uint32_t *)(g + head + 4 * j) = v;
+        }
+        if (lane == 0)
+            for (int b = 0; b < head; ++b) g[b] = (uint8_t)ke_turn_luma_px(srow + b * CH, CH);
+        if (lane == 63)
+            for (int b = done; b < job.bw; ++b) g[b] = (uint8_t)ke_turn_luma_px(srow + b * CH, CH);
+    }
+}
+
+__global__ __launch_bounds__(256) void ke_crop_luma_kernel(const uint8_t *__restrict__ src, const KeCropLumaJob *__restrict__ jobs,
+                                                           int64_t first, uint8_t *__restrict__ dst) {
+    const KeCropLumaJob job = jobs[first + blockIdx.y];
+    const uint8_t *s = src + job.src_off;
+    const uint8_t *s_end = s + (size_t)job.w * job.h * job.channels;
+    uint8_t *d = dst + job.dst_off;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (job.channels == 1) crop_luma_rows<1>(s, s_end, d, job, lane, wave);
+    else if (job.channels == 3) crop_luma_rows<3>(s, s_end, d, job, lane, wave);
+    else crop_luma_rows<4>(s, s_end, d, job, lane, wave);
+}
+
 bool shape_ok(int32_t w, int32_t h, int ch) { return w > 0 && h > 0 && (int64_t)w * ch <= INT32_MAX - 64; }
 
 // Boxes of n images in device memory, into a host array; images with take[i] == 0 get four zeros.  Drains the stream.
@@ -236,6 +294,8 @@ int launch_crop_pack(ke_ctx *ctx, const uint8_t *d_src, const std::vector<CropJo
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return KE_OK;
 }
+
+bool box_inside(const int32_t *b, int32_t w, int32_t h) { return b[0] >= 0 && b[1] >= 0 && b[2] > b[0] && b[3] > b[1] && b[2] <= w && b[3] <= h; }
 
 // Host pixels reach the device in chunks of whole images, packed, of at most kStageBytes (or one image): [lo, hi) and the
 // packed offsets of its images.
@@ -376,6 +436,47 @@ KE_API int ke_crop_pack(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_off
         jobs[(size_t)i] = CropJob{src_offsets[i], dst_offsets[i], widths[i], heights[i], b[0], b[1], b[2] - b[0], b[3] - b[1]};
     }
     return launch_crop_pack(ctx, src, jobs, channels, dst);
+}
+
+int ke_launch_crop_luma(ke_ctx *ctx, const uint8_t *d_src, const KeCropLumaJob *jobs, int64_t n, uint8_t *d_dst) {
+    if (n == 0) return KE_OK;
+    int most = 1;
+    for (int64_t i = 0; i < n; ++i) most = std::max(most, jobs[i].bh);
+    void *d_jobs;
+    KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)n * sizeof(KeCropLumaJob), &d_jobs));
+    KE_HIP(ctx, hipMemcpyAsync(d_jobs, jobs, (size_t)n * sizeof(KeCropLumaJob), hipMemcpyHostToDevice, ctx->stream));
+    // a wave takes eight rows or more of the tallest box: a row costs it CH dwords in for one out, and the job record and the
+    // row set-up are paid once per wave
+    const unsigned gx = (unsigned)std::min(std::max((most + 31) / 32, 1), 256);
+    ke_time_begin(ctx, KE_T_TRIM_LUMA);
+    for (int64_t first = 0; first < n; first += 65535) {
+        const unsigned gy = (unsigned)std::min<int64_t>(65535, n - first);
+        hipLaunchKernelGGL(ke_crop_luma_kernel, dim3(gx, gy), dim3(256), 0, ctx->stream, d_src, (const KeCropLumaJob *)d_jobs, first, d_dst);
+    }
+    ke_time_end(ctx, KE_T_TRIM_LUMA);
+    KE_HIP(ctx, hipGetLastError());
+    KE_HIP(ctx, hipStreamSynchronize(ctx->stream));       // `jobs` is the caller's host array
+    return KE_OK;
+}
+
+KE_API int ke_crop_luma(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offsets, const int32_t *widths, const int32_t *heights,
+                        const int32_t *channels, const int32_t *boxes, int64_t n, uint8_t *dst, const uint64_t *dst_offsets) {
+    if (!ctx) return KE_EINVAL;
+    if (n < 0 || (n > 0 && (!src || !src_offsets || !widths || !heights || !channels || !boxes || !dst || !dst_offsets)))
+        return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    if (n == 0) return KE_OK;
+    if (!ke_is_device_ptr(src) || !ke_is_device_ptr(dst)) return ke_fail(ctx, KE_EINVAL, "src and dst are device memory");
+    KE_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<KeCropLumaJob> jobs((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t *b = boxes + 4 * i;
+        const int ch = channels[i];
+        if ((ch != 1 && ch != 3 && ch != 4) || !shape_ok(widths[i], heights[i], ch) || !box_inside(b, widths[i], heights[i]))
+            return ke_fail(ctx, KE_EINVAL, "image %lld: %dx%d, %d channels, box (%d, %d, %d, %d)", (long long)i, widths[i], heights[i], ch, b[0],
+                           b[1], b[2], b[3]);
+        jobs[(size_t)i] = KeCropLumaJob{src_offsets[i], dst_offsets[i], widths[i], heights[i], ch, b[0], b[1], b[2] - b[0], b[3] - b[1]};
+    }
+    return ke_launch_crop_luma(ctx, src, jobs.data(), n, dst);
 }
 
 KE_API int ke_hash_images_trimmed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,

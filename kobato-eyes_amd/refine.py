@@ -173,11 +173,32 @@ def _upload(ctx, arrays: dict, placed: dict, buffers: list) -> None:
     ctx.memcpy(dev, flat, len(flat))
 
 
+PLAIN, TURNED, TRIMMED = "plain", "turned", "trimmed"     # what a row of _refine_runs carries after its two paths
+
+
+def _seam_boxes(ctx, pairs: Sequence[tuple], live: list, paths: list, index: dict, placed: dict, count: dict, tolerance: int):
+    """The boxes of a trimmed run, (box_a, box_b) as int32[len(live), 4]: one ``ke_content_boxes`` call on the pictures that
+    have a trimmed side, as they are placed on the device.  A side that is not trimmed, and a trimmed side whose picture has
+    no box here, stays four zeros: the picture as it lies."""
+    sides = [(n, 4 + s, index[str(pairs[k][2 + s])]) for n, k in enumerate(live) for s in (0, 1) if pairs[k][4 + s]]
+    boxes = np.zeros((2, len(live), 4), np.int32)
+    files = sorted({i for _, _, i in sides})
+    if files:
+        found, _ = ctx.content_boxes_on_device([placed[paths[i]][0] for i in files], [placed[paths[i]][1] for i in files],
+                                               [placed[paths[i]][2] for i in files], 3, tolerance)
+        row = {i: r for r, i in enumerate(files)}
+        for n, item, i in sides:
+            boxes[item - 4, n] = found[row[i]]
+        count["box_files"] += len(files)
+    return boxes[0], boxes[1]
+
+
 def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, count: dict, cfg: RefinementThresholds,
-           turned: bool = False) -> None:
+           mode: str = PLAIN, tolerance: int = 48) -> None:
     """One ``ke_ssim_pairs`` call for the pairs of this run (the library groups them: one fit launch per (source size,
-    common size), one SSIM launch per common size).  ``turned``: a pair carries an orientation as its fifth item and the
-    call is ``ke_ssim_pairs_turned``, which scores a against that orientation of b."""
+    common size), one SSIM launch per common size).  TURNED: a pair carries an orientation as its fifth item and the
+    call is ``ke_ssim_pairs_turned``, which scores a against that orientation of b.  TRIMMED: a pair carries two flags, and
+    the call is ``ke_ssim_pairs_boxed`` with the content box, found here, of every flagged side."""
     live = []
     for k in chunk:
         pa, pb = pairs[k][2], pairs[k][3]
@@ -191,12 +212,17 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
     index = {p: i for i, p in enumerate(paths)}
     where = ([placed[p][0] for p in paths], [placed[p][1] for p in paths], [placed[p][2] for p in paths], 3,
              [index[str(pairs[k][2])] for k in live], [index[str(pairs[k][3])] for k in live])
-    if turned:
+    zeros = np.zeros((len(live), 4), np.int32)
+    box_a = box_b = zeros
+    if mode == TURNED:
         scores, status = ctx.ssim_pairs_turned_on_device(*where, [int(pairs[k][4]) for k in live])
+    elif mode == TRIMMED:
+        box_a, box_b = _seam_boxes(ctx, pairs, live, paths, index, placed, count, tolerance)
+        scores, status = ctx.ssim_pairs_boxed_on_device(*where, box_a, box_b)
     else:
         scores, status = ctx.ssim_pairs_on_device(*where)
-    common, fits = set(), set()
-    for k, sc, st in zip(live, scores.tolist(), status.tolist()):
+    common, fits, cropped = set(), set(), False
+    for n, (k, sc, st) in enumerate(zip(live, scores.tolist(), status.tolist())):
         fid_a, fid_b, pa, pb = pairs[k][:4]
         if st != 0:                                            # skimage raises for images smaller than its window
             logger.warning("SSIM refinement failed for %s and %s: win_size exceeds image extent", pa, pb)
@@ -204,14 +230,23 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
             continue
         out[k] = _decide(fid_a, fid_b, float(sc), [], cfg)
         (_, wa, ha), (_, wb, hb) = placed[str(pa)], placed[str(pb)]
-        o = int(pairs[k][4]) if turned else 0
+        o = int(pairs[k][4]) if mode == TURNED else 0
         if o & 4:
             wb, hb = hb, wb
+        # a box other than the whole picture is a source of its own, as a turned plane is
+        cut_a, cut_b = (bool(b.any()) and tuple(b) != (0, 0, w, h) for b, w, h in ((box_a[n], wa, ha), (box_b[n], wb, hb)))
+        if cut_a:
+            wa, ha = int(box_a[n][2] - box_a[n][0]), int(box_a[n][3] - box_a[n][1])
+        if cut_b:
+            wb, hb = int(box_b[n][2] - box_b[n][0]), int(box_b[n][3] - box_b[n][1])
+        cropped = cropped or cut_a or cut_b
         size = (min(wa, wb), min(ha, hb))
         common.add(size)
-        fits.update({((ha, wa), False, size), ((hb, wb), o != 0, size)})    # a turned plane is a source of its own
+        fits.update({((ha, wa), cut_a, size), ((hb, wb), o != 0 or cut_b, size)})
     count["fit_launches"] += len(fits)
     count["ssim_launches"] += len(common)
+    if mode == TRIMMED:
+        count["crop_launches"] += int(cropped)
 
 
 def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThresholds] = None, device: int = 0,
@@ -240,19 +275,21 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
 
         return ranks.refine_pairs(pairs, devices, thresholds=thresholds, io_workers=io_workers,
                                   max_decoded_bytes=max_decoded_bytes, stats=stats, max_side=max_side)
-    return _refine_runs(pairs, False, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, _after_run)
+    return _refine_runs(pairs, PLAIN, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, _after_run)
 
 
-def _refine_runs(pairs: Sequence[tuple], turned: bool, thresholds, device: int, io_workers: int, max_decoded_bytes: int,
-                 stats: Optional[dict], max_side: int, _after_run=None) -> list:
-    """The run loop of refine_pairs and refine_turned_pairs: decode what a run of pairs needs, once per file and within
-    the budget, score the run with one library call, free, go on."""
+def _refine_runs(pairs: Sequence[tuple], mode: str, thresholds, device: int, io_workers: int, max_decoded_bytes: int,
+                 stats: Optional[dict], max_side: int, _after_run=None, tolerance: int = 48) -> list:
+    """The run loop of refine_pairs, refine_turned_pairs and refine_trimmed_pairs (``mode``: PLAIN, TURNED, TRIMMED): decode
+    what a run of pairs needs, once per file and within the budget, score the run with one library call, free, go on."""
     from concurrent.futures import ThreadPoolExecutor
 
     cfg = thresholds or RefinementThresholds()
     ctx = _native.get_context(device)
     out: list = [None] * len(pairs)
     count = {"decodes": 0, "gpu_decodes": 0, "fit_launches": 0, "ssim_launches": 0, "pairs": len(pairs)}
+    if mode == TRIMMED:
+        count.update(box_files=0, crop_launches=0)
     with ThreadPoolExecutor(max_workers=max(1, io_workers)) as pool:
         start = 0
         while start < len(pairs):
@@ -273,7 +310,7 @@ def _refine_runs(pairs: Sequence[tuple], turned: bool, thresholds, device: int, 
                 arrays = dict(zip(rest, pool.map(lambda p: _load(p, max_side), rest)))
                 count["decodes"] += len(need)
                 _upload(ctx, arrays, placed, buffers)
-                _score(ctx, pairs, range(start, stop), placed, out, count, cfg, turned)
+                _score(ctx, pairs, range(start, stop), placed, out, count, cfg, mode, tolerance)
             finally:
                 for dev in buffers:
                     ctx.free(dev)
@@ -303,7 +340,33 @@ def refine_turned_pairs(pairs: Sequence[tuple], *, thresholds: Optional[Refineme
     for pair in pairs:
         if not 0 <= int(pair[4]) < 8:
             raise ValueError(f"orientation {pair[4]} outside 0..7")
-    return _refine_runs(pairs, True, thresholds, device, io_workers, max_decoded_bytes, stats, max_side)
+    return _refine_runs(pairs, TURNED, thresholds, device, io_workers, max_decoded_bytes, stats, max_side)
+
+
+def refine_trimmed_pairs(pairs: Sequence[tuple], *, tolerance: int = 48, thresholds: Optional[RefinementThresholds] = None, device: int = 0,
+                         io_workers: int = 8, max_decoded_bytes: int = 1 << 30, stats: Optional[dict] = None,
+                         max_side: int = MAX_SIDE) -> list:
+    """``refine_pairs`` for a list of ``(file_id_a, file_id_b, path_a, path_b, trimmed_a, trimmed_b)``: a side whose flag is
+    set takes part with its content box (include/keyes.h, ``ke_content_boxes`` at ``tolerance``) instead of the whole picture,
+    as ``refine_pairs`` would score a file that holds Pillow's ``crop`` of it.  A capability of this library only: the
+    reference has no bordered copies.
+
+    Both files are decoded as they lie (the same decode runs, budget and loader fallback as ``refine_pairs``, the same
+    ``stats``).  The boxes are made here, per run, by one ``ke_content_boxes`` call on the pictures as they are placed on the
+    device, not taken from ``trimmed.trimmed_signatures``: this seam's loader applies the EXIF orientation, composites RGBA
+    over white and shrinks oversized files, so a box found at the hashing seam may describe another pixel grid.  A flagged
+    side whose picture has no box here is scored as it lies.  Then one ``ke_ssim_pairs_boxed`` call: every distinct (file,
+    box) is cut out once, luma only (``ke_crop_luma``), and the crop is fitted -- crop first, then fit, so that the margin
+    cannot bleed into the crop's edge through the resampler's taps.  Luma is per pixel and the resampler is bit-exact with
+    Pillow on every source, so the score is the one the cropped file would get, bit for bit.  ``stats`` also receives
+    ``box_files`` (pictures whose box was looked for) and ``crop_launches``.  Returns a ``RefinedMatch`` or ``None``
+    (unreadable file) per pair, in input order.
+
+    There is no ``devices=``: ``ranks.refine_pairs`` ships 4-tuples to its workers.  A tolerance outside 0..255 is a
+    ``ValueError`` before anything is decoded."""
+    if not 0 <= int(tolerance) <= 255:
+        raise ValueError(f"tolerance {tolerance} outside 0..255")
+    return _refine_runs(pairs, TRIMMED, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, tolerance=int(tolerance))
 
 
 def refine_pair(file_id_a: int, file_id_b: int, path_a, path_b, *, thresholds: Optional[RefinementThresholds] = None,
@@ -322,4 +385,5 @@ def refine_pair(file_id_a: int, file_id_b: int, path_a, path_b, *, thresholds: O
     return _decide(file_id_a, file_id_b, ssim_value, errors, cfg)
 
 
-__all__ = ["RefinementThresholds", "RefinedMatch", "refine_pair", "refine_pairs", "refine_turned_pairs", "compute_ssim", "ssim_pairs"]
+__all__ = ["RefinementThresholds", "RefinedMatch", "refine_pair", "refine_pairs", "refine_turned_pairs", "refine_trimmed_pairs", "compute_ssim",
+           "ssim_pairs"]

@@ -169,7 +169,9 @@ class TurnedMatch:
 class TrimmedMatch:
     """Two files of which one looks like the other with a margin round it, to within ``hamming`` bits of the pHash.
     ``trimmed_a`` / ``trimmed_b``: whether that side entered the comparison cut to its content box; ``box_a`` / ``box_b``: that
-    box as (x0, y0, x1, y1), None where the side is the file as it is.  file_id_a < file_id_b."""
+    box as (x0, y0, x1, y1), None where the side is the file as it is.  file_id_a < file_id_b.  ``ssim``: the score of the two
+    sides, each cut to its box where it is trimmed, where the pair went through the SSIM re-check
+    (api.find_trimmed_duplicates with ``ssim_threshold``), else None."""
 
     file_id_a: int
     file_id_b: int
@@ -178,6 +180,7 @@ class TrimmedMatch:
     hamming: int
     box_a: Optional[tuple] = None
     box_b: Optional[tuple] = None
+    ssim: Optional[float] = None
 
 
 def _safe_positive_int(value: Optional[str]) -> Optional[int]:
