@@ -704,6 +704,44 @@ int ke_ssim_pairs_boxed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offs
                         int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *box_a,
                         const int32_t *box_b, int64_t n_pairs, double *ssim_out, int32_t *status_out);
 
+/* ---- copies that are bordered AND turned.  A capability of this library only (the reference has neither feature): a VIEW of
+ * an image is a box of it, then an orientation of that crop -- turned.turn(k, image[y0:y1, x0:x1]), crop first.
+ *
+ * ke_crop_turn_luma: image i (widths[i] x heights[i], channels[i] = 1, 3 or 4, the fourth byte ignored, at src + src_offsets[i]),
+ *   box boxes[4 i ..] = (x0, y0, x1, y1), orientation orientations[i] (0..7, as ke_turn_luma) -> the convert("L") luma of that
+ *   orientation of the box's pixels, 1 byte per pixel, rows packed, at dst + dst_offsets[i]: (x1 - x0) x (y1 - y0), sides swapped
+ *   for k & 4; byte for byte the luma of Pillow's crop(box).transpose(...).  A channel count other than 1, 3, 4, an empty box or
+ *   one not inside its image, an orientation outside 0..7: KE_EINVAL, nothing launched.  n == 0: KE_OK.  Any byte offset is
+ *   legal on both sides; nothing is read outside [src + src_offsets[i], + w * h * channels[i]) -- the margin pixels beside the box
+ *   may be -- and nothing is written outside the plane.  ke_turn_luma's kernel shape (64 x 64 destination tiles through LDS
+ *   twice, aligned dwords on both sides) with the tile's source rectangle at the box's origin and the image's row pitch.  src,
+ *   dst: device; the arrays: host.  Blocks.  ke_last_kernel_ms kind 8 times the kernel.
+ * ke_ssim_pairs_viewed: ke_ssim_pairs_boxed with ke_ssim_pairs_turned's orient_b: pair k is box_a of image pair_a[k] against
+ *   orientation orient_b[k] of box_b of image pair_b[k].  CROP, THEN TURN, THEN FIT.  The common size is the minimum of the two
+ *   view sizes, b's swapped for k & 4; the fit, the SSIM and the statuses are ke_ssim_pairs'.  Every distinct (image, box,
+ *   orientation) of a call is made once into scratch of 1 byte per pixel, by one launch per kind of view: a whole picture (box
+ *   NULL, zeros or (0, 0, w, h)) at orientation 0 enters the fit straight from `pixels`; a real box at 0 is ke_crop_luma's; a
+ *   whole picture turned is ke_turn_luma's; a real box turned is ke_crop_turn_luma's.  orient_b NULL or all zeros:
+ *   ke_ssim_pairs_boxed's answers, bit for bit; both box arrays NULL: ke_ssim_pairs_turned's.  A bad box or orientation:
+ *   KE_EINVAL naming the pair, nothing launched.
+ * ke_hash_images_turned_trimmed: one call for what ke_hash_images_turned and ke_hash_images_trimmed give, and the turned hashes
+ *   of the crop.  turned_out[8 i + k]: exactly ke_hash_images_turned's.  boxes_out, has_out: exactly ke_hash_images_trimmed's.
+ *   trimmed_turned_out[8 i + k]: turned pHash k of im.crop(box) -- the pHash arithmetic on orientation k of the crop's 32 x 32
+ *   tile, so column 0 is the trimmed pHash --, eight zeros where the box does not qualify.  THE BOX IS ALWAYS FOUND ON THE PICTURE
+ *   AS IT LIES, with the reference pixel at (0, 0): turning does not commute with that choice of corner, so the box of a turned
+ *   picture need not be the turned box.  Built from the existing passes: the box kernel, ke_crop_pack in chunks of at most 1 GiB,
+ *   ke_hash_images_turned on the pixels and on the crops.  pixels: device, or host -- then every chunk of at most 1 GiB is
+ *   staged once and both passes walk it on the device; the rest host arrays.  Blocks. */
+int ke_crop_turn_luma(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offsets, const int32_t *widths, const int32_t *heights,
+                      const int32_t *channels, const int32_t *boxes, const int32_t *orientations, int64_t n, uint8_t *dst,
+                      const uint64_t *dst_offsets);
+int ke_ssim_pairs_viewed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                         int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *box_a,
+                         const int32_t *box_b, const int32_t *orient_b, int64_t n_pairs, double *ssim_out, int32_t *status_out);
+int ke_hash_images_turned_trimmed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths,
+                                  const int32_t *heights, int32_t channels, int64_t n, int32_t tolerance, uint64_t *turned_out,
+                                  uint64_t *trimmed_turned_out, int32_t *boxes_out, uint8_t *has_out, int32_t *status_out);
+
 /* ---- shipped refine stage ("next" row of SURVEY 8f): replaces the per-file work of
  * ui.dup_refine_parallel -- tile_ahash_bits (src/ui/dup_refine_parallel.py:59-83), _load_small_gray
  * (:203-207) and _mae01 (:208-210).

@@ -30,6 +30,7 @@ EXPORTS = (
     "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan",
     "ke_hamming_scan_from", "ke_hamming_scan_cross", "ke_tiles_turned", "ke_hash_images_turned", "ke_band_pairs_after_size",
     "ke_content_boxes", "ke_crop_pack", "ke_hash_images_trimmed", "ke_crop_luma", "ke_ssim_pairs_boxed",
+    "ke_crop_turn_luma", "ke_ssim_pairs_viewed", "ke_hash_images_turned_trimmed",
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
     "ke_comm_unique_id", "ke_comm_create", "ke_comm_destroy", "ke_allgather_u64", "ke_allgather_hashes", "ke_allgather_edges",
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
@@ -153,6 +154,9 @@ def load_library() -> C.CDLL:
         lib.ke_hash_images_trimmed.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp]
         lib.ke_crop_luma.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
         lib.ke_ssim_pairs_boxed.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp]
+        lib.ke_crop_turn_luma.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+        lib.ke_ssim_pairs_viewed.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp]
+        lib.ke_hash_images_turned_trimmed.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
         lib.ke_cluster_labels.argtypes = [vp, i64, i64, vp]
         lib.ke_ssim_pairs_uniform.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, i64, vp]
         lib.ke_ssim_set_mode.argtypes = [vp, i32]
@@ -578,6 +582,31 @@ class Context:
                         "ke_hash_images_trimmed")
         return ph, boxes, has.astype(bool), status
 
+    def hash_images_turned_trimmed(self, images: Sequence[np.ndarray], tolerance: int):
+        """``hash_images_turned`` and ``hash_images_trimmed`` in one call, with the turned pHashes of the crop
+        (ke_hash_images_turned_trimmed): (turned u64[n, 8], trimmed_turned u64[n, 8], boxes int32[n, 4], has bool[n], status
+        int32[n]).  Column 0 of ``trimmed_turned`` is the trimmed pHash; a row is zeros where the box does not qualify."""
+        n = len(images)
+        if n == 0:
+            return (np.zeros((0, 8), np.uint64), np.zeros((0, 8), np.uint64), np.zeros((0, 4), np.int32), np.zeros(0, bool),
+                    np.zeros(0, np.int32))
+        flat, offsets, widths, heights, ch = _pack_images(images)
+        return self.hash_images_turned_trimmed_at(flat, offsets, widths, heights, ch, tolerance)
+
+    def hash_images_turned_trimmed_at(self, pixels, offsets, widths, heights, channels: int, tolerance: int):
+        """``hash_images_turned_trimmed`` of images that lie in one buffer already -- a host array or a device pointer -- at any
+        byte offsets."""
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        widths, heights = np.ascontiguousarray(widths, np.int32), np.ascontiguousarray(heights, np.int32)
+        n = len(offsets)
+        turned, cut = np.zeros((n, 8), np.uint64), np.zeros((n, 8), np.uint64)
+        boxes, has, status = np.zeros((n, 4), np.int32), np.zeros(n, np.uint8), np.zeros(n, np.int32)
+        with self._lock:
+            self._check(self._lib.ke_hash_images_turned_trimmed(self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights),
+                                                                int(channels), n, int(tolerance), _addr(turned), _addr(cut), _addr(boxes),
+                                                                _addr(has), _addr(status)), "ke_hash_images_turned_trimmed")
+        return turned, cut, boxes, has.astype(bool), status
+
     # -- pinned staging ---------------------------------------------------------------------
     def stage_create(self, bytes_per_buffer: int, max_images: int, n_buffers: int = 2) -> None:
         self._stage_geom = None                              # whoever cached "my buffers are in place" (fastsig) must look again
@@ -987,11 +1016,19 @@ class Context:
         ph, _, st, (boxes, has) = self._hash_chain(blobs, False, kind, paths, None, None, mode="trimmed", tolerance=tolerance)
         return ph, boxes, has, st
 
+    def hash_turned_trimmed(self, blobs, *, kind: str, paths=None, tolerance: int = 48):
+        """``hash``'s chain with ke_hash_images_turned_trimmed behind the decode: (turned u64[n, 8], trimmed_turned u64[n, 8],
+        boxes int32[n, 4], has bool[n], status int32[n]); status != 0 = not handled here, zeros."""
+        turned, _, st, (boxes, has, cut) = self._hash_chain(blobs, False, kind, paths, None, None, mode="turned_trimmed", tolerance=tolerance)
+        return turned, cut, boxes, has, st
+
     def _hash_chain(self, blobs, want_dhash, kind, paths, ahead, skip, *, mode: str, tolerance: int = 0):
         """(phash, dhash | None, status, extra) of one of the three calls behind the decode: "plain" ke_hash_images, "turned"
-        ke_hash_images_turned (phash is u64[n, 8]), "trimmed" ke_hash_images_trimmed (extra = (boxes, has), else None)."""
-        turned, trimmed = mode == "turned", mode == "trimmed"
-        shape = (0, 8) if turned else (0,)
+        ke_hash_images_turned (phash is u64[n, 8]), "trimmed" ke_hash_images_trimmed (extra = (boxes, has), else None),
+        "turned_trimmed" ke_hash_images_turned_trimmed (phash is the turned u64[n, 8], extra = (boxes, has, trimmed_turned))."""
+        both = mode == "turned_trimmed"
+        turned, trimmed = mode == "turned", mode == "trimmed" or both
+        shape = (0, 8) if turned or both else (0,)
         if ahead is not None:                            # where the files come from is settled here, once
             n = ahead[2] - ahead[1]
             take = lambda lo, hi: ahead[0].part(ahead[1] + lo, ahead[1] + hi)
@@ -1003,12 +1040,13 @@ class Context:
             take = lambda lo, hi: self._packed(blobs[lo:hi])
         if n == 0:
             return (np.zeros(shape, np.uint64), (np.zeros(0, np.uint64) if want_dhash else None), np.zeros(0, np.int32),
-                    (np.zeros((0, 4), np.int32), np.zeros(0, bool)) if trimmed else None)
+                    ((np.zeros((0, 4), np.int32), np.zeros(0, bool)) + ((np.zeros((0, 8), np.uint64),) if both else ())) if trimmed else None)
         skip = None if skip is None else np.asarray(skip, bool)
 
         def run(lo: int, hi: int):
             ph = np.zeros((hi - lo,) + shape[1:], np.uint64)
             boxes, has = (np.zeros((hi - lo, 4), np.int32), np.zeros(hi - lo, bool)) if trimmed else (None, None)
+            cut = np.zeros((hi - lo, 8), np.uint64) if both else None
             dh = np.zeros(hi - lo, np.uint64) if want_dhash else None
             dev, out_off, w, h, c, st, _ = self._decode_packed(take(lo, hi), kind, skip=None if skip is None else skip[lo:hi])
             for ch in (1, 3, 4):
@@ -1023,6 +1061,12 @@ class Context:
                 if turned:
                     self._check(self._lib.ke_hash_images_turned(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p),
                                                                 _addr(status)), "ke_hash_images_turned")
+                elif both:
+                    b, t, q = np.zeros((len(idx), 4), np.int32), np.zeros(len(idx), np.uint8), np.zeros((len(idx), 8), np.uint64)
+                    self._check(self._lib.ke_hash_images_turned_trimmed(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx),
+                                                                        int(tolerance), _addr(p), _addr(q), _addr(b), _addr(t), _addr(status)),
+                                "ke_hash_images_turned_trimmed")
+                    boxes[idx], has[idx], cut[idx] = b, t.astype(bool), q
                 elif trimmed:
                     b, t = np.zeros((len(idx), 4), np.int32), np.zeros(len(idx), np.uint8)
                     self._check(self._lib.ke_hash_images_trimmed(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), int(tolerance),
@@ -1035,13 +1079,14 @@ class Context:
                 if want_dhash:
                     dh[idx] = d
                 st[idx[status != 0]] = 2
-            return ph, dh, st, boxes, has
+            return ph, dh, st, boxes, has, cut
 
         with self._lock:                                 # the decode buffer is this call's until the pixels are hashed
             parts = _in_halves(run, 0, n)
         return (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]) if want_dhash else None,
                 np.concatenate([p[2] for p in parts]),
-                (np.concatenate([p[3] for p in parts]), np.concatenate([p[4] for p in parts])) if trimmed else None)
+                ((np.concatenate([p[3] for p in parts]), np.concatenate([p[4] for p in parts])) +
+                 ((np.concatenate([p[5] for p in parts]),) if both else ())) if trimmed else None)
 
     # -- scan -------------------------------------------------------------------------------
     def hamming_scan(self, hashes, n: int, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4,
@@ -1213,6 +1258,58 @@ class Context:
         widths = np.ascontiguousarray(widths, np.int32)
         heights = np.ascontiguousarray(heights, np.int32)
         return self._ssim_pairs_boxed(base, offsets, widths, heights, channels, len(ptrs), pair_a, pair_b, box_a, box_b)
+
+    def _ssim_pairs_viewed(self, pixels, offsets, widths, heights, channels: int, n: int, pair_a, pair_b, box_a, box_b, orient_b):
+        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
+        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
+        boxes = []
+        for b in (box_a, box_b):
+            b = None if b is None else np.ascontiguousarray(b, dtype=np.int32).reshape(-1, 4)
+            if b is not None and len(b) != len(pa):
+                raise ValueError("ssim_pairs_viewed: a box array holds one box per pair")
+            boxes.append(b)
+        ob = None if orient_b is None else np.ascontiguousarray(orient_b, dtype=np.int32)
+        if len(pb) != len(pa) or (ob is not None and len(ob) != len(pa)):
+            raise ValueError("ssim_pairs_viewed: the pair arrays differ in length")
+        out = np.empty(len(pa), np.float64)
+        status = np.empty(len(pa), np.int32)
+        with self._lock:
+            self._check(self._lib.ke_ssim_pairs_viewed(self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights), int(channels), n,
+                                                       _addr(pa), _addr(pb), _addr(boxes[0]), _addr(boxes[1]), _addr(ob), len(pa), _addr(out),
+                                                       _addr(status)), "ke_ssim_pairs_viewed")
+        return out, status
+
+    def ssim_pairs_viewed(self, images: Sequence[np.ndarray], pair_a, pair_b, box_a, box_b, orient_b):
+        """ssim_pairs on views of the images (ke_ssim_pairs_viewed): pair k is box ``box_a[k]`` of image ``pair_a[k]`` against
+        orientation ``orient_b[k]`` (0..7, turned.ORIENTATIONS; None: all 0) of box ``box_b[k]`` of image ``pair_b[k]`` -- crop,
+        then turn, then fit.  Boxes as in ``ssim_pairs_boxed``.  The scores are those of ``ssim_pairs`` on images that hold
+        ``turn(k, crop)``, bit for bit."""
+        flat, offsets, widths, heights, ch = _pack_images(images)
+        return self._ssim_pairs_viewed(flat, offsets, widths, heights, ch, len(images), pair_a, pair_b, box_a, box_b, orient_b)
+
+    def ssim_pairs_viewed_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b, box_a, box_b, orient_b):
+        """ssim_pairs_on_device on views of the images: each distinct (image, box, orientation) is made once on the device, luma
+        only (ke_crop_luma, ke_turn_luma or ke_crop_turn_luma), before the fit."""
+        ptrs = np.asarray(pointers, np.uint64)
+        base = int(ptrs.min())
+        offsets = np.ascontiguousarray(ptrs - np.uint64(base))
+        widths = np.ascontiguousarray(widths, np.int32)
+        heights = np.ascontiguousarray(heights, np.int32)
+        return self._ssim_pairs_viewed(base, offsets, widths, heights, channels, len(ptrs), pair_a, pair_b, box_a, box_b, orient_b)
+
+    def crop_turn_luma(self, src: int, src_offsets, widths, heights, channels, boxes, orientations, dst: int, dst_offsets) -> None:
+        """The ``convert("L")`` luma of orientation ``orientations[i]`` (0..7, turned.ORIENTATIONS) of box ``boxes[i]`` of image i of
+        a device buffer -> ``dst + dst_offsets[i]`` of the caller's device buffer, one byte per pixel, rows packed, the box's
+        sides swapped for k & 4 (ke_crop_turn_luma)."""
+        so, do = np.ascontiguousarray(src_offsets, dtype=np.uint64), np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        w, h = np.ascontiguousarray(widths, dtype=np.int32), np.ascontiguousarray(heights, dtype=np.int32)
+        c, o = np.ascontiguousarray(channels, dtype=np.int32), np.ascontiguousarray(orientations, dtype=np.int32)
+        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        if not len(so) == len(do) == len(w) == len(h) == len(c) == len(o) == len(b):
+            raise ValueError("crop_turn_luma: the arrays differ in length")
+        with self._lock:
+            self._check(self._lib.ke_crop_turn_luma(self._h, src, _addr(so), _addr(w), _addr(h), _addr(c), _addr(b), _addr(o), len(so), dst,
+                                                    _addr(do)), "ke_crop_turn_luma")
 
     def turn_luma(self, src: int, src_offsets, widths, heights, channels, orientations, dst: int, dst_offsets) -> None:
         """Images on the device (``widths[i]`` x ``heights[i]``, 1, 3 or 4 channels, at ``src + src_offsets[i]``) -> the luma plane

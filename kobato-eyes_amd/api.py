@@ -209,7 +209,8 @@ def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_
     its ``ssim``.  A pair that is both a plain edge and a match stays linked if either passes; a pair with an unreadable
     file is dropped.  Unset: no pixels are compared and ``ssim`` is None.
 
-    Out of scope here: persisting turned hashes, ``devices=[...]`` (one process, one GPU) and dHash."""
+    Out of scope here: persisting turned hashes, ``devices=[...]`` (one process, one GPU) and dHash.  A copy that is turned AND has a
+    margin round it is ``find_turned_trimmed_duplicates``'."""
     clusters, matches, _ = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
                                         band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)
     return clusters, matches
@@ -277,9 +278,89 @@ def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tole
     linked if either passes; a pair with an unreadable file is dropped.  Unset: no pixels are compared and ``ssim`` is None.
 
     Out of scope here: an MAE re-check on the crop, ``devices=[...]`` (one process, one GPU), persisting trimmed
-    hashes, borders of two colours or gradients, trimmed and turned together, and dHash."""
+    hashes, borders of two colours or gradients, and dHash.  Trimmed and turned together is ``find_turned_trimmed_duplicates``'."""
     return _trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio, band_bits=band_bits,
                          band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)
+
+
+def _turned_trimmed_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, tolerance: int,
+                              device: int) -> tuple:
+    """The plain candidate edges and the matches that pass the SSIM re-check, from one refine_turned_trimmed_pairs call: a plain
+    edge goes as (False, False, 0), a match with its flags and its orientation.  A surviving match carries its score; a pair
+    whose files cannot be read is dropped, as _ssim_kept drops it."""
+    from dataclasses import replace
+
+    by_id = {f.file_id: f for f in candidates}
+    keys = list(plain)
+    rows = [(plain[k].file_id_a, plain[k].file_id_b, by_id[plain[k].file_id_a].path, by_id[plain[k].file_id_b].path, False, False, 0)
+            for k in keys]
+    rows += [(m.file_id_a, m.file_id_b, by_id[m.file_id_a].path, by_id[m.file_id_b].path, m.trimmed_a, m.trimmed_b, m.orientation)
+             for m in matches]
+    refined = _refine.refine_turned_trimmed_pairs(rows, tolerance=tolerance, thresholds=_refine.RefinementThresholds(ssim=ssim_threshold),
+                                                  device=device)
+    passed = [r is not None and r.is_duplicate for r in refined]
+    kept_plain = {k: plain[k] for k, yes in zip(keys, passed) if yes}
+    kept_matches = [replace(m, ssim=r.ssim) for m, r, yes in zip(matches, refined[len(keys):], passed[len(keys):]) if yes]
+    return kept_plain, kept_matches
+
+
+def _turned_trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, band_bits, band_count, device, ssim_threshold=None):
+    """find_turned_trimmed_duplicates' work: (clusters, matches, the (id, id) keys of the plain candidate edges).  With
+    ``ssim_threshold`` the matches and the keys are the ones that passed the re-check."""
+    from . import turned_trimmed as _views
+    from .scanner import DuplicateEdge, TransformedMatch, assemble_clusters, view_rank
+
+    candidates = [f for f in _parse_files(files) if f.phash is not None]
+    if len(candidates) < 2:
+        return [], [], set()
+    config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
+                                 band_count=band_count)
+    scanner = DuplicateScanner(config, device=device)
+    turned, cut, boxes, has, ok = _views.turned_trimmed_signatures([f.path for f in candidates], tolerance=tolerance, device=device)
+    plain = scanner.candidate_edges(candidates)
+    found = [TransformedMatch(m.file_id_a, m.file_id_b, m.trimmed_a, m.trimmed_b, 0, m.hamming, m.box_a, m.box_b)
+             for m in scanner.trimmed_edges(candidates, cut[:, 0], has & ok, boxes)]
+    found += scanner.turned_trimmed_edges(candidates, turned, cut, has & ok, ok, boxes)
+    best: dict = {}
+    for m in found:
+        key = (m.file_id_a, m.file_id_b)
+        rank = view_rank(m.hamming, m.orientation, m.trimmed_a, m.trimmed_b)
+        if key not in best or rank < best[key][0]:
+            best[key] = (rank, m)
+    matches = [best[key][1] for key in sorted(best)]
+    if ssim_threshold is not None and (plain or matches):
+        plain, matches = _turned_trimmed_ssim_kept(plain, matches, candidates, ssim_threshold, tolerance, device)
+    edges = list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
+    return (assemble_clusters(candidates, edges) if edges else []), matches, set(plain)
+
+
+def find_turned_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tolerance: int = 48, size_ratio: Optional[float] = None,
+                                   band_bits: int = 16, band_count: int = 4, device: Optional[int] = None,
+                                   ssim_threshold: Optional[float] = None) -> tuple:
+    """(clusters, matches): near-duplicates including copies that were given a margin, turned, or both -- a scan laid on the
+    glass sideways with a white margin, a letterboxed frame that was mirrored, a framed repost rotated a quarter turn.
+
+    ``files``: as for ``find_duplicates``, each with a readable ``path``.  Every file is read once
+    (``turned_trimmed.turned_trimmed_signatures``; nothing is stored): the eight turned pHashes of the picture, its content box
+    at ``tolerance``, and the eight turned pHashes of the picture cut to a qualifying box.  ``matches``: ``scanner.TransformedMatch``
+    -- file a, file b, which side was cut, the orientation that turns b's (cut) picture into a's (cut) picture, the hamming
+    distance, the boxes --, the best per pair of files, by (hamming, orientation, trimmed_a, trimmed_b), over
+    ``DuplicateScanner.trimmed_edges`` (orientation 0) and ``DuplicateScanner.turned_trimmed_edges`` (orientations 1..7, either
+    side whole or cut).  Plain edges stay edges.  ``clusters``: ``assemble_clusters`` over the plain candidate edges of the
+    stored hashes together with the matches as edges.  A file that cannot be opened takes part with its stored pHash only.
+
+    With ``ssim_threshold`` set, every plain candidate edge and every match is re-checked on the files' pixels by one
+    ``refine.refine_turned_trimmed_pairs`` call: a's view against b's, cut (to the box found at that seam) and turned on the
+    device.  Only edges with ``ssim >= ssim_threshold`` reach the clusters, and ``matches`` holds the surviving matches, each
+    with its ``ssim``.  A pair that is both a plain edge and a match stays linked if either passes; a pair with an unreadable
+    file is dropped.  Unset: no pixels are compared and ``ssim`` is None.
+
+    Out of scope here: ``devices=[...]`` (one process, one GPU), persisting any of these hashes, turning side a, dHash, borders
+    of two colours or gradients, and an MAE re-check."""
+    clusters, matches, _ = _turned_trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio,
+                                                band_bits=band_bits, band_count=band_count, device=0 if device is None else int(device),
+                                                ssim_threshold=ssim_threshold)
+    return clusters, matches
 
 
 def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None, config: Optional[DuplicateScanConfig] = None,
@@ -323,4 +404,4 @@ def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None
 
 
 __all__ = ["DedupSettings", "compute_signature", "find_duplicates", "find_new_duplicates", "find_turned_duplicates", "find_trimmed_duplicates",
-           "run_duplicate_scan", "ClusterBuilder"]
+           "find_turned_trimmed_duplicates", "run_duplicate_scan", "ClusterBuilder"]

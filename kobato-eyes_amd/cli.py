@@ -4,6 +4,7 @@
                                             [--added-like '%/incoming/%'] [--refine] [--csv out.csv] [--device 0]
                                             [--devices 0,1,2] [--turned [--turned-ssim 0.9]]
                                             [--trimmed [--trim-tolerance 48] [--trimmed-ssim 0.9]]
+                                            [--turned-trimmed [--trim-tolerance 48] [--turned-trimmed-ssim 0.9]]
 
 Reproduces the call sequence of DuplicateScanRunnable.run (src/ui/dup_workers.py:148-239) without Qt: rows in
 the shape of db.repository.iter_files_for_dup (src/db/repository.py:416-454), missing signatures filled and
@@ -50,7 +51,8 @@ def export_duplicate_clusters_csv(clusters: Sequence, file_path, orientations: O
     """``orientations`` (scan-dups --turned): {file_id: orientation}; the CSV then has a ninth column ``orientation``,
     filled for the files that are linked to their group's keeper only through a turn (``orientations_to_keeper``).
     ``boxes`` (scan-dups --trimmed): {file_id: (x0, y0, x1, y1)}; the ninth column is then ``box``, ``x0 y0 x1 y1`` for a file
-    that is linked through its content box (``boxes_of_matches``) and empty for a file linked as it is."""
+    that is linked through its content box (``boxes_of_matches``) and empty for a file linked as it is.  With both (scan-dups
+    --turned-trimmed) ``orientation`` is the ninth column and ``box`` the tenth."""
     with open(file_path, "w", encoding="utf-8", newline="") as handle:
         writer = csv.writer(handle)
         writer.writerow(CSV_HEADER + (["orientation"] if orientations is not None else []) + (["box"] if boxes is not None else []))
@@ -68,7 +70,8 @@ def export_duplicate_clusters_csv(clusters: Sequence, file_path, orientations: O
 
 
 def boxes_of_matches(matches: Sequence) -> dict:
-    """{file_id: box} for the files that some ``scanner.TrimmedMatch`` links through their content box."""
+    """{file_id: box} for the files that some ``scanner.TrimmedMatch`` or ``scanner.TransformedMatch`` links through their
+    content box."""
     out: dict = {}
     for m in matches:
         if m.trimmed_a and m.box_a is not None:
@@ -110,7 +113,8 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
                   refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
                   devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None, turned: bool = False,
                   orientations_out: Optional[dict] = None, turned_ssim: Optional[float] = None, trimmed: bool = False,
-                  trim_tolerance: int = 48, boxes_out: Optional[dict] = None, trimmed_ssim: Optional[float] = None) -> list:
+                  trim_tolerance: int = 48, boxes_out: Optional[dict] = None, trimmed_ssim: Optional[float] = None,
+                  turned_trimmed: bool = False, turned_trimmed_ssim: Optional[float] = None) -> list:
     """``devices``: the missing signatures are computed by one worker process per entry; the scan and the tile-aHash / MAE
     refine stay in this process, on ``device`` (default ``devices[0]``, else 0).  ``added_like``: the files of the
     selection whose path matches this LIKE pattern are the added set, the rest the library; only the pairs that touch an
@@ -125,7 +129,16 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
     not together with ``turned``, ``added_like`` or ``refine``); ``boxes_out`` then receives ``boxes_of_matches`` of the
     result.  ``trimmed_ssim`` (only with ``trimmed``): the candidate edges and the trimmed matches are re-checked with SSIM, a
     match with its trimmed sides cut to their content boxes on the device, and only those at or above this score link files
-    (``find_trimmed_duplicates``' ``ssim_threshold``); the boxes are then those of the survivors."""
+    (``find_trimmed_duplicates``' ``ssim_threshold``); the boxes are then those of the survivors.  ``turned_trimmed``: a mode of
+    its own -- copies that were given a margin, turned, or both are linked (``find_turned_trimmed_duplicates`` with
+    ``trim_tolerance``; not together with ``turned``, ``trimmed``, ``added_like`` or ``refine``); ``orientations_out`` and
+    ``boxes_out`` receive what they receive in those two modes.  ``turned_trimmed_ssim`` (only with ``turned_trimmed``): its
+    ``ssim_threshold``."""
+    if turned_trimmed_ssim is not None and not turned_trimmed:
+        raise ValueError("--turned-trimmed-ssim needs --turned-trimmed")
+    if turned_trimmed and (turned or trimmed or added_like or refine):
+        # --turned and --trimmed are this mode's halves; the refine pipeline compares whole pictures as they lie
+        raise ValueError("--turned-trimmed cannot be combined with --turned, --trimmed, --added-like or --refine")
     if turned_ssim is not None and not turned:
         raise ValueError("--turned-ssim needs --turned")
     if trimmed_ssim is not None and not trimmed:
@@ -171,7 +184,17 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
         except ValueError:
             continue                                   # rows still without a hash are skipped, as the reference does
     tick("Clustering duplicates", 0, len(files))
-    if turned:
+    if turned_trimmed:
+        from .api import _turned_trimmed_scan
+
+        clusters, matches, plain_keys = _turned_trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=trim_tolerance,
+                                                             size_ratio=size_ratio, band_bits=16, band_count=4, device=device,
+                                                             ssim_threshold=turned_trimmed_ssim)
+        if orientations_out is not None:
+            orientations_out.update(orientations_to_keeper(clusters, matches, plain_keys))
+        if boxes_out is not None:
+            boxes_out.update(boxes_of_matches(matches))
+    elif turned:
         from .api import _turned_scan
 
         clusters, matches, plain_keys = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio,
@@ -227,6 +250,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("--trimmed-ssim", type=float, default=None,
                     help="with --trimmed: re-check every candidate edge and trimmed match with SSIM on the pixels (a trimmed side cut "
                          "to its content box on the device) and link only those at or above this score, e.g. 0.9")
+    sp.add_argument("--turned-trimmed", action="store_true",
+                    help="a mode of its own: read the files of the selection and link copies that were given a margin, turned, or both; "
+                         "the CSV gains an orientation and a box column; --trim-tolerance applies")
+    sp.add_argument("--turned-trimmed-ssim", type=float, default=None,
+                    help="with --turned-trimmed: re-check every candidate edge and match with SSIM on the pixels (cut and turned on the "
+                         "device) and link only those at or above this score, e.g. 0.9")
     sp.add_argument("--refine", action="store_true", help="run the tile-aHash + pixel-MAE refine pipeline on the clusters")
     sp.add_argument("--tile-max-bits", type=int, default=32)
     sp.add_argument("--mae-thr", type=float, default=0.004)
@@ -237,13 +266,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARNING)
-    orientations = {} if args.turned else None
-    boxes = {} if args.trimmed else None
+    orientations = {} if args.turned or args.turned_trimmed else None
+    boxes = {} if args.trimmed or args.turned_trimmed else None
     clusters = scan_database(args.db, hamming_threshold=args.hamming, size_ratio=args.size_ratio, path_like=args.like,
                              refine=args.refine, tile_max_bits=args.tile_max_bits, mae_thr=args.mae_thr, device=args.device,
                              devices=args.devices, added_like=args.added_like, turned=args.turned, orientations_out=orientations,
                              turned_ssim=args.turned_ssim, trimmed=args.trimmed, trim_tolerance=args.trim_tolerance, boxes_out=boxes,
-                             trimmed_ssim=args.trimmed_ssim)
+                             trimmed_ssim=args.trimmed_ssim, turned_trimmed=args.turned_trimmed,
+                             turned_trimmed_ssim=args.turned_trimmed_ssim)
     if args.csv:
         export_duplicate_clusters_csv(clusters, args.csv, orientations, boxes)
     members = sum(len(c.files) for c in clusters)

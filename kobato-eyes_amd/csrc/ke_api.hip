@@ -1391,6 +1391,108 @@ KE_API int ke_ssim_pairs_boxed(ke_ctx *ctx, const uint8_t *pixels, const uint64_
     return KE_OK;
 }
 
+// ke_ssim_pairs_boxed with ke_ssim_pairs_turned's orient_b: pair k is box_a of image a against orientation orient_b[k] of box_b
+// of image b -- crop, then turn, then fit.  Every distinct (image, box, orientation) is a plane source; the made ones share one
+// scratch (KE_BUF_VIEW_LUMA) and each kind of view is made by one launch: a box as it lies by ke_crop_luma, a whole picture turned
+// by ke_turn_luma, a box turned by ke_crop_turn_luma.
+KE_API int ke_ssim_pairs_viewed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                                int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *box_a,
+                                const int32_t *box_b, const int32_t *orient_b, int64_t n_pairs, double *ssim_out, int32_t *status_out) {
+    if (!ctx) return KE_EINVAL;
+    KE_TRY(check_pair_call(ctx, pixels, widths, heights, channels, n_images, pair_a, pair_b, n_pairs, ssim_out,
+                           {offsets, widths, heights, pair_a, pair_b, box_a, box_b, orient_b, ssim_out, status_out}));
+    if (n_pairs == 0) return KE_OK;
+    auto image_ok = [&](int64_t i) { return i >= 0 && i < n_images && widths[i] > 0 && heights[i] > 0; };
+    // the view of pair k's side: the box (four zeros for the image as it lies) and the orientation
+    struct View { int32_t x0, y0, x1, y1, o; };
+    auto view_of = [&](const int32_t *boxes, int64_t k, int64_t i, int o) {
+        if (!boxes) return View{0, 0, 0, 0, o};
+        const int32_t *b = boxes + 4 * k;
+        if (b[0] == 0 && b[1] == 0 && ((b[2] == 0 && b[3] == 0) || (b[2] == widths[i] && b[3] == heights[i]))) return View{0, 0, 0, 0, o};
+        return View{b[0], b[1], b[2], b[3], o};
+    };
+    auto cut = [](View v) { return v.x1 != 0 || v.y1 != 0 || v.x0 != 0 || v.y0 != 0; };
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        if (orient_b && (orient_b[k] < 0 || orient_b[k] > 7))
+            return ke_fail(ctx, KE_EINVAL, "pair %lld: orientation %d outside 0..7", (long long)k, orient_b[k]);
+        for (int side = 0; side < 2; ++side) {
+            const int64_t i = side ? pair_b[k] : pair_a[k];
+            if (!image_ok(i)) continue;                                 // KE_PAIR_BAD_IMAGE below
+            const View v = view_of(side ? box_b : box_a, k, i, 0);
+            if (cut(v) && (v.x0 < 0 || v.y0 < 0 || v.x1 <= v.x0 || v.y1 <= v.y0 || v.x1 > widths[i] || v.y1 > heights[i]))
+                return ke_fail(ctx, KE_EINVAL, "pair %lld: box_%c (%d, %d, %d, %d) is empty or outside image %lld (%dx%d)", (long long)k,
+                               side ? 'b' : 'a', v.x0, v.y0, v.x1, v.y1, (long long)i, widths[i], heights[i]);
+        }
+    }
+    KE_HIP(ctx, hipSetDevice(ctx->device));
+    trim_coeff_cache(ctx);
+    std::vector<uint64_t> off;
+    const uint64_t total_bytes = image_offsets(offsets, widths, heights, channels, n_images, off);
+    PlanePairs pp;
+    pp.channels = channels;
+    pp.a.assign((size_t)n_pairs, -1);
+    pp.b.assign((size_t)n_pairs, -1);
+    std::map<std::tuple<int64_t, int32_t, int32_t, int32_t, int32_t, int32_t>, int64_t> src_of;   // (image, view) -> its source
+    std::vector<KeCropLumaJob> crops;
+    std::vector<KeTurnJob> turns;
+    std::vector<KeViewJob> views;
+    uint64_t made_bytes = 0;
+    // size of a view as the fit sees it
+    auto size_of = [&](int64_t i, View v, int *w, int *h) {
+        const int bw = cut(v) ? v.x1 - v.x0 : widths[i], bh = cut(v) ? v.y1 - v.y0 : heights[i];
+        *w = (v.o & 4) ? bh : bw;
+        *h = (v.o & 4) ? bw : bh;
+    };
+    auto source = [&](int64_t i, View v) {
+        const auto key = std::make_tuple(i, v.x0, v.y0, v.x1, v.y1, v.o);
+        auto it = src_of.find(key);
+        if (it != src_of.end()) return it->second;
+        int vw, vh;
+        size_of(i, v, &vw, &vh);
+        if (!cut(v) && v.o == 0) {
+            pp.srcs.push_back(PlaneSrc{0, off[i], widths[i], heights[i]});
+        } else {
+            pp.srcs.push_back(PlaneSrc{1, made_bytes, vw, vh});
+            if (v.o == 0) crops.push_back(KeCropLumaJob{off[i], made_bytes, widths[i], heights[i], channels, v.x0, v.y0, v.x1 - v.x0, v.y1 - v.y0});
+            else if (!cut(v)) turns.push_back(KeTurnJob{off[i], made_bytes, widths[i], heights[i], channels, v.o});
+            else views.push_back(KeViewJob{off[i], made_bytes, widths[i], heights[i], channels, v.o, v.x0, v.y0, v.x1 - v.x0, v.y1 - v.y0});
+            made_bytes += ((uint64_t)vw * vh + 255) & ~(uint64_t)255;                         // every plane starts on a dword
+        }
+        return src_of[key] = (int64_t)pp.srcs.size() - 1;
+    };
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int64_t ia = pair_a[k], ib = pair_b[k];
+        const bool ok = image_ok(ia) && image_ok(ib);
+        View va{0, 0, 0, 0, 0}, vb{0, 0, 0, 0, 0};
+        int wa = 0, ha = 0, wb = 0, hb = 0;
+        if (ok) {
+            va = view_of(box_a, k, ia, 0);
+            vb = view_of(box_b, k, ib, orient_b ? orient_b[k] : 0);
+            size_of(ia, va, &wa, &ha);
+            size_of(ib, vb, &wb, &hb);
+        }
+        if (!classify_pair(pp, k, ok, wa, ha, wb, hb, ssim_out, status_out)) continue;
+        pp.a[(size_t)k] = source(ia, va);
+        pp.b[(size_t)k] = source(ib, vb);
+    }
+    if (pp.by_size.empty()) return KE_OK;
+    const void *d_px;
+    KE_TRY(ke_to_device(ctx, pixels, (size_t)total_bytes, KE_BUF_PIXELS, &d_px));
+    pp.buf[0] = (const uint8_t *)d_px;
+    ke_time_begin(ctx, KE_T_SSIM);
+    if (made_bytes) {
+        void *d_made;
+        KE_TRY(ke_reserve(ctx, KE_BUF_VIEW_LUMA, (size_t)made_bytes, &d_made));
+        KE_TRY(ke_launch_crop_luma(ctx, pp.buf[0], crops.data(), (int64_t)crops.size(), (uint8_t *)d_made));
+        KE_TRY(ke_launch_turn_luma(ctx, pp.buf[0], turns.data(), (int64_t)turns.size(), (uint8_t *)d_made));
+        KE_TRY(ke_launch_crop_turn_luma(ctx, pp.buf[0], views.data(), (int64_t)views.size(), (uint8_t *)d_made));
+        pp.buf[1] = (const uint8_t *)d_made;
+    }
+    KE_TRY(ssim_over_planes(ctx, pp, ssim_out));
+    ke_time_end(ctx, KE_T_SSIM);
+    return KE_OK;
+}
+
 // ---- shipped refine stage: thumbnails, tile aHash, pixel MAE --------------------------------------
 static int resize_luma_common(ke_ctx *ctx, const uint8_t *pixels, int64_t n, int32_t width, int32_t height, int32_t channels,
                               int32_t out_w, int32_t out_h, int32_t filter, const float *box, uint8_t *tiles_out);

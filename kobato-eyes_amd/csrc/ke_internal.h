@@ -22,7 +22,7 @@ struct KeDevBuf {
     size_t bytes = 0;
 };
 
-enum { KE_T_HASH = 0, KE_T_SCAN = 1, KE_T_SSIM = 2, KE_T_SYNTH = 3, KE_T_JPEG = 4, KE_T_TRIM_BOX = 5, KE_T_TRIM_CROP = 6, KE_T_TRIM_LUMA = 7, KE_T_COUNT = 8 };
+enum { KE_T_HASH = 0, KE_T_SCAN = 1, KE_T_SSIM = 2, KE_T_SYNTH = 3, KE_T_JPEG = 4, KE_T_TRIM_BOX = 5, KE_T_TRIM_CROP = 6, KE_T_TRIM_LUMA = 7, KE_T_VIEW_LUMA = 8, KE_T_COUNT = 9 };
 enum {
     KE_BUF_PIXELS = 0,   // staged input images
     KE_BUF_TMP,          // first-pass output of the generic resampler
@@ -49,6 +49,7 @@ enum {
     KE_BUF_TRIM_BOXES,   // ke_content_boxes: the boxes of a call's images, 16 B each
     KE_BUF_TRIM_CROPS,   // ke_hash_images_trimmed: the packed crops of one chunk of qualifying images
     KE_BUF_TRIM_LUMA,    // ke_ssim_pairs_boxed: the cropped luma planes of a call, 1 B/px per distinct (image, box)
+    KE_BUF_VIEW_LUMA,    // ke_ssim_pairs_viewed: the luma planes of a call's views, 1 B/px per distinct (image, box, orientation)
     KE_BUF_COUNT
 };
 
@@ -179,6 +180,15 @@ struct KeCropLumaJob {
     int32_t x0, y0, bw, bh;      // the box
 };
 int ke_launch_crop_luma(ke_ctx *ctx, const uint8_t *d_src, const KeCropLumaJob *jobs, int64_t n, uint8_t *d_dst);
+// the luma plane of orientation `orientation` of box (x0, y0, x0 + bw, y0 + bh) of each image, rows packed, bw x bh swapped for
+// orientation & 4 (ke_turn.hip); the box lies inside its image, the job table goes through KE_BUF_META and the stream is drained
+// before the call returns
+struct KeViewJob {
+    uint64_t src_off, dst_off;   // bytes from d_src / d_dst
+    int32_t w, h, channels, orientation;
+    int32_t x0, y0, bw, bh;
+};
+int ke_launch_crop_turn_luma(ke_ctx *ctx, const uint8_t *d_src, const KeViewJob *jobs, int64_t n, uint8_t *d_dst);
 int ke_launch_tile_ahash(ke_ctx *ctx, const uint8_t *d_tiles, int64_t n, int grid, int tile, uint64_t *d_bits);
 int ke_launch_sad_pairs(ke_ctx *ctx, const uint8_t *d_thumbs, int64_t pixels, const int64_t *d_pa, const int64_t *d_pb,
                         int64_t n_pairs, uint64_t *d_out);

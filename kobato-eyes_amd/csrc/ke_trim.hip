@@ -352,11 +352,13 @@ int check_images(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, co
 
 // boxes, the qualifying rule, crops in chunks, the hash dispatch on the crops: n images in device memory, host outputs
 int trimmed_on_device(ke_ctx *ctx, const uint8_t *d_px, const uint64_t *off, const int32_t *w, const int32_t *h, const uint8_t *take, int ch,
-                      int64_t n, int tol, uint64_t *phash, int32_t *boxes, uint8_t *has, int32_t *status) {
+                      int64_t n, int tol, uint64_t *phash, int32_t *boxes, uint8_t *has, int32_t *status, uint64_t *turned8 = nullptr) {
+    // turned8 (ke_hash_images_turned_trimmed; phash is NULL then): the crops go to ke_hash_images_turned instead, eight hashes each
     KE_TRY(boxes_on_device(ctx, d_px, off, w, h, take, ch, n, tol, boxes));
     std::vector<int64_t> q;
     for (int64_t i = 0; i < n; ++i) {
-        phash[i] = 0;
+        if (turned8) std::memset(turned8 + 8 * i, 0, 64);
+        else phash[i] = 0;
         has[i] = 0;
         if (take[i] && ke_trim_qualifies(w[i], h[i], boxes + 4 * i)) q.push_back(i);
     }
@@ -380,13 +382,15 @@ int trimmed_on_device(ke_ctx *ctx, const uint8_t *d_px, const uint64_t *off, con
         void *d_crops;
         KE_TRY(ke_reserve(ctx, KE_BUF_TRIM_CROPS, bytes, &d_crops));
         KE_TRY(launch_crop_pack(ctx, d_px, jobs, ch, (uint8_t *)d_crops));
-        c_hash.assign((size_t)m, 0);
         c_st.assign((size_t)m, 0);
-        KE_TRY(ke_hash_images(ctx, (const uint8_t *)d_crops, c_off.data(), c_w.data(), c_h.data(), ch, m, c_hash.data(), nullptr, c_st.data()));
+        c_hash.assign((size_t)m * (turned8 ? 8 : 1), 0);
+        if (turned8) KE_TRY(ke_hash_images_turned(ctx, (const uint8_t *)d_crops, c_off.data(), c_w.data(), c_h.data(), ch, m, c_hash.data(), c_st.data()));
+        else KE_TRY(ke_hash_images(ctx, (const uint8_t *)d_crops, c_off.data(), c_w.data(), c_h.data(), ch, m, c_hash.data(), nullptr, c_st.data()));
         for (int64_t k = 0; k < m; ++k) {
             const int64_t i = q[lo + (size_t)k];
             if (c_st[(size_t)k] == KE_IMG_OK) {
-                phash[i] = c_hash[(size_t)k];
+                if (turned8) std::memcpy(turned8 + 8 * i, c_hash.data() + 8 * (size_t)k, 64);
+                else phash[i] = c_hash[(size_t)k];
                 has[i] = 1;
             } else {
                 status[i] = c_st[(size_t)k];
@@ -501,6 +505,49 @@ KE_API int ke_hash_images_trimmed(ke_ctx *ctx, const uint8_t *pixels, const uint
         KE_TRY(rc);
         KE_TRY(trimmed_on_device(ctx, d_px, packed.data(), widths + lo, heights + lo, c.take.data() + lo, channels, hi - lo, tolerance,
                                  phash_out + lo, boxes_out + 4 * lo, has_out + lo, status_out + lo));
+        lo = hi;
+    }
+    return KE_OK;
+}
+
+// One resident chunk of ke_hash_images_turned_trimmed: the turned hashes of the pictures as they lie, then boxes and the turned
+// hashes of the qualifying crops.  `w` and `h` hold zeros for the images the box pass does not take, so neither pass reads them.
+static int turned_trimmed_on_device(ke_ctx *ctx, const uint8_t *d_px, const uint64_t *off, const int32_t *w, const int32_t *h, const uint8_t *take,
+                                    int ch, int64_t n, int tol, uint64_t *turned, uint64_t *trimmed_turned, int32_t *boxes, uint8_t *has,
+                                    int32_t *status) {
+    std::vector<int32_t> st((size_t)n);
+    KE_TRY(ke_hash_images_turned(ctx, d_px, off, w, h, ch, n, turned, st.data()));
+    for (int64_t i = 0; i < n; ++i)
+        if (take[i] && st[(size_t)i] != KE_IMG_OK) status[i] = st[(size_t)i];
+    return trimmed_on_device(ctx, d_px, off, w, h, take, ch, n, tol, nullptr, boxes, has, status, trimmed_turned);
+}
+
+KE_API int ke_hash_images_turned_trimmed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                                         int32_t channels, int64_t n, int32_t tolerance, uint64_t *turned_out, uint64_t *trimmed_turned_out,
+                                         int32_t *boxes_out, uint8_t *has_out, int32_t *status_out) {
+    if (!ctx) return KE_EINVAL;
+    if (n > 0 && (!turned_out || !trimmed_turned_out || !boxes_out || !has_out || !status_out || ke_is_device_ptr(turned_out) ||
+                  ke_is_device_ptr(trimmed_turned_out) || ke_is_device_ptr(boxes_out) || ke_is_device_ptr(has_out)))
+        return ke_fail(ctx, KE_EINVAL, "turned_out/trimmed_turned_out/boxes_out/has_out/status_out must be host arrays");
+    TrimCall c;
+    KE_TRY(check_images(ctx, pixels, offsets, widths, heights, channels, n, tolerance, status_out, c));
+    if (n == 0) return KE_OK;
+    KE_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<int32_t> w(widths, widths + n), h(heights, heights + n);
+    for (int64_t i = 0; i < n; ++i)
+        if (!c.take[(size_t)i]) w[(size_t)i] = h[(size_t)i] = 0;
+    if (ke_is_device_ptr(pixels))
+        return turned_trimmed_on_device(ctx, pixels, c.off.data(), w.data(), h.data(), c.take.data(), channels, n, tolerance, turned_out,
+                                        trimmed_turned_out, boxes_out, has_out, status_out);
+    // host pixels: a chunk is staged once and both passes walk it where it lies
+    std::vector<uint64_t> packed;
+    for (int64_t lo = 0; lo < n;) {
+        const uint8_t *d_px = nullptr;
+        int rc = KE_OK;
+        const int64_t hi = stage_chunk(ctx, pixels, c.off, widths, heights, c.take, channels, lo, n, packed, &d_px, &rc);
+        KE_TRY(rc);
+        KE_TRY(turned_trimmed_on_device(ctx, d_px, packed.data(), w.data() + lo, h.data() + lo, c.take.data() + lo, channels, hi - lo, tolerance,
+                                        turned_out + 8 * lo, trimmed_turned_out + 8 * lo, boxes_out + 4 * lo, has_out + lo, status_out + lo));
         lo = hi;
     }
     return KE_OK;

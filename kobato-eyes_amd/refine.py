@@ -173,7 +173,7 @@ def _upload(ctx, arrays: dict, placed: dict, buffers: list) -> None:
     ctx.memcpy(dev, flat, len(flat))
 
 
-PLAIN, TURNED, TRIMMED = "plain", "turned", "trimmed"     # what a row of _refine_runs carries after its two paths
+PLAIN, TURNED, TRIMMED, VIEWED = "plain", "turned", "trimmed", "viewed"     # what a row of _refine_runs carries after its two paths
 
 
 def _seam_boxes(ctx, pairs: Sequence[tuple], live: list, paths: list, index: dict, placed: dict, count: dict, tolerance: int):
@@ -198,7 +198,8 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
     """One ``ke_ssim_pairs`` call for the pairs of this run (the library groups them: one fit launch per (source size,
     common size), one SSIM launch per common size).  TURNED: a pair carries an orientation as its fifth item and the
     call is ``ke_ssim_pairs_turned``, which scores a against that orientation of b.  TRIMMED: a pair carries two flags, and
-    the call is ``ke_ssim_pairs_boxed`` with the content box, found here, of every flagged side."""
+    the call is ``ke_ssim_pairs_boxed`` with the content box, found here, of every flagged side.  VIEWED: two flags and an
+    orientation (seventh item), and the call is ``ke_ssim_pairs_viewed``: a's box against that orientation of b's box."""
     live = []
     for k in chunk:
         pa, pb = pairs[k][2], pairs[k][3]
@@ -219,9 +220,12 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
     elif mode == TRIMMED:
         box_a, box_b = _seam_boxes(ctx, pairs, live, paths, index, placed, count, tolerance)
         scores, status = ctx.ssim_pairs_boxed_on_device(*where, box_a, box_b)
+    elif mode == VIEWED:
+        box_a, box_b = _seam_boxes(ctx, pairs, live, paths, index, placed, count, tolerance)
+        scores, status = ctx.ssim_pairs_viewed_on_device(*where, box_a, box_b, [int(pairs[k][6]) for k in live])
     else:
         scores, status = ctx.ssim_pairs_on_device(*where)
-    common, fits, cropped = set(), set(), False
+    common, fits, cropped, turned, viewed = set(), set(), False, False, False
     for n, (k, sc, st) in enumerate(zip(live, scores.tolist(), status.tolist())):
         fid_a, fid_b, pa, pb = pairs[k][:4]
         if st != 0:                                            # skimage raises for images smaller than its window
@@ -230,23 +234,28 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
             continue
         out[k] = _decide(fid_a, fid_b, float(sc), [], cfg)
         (_, wa, ha), (_, wb, hb) = placed[str(pa)], placed[str(pb)]
-        o = int(pairs[k][4]) if mode == TURNED else 0
-        if o & 4:
-            wb, hb = hb, wb
-        # a box other than the whole picture is a source of its own, as a turned plane is
+        o = int(pairs[k][4]) if mode == TURNED else int(pairs[k][6]) if mode == VIEWED else 0
+        # a box other than the whole picture (as it lies) is a source of its own, as a turned plane is
         cut_a, cut_b = (bool(b.any()) and tuple(b) != (0, 0, w, h) for b, w, h in ((box_a[n], wa, ha), (box_b[n], wb, hb)))
         if cut_a:
             wa, ha = int(box_a[n][2] - box_a[n][0]), int(box_a[n][3] - box_a[n][1])
         if cut_b:
             wb, hb = int(box_b[n][2] - box_b[n][0]), int(box_b[n][3] - box_b[n][1])
-        cropped = cropped or cut_a or cut_b
+        if o & 4:                                              # crop, then turn
+            wb, hb = hb, wb
+        cropped = cropped or cut_a or (cut_b and o == 0)
+        turned = turned or (o != 0 and not cut_b)
+        viewed = viewed or (o != 0 and cut_b)
         size = (min(wa, wb), min(ha, hb))
         common.add(size)
         fits.update({((ha, wa), cut_a, size), ((hb, wb), o != 0 or cut_b, size)})
     count["fit_launches"] += len(fits)
     count["ssim_launches"] += len(common)
-    if mode == TRIMMED:
+    if mode in (TRIMMED, VIEWED):
         count["crop_launches"] += int(cropped)
+    if mode == VIEWED:
+        count["turn_launches"] += int(turned)
+        count["view_launches"] += int(viewed)
 
 
 def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThresholds] = None, device: int = 0,
@@ -280,7 +289,8 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
 
 def _refine_runs(pairs: Sequence[tuple], mode: str, thresholds, device: int, io_workers: int, max_decoded_bytes: int,
                  stats: Optional[dict], max_side: int, _after_run=None, tolerance: int = 48) -> list:
-    """The run loop of refine_pairs, refine_turned_pairs and refine_trimmed_pairs (``mode``: PLAIN, TURNED, TRIMMED): decode
+    """The run loop of refine_pairs, refine_turned_pairs, refine_trimmed_pairs and refine_turned_trimmed_pairs (``mode``: PLAIN,
+    TURNED, TRIMMED, VIEWED): decode
     what a run of pairs needs, once per file and within the budget, score the run with one library call, free, go on."""
     from concurrent.futures import ThreadPoolExecutor
 
@@ -290,6 +300,8 @@ def _refine_runs(pairs: Sequence[tuple], mode: str, thresholds, device: int, io_
     count = {"decodes": 0, "gpu_decodes": 0, "fit_launches": 0, "ssim_launches": 0, "pairs": len(pairs)}
     if mode == TRIMMED:
         count.update(box_files=0, crop_launches=0)
+    if mode == VIEWED:
+        count.update(box_files=0, crop_launches=0, turn_launches=0, view_launches=0)
     with ThreadPoolExecutor(max_workers=max(1, io_workers)) as pool:
         start = 0
         while start < len(pairs):
@@ -369,6 +381,35 @@ def refine_trimmed_pairs(pairs: Sequence[tuple], *, tolerance: int = 48, thresho
     return _refine_runs(pairs, TRIMMED, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, tolerance=int(tolerance))
 
 
+def refine_turned_trimmed_pairs(pairs: Sequence[tuple], *, tolerance: int = 48, thresholds: Optional[RefinementThresholds] = None,
+                                device: int = 0, io_workers: int = 8, max_decoded_bytes: int = 1 << 30, stats: Optional[dict] = None,
+                                max_side: int = MAX_SIDE) -> list:
+    """``refine_pairs`` for a list of ``(file_id_a, file_id_b, path_a, path_b, trimmed_a, trimmed_b, orientation)``: a's view is
+    scored against orientation ``orientation`` (0..7, ``turned.ORIENTATIONS``) of b's view, a view being the file's content box
+    (include/keyes.h, ``ke_content_boxes`` at ``tolerance``) where its flag is set and the whole picture otherwise -- crop, then
+    turn, then fit -- as ``refine_pairs`` would score files that hold Pillow's ``crop(box)`` of a and ``crop(box).transpose(...)``
+    of b.  A capability of this library only: the reference has neither bordered nor turned copies.
+
+    Both files are decoded as they lie (the same decode runs, budget and loader fallback as ``refine_pairs``, the same
+    ``stats``).  The boxes are made here, per run, on the pictures as they are placed on the device, as
+    ``refine_trimmed_pairs`` makes them and for its reason; a flagged side whose picture has no box here is scored as it lies.
+    Then one ``ke_ssim_pairs_viewed`` call per run: every distinct (file, box, orientation) is made once, luma only, by one launch
+    per kind of view -- a box as it lies (``ke_crop_luma``), a whole picture turned (``ke_turn_luma``), a box turned
+    (``ke_crop_turn_luma``).  Luma is per pixel, the turn a permutation and the resampler bit-exact with Pillow on every source,
+    so the planes the score is taken from are those of the cropped and turned files, byte for byte.  ``stats`` also receives
+    ``box_files`` (pictures whose box was looked for), ``crop_launches``, ``turn_launches`` and ``view_launches`` (the three
+    kernels above, in that order).  Returns a ``RefinedMatch`` or ``None`` (unreadable file) per pair, in input order.
+
+    There is no ``devices=``: ``ranks.refine_pairs`` ships 4-tuples to its workers.  A tolerance outside 0..255 or an
+    orientation outside 0..7 is a ``ValueError`` before anything is decoded."""
+    if not 0 <= int(tolerance) <= 255:
+        raise ValueError(f"tolerance {tolerance} outside 0..255")
+    for pair in pairs:
+        if not 0 <= int(pair[6]) < 8:
+            raise ValueError(f"orientation {pair[6]} outside 0..7")
+    return _refine_runs(pairs, VIEWED, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, tolerance=int(tolerance))
+
+
 def refine_pair(file_id_a: int, file_id_b: int, path_a, path_b, *, thresholds: Optional[RefinementThresholds] = None,
                 device: int = 0) -> Optional[RefinedMatch]:
     image_a, image_b = load_rgb(path_a), load_rgb(path_b)
@@ -385,5 +426,6 @@ def refine_pair(file_id_a: int, file_id_b: int, path_a, path_b, *, thresholds: O
     return _decide(file_id_a, file_id_b, ssim_value, errors, cfg)
 
 
-__all__ = ["RefinementThresholds", "RefinedMatch", "refine_pair", "refine_pairs", "refine_turned_pairs", "refine_trimmed_pairs", "compute_ssim",
+__all__ = ["RefinementThresholds", "RefinedMatch", "refine_pair", "refine_pairs", "refine_turned_pairs", "refine_trimmed_pairs", "refine_turned_trimmed_pairs",
+           "compute_ssim",
            "ssim_pairs"]

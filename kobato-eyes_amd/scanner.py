@@ -183,6 +183,54 @@ class TrimmedMatch:
     ssim: Optional[float] = None
 
 
+@dataclass(frozen=True)
+class TransformedMatch:
+    """Two files of which one looks like a copy of the other that was given a margin, turned, or both: orientation
+    ``orientation`` (turned.ORIENTATIONS) of file_id_b's picture -- cut to its content box first where ``trimmed_b`` -- is
+    file_id_a's picture -- cut to its box where ``trimmed_a`` --, to within ``hamming`` bits of the pHash.  ``box_a`` / ``box_b``:
+    that box as (x0, y0, x1, y1) on the file as it lies, None where the side is the whole file.  file_id_a < file_id_b.  ``ssim``:
+    the score of the two views where the pair went through the SSIM re-check (api.find_turned_trimmed_duplicates with
+    ``ssim_threshold``), else None."""
+
+    file_id_a: int
+    file_id_b: int
+    trimmed_a: bool
+    trimmed_b: bool
+    orientation: int
+    hamming: int
+    box_a: Optional[tuple] = None
+    box_b: Optional[tuple] = None
+    ssim: Optional[float] = None
+
+
+def view_edge(a: int, b: int, n: int, trimmed_rows: Sequence[int], turned_rows: Sequence[int]) -> tuple:
+    """An edge (a, b) of turned_trimmed_edges' table -> (candidate a, trimmed_a, candidate b, trimmed_b, k): the first part is
+    [n stored pHashes | the trimmed pHash of candidates ``trimmed_rows``], the second [seven turned hashes of each of candidates
+    ``turned_rows`` | seven turned hashes of the crop of each of ``trimmed_rows``]; a lies in the first part, b in the second."""
+    m = len(trimmed_rows)
+    side_a = (int(trimmed_rows[a - n]), True) if a >= n else (int(a), False)
+    at = b - (n + m)
+    if at < 7 * len(turned_rows):
+        return side_a + (int(turned_rows[at // 7]), False, at % 7 + 1)
+    at -= 7 * len(turned_rows)
+    return side_a + (int(trimmed_rows[at // 7]), True, at % 7 + 1)
+
+
+def ordered_view(id_a: int, trimmed_a: bool, id_b: int, trimmed_b: bool, k: int) -> tuple:
+    """(id_a, trimmed_a, id_b, trimmed_b, k) with the smaller id first: a match found from the file with the larger id has its
+    flags exchanged and its orientation mapped through turned.INVERSE, so that k always turns b's view into a's."""
+    from .turned import INVERSE
+
+    if id_a > id_b:
+        return id_b, trimmed_b, id_a, trimmed_a, INVERSE[k]
+    return id_a, trimmed_a, id_b, trimmed_b, k
+
+
+def view_rank(hamming: int, orientation: int, trimmed_a: bool, trimmed_b: bool) -> tuple:
+    """What the one match kept per unordered pair of files is the smallest of."""
+    return (int(hamming), int(orientation), bool(trimmed_a), bool(trimmed_b))
+
+
 def _safe_positive_int(value: Optional[str]) -> Optional[int]:
     if value is None or not value.strip():
         return None
@@ -338,6 +386,59 @@ class DuplicateScanner:
             return tuple(int(v) for v in np.asarray(boxes)[c]) if trimmed and boxes is not None else None
 
         return [TrimmedMatch(a, b, ta, tb, h, box(ca, ta), box(cb, tb)) for (a, b), (h, ta, tb, ca, cb) in sorted(best.items())]
+
+    def turned_trimmed_edges(self, candidates: Sequence[DuplicateFile], turned, trimmed_turned, has, ok=None, boxes=None) -> list:
+        """[TransformedMatch] of orientation 1..7: the pairs of files of which one looks like a turned copy of the other, either
+        side whole or cut to its content box -- a scan laid on the glass sideways with a white margin, a letterboxed frame that
+        was mirrored.
+
+        ``turned``: u64[n, 8], the turned pHashes of candidates[i]; ``ok``: the rows that hold them.  ``trimmed_turned``: u64[n, 8],
+        the turned pHashes of the crop; ``has``: the files whose box qualifies; ``boxes``: int32[n, 4], the boxes the matches carry
+        (all from turned_trimmed.turned_trimmed_signatures).  One cross scan (``ke_hamming_scan_cross``) whose first_new is the
+        length of the first part: [stored pHash of the n candidates | trimmed pHash (column 0) of the m files with one] against
+        [turned[:, 1:8] of the files with hashes | trimmed_turned[:, 1:8] of the m files]; neither part is compared with itself.
+        Every entry carries its file's id and size, so a file never meets itself, and size_ratio, the band config,
+        KE_DUP_BUCKET_PAIR_CAP and this scanner's part_index / part_count apply as in ``turned_edges``.  An edge decodes to (a's
+        side trimmed or not, b's side trimmed or not, k) (``view_edge``); found from the file with the larger id, the flags are
+        exchanged and k goes through turned.INVERSE (``ordered_view``), so that ``orientation`` always turns b's (cut) picture
+        into a's (cut) picture.  One match is kept per unordered pair of files: the smallest (hamming, orientation, trimmed_a,
+        trimmed_b).  Orientation 0 is not in the table: those pairs are ``candidate_edges``' and ``trimmed_edges``'."""
+        cfg = self._config
+        n = len(candidates)
+        turned = np.asarray(turned, dtype=np.uint64).reshape(n, 8)
+        cut = np.asarray(trimmed_turned, dtype=np.uint64).reshape(n, 8)
+        src_o = np.arange(n) if ok is None else np.nonzero(np.asarray(ok, bool).reshape(n))[0]
+        src_t = np.nonzero(np.asarray(has, bool).reshape(n))[0]
+        if n == 0 or len(src_o) + len(src_t) == 0:
+            return []
+        base_h = np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=n)
+        base_ids = np.fromiter((f.file_id for f in candidates), dtype=np.int64, count=n)
+        base_sizes = np.fromiter(((f.size or 0) for f in candidates), dtype=np.int64, count=n)
+        table = np.concatenate([base_h, cut[src_t, 0], turned[src_o, 1:8].reshape(-1), cut[src_t, 1:8].reshape(-1)])
+        rows = np.concatenate([np.arange(n), src_t, np.repeat(src_o, 7), np.repeat(src_t, 7)])
+        ids, sizes = base_ids[rows], base_sizes[rows]
+        first_new = n + len(src_t)
+        cap = _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
+        ratio = cfg.size_ratio if (cfg.size_ratio is not None and cfg.size_ratio > 0) else 0.0
+        ctx = _native.get_context(self._device)
+        raw, _ = ctx.hamming_scan(
+            table, len(table), ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
+            band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
+            part_index=self._part[0], part_count=self._part[1], first_new=first_new, cross=True)
+        best: dict[tuple[int, int], tuple] = {}
+        for a, b, h in zip(raw["a"].tolist(), raw["b"].tolist(), raw["h"].tolist()):
+            ca, ta, cb, tb, k = view_edge(a, b, n, src_t, src_o)
+            id_a, t_a, id_b, t_b, k = ordered_view(int(base_ids[ca]), ta, int(base_ids[cb]), tb, k)
+            if id_a != int(base_ids[ca]):
+                ca, cb = cb, ca
+            found = view_rank(h, k, t_a, t_b) + (ca, cb)
+            if (id_a, id_b) not in best or found[:4] < best[(id_a, id_b)][:4]:
+                best[(id_a, id_b)] = found
+
+        def box(c: int, trimmed: bool) -> Optional[tuple]:
+            return tuple(int(v) for v in np.asarray(boxes)[c]) if trimmed and boxes is not None else None
+
+        return [TransformedMatch(a, b, ta, tb, k, h, box(ca, ta), box(cb, tb)) for (a, b), (h, k, ta, tb, ca, cb) in sorted(best.items())]
 
     # -- the reference's funnel counters (src/dup/scanner.py:258-299) ---------------------------------------------
     def _band_values(self, hashes: np.ndarray, band: int) -> np.ndarray:
