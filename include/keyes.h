@@ -561,6 +561,27 @@ int ke_hamming_scan_cross(ke_ctx *ctx, const uint64_t *hashes, const int64_t *id
                           int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
                           int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out);
 
+/* ---- ranked search.  A capability of this library only (the reference has no such call): the k nearest entries of a table
+ * for each of m queries, by Hamming distance alone.  For query q
+ *   S_q = { i < n : popcount(hashes[i] ^ queries[q]) <= max_distance,
+ *                   and not (ids && query_ids && ids[i] == query_ids[q]) }
+ * and row q of the output is the first min(k, |S_q|) elements of S_q ordered by (distance ascending, position ascending):
+ * fully deterministic, ties included.  There is no band predicate, no size filter and no bucket cap -- a pair 4..8 bits apart
+ * with a differing bit in every 16-bit band, which ke_hamming_scan never sees, is found here.
+ *   index_out    m * k : the positions i, -1 beyond count_out[q]
+ *   distance_out m * k : their distances, -1 beyond count_out[q]
+ *   count_out    m     : min(k, |S_q|)
+ *   within_out   m     : |S_q|                                         (nullable)
+ *   histogram_out m * 65 : entries of S_q at each distance 0..64, so 0 above max_distance   (nullable)
+ * ids / query_ids may be NULL; with either one NULL nothing is excluded.  1 <= k <= KE_NEAREST_MAX_K, 0 <= max_distance <= 64,
+ * n, m >= 0, n <= 2^31 - 1; anything else is KE_EINVAL.  n == 0: every count 0, the rows -1.  m == 0: KE_OK, nothing touched.
+ * Every pointer may be host or device memory, each on its own.  Exhaustive: n * m pairs, the table read twice per query by
+ * one workgroup.  Blocks.  ke_last_kernel_ms kind 9 times the kernel. */
+#define KE_NEAREST_MAX_K 1024
+int ke_hamming_nearest(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, int64_t n, const uint64_t *queries,
+                       const int64_t *query_ids, int64_t m, int32_t k, int32_t max_distance, int64_t *index_out,
+                       int32_t *distance_out, int32_t *count_out, int64_t *within_out, uint32_t *histogram_out);
+
 /* The reference's "size=" funnel counter (src/dup/scanner.py:268-270 with _passes_size_ratio, :358-370): over every band
  * and band value whose bucket the reference walks (>= 2 members, under the pair cap), the member pairs that pass the size
  * filter -- pairs of equal file id included (the host takes those out, as for counters_out[3] of ke_hamming_scan).  A log
@@ -782,7 +803,7 @@ int ke_synth_hashes(ke_ctx *ctx, uint64_t seed, int64_t n, uint64_t *hashes_out)
 /* ---- timing hook for bench.py: wall time of the kernels enqueued by the LAST call of the
  * named kind on this context, measured with hipEvents on the context's stream.
  * kind: 0 = hash kernel(s), 1 = scan kernel, 2 = ssim kernel, 3 = synth kernel, 4 = JPEG / PNG decode kernels,
- * 5 = content-box kernel, 6 = crop kernel, 7 = luma-crop kernel.
+ * 5 = content-box kernel, 6 = crop kernel, 7 = luma-crop kernel, 8 = crop-and-turn kernel, 9 = nearest-neighbour kernel.
  * Returns milliseconds, or a negative value if nothing was recorded.  Blocks until done. */
 double ke_last_kernel_ms(ke_ctx *ctx, int32_t kind);
 

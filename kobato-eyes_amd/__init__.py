@@ -6,7 +6,7 @@ name carries a hyphen).  All arithmetic runs in libkeyes_hip.so (csrc/, C ABI in
 include/keyes.h); nothing here falls back to the CPU.
 """
 from . import _native
-from .api import DedupSettings, compute_signature, find_duplicates, find_new_duplicates, find_trimmed_duplicates, find_turned_duplicates, find_turned_trimmed_duplicates, run_duplicate_scan
+from .api import DedupSettings, compute_signature, find_duplicates, find_new_duplicates, find_similar, find_trimmed_duplicates, find_turned_duplicates, find_turned_trimmed_duplicates, run_duplicate_scan
 from .cluster import Cluster, ClusterBuilder
 from .cluster_update import (choose_keeper, cluster_hamming_score, default_checked_entries, rebuild_cluster_after_removal,
                              rebuild_clusters_after_removal, sort_entries_for_display)
@@ -16,7 +16,7 @@ from .refine_parallel import (refine_by_pixels_parallel, refine_by_tilehash_para
                               tile_ahash_from_arrays, tile_hamming)
 from .refine import RefinedMatch, RefinementThresholds, compute_ssim, refine_pair, refine_pairs, ssim_pairs
 from .scanner import (DuplicateCluster, DuplicateClusterEntry, DuplicateFile, DuplicateScanConfig, DuplicateScanner,
-                      TransformedMatch, TrimmedMatch, TurnedMatch, assemble_clusters)
+                      SimilarFile, TransformedMatch, TrimmedMatch, TurnedMatch, assemble_clusters)
 from .trimmed import trimmed_signatures
 from .turned import INVERSE, ORIENTATIONS, turned_signatures
 from .turned_trimmed import turned_trimmed_signatures
@@ -24,6 +24,7 @@ from .signature import compute_signatures_from_image, ensure_signatures
 
 __all__ = [
     "phash", "dhash", "hamming64", "phash_dhash", "hash_batch", "compute_signature", "find_duplicates", "find_new_duplicates",
+    "find_similar", "SimilarFile",
     "find_turned_duplicates", "phash_turned", "turned_signatures", "TurnedMatch", "ORIENTATIONS", "INVERSE",
     "find_trimmed_duplicates", "trimmed_signatures", "TrimmedMatch",
     "find_turned_trimmed_duplicates", "turned_trimmed_signatures", "TransformedMatch",

@@ -28,7 +28,7 @@ EXPORTS = (
     "ke_abi_version", "ke_create", "ke_create_error", "ke_destroy", "ke_last_error", "ke_set_stream",
     "ke_get_stream", "ke_synchronize", "ke_device_info", "ke_malloc", "ke_free", "ke_memcpy",
     "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan",
-    "ke_hamming_scan_from", "ke_hamming_scan_cross", "ke_tiles_turned", "ke_hash_images_turned", "ke_band_pairs_after_size",
+    "ke_hamming_scan_from", "ke_hamming_scan_cross", "ke_hamming_nearest", "ke_tiles_turned", "ke_hash_images_turned", "ke_band_pairs_after_size",
     "ke_content_boxes", "ke_crop_pack", "ke_hash_images_trimmed", "ke_crop_luma", "ke_ssim_pairs_boxed",
     "ke_crop_turn_luma", "ke_ssim_pairs_viewed", "ke_hash_images_turned_trimmed",
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
@@ -147,6 +147,7 @@ def load_library() -> C.CDLL:
         lib.ke_hamming_scan_from.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, dbl, i64, vp, i64,
                                              C.POINTER(i64), vp]
         lib.ke_hamming_scan_cross.argtypes = lib.ke_hamming_scan_from.argtypes
+        lib.ke_hamming_nearest.argtypes = [vp, vp, vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]
         lib.ke_tiles_turned.argtypes = [vp, vp, i64, vp]
         lib.ke_hash_images_turned.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp]
         lib.ke_content_boxes.argtypes = [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp]
@@ -1129,6 +1130,36 @@ class Context:
             if n_edges.value <= cap:
                 return edges[: n_edges.value], counters
             cap = int(n_edges.value)  # overflow protocol: retry with the reported size
+
+    def hamming_nearest(self, hashes, queries, *, k: int, max_distance: int = 64, ids=None, query_ids=None, histogram: bool = False,
+                        n: Optional[int] = None, m: Optional[int] = None):
+        """The k nearest entries of ``hashes`` for every query, by Hamming distance alone (ke_hamming_nearest): row q holds the
+        first min(k, |S_q|) of S_q = {i : popcount(hashes[i] ^ queries[q]) <= max_distance, ids[i] != query_ids[q] where both id
+        arrays are given}, ordered by (distance, position).  No band predicate, no size filter, no bucket cap.
+        Returns (index int64[m, k], distance int32[m, k], count int32[m], within int64[m]), -1 beyond count, and
+        histogram uint32[m, 65] after them when asked.  Inputs: host arrays or device pointers; a device pointer needs its
+        length in ``n`` (hashes, ids) or ``m`` (queries, query_ids)."""
+        def host(a, dt):
+            return np.ascontiguousarray(a, dtype=dt) if isinstance(a, (np.ndarray, list, tuple)) else a
+
+        hashes, queries = host(hashes, np.uint64), host(queries, np.uint64)
+        ids, query_ids = host(ids, np.int64), host(query_ids, np.int64)
+        n = int(len(hashes) if n is None else n)
+        m = int(len(queries) if m is None else m)
+        for name, a, want in (("hashes", hashes, n), ("ids", ids, n), ("queries", queries, m), ("query_ids", query_ids, m)):
+            if isinstance(a, np.ndarray) and a.size != want:
+                raise ValueError(f"{name} has {a.size} entries, expected {want}")
+        rows, width = max(m, 0), max(int(k), 0)
+        index = np.full((rows, width), -1, np.int64)
+        distance = np.full((rows, width), -1, np.int32)
+        count = np.zeros(rows, np.int32)
+        within = np.zeros(rows, np.int64)
+        hist = np.zeros((rows, 65), np.uint32) if histogram else None
+        with self._lock:
+            self._check(self._lib.ke_hamming_nearest(self._h, _addr(hashes), _addr(ids), n, _addr(queries), _addr(query_ids), m,
+                                                     int(k), int(max_distance), _addr(index), _addr(distance), _addr(count),
+                                                     _addr(within), _addr(hist)), "ke_hamming_nearest")
+        return (index, distance, count, within) + ((hist,) if histogram else ())
 
     def band_pairs_after_size(self, hashes, sizes, n: int, *, band_bits=16, band_count=4, size_ratio: float, bucket_pair_cap: int = 0) -> int:
         """The reference's "size=" funnel counter before pairs of equal file id are taken out (ke_band_pairs_after_size)."""

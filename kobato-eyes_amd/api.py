@@ -18,7 +18,7 @@ from . import fastsig, refine as _refine
 
 _phash = importlib.import_module(".phash", __package__)   # the package also exports a function named phash
 from .cluster import ClusterBuilder
-from .scanner import DuplicateCluster, DuplicateFile, DuplicateScanConfig, DuplicateScanner
+from .scanner import DuplicateCluster, DuplicateFile, DuplicateScanConfig, DuplicateScanner, SimilarFile
 
 logger = logging.getLogger(__name__)
 
@@ -152,6 +152,41 @@ def find_new_duplicates(library: Iterable, added: Iterable, *, previous: Optiona
         clusters = assemble_clusters(candidates, edges, previous=previous or ())
     new_ids = {f.file_id for f in new}
     return [c for c in clusters if any(e.file.file_id in new_ids for e in c.files)]
+
+
+def _parse_query(item, device: int) -> DuplicateFile:
+    """A query of ``find_similar`` -> a DuplicateFile; one without a usable hash keeps its place with ``phash`` None."""
+    if isinstance(item, DuplicateFile):
+        return item
+    if isinstance(item, (str, Path)):
+        return DuplicateFile(file_id=-1, path=Path(item), size=None, width=None, height=None,
+                             phash=compute_signature(item, device=device)[0] & ((1 << 64) - 1))
+    if isinstance(item, Mapping) or hasattr(item, "keys"):
+        try:
+            return DuplicateFile.from_row(item)
+        except ValueError:
+            return DuplicateFile(file_id=-1, path=Path(""), size=None, width=None, height=None, phash=None)
+    return DuplicateFile(file_id=-1, path=Path(""), size=None, width=None, height=None,              # a PIL image
+                         phash=compute_signature(item, device=device)[0] & ((1 << 64) - 1))
+
+
+def find_similar(library: Iterable, queries: Iterable, *, k: int = 10, max_distance: Optional[int] = None, device: Optional[int] = None,
+                 scanner_factory: Callable[[DuplicateScanConfig], DuplicateScanner] = DuplicateScanner) -> list:
+    """For every query the ``k`` library files most like it, best first: one list of ``SimilarFile(file, distance)`` per
+    query, ordered by the Hamming distance of the pHashes, ties by the file's place in ``library``
+    (``DuplicateScanner.nearest``).  A ranked, threshold-free answer: no band predicate, no size filter -- it finds the
+    pairs 4..8 bits apart that share no 16-bit band, which ``find_duplicates`` never links.
+
+    ``library``: as ``files`` of ``find_duplicates``.  An item of ``queries`` is a DuplicateFile, a row mapping, or a ``str`` /
+    ``Path`` / PIL image; the last three are hashed here through ``compute_signature``, one at a time -- meant for a handful of
+    queries, hash a collection with the batch hasher instead -- and carry no file id.  A query with a file id never gets the
+    library file of that id; a query without a usable hash gets [].  ``max_distance``: leave out files further away (None:
+    64, no limit).  ``k`` is at most 1024."""
+    device = 0 if device is None else int(device)
+    files = _parse_files(library)
+    asked = [_parse_query(item, device) for item in queries]
+    scanner = _make_scanner(scanner_factory, DuplicateScanConfig(), device)
+    return scanner.nearest(files, asked, k, max_distance)
 
 
 def _turned_scan(files: Iterable, *, hamming_threshold, size_ratio, band_bits, band_count, device, ssim_threshold=None):
@@ -403,5 +438,5 @@ def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None
     return DuplicateScanner(config or DuplicateScanConfig(), device=device).build_clusters(files)
 
 
-__all__ = ["DedupSettings", "compute_signature", "find_duplicates", "find_new_duplicates", "find_turned_duplicates", "find_trimmed_duplicates",
+__all__ = ["DedupSettings", "compute_signature", "find_duplicates", "find_similar", "SimilarFile", "find_new_duplicates", "find_turned_duplicates", "find_trimmed_duplicates",
            "find_turned_trimmed_duplicates", "run_duplicate_scan", "ClusterBuilder"]

@@ -5,6 +5,8 @@
                                             [--devices 0,1,2] [--turned [--turned-ssim 0.9]]
                                             [--trimmed [--trim-tolerance 48] [--trimmed-ssim 0.9]]
                                             [--turned-trimmed [--trim-tolerance 48] [--turned-trimmed-ssim 0.9]]
+    python -m kobato_eyes_amd.cli similar --db kobato.db (--to PATH ... | --to-like '%/incoming/%') [--like '%/photos/%']
+                                          [--k 10] [--max-distance N] [--csv out.csv] [--device 0]
 
 Reproduces the call sequence of DuplicateScanRunnable.run (src/ui/dup_workers.py:148-239) without Qt: rows in
 the shape of db.repository.iter_files_for_dup (src/db/repository.py:416-454), missing signatures filled and
@@ -109,6 +111,65 @@ def orientations_to_keeper(clusters: Sequence, matches: Sequence, plain_keys) ->
     return out
 
 
+def load_files_for_dup(db_path: str, path_like: Optional[str], added_like: Optional[str] = None, *, device: int = 0,
+                       devices: Optional[Sequence[int]] = None, tick=lambda stage, done, total: None) -> tuple:
+    """(rows, files) of a selection: the rows of ``iter_files_for_dup`` with missing signatures computed and upserted as
+    core.fastsig does, and their DuplicateFile objects, rows still without a hash skipped as the reference does."""
+    from . import DuplicateFile, fast_fill_missing_signatures
+
+    conn = sqlite3.connect(db_path)
+    try:
+        rows = list(iter_files_for_dup(conn, path_like, added_like))
+    finally:
+        conn.close()
+    tick("Loading files", len(rows), len(rows))
+    missing = [(r["file_id"], r["path"]) for r in rows if r["phash_u64"] is None and r["path"]]
+    if missing:
+        workers = int(os.environ.get("KE_SIG_WORKERS", "8"))
+        chunk = int(os.environ.get("KE_SIG_CHUNK", "64"))
+        filled = fast_fill_missing_signatures(db_path, missing, max_workers=workers, chunksize=chunk,
+                                              progress=lambda d, t: tick("Computing signatures", d, t), device=device,
+                                              devices=devices)
+        by_id = {fid: ph for fid, ph, _ in filled}
+        for r in rows:
+            if r["phash_u64"] is None:
+                r["phash_u64"] = by_id.get(r["file_id"])
+    tick("Building groups", 0, len(rows))
+    files = []
+    for r in rows:
+        try:
+            files.append(DuplicateFile.from_row(r))
+        except ValueError:
+            continue                                   # rows still without a hash are skipped, as the reference does
+    return rows, files
+
+
+SIMILAR_HEADER = ["query", "rank", "path", "distance"]
+
+
+def similar_in_database(db_path: str, *, to: Sequence[str] = (), to_like: Optional[str] = None, path_like: Optional[str] = None,
+                        k: int = 10, max_distance: Optional[int] = None, device: Optional[int] = None) -> list:
+    """[(query, rank, path, distance)], rank from 1, for the ``similar`` sub-command: the library is the selection
+    (``path_like``) loaded as scan-dups loads it; the queries are either the files of the selection whose path matches
+    ``to_like`` -- each left out of its own answer -- or the files ``to``, which are hashed here and need not be in the
+    database.  Ranking by pHash distance alone (``find_similar``): no threshold, no band predicate."""
+    from .api import find_similar
+
+    if bool(to) == bool(to_like):
+        raise ValueError("similar needs either --to PATH ... or --to-like PATTERN")
+    device = 0 if device is None else int(device)
+    rows, files = load_files_for_dup(db_path, path_like, to_like, device=device)
+    if to_like:
+        asked_ids = {r["file_id"] for r in rows if r["added"]}
+        queries = [f for f in files if f.file_id in asked_ids]
+        names = [f.path.as_posix() for f in queries]
+    else:
+        queries, names = list(to), [str(p) for p in to]
+    found = find_similar(files, queries, k=k, max_distance=max_distance, device=device)
+    return [(name, rank, hit.file.path.as_posix(), hit.distance)
+            for name, hits in zip(names, found) for rank, hit in enumerate(hits, start=1)]
+
+
 def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, path_like: Optional[str] = None,
                   refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
                   devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None, turned: bool = False,
@@ -149,7 +210,7 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
     if turned and (added_like or refine):
         # the refine pipeline compares pixels as they lie and would cut every link that exists through a turn
         raise ValueError("--turned cannot be combined with --added-like or --refine")
-    from . import DuplicateFile, DuplicateScanConfig, DuplicateScanner, fast_fill_missing_signatures
+    from . import DuplicateScanConfig, DuplicateScanner
     from .refine_parallel import refine_by_pixels_parallel, refine_by_tilehash_parallel
 
     if device is None:
@@ -159,30 +220,7 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
         if progress:
             progress(stage, done, total)
 
-    conn = sqlite3.connect(db_path)
-    try:
-        rows = list(iter_files_for_dup(conn, path_like, added_like))
-    finally:
-        conn.close()
-    tick("Loading files", len(rows), len(rows))
-    missing = [(r["file_id"], r["path"]) for r in rows if r["phash_u64"] is None and r["path"]]
-    if missing:
-        workers = int(os.environ.get("KE_SIG_WORKERS", "8"))
-        chunk = int(os.environ.get("KE_SIG_CHUNK", "64"))
-        filled = fast_fill_missing_signatures(db_path, missing, max_workers=workers, chunksize=chunk,
-                                              progress=lambda d, t: tick("Computing signatures", d, t), device=device,
-                                              devices=devices)
-        by_id = {fid: ph for fid, ph, _ in filled}
-        for r in rows:
-            if r["phash_u64"] is None:
-                r["phash_u64"] = by_id.get(r["file_id"])
-    tick("Building groups", 0, len(rows))
-    files = []
-    for r in rows:
-        try:
-            files.append(DuplicateFile.from_row(r))
-        except ValueError:
-            continue                                   # rows still without a hash are skipped, as the reference does
+    rows, files = load_files_for_dup(db_path, path_like, added_like, device=device, devices=devices, tick=tick)
     tick("Clustering duplicates", 0, len(files))
     if turned_trimmed:
         from .api import _turned_trimmed_scan
@@ -264,8 +302,34 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("--devices", default=None, type=lambda text: [int(d) for d in text.split(",") if d.strip()],
                     help="e.g. 0,1,2: missing signatures are computed by one worker process per entry (at most 15)")
     sp.add_argument("-v", "--verbose", action="store_true")
+    sm = sub.add_parser("similar", help="rank the files of a kobato-eyes database by pHash distance to given pictures")
+    sm.add_argument("--db", required=True)
+    target = sm.add_mutually_exclusive_group(required=True)
+    target.add_argument("--to", nargs="+", default=None, metavar="PATH", help="picture files to find neighbours of; they need not be in the database")
+    target.add_argument("--to-like", default=None,
+                        help="SQL LIKE pattern: the matching files of the selection are the queries, each left out of its own answer")
+    sm.add_argument("--like", default=None, help="SQL LIKE pattern on files.path: the library")
+    sm.add_argument("--k", type=int, default=10, help="neighbours per query, at most 1024")
+    sm.add_argument("--max-distance", type=int, default=None, help="leave out files more than this many bits away (default: no limit)")
+    sm.add_argument("--csv", default=None)
+    sm.add_argument("--device", type=int, default=None)
+    sm.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARNING)
+    if args.cmd == "similar":
+        found = similar_in_database(args.db, to=args.to or (), to_like=args.to_like, path_like=args.like, k=args.k,
+                                    max_distance=args.max_distance, device=args.device)
+        handle = open(args.csv, "w", encoding="utf-8", newline="") if args.csv else sys.stdout
+        try:
+            writer = csv.writer(handle)
+            writer.writerow(SIMILAR_HEADER)
+            writer.writerows(found)
+        finally:
+            if args.csv:
+                handle.close()
+        if args.csv:
+            print(f"{len(found)} neighbour(s) of {len({row[0] for row in found})} querie(s) -> {args.csv}")
+        return 0
     orientations = {} if args.turned or args.turned_trimmed else None
     boxes = {} if args.trimmed or args.turned_trimmed else None
     clusters = scan_database(args.db, hamming_threshold=args.hamming, size_ratio=args.size_ratio, path_like=args.like,

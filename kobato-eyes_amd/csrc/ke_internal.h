@@ -22,7 +22,7 @@ struct KeDevBuf {
     size_t bytes = 0;
 };
 
-enum { KE_T_HASH = 0, KE_T_SCAN = 1, KE_T_SSIM = 2, KE_T_SYNTH = 3, KE_T_JPEG = 4, KE_T_TRIM_BOX = 5, KE_T_TRIM_CROP = 6, KE_T_TRIM_LUMA = 7, KE_T_VIEW_LUMA = 8, KE_T_COUNT = 9 };
+enum { KE_T_HASH = 0, KE_T_SCAN = 1, KE_T_SSIM = 2, KE_T_SYNTH = 3, KE_T_JPEG = 4, KE_T_TRIM_BOX = 5, KE_T_TRIM_CROP = 6, KE_T_TRIM_LUMA = 7, KE_T_VIEW_LUMA = 8, KE_T_NEAREST = 9, KE_T_COUNT = 10 };
 enum {
     KE_BUF_PIXELS = 0,   // staged input images
     KE_BUF_TMP,          // first-pass output of the generic resampler
@@ -50,6 +50,8 @@ enum {
     KE_BUF_TRIM_CROPS,   // ke_hash_images_trimmed: the packed crops of one chunk of qualifying images
     KE_BUF_TRIM_LUMA,    // ke_ssim_pairs_boxed: the cropped luma planes of a call, 1 B/px per distinct (image, box)
     KE_BUF_VIEW_LUMA,    // ke_ssim_pairs_viewed: the luma planes of a call's views, 1 B/px per distinct (image, box, orientation)
+    KE_BUF_NEAREST_IN,   // ke_hamming_nearest: the host's arrays among [hashes | ids | queries | query_ids]
+    KE_BUF_NEAREST_OUT,  // ke_hamming_nearest: the host's arrays among [index | within | distance | count | histogram]
     KE_BUF_COUNT
 };
 

@@ -203,6 +203,15 @@ class TransformedMatch:
     ssim: Optional[float] = None
 
 
+@dataclass(frozen=True)
+class SimilarFile:
+    """One neighbour of a query of ``DuplicateScanner.nearest``: a library file and the bits its pHash differs from the
+    query's in."""
+
+    file: DuplicateFile
+    distance: int
+
+
 def view_edge(a: int, b: int, n: int, trimmed_rows: Sequence[int], turned_rows: Sequence[int]) -> tuple:
     """An edge (a, b) of turned_trimmed_edges' table -> (candidate a, trimmed_a, candidate b, trimmed_b, k): the first part is
     [n stored pHashes | the trimmed pHash of candidates ``trimmed_rows``], the second [seven turned hashes of each of candidates
@@ -633,9 +642,50 @@ class DuplicateScanner:
             if paused:
                 gc.enable()
 
+    def nearest(self, library: Iterable[DuplicateFile], queries: Iterable[DuplicateFile], k: int,
+                max_distance: Optional[int] = None) -> list:
+        """One list per query of at most ``k`` ``SimilarFile(file, distance)``: the library files whose pHash lies nearest the
+        query's, best first -- by distance, then by the file's place in ``library`` (``ke_hamming_nearest``).
+
+        This is a ranking by Hamming distance ALONE.  It does not read ``hamming_threshold``, the band config, ``size_ratio``
+        or ``cosine_threshold`` from the scanner's config: a pair that shares no 16-bit band, which ``build_clusters`` cannot
+        link, is found here.  ``max_distance``: leave out library files further away than this; None means 64, no limit.
+        Library files without a pHash are left out; a query without one gets [].  A query whose ``file_id`` is a real id (not
+        None, not negative) never gets the library files with that id -- itself, when it comes from the library -- but does
+        get another file with the same hash; a query without an id excludes nothing.  ``k`` may exceed the library: a row
+        is as long as there are files within ``max_distance``.  ``k`` is at most 1024 (KE_NEAREST_MAX_K)."""
+        files = [f for f in library if f.phash is not None]
+        queries = list(queries)
+        out: list = [[] for _ in queries]
+        asked = [i for i, q in enumerate(queries) if q.phash is not None]
+        if not files or not asked:
+            return out
+        hashes = np.fromiter((f.phash & _MASK64 for f in files), dtype=np.uint64, count=len(files))
+        q_hashes = np.fromiter((queries[i].phash & _MASK64 for i in asked), dtype=np.uint64, count=len(asked))
+        # the kernel's id rule on codes of this call's own: a real file id -> its first position in the library; a library file
+        # without an id (-2) and a query without one or with one the library does not hold (-1) match nothing
+        code: dict = {}
+        ids = np.empty(len(files), np.int64)
+        for at, f in enumerate(files):
+            ids[at] = code.setdefault(f.file_id, at) if _has_id(f) else -2
+        q_ids = np.fromiter((code.get(queries[i].file_id, -1) if _has_id(queries[i]) else -1 for i in asked), dtype=np.int64,
+                            count=len(asked))
+        ctx = _native.get_context(self._device)
+        index, distance, count, _within = ctx.hamming_nearest(hashes, q_hashes, k=int(k), max_distance=64 if max_distance is None else int(max_distance),
+                                                              ids=ids, query_ids=q_ids)
+        for row, i in enumerate(asked):
+            c = int(count[row])
+            out[i] = [SimilarFile(files[p], d) for p, d in zip(index[row, :c].tolist(), distance[row, :c].tolist())]
+        return out
+
     @staticmethod
     def _choose_keeper(entries: Sequence[DuplicateClusterEntry]) -> int:
         return min(entries, key=_keeper_key).file.file_id
+
+
+def _has_id(f: DuplicateFile) -> bool:
+    """A file id that names a file: ``from_row`` gives -1 to a row without one."""
+    return f.file_id is not None and f.file_id >= 0
 
 
 def _keeper_key(entry: DuplicateClusterEntry) -> tuple:
