@@ -293,6 +293,13 @@ def _pack_images(images):
     return flat, offsets, widths, heights, ch
 
 
+def _base_and_offsets(pointers):
+    """Device images, each at its own address, as one buffer: (the lowest address, every image's uint64 offset from it)."""
+    ptrs = np.asarray(pointers, np.uint64)
+    base = int(ptrs.min())
+    return base, np.ascontiguousarray(ptrs - np.uint64(base))
+
+
 class _Files:
     """Files packed in host memory, as the probe and decode calls take them: file i is ``flat[offsets[i]:offsets[i] + sizes[i]]``
     (size 0 = unreadable).  ``probed``: (kind, lo, hi) -> (widths, heights, channels, status) where the headers of files lo..hi
@@ -1191,169 +1198,104 @@ class Context:
                                                         _addr(pb), len(pa), _addr(out)), "ke_ssim_pairs_uniform")
         return out
 
-    def ssim_pairs(self, images: Sequence[np.ndarray], pair_a, pair_b):
-        """src/dup/refine.py:44-52 for pairs of images of any sizes (one channel count): common size, ImageOps.fit + BICUBIC
-        of both, SSIM.  Returns (float64 scores, NaN where the status is not 0; int32 statuses KE_PAIR_*)."""
-        n = len(images)
-        flat, offsets, widths, heights, ch = _pack_images(images)
-        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
-        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
-        out = np.empty(len(pa), np.float64)
-        status = np.empty(len(pa), np.int32)
-        with self._lock:
-            self._check(self._lib.ke_ssim_pairs(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n, _addr(pa),
-                                                _addr(pb), len(pa), _addr(out), _addr(status)), "ke_ssim_pairs")
-        return out, status
-
-    def ssim_pairs_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b):
-        """ssim_pairs for images that already lie in device memory, each at its own address (decoded there, or uploaded)."""
-        ptrs = np.asarray(pointers, np.uint64)
-        base = int(ptrs.min())
-        offsets = np.ascontiguousarray(ptrs - np.uint64(base))
-        widths = np.ascontiguousarray(widths, np.int32)
-        heights = np.ascontiguousarray(heights, np.int32)
-        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
-        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
-        out = np.empty(len(pa), np.float64)
-        status = np.empty(len(pa), np.int32)
-        with self._lock:
-            self._check(self._lib.ke_ssim_pairs(self._h, base, _addr(offsets), _addr(widths), _addr(heights), channels, len(ptrs), _addr(pa),
-                                                _addr(pb), len(pa), _addr(out), _addr(status)), "ke_ssim_pairs")
-        return out, status
-
-    def ssim_pairs_turned(self, images: Sequence[np.ndarray], pair_a, pair_b, orient_b):
-        """ssim_pairs with image ``pair_b[k]`` under orientation ``orient_b[k]`` (0..7, turned.ORIENTATIONS; None: all 0)."""
-        n = len(images)
-        flat, offsets, widths, heights, ch = _pack_images(images)
-        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
-        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
-        ob = None if orient_b is None else np.ascontiguousarray(orient_b, dtype=np.int32)
-        out = np.empty(len(pa), np.float64)
-        status = np.empty(len(pa), np.int32)
-        with self._lock:
-            self._check(self._lib.ke_ssim_pairs_turned(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n, _addr(pa),
-                                                       _addr(pb), _addr(ob), len(pa), _addr(out), _addr(status)), "ke_ssim_pairs_turned")
-        return out, status
-
-    def ssim_pairs_turned_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b, orient_b):
-        """ssim_pairs_on_device with image ``pair_b[k]`` under orientation ``orient_b[k]`` (0..7, turned.ORIENTATIONS): each
-        distinct (image, orientation != 0) is turned once on the device (ke_turn_luma) before the fit."""
-        ptrs = np.asarray(pointers, np.uint64)
-        base = int(ptrs.min())
-        offsets = np.ascontiguousarray(ptrs - np.uint64(base))
-        widths = np.ascontiguousarray(widths, np.int32)
-        heights = np.ascontiguousarray(heights, np.int32)
-        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
-        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
-        ob = np.ascontiguousarray(orient_b, dtype=np.int32)
-        out = np.empty(len(pa), np.float64)
-        status = np.empty(len(pa), np.int32)
-        with self._lock:
-            self._check(self._lib.ke_ssim_pairs_turned(self._h, base, _addr(offsets), _addr(widths), _addr(heights), channels, len(ptrs),
-                                                       _addr(pa), _addr(pb), _addr(ob), len(pa), _addr(out), _addr(status)),
-                        "ke_ssim_pairs_turned")
-        return out, status
-
-    def _ssim_pairs_boxed(self, pixels, offsets, widths, heights, channels: int, n: int, pair_a, pair_b, box_a, box_b):
+    def _ssim_pairs_views(self, what: str, pixels, offsets, widths, heights, channels: int, pair_a, pair_b, box_a=None, box_b=None,
+                          orient_b=None, plain: bool = False):
+        """The four pair calls: ``pixels`` a host array or a base address, ``offsets`` from it.  One ``ke_ssim_pairs_viewed`` call
+        (``plain``: ``ke_ssim_pairs``, which has neither boxes nor orientations) -> (float64 scores, int32 statuses)."""
         pa = np.ascontiguousarray(pair_a, dtype=np.int64)
         pb = np.ascontiguousarray(pair_b, dtype=np.int64)
         boxes = []
         for b in (box_a, box_b):
             b = None if b is None else np.ascontiguousarray(b, dtype=np.int32).reshape(-1, 4)
             if b is not None and len(b) != len(pa):
-                raise ValueError("ssim_pairs_boxed: a box array holds one box per pair")
+                raise ValueError(f"{what}: a box array holds one box per pair")
             boxes.append(b)
-        if len(pb) != len(pa):
-            raise ValueError("ssim_pairs_boxed: the pair arrays differ in length")
+        ob = None if orient_b is None else np.ascontiguousarray(orient_b, dtype=np.int32)
+        if len(pb) != len(pa) or (ob is not None and len(ob) != len(pa)):
+            raise ValueError(f"{what}: the pair arrays differ in length")
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        widths = np.ascontiguousarray(widths, np.int32)
+        heights = np.ascontiguousarray(heights, np.int32)
         out = np.empty(len(pa), np.float64)
         status = np.empty(len(pa), np.int32)
+        head = (self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights), int(channels), len(widths), _addr(pa), _addr(pb))
+        tail = (len(pa), _addr(out), _addr(status))
         with self._lock:
-            self._check(self._lib.ke_ssim_pairs_boxed(self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights), int(channels), n,
-                                                      _addr(pa), _addr(pb), _addr(boxes[0]), _addr(boxes[1]), len(pa), _addr(out),
-                                                      _addr(status)), "ke_ssim_pairs_boxed")
+            if plain:
+                self._check(self._lib.ke_ssim_pairs(*head, *tail), "ke_ssim_pairs")
+            else:
+                self._check(self._lib.ke_ssim_pairs_viewed(*head, _addr(boxes[0]), _addr(boxes[1]), _addr(ob), *tail), "ke_ssim_pairs_viewed")
         return out, status
+
+    def ssim_pairs(self, images: Sequence[np.ndarray], pair_a, pair_b):
+        """src/dup/refine.py:44-52 for pairs of images of any sizes (one channel count): common size, ImageOps.fit + BICUBIC
+        of both, SSIM.  Returns (float64 scores, NaN where the status is not 0; int32 statuses KE_PAIR_*)."""
+        return self._ssim_pairs_views("ssim_pairs", *_pack_images(images), pair_a, pair_b, plain=True)
+
+    def ssim_pairs_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b):
+        """ssim_pairs for images that already lie in device memory, each at its own address (decoded there, or uploaded)."""
+        return self._ssim_pairs_views("ssim_pairs", *_base_and_offsets(pointers), widths, heights, channels, pair_a, pair_b, plain=True)
+
+    def ssim_pairs_turned(self, images: Sequence[np.ndarray], pair_a, pair_b, orient_b):
+        """ssim_pairs with image ``pair_b[k]`` under orientation ``orient_b[k]`` (0..7, turned.ORIENTATIONS; None: all 0)."""
+        return self._ssim_pairs_views("ssim_pairs_turned", *_pack_images(images), pair_a, pair_b, None, None, orient_b)
+
+    def ssim_pairs_turned_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b, orient_b):
+        """ssim_pairs_on_device with image ``pair_b[k]`` under orientation ``orient_b[k]`` (0..7, turned.ORIENTATIONS): each
+        distinct (image, orientation != 0) is turned once on the device (ke_turn_luma) before the fit."""
+        return self._ssim_pairs_views("ssim_pairs_turned", *_base_and_offsets(pointers), widths, heights, channels, pair_a, pair_b, None, None,
+                                      orient_b)
 
     def ssim_pairs_boxed(self, images: Sequence[np.ndarray], pair_a, pair_b, box_a, box_b):
         """ssim_pairs on boxes of the images (ke_ssim_pairs_boxed): pair k is box ``box_a[k]`` of image ``pair_a[k]`` against box
         ``box_b[k]`` of image ``pair_b[k]``, boxes as (x0, y0, x1, y1).  ``None``, four zeros and (0, 0, w, h) mean the image as it
         lies.  The scores are those of ``ssim_pairs`` on images that hold the crops, bit for bit."""
-        flat, offsets, widths, heights, ch = _pack_images(images)
-        return self._ssim_pairs_boxed(flat, offsets, widths, heights, ch, len(images), pair_a, pair_b, box_a, box_b)
+        return self._ssim_pairs_views("ssim_pairs_boxed", *_pack_images(images), pair_a, pair_b, box_a, box_b)
 
     def ssim_pairs_boxed_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b, box_a, box_b):
         """ssim_pairs_on_device on boxes of the images: each distinct (image, box) is cut out once on the device, luma only
         (ke_crop_luma), before the fit."""
-        ptrs = np.asarray(pointers, np.uint64)
-        base = int(ptrs.min())
-        offsets = np.ascontiguousarray(ptrs - np.uint64(base))
-        widths = np.ascontiguousarray(widths, np.int32)
-        heights = np.ascontiguousarray(heights, np.int32)
-        return self._ssim_pairs_boxed(base, offsets, widths, heights, channels, len(ptrs), pair_a, pair_b, box_a, box_b)
-
-    def _ssim_pairs_viewed(self, pixels, offsets, widths, heights, channels: int, n: int, pair_a, pair_b, box_a, box_b, orient_b):
-        pa = np.ascontiguousarray(pair_a, dtype=np.int64)
-        pb = np.ascontiguousarray(pair_b, dtype=np.int64)
-        boxes = []
-        for b in (box_a, box_b):
-            b = None if b is None else np.ascontiguousarray(b, dtype=np.int32).reshape(-1, 4)
-            if b is not None and len(b) != len(pa):
-                raise ValueError("ssim_pairs_viewed: a box array holds one box per pair")
-            boxes.append(b)
-        ob = None if orient_b is None else np.ascontiguousarray(orient_b, dtype=np.int32)
-        if len(pb) != len(pa) or (ob is not None and len(ob) != len(pa)):
-            raise ValueError("ssim_pairs_viewed: the pair arrays differ in length")
-        out = np.empty(len(pa), np.float64)
-        status = np.empty(len(pa), np.int32)
-        with self._lock:
-            self._check(self._lib.ke_ssim_pairs_viewed(self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights), int(channels), n,
-                                                       _addr(pa), _addr(pb), _addr(boxes[0]), _addr(boxes[1]), _addr(ob), len(pa), _addr(out),
-                                                       _addr(status)), "ke_ssim_pairs_viewed")
-        return out, status
+        return self._ssim_pairs_views("ssim_pairs_boxed", *_base_and_offsets(pointers), widths, heights, channels, pair_a, pair_b, box_a, box_b)
 
     def ssim_pairs_viewed(self, images: Sequence[np.ndarray], pair_a, pair_b, box_a, box_b, orient_b):
         """ssim_pairs on views of the images (ke_ssim_pairs_viewed): pair k is box ``box_a[k]`` of image ``pair_a[k]`` against
         orientation ``orient_b[k]`` (0..7, turned.ORIENTATIONS; None: all 0) of box ``box_b[k]`` of image ``pair_b[k]`` -- crop,
         then turn, then fit.  Boxes as in ``ssim_pairs_boxed``.  The scores are those of ``ssim_pairs`` on images that hold
         ``turn(k, crop)``, bit for bit."""
-        flat, offsets, widths, heights, ch = _pack_images(images)
-        return self._ssim_pairs_viewed(flat, offsets, widths, heights, ch, len(images), pair_a, pair_b, box_a, box_b, orient_b)
+        return self._ssim_pairs_views("ssim_pairs_viewed", *_pack_images(images), pair_a, pair_b, box_a, box_b, orient_b)
 
     def ssim_pairs_viewed_on_device(self, pointers, widths, heights, channels: int, pair_a, pair_b, box_a, box_b, orient_b):
         """ssim_pairs_on_device on views of the images: each distinct (image, box, orientation) is made once on the device, luma
         only (ke_crop_luma, ke_turn_luma or ke_crop_turn_luma), before the fit."""
-        ptrs = np.asarray(pointers, np.uint64)
-        base = int(ptrs.min())
-        offsets = np.ascontiguousarray(ptrs - np.uint64(base))
-        widths = np.ascontiguousarray(widths, np.int32)
-        heights = np.ascontiguousarray(heights, np.int32)
-        return self._ssim_pairs_viewed(base, offsets, widths, heights, channels, len(ptrs), pair_a, pair_b, box_a, box_b, orient_b)
+        return self._ssim_pairs_views("ssim_pairs_viewed", *_base_and_offsets(pointers), widths, heights, channels, pair_a, pair_b, box_a,
+                                      box_b, orient_b)
+
+    def _view_luma(self, what: str, src: int, src_offsets, widths, heights, channels, boxes, orientations, dst: int, dst_offsets) -> None:
+        """turn_luma (``boxes`` None: ke_turn_luma) and crop_turn_luma (ke_crop_turn_luma)."""
+        so, do = np.ascontiguousarray(src_offsets, dtype=np.uint64), np.ascontiguousarray(dst_offsets, dtype=np.uint64)
+        w, h = np.ascontiguousarray(widths, dtype=np.int32), np.ascontiguousarray(heights, dtype=np.int32)
+        c, o = np.ascontiguousarray(channels, dtype=np.int32), np.ascontiguousarray(orientations, dtype=np.int32)
+        b = None if boxes is None else np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        if not len(so) == len(do) == len(w) == len(h) == len(c) == len(o) == (len(so) if b is None else len(b)):
+            raise ValueError(f"{what}: the arrays differ in length")
+        head, tail = (self._h, src, _addr(so), _addr(w), _addr(h), _addr(c)), (_addr(o), len(so), dst, _addr(do))
+        with self._lock:
+            if b is None:
+                self._check(self._lib.ke_turn_luma(*head, *tail), "ke_turn_luma")
+            else:
+                self._check(self._lib.ke_crop_turn_luma(*head, _addr(b), *tail), "ke_crop_turn_luma")
 
     def crop_turn_luma(self, src: int, src_offsets, widths, heights, channels, boxes, orientations, dst: int, dst_offsets) -> None:
         """The ``convert("L")`` luma of orientation ``orientations[i]`` (0..7, turned.ORIENTATIONS) of box ``boxes[i]`` of image i of
         a device buffer -> ``dst + dst_offsets[i]`` of the caller's device buffer, one byte per pixel, rows packed, the box's
         sides swapped for k & 4 (ke_crop_turn_luma)."""
-        so, do = np.ascontiguousarray(src_offsets, dtype=np.uint64), np.ascontiguousarray(dst_offsets, dtype=np.uint64)
-        w, h = np.ascontiguousarray(widths, dtype=np.int32), np.ascontiguousarray(heights, dtype=np.int32)
-        c, o = np.ascontiguousarray(channels, dtype=np.int32), np.ascontiguousarray(orientations, dtype=np.int32)
-        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
-        if not len(so) == len(do) == len(w) == len(h) == len(c) == len(o) == len(b):
-            raise ValueError("crop_turn_luma: the arrays differ in length")
-        with self._lock:
-            self._check(self._lib.ke_crop_turn_luma(self._h, src, _addr(so), _addr(w), _addr(h), _addr(c), _addr(b), _addr(o), len(so), dst,
-                                                    _addr(do)), "ke_crop_turn_luma")
+        self._view_luma("crop_turn_luma", src, src_offsets, widths, heights, channels, boxes, orientations, dst, dst_offsets)
 
     def turn_luma(self, src: int, src_offsets, widths, heights, channels, orientations, dst: int, dst_offsets) -> None:
         """Images on the device (``widths[i]`` x ``heights[i]``, 1, 3 or 4 channels, at ``src + src_offsets[i]``) -> the luma plane
         of orientation ``orientations[i]`` (0..7, turned.ORIENTATIONS) of each, one byte per pixel, rows packed, at
         ``dst + dst_offsets[i]`` of the caller's device buffer (ke_turn_luma): ``heights[i]`` x ``widths[i]`` for k & 4."""
-        so, do = np.ascontiguousarray(src_offsets, dtype=np.uint64), np.ascontiguousarray(dst_offsets, dtype=np.uint64)
-        w, h = np.ascontiguousarray(widths, dtype=np.int32), np.ascontiguousarray(heights, dtype=np.int32)
-        c, o = np.ascontiguousarray(channels, dtype=np.int32), np.ascontiguousarray(orientations, dtype=np.int32)
-        if not len(so) == len(do) == len(w) == len(h) == len(c) == len(o):
-            raise ValueError("turn_luma: the arrays differ in length")
-        with self._lock:
-            self._check(self._lib.ke_turn_luma(self._h, src, _addr(so), _addr(w), _addr(h), _addr(c), _addr(o), len(so), dst, _addr(do)),
-                        "ke_turn_luma")
+        self._view_luma("turn_luma", src, src_offsets, widths, heights, channels, None, orientations, dst, dst_offsets)
 
     # -- shipped refine stage -------------------------------------------------------------------
     def resize_luma_uniform(self, pixels, n: int, width: int, height: int, channels: int, out_w: int, out_h: int,

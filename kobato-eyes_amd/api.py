@@ -210,21 +210,41 @@ def _turned_scan(files: Iterable, *, hamming_threshold, size_ratio, band_bits, b
     return (assemble_clusters(candidates, edges) if edges else []), matches, set(plain)
 
 
-def _turned_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, device: int) -> tuple:
-    """The plain candidate edges and the turned matches that pass the SSIM re-check, from one refine_turned_pairs call: a
-    plain edge is scored as the pixels lie (orientation 0), a match as file a against its orientation of file b.  A
-    surviving match carries its score; a pair whose files cannot be read is dropped, as _ssim_kept drops it."""
+def _views_ssim_kept(refine_name: str, tail: tuple, plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float,
+                     device: int, **keywords) -> tuple:
+    """The plain candidate edges and the matches that pass the SSIM re-check, from one call of ``refine.<refine_name>``: a row
+    is the two ids and paths and then the match's ``tail`` attributes; a plain edge is scored as the pixels lie (every flag
+    False, orientation 0).  A surviving match carries its score; a pair whose files cannot be read is dropped, as _ssim_kept
+    drops it."""
     from dataclasses import replace
 
     by_id = {f.file_id: f for f in candidates}
     keys = list(plain)
-    rows = [(plain[k].file_id_a, plain[k].file_id_b, by_id[plain[k].file_id_a].path, by_id[plain[k].file_id_b].path, 0) for k in keys]
-    rows += [(m.file_id_a, m.file_id_b, by_id[m.file_id_a].path, by_id[m.file_id_b].path, m.orientation) for m in matches]
-    refined = _refine.refine_turned_pairs(rows, thresholds=_refine.RefinementThresholds(ssim=ssim_threshold), device=device)
+    as_it_lies = tuple(0 if name == "orientation" else False for name in tail)
+    rows = [(plain[k].file_id_a, plain[k].file_id_b, by_id[plain[k].file_id_a].path, by_id[plain[k].file_id_b].path) + as_it_lies for k in keys]
+    rows += [(m.file_id_a, m.file_id_b, by_id[m.file_id_a].path, by_id[m.file_id_b].path) + tuple(getattr(m, name) for name in tail)
+             for m in matches]
+    refined = getattr(_refine, refine_name)(rows, thresholds=_refine.RefinementThresholds(ssim=ssim_threshold), device=device, **keywords)
     passed = [r is not None and r.is_duplicate for r in refined]
     kept_plain = {k: plain[k] for k, yes in zip(keys, passed) if yes}
     kept_matches = [replace(m, ssim=r.ssim) for m, r, yes in zip(matches, refined[len(keys):], passed[len(keys):]) if yes]
     return kept_plain, kept_matches
+
+
+def _turned_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, device: int) -> tuple:
+    return _views_ssim_kept("refine_turned_pairs", ("orientation",), plain, matches, candidates, ssim_threshold, device)
+
+
+def _trimmed_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, tolerance: int,
+                       device: int) -> tuple:
+    return _views_ssim_kept("refine_trimmed_pairs", ("trimmed_a", "trimmed_b"), plain, matches, candidates, ssim_threshold, device,
+                            tolerance=tolerance)
+
+
+def _turned_trimmed_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, tolerance: int,
+                              device: int) -> tuple:
+    return _views_ssim_kept("refine_turned_trimmed_pairs", ("trimmed_a", "trimmed_b", "orientation"), plain, matches, candidates,
+                            ssim_threshold, device, tolerance=tolerance)
 
 
 def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, band_bits: int = 16,
@@ -249,26 +269,6 @@ def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_
     clusters, matches, _ = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
                                         band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)
     return clusters, matches
-
-
-def _trimmed_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, tolerance: int,
-                       device: int) -> tuple:
-    """The plain candidate edges and the trimmed matches that pass the SSIM re-check, from one refine_trimmed_pairs call: a
-    plain edge is scored as the pixels lie (neither side trimmed), a match with its ``trimmed_a`` / ``trimmed_b``.  A
-    surviving match carries its score; a pair whose files cannot be read is dropped, as _ssim_kept drops it."""
-    from dataclasses import replace
-
-    by_id = {f.file_id: f for f in candidates}
-    keys = list(plain)
-    rows = [(plain[k].file_id_a, plain[k].file_id_b, by_id[plain[k].file_id_a].path, by_id[plain[k].file_id_b].path, False, False)
-            for k in keys]
-    rows += [(m.file_id_a, m.file_id_b, by_id[m.file_id_a].path, by_id[m.file_id_b].path, m.trimmed_a, m.trimmed_b) for m in matches]
-    refined = _refine.refine_trimmed_pairs(rows, tolerance=tolerance, thresholds=_refine.RefinementThresholds(ssim=ssim_threshold),
-                                           device=device)
-    passed = [r is not None and r.is_duplicate for r in refined]
-    kept_plain = {k: plain[k] for k, yes in zip(keys, passed) if yes}
-    kept_matches = [replace(m, ssim=r.ssim) for m, r, yes in zip(matches, refined[len(keys):], passed[len(keys):]) if yes]
-    return kept_plain, kept_matches
 
 
 def _trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, band_bits, band_count, device, ssim_threshold=None):
@@ -316,27 +316,6 @@ def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tole
     hashes, borders of two colours or gradients, and dHash.  Trimmed and turned together is ``find_turned_trimmed_duplicates``'."""
     return _trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio, band_bits=band_bits,
                          band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)
-
-
-def _turned_trimmed_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, tolerance: int,
-                              device: int) -> tuple:
-    """The plain candidate edges and the matches that pass the SSIM re-check, from one refine_turned_trimmed_pairs call: a plain
-    edge goes as (False, False, 0), a match with its flags and its orientation.  A surviving match carries its score; a pair
-    whose files cannot be read is dropped, as _ssim_kept drops it."""
-    from dataclasses import replace
-
-    by_id = {f.file_id: f for f in candidates}
-    keys = list(plain)
-    rows = [(plain[k].file_id_a, plain[k].file_id_b, by_id[plain[k].file_id_a].path, by_id[plain[k].file_id_b].path, False, False, 0)
-            for k in keys]
-    rows += [(m.file_id_a, m.file_id_b, by_id[m.file_id_a].path, by_id[m.file_id_b].path, m.trimmed_a, m.trimmed_b, m.orientation)
-             for m in matches]
-    refined = _refine.refine_turned_trimmed_pairs(rows, tolerance=tolerance, thresholds=_refine.RefinementThresholds(ssim=ssim_threshold),
-                                                  device=device)
-    passed = [r is not None and r.is_duplicate for r in refined]
-    kept_plain = {k: plain[k] for k, yes in zip(keys, passed) if yes}
-    kept_matches = [replace(m, ssim=r.ssim) for m, r, yes in zip(matches, refined[len(keys):], passed[len(keys):]) if yes]
-    return kept_plain, kept_matches
 
 
 def _turned_trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, band_bits, band_count, device, ssim_threshold=None):

@@ -1026,471 +1026,113 @@ static int fit_box(int width, int height, int out_w, int out_h, float box[4]) {
     return (box[0] < 0 || box[1] < 0 || box[2] > width || box[3] > height) ? KE_EINVAL : KE_OK;
 }
 
-KE_API int ke_ssim_pairs(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
-                         int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
-                         double *ssim_out, int32_t *status_out) {
+// ---- the four pair calls: one plan (ke_view_plan.h), one sequence -----------------------------------
+namespace {
+
+// per common size: the fit of every source that a pair of that size uses, one launch per group, and one SSIM launch.
+// from[made]: the device buffer of the sources that are made or not -- the scratch planes, the pixels at `channels`.
+int ssim_over_planes(ke_ctx *ctx, const KeViewPlan &plan, const uint8_t *const from[2], int channels, double *ssim_out) {
+    for (const KeSizePlan &sp : plan.sizes) {
+        const size_t plane = (size_t)sp.w * sp.h;
+        void *planes, *meta, *aux;
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)sp.planes * plane, &planes));
+        KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)sp.planes * 8, &meta));
+        std::vector<uint64_t> meta_h((size_t)sp.planes);
+        for (const KeFitGroup &g : sp.groups)
+            for (size_t j = 0; j < g.srcs.size(); ++j) meta_h[(size_t)g.base + j] = plan.srcs[(size_t)g.srcs[j]].off;
+        KE_HIP(ctx, hipMemcpyAsync(meta, meta_h.data(), (size_t)sp.planes * 8, hipMemcpyHostToDevice, ctx->stream));
+        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // meta_h is a local
+        for (const KeFitGroup &g : sp.groups) {
+            const int ch = g.made ? 1 : channels;
+            const int64_t m = (int64_t)g.srcs.size();
+            KeHashGroup hg{from[g.made], (const uint64_t *)meta + g.base, (uint64_t)g.w * g.h * ch, nullptr, m, g.w, g.h, ch};
+            hg.misaligned = ke_any_misaligned((uintptr_t)from[g.made], meta_h.data() + g.base, m);
+            float box[4];
+            if (fit_box(g.w, g.h, sp.w, sp.h, box) != KE_OK) return ke_fail(ctx, KE_EINVAL, "crop box outside the image");
+            KE_TRY(ke_launch_resize_group(ctx, hg, sp.w, sp.h, KE_FILTER_BICUBIC, (uint8_t *)planes + (size_t)g.base * plane, box));
+        }
+        // pair indices into the plane stack, then one SSIM launch
+        const int64_t np = (int64_t)sp.pairs.size();
+        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, (size_t)np * 24, &aux));
+        KE_HIP(ctx, hipMemcpyAsync(aux, sp.idx.data(), (size_t)2 * np * 8, hipMemcpyHostToDevice, ctx->stream));
+        double *d_out = (double *)((uint8_t *)aux + (size_t)2 * np * 8);
+        KE_TRY(ke_launch_ssim(ctx, (const uint8_t *)planes, sp.w, sp.h, 1, (const int64_t *)aux, (const int64_t *)aux + np, np, d_out));
+        std::vector<double> scores((size_t)np);
+        KE_HIP(ctx, hipMemcpyAsync(scores.data(), d_out, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
+        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // scores is a local
+        for (int64_t j = 0; j < np; ++j) ssim_out[sp.pairs[(size_t)j]] = scores[(size_t)j];
+    }
+    return KE_OK;
+}
+
+// Every view the pairs name is made once, one launch per kind of view -- a box as it lies (ke_crop_luma), a whole picture turned,
+// a box turned (both ke_turn.hip) -- into one scratch, then ssim_over_planes.  Crop, then turn, then fit: the resampler clips its
+// taps to the source it is given, so a box folded into the fit's resample box would let the margin bleed into the crop's edge.
+int ssim_pairs_viewed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights, int32_t channels,
+                      int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *box_a, const int32_t *box_b,
+                      const int32_t *orient_b, int64_t n_pairs, double *ssim_out, int32_t *status_out) {
     if (!ctx) return KE_EINVAL;
     if (n_pairs < 0 || n_images < 0) return ke_fail(ctx, KE_EINVAL, "negative count");
     if (n_pairs == 0) return KE_OK;
     if (!pixels || !widths || !heights || !pair_a || !pair_b || !ssim_out) return ke_fail(ctx, KE_EINVAL, "NULL argument");
     if (channels != 1 && channels != 3 && channels != 4) return ke_fail(ctx, KE_EINVAL, "channels must be 1, 3 or 4");
     for (const void *p : {(const void *)offsets, (const void *)widths, (const void *)heights, (const void *)pair_a, (const void *)pair_b,
-                          (const void *)ssim_out, (const void *)status_out})
-        if (p && ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "offsets/widths/heights/pairs/outputs are host arrays");
+                          (const void *)box_a, (const void *)box_b, (const void *)orient_b, (const void *)ssim_out, (const void *)status_out})
+        if (p && ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "every array but the pixels is a host array");
+    const KeViewPlan plan = ke_plan_view_pairs(offsets, widths, heights, channels, n_images, pair_a, pair_b, n_pairs, box_a, box_b, orient_b,
+                                               ssim_out, status_out);
+    if (plan.bad_pair >= 0) return ke_fail(ctx, KE_EINVAL, "%s", plan.error.c_str());
     KE_HIP(ctx, hipSetDevice(ctx->device));
     trim_coeff_cache(ctx);
-    const double nan = std::nan("");
-    // byte offsets; classify the pairs
-    std::vector<uint64_t> off((size_t)n_images);
-    uint64_t run = 0;
-    for (int64_t i = 0; i < n_images; ++i) {
-        off[i] = offsets ? offsets[i] : run;
-        if (widths[i] > 0 && heights[i] > 0) run += (uint64_t)widths[i] * heights[i] * channels;
-    }
-    uint64_t total_bytes = 0;
-    for (int64_t i = 0; i < n_images; ++i)
-        if (widths[i] > 0 && heights[i] > 0) total_bytes = std::max<uint64_t>(total_bytes, off[i] + (uint64_t)widths[i] * heights[i] * channels);
-    std::map<std::pair<int, int>, std::vector<int64_t>> by_size;        // common (w, h) -> pairs
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        ssim_out[k] = nan;
-        const int64_t ia = pair_a[k], ib = pair_b[k];
-        const bool ok = ia >= 0 && ia < n_images && ib >= 0 && ib < n_images && widths[ia] > 0 && heights[ia] > 0 && widths[ib] > 0 &&
-                        heights[ib] > 0;
-        if (!ok) { if (status_out) status_out[k] = KE_PAIR_BAD_IMAGE; continue; }
-        const int w = std::min(widths[ia], widths[ib]), h = std::min(heights[ia], heights[ib]);   // src/dup/refine.py:45-47
-        if (w < 7 || h < 7) { if (status_out) status_out[k] = KE_PAIR_TOO_SMALL; continue; }
-        if (status_out) status_out[k] = KE_PAIR_OK;
-        by_size[{w, h}].push_back(k);
-    }
-    if (by_size.empty()) return KE_OK;
+    if (plan.sizes.empty()) return KE_OK;
     const void *d_px;
-    KE_TRY(ke_to_device(ctx, pixels, (size_t)total_bytes, KE_BUF_PIXELS, &d_px));
+    KE_TRY(ke_to_device(ctx, pixels, (size_t)plan.total_bytes, KE_BUF_PIXELS, &d_px));
+    const uint8_t *from[2] = {(const uint8_t *)d_px, nullptr};
     ke_time_begin(ctx, KE_T_SSIM);
-    for (auto &kv : by_size) {
-        const int w = kv.first.first, h = kv.first.second;
-        const std::vector<int64_t> &ks = kv.second;
-        // plane stack of this common size: the images of one source size sit next to each other, so a fit launch writes
-        // its whole group straight into place
-        std::map<std::pair<int, int>, std::vector<int64_t>> groups;     // source (w, h) -> images, first use order
-        std::map<int64_t, int64_t> slot;                                 // image -> position inside its group
-        for (int64_t k : ks)
-            for (int64_t i : {pair_a[k], pair_b[k]})
-                if (!slot.count(i)) {
-                    auto &g = groups[{widths[i], heights[i]}];
-                    slot[i] = (int64_t)g.size();
-                    g.push_back(i);
-                }
-        int64_t base = 0;
-        std::map<std::pair<int, int>, int64_t> group_base;
-        for (auto &g : groups) { group_base[g.first] = base; base += (int64_t)g.second.size(); }
-        const size_t plane = (size_t)w * h;
-        void *planes, *meta, *aux;
-        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)base * plane, &planes));
-        KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)base * 8, &meta));
-        std::vector<uint64_t> meta_h((size_t)base);
-        for (auto &g : groups)
-            for (size_t j = 0; j < g.second.size(); ++j) meta_h[(size_t)group_base[g.first] + j] = off[g.second[j]];
-        KE_HIP(ctx, hipMemcpyAsync(meta, meta_h.data(), (size_t)base * 8, hipMemcpyHostToDevice, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // meta_h is a local
-        for (auto &g : groups) {
-            const int sw = g.first.first, sh = g.first.second;
-            const int64_t gb = group_base[g.first], m = (int64_t)g.second.size();
-            KeHashGroup hg{(const uint8_t *)d_px, (const uint64_t *)meta + gb, (uint64_t)sw * sh * channels, nullptr, m, sw, sh, channels};
-            hg.misaligned = ke_any_misaligned((uintptr_t)d_px, meta_h.data() + gb, m);
-            float box[4];
-            if (fit_box(sw, sh, w, h, box) != KE_OK) return ke_fail(ctx, KE_EINVAL, "crop box outside the image");
-            KE_TRY(ke_launch_resize_group(ctx, hg, w, h, KE_FILTER_BICUBIC, (uint8_t *)planes + (size_t)gb * plane, box));
-        }
-        // pair indices into the plane stack, then one SSIM launch
-        const int64_t np = (int64_t)ks.size();
-        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, (size_t)np * 24, &aux));
-        std::vector<int64_t> idx((size_t)2 * np);
-        for (int64_t j = 0; j < np; ++j) {
-            const int64_t ia = pair_a[ks[j]], ib = pair_b[ks[j]];
-            idx[j] = group_base[{widths[ia], heights[ia]}] + slot[ia];
-            idx[np + j] = group_base[{widths[ib], heights[ib]}] + slot[ib];
-        }
-        KE_HIP(ctx, hipMemcpyAsync(aux, idx.data(), (size_t)2 * np * 8, hipMemcpyHostToDevice, ctx->stream));
-        double *d_out = (double *)((uint8_t *)aux + (size_t)2 * np * 8);
-        KE_TRY(ke_launch_ssim(ctx, (const uint8_t *)planes, w, h, 1, (const int64_t *)aux, (const int64_t *)aux + np, np, d_out));
-        std::vector<double> scores((size_t)np);
-        KE_HIP(ctx, hipMemcpyAsync(scores.data(), d_out, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int64_t j = 0; j < np; ++j) ssim_out[ks[j]] = scores[j];
+    if (plan.made_bytes) {
+        void *d_made;
+        KE_TRY(ke_reserve(ctx, KE_BUF_VIEW_LUMA, (size_t)plan.made_bytes, &d_made));
+        KE_TRY(ke_launch_crop_luma(ctx, from[0], plan.crops.data(), (int64_t)plan.crops.size(), (uint8_t *)d_made));
+        KE_TRY(ke_launch_view_luma(ctx, from[0], plan.turns.data(), (int64_t)plan.turns.size(), (uint8_t *)d_made, -1));
+        KE_TRY(ke_launch_view_luma(ctx, from[0], plan.views.data(), (int64_t)plan.views.size(), (uint8_t *)d_made, KE_T_VIEW_LUMA));
+        from[1] = (const uint8_t *)d_made;
     }
+    KE_TRY(ssim_over_planes(ctx, plan, from, channels, ssim_out));
     ke_time_end(ctx, KE_T_SSIM);
-    return KE_OK;
-}
-
-// ---- ke_ssim_pairs over "plane sources" ----------------------------------------------------------
-// A plane source is what the fit step reads: an image as it lies in `pixels`, or a one-channel plane the call made of an image
-// in scratch -- the turned luma of an (image, orientation) in KE_BUF_TURN_LUMA, the luma of an (image, box) in
-// KE_BUF_TRIM_LUMA.  Everything from the fit on is ke_ssim_pairs' sequence over plane sources instead of images.
-namespace {
-
-struct PlaneSrc {
-    int made;            // 0: in the call's pixels, at the call's channel count; 1: in the call's scratch, one channel
-    uint64_t off;        // bytes into that buffer
-    int32_t w, h;
-};
-
-struct PlanePairs {
-    const uint8_t *buf[2] = {nullptr, nullptr};                         // device: the pixels, the scratch planes
-    int channels = 0;                                                   // of buf[0]
-    std::vector<PlaneSrc> srcs;
-    std::vector<int64_t> a, b;                                          // per pair: its two sources
-    std::map<std::pair<int, int>, std::vector<int64_t>> by_size;        // common (w, h) -> the pairs that are scored
-};
-
-// offsets (packed back to back where NULL) and the bytes the images span
-uint64_t image_offsets(const uint64_t *offsets, const int32_t *widths, const int32_t *heights, int channels, int64_t n_images,
-                       std::vector<uint64_t> &off) {
-    off.resize((size_t)n_images);
-    uint64_t run = 0, total = 0;
-    for (int64_t i = 0; i < n_images; ++i) {
-        off[i] = offsets ? offsets[i] : run;
-        if (widths[i] > 0 && heights[i] > 0) {
-            run += (uint64_t)widths[i] * heights[i] * channels;
-            total = std::max<uint64_t>(total, off[i] + (uint64_t)widths[i] * heights[i] * channels);
-        }
-    }
-    return total;
-}
-
-// ke_ssim_pairs' statuses for pair k of views wa x ha and wb x hb (`ok`: both images exist); true where the pair is scored
-bool classify_pair(PlanePairs &pp, int64_t k, bool ok, int wa, int ha, int wb, int hb, double *ssim_out, int32_t *status_out) {
-    ssim_out[k] = std::nan("");
-    if (!ok) { if (status_out) status_out[k] = KE_PAIR_BAD_IMAGE; return false; }
-    const int w = std::min(wa, wb), h = std::min(ha, hb);               // src/dup/refine.py:45-47
-    if (w < 7 || h < 7) { if (status_out) status_out[k] = KE_PAIR_TOO_SMALL; return false; }
-    if (status_out) status_out[k] = KE_PAIR_OK;
-    pp.by_size[{w, h}].push_back(k);
-    return true;
-}
-
-// per common size: the fit of every source that a pair of that size uses, one launch per group, and one SSIM launch
-int ssim_over_planes(ke_ctx *ctx, const PlanePairs &pp, double *ssim_out) {
-    for (auto &kv : pp.by_size) {
-        const int w = kv.first.first, h = kv.first.second;
-        const std::vector<int64_t> &ks = kv.second;
-        // a fit launch reads one buffer at one channel count, so a group is (source w, source h, made or not)
-        using Key = std::tuple<int, int, int>;
-        auto key_of = [&](int64_t s) { return Key{pp.srcs[(size_t)s].w, pp.srcs[(size_t)s].h, pp.srcs[(size_t)s].made}; };
-        std::map<Key, std::vector<int64_t>> groups;                      // first use order inside a group
-        std::map<int64_t, int64_t> slot;                                 // plane source -> position inside its group
-        for (int64_t k : ks)
-            for (int64_t s : {pp.a[(size_t)k], pp.b[(size_t)k]})
-                if (!slot.count(s)) {
-                    auto &g = groups[key_of(s)];
-                    slot[s] = (int64_t)g.size();
-                    g.push_back(s);
-                }
-        int64_t base = 0;
-        std::map<Key, int64_t> group_base;
-        for (auto &g : groups) { group_base[g.first] = base; base += (int64_t)g.second.size(); }
-        const size_t plane = (size_t)w * h;
-        void *planes, *meta, *aux;
-        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_IN, (size_t)base * plane, &planes));
-        KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)base * 8, &meta));
-        std::vector<uint64_t> meta_h((size_t)base);
-        for (auto &g : groups)
-            for (size_t j = 0; j < g.second.size(); ++j) meta_h[(size_t)group_base[g.first] + j] = pp.srcs[(size_t)g.second[j]].off;
-        KE_HIP(ctx, hipMemcpyAsync(meta, meta_h.data(), (size_t)base * 8, hipMemcpyHostToDevice, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // meta_h is a local
-        for (auto &g : groups) {
-            const int sw = std::get<0>(g.first), sh = std::get<1>(g.first), made = std::get<2>(g.first);
-            const int ch = made ? 1 : pp.channels;
-            const uint8_t *from = pp.buf[made];
-            const int64_t gb = group_base[g.first], m = (int64_t)g.second.size();
-            KeHashGroup hg{from, (const uint64_t *)meta + gb, (uint64_t)sw * sh * ch, nullptr, m, sw, sh, ch};
-            hg.misaligned = ke_any_misaligned((uintptr_t)from, meta_h.data() + gb, m);
-            float box[4];
-            if (fit_box(sw, sh, w, h, box) != KE_OK) return ke_fail(ctx, KE_EINVAL, "crop box outside the image");
-            KE_TRY(ke_launch_resize_group(ctx, hg, w, h, KE_FILTER_BICUBIC, (uint8_t *)planes + (size_t)gb * plane, box));
-        }
-        // pair indices into the plane stack, then one SSIM launch
-        const int64_t np = (int64_t)ks.size();
-        KE_TRY(ke_reserve(ctx, KE_BUF_SSIM_AUX, (size_t)np * 24, &aux));
-        std::vector<int64_t> idx((size_t)2 * np);
-        for (int64_t j = 0; j < np; ++j) {
-            const int64_t a = pp.a[(size_t)ks[j]], b = pp.b[(size_t)ks[j]];
-            idx[j] = group_base[key_of(a)] + slot[a];
-            idx[np + j] = group_base[key_of(b)] + slot[b];
-        }
-        KE_HIP(ctx, hipMemcpyAsync(aux, idx.data(), (size_t)2 * np * 8, hipMemcpyHostToDevice, ctx->stream));
-        double *d_out = (double *)((uint8_t *)aux + (size_t)2 * np * 8);
-        KE_TRY(ke_launch_ssim(ctx, (const uint8_t *)planes, w, h, 1, (const int64_t *)aux, (const int64_t *)aux + np, np, d_out));
-        std::vector<double> scores((size_t)np);
-        KE_HIP(ctx, hipMemcpyAsync(scores.data(), d_out, (size_t)np * 8, hipMemcpyDeviceToHost, ctx->stream));
-        KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int64_t j = 0; j < np; ++j) ssim_out[ks[j]] = scores[j];
-    }
-    return KE_OK;
-}
-
-int check_pair_call(ke_ctx *ctx, const uint8_t *pixels, const int32_t *widths, const int32_t *heights, int32_t channels, int64_t n_images,
-                    const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs, const double *ssim_out,
-                    std::initializer_list<const void *> host_arrays) {
-    if (n_pairs < 0 || n_images < 0) return ke_fail(ctx, KE_EINVAL, "negative count");
-    if (n_pairs == 0) return KE_OK;
-    if (!pixels || !widths || !heights || !pair_a || !pair_b || !ssim_out) return ke_fail(ctx, KE_EINVAL, "NULL argument");
-    if (channels != 1 && channels != 3 && channels != 4) return ke_fail(ctx, KE_EINVAL, "channels must be 1, 3 or 4");
-    for (const void *p : host_arrays)
-        if (p && ke_is_device_ptr(p)) return ke_fail(ctx, KE_EINVAL, "every array but the pixels is a host array");
     return KE_OK;
 }
 
 }  // namespace
 
-// ke_ssim_pairs with image b of pair k under orientation orient_b[k]: its turned luma plane is a source of the turned size.
+KE_API int ke_ssim_pairs(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
+                         int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, int64_t n_pairs,
+                         double *ssim_out, int32_t *status_out) {
+    return ssim_pairs_viewed(ctx, pixels, offsets, widths, heights, channels, n_images, pair_a, pair_b, nullptr, nullptr, nullptr, n_pairs,
+                             ssim_out, status_out);
+}
+
+// ke_ssim_pairs with image b of pair k under orientation orient_b[k]
 KE_API int ke_ssim_pairs_turned(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
                                 int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *orient_b,
                                 int64_t n_pairs, double *ssim_out, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    KE_TRY(check_pair_call(ctx, pixels, widths, heights, channels, n_images, pair_a, pair_b, n_pairs, ssim_out,
-                           {offsets, widths, heights, pair_a, pair_b, orient_b, ssim_out, status_out}));
-    if (n_pairs == 0) return KE_OK;
-    if (orient_b)
-        for (int64_t k = 0; k < n_pairs; ++k)
-            if (orient_b[k] < 0 || orient_b[k] > 7) return ke_fail(ctx, KE_EINVAL, "pair %lld: orientation %d outside 0..7", (long long)k, orient_b[k]);
-    KE_HIP(ctx, hipSetDevice(ctx->device));
-    trim_coeff_cache(ctx);
-    std::vector<uint64_t> off;
-    const uint64_t total_bytes = image_offsets(offsets, widths, heights, channels, n_images, off);
-    PlanePairs pp;
-    pp.channels = channels;
-    pp.a.assign((size_t)n_pairs, -1);
-    pp.b.assign((size_t)n_pairs, -1);
-    std::map<std::pair<int64_t, int>, int64_t> src_of;                  // (image, orientation) -> its source
-    std::vector<KeTurnJob> jobs;
-    uint64_t turned_bytes = 0;
-    auto source = [&](int64_t i, int o) {
-        auto it = src_of.find({i, o});
-        if (it != src_of.end()) return it->second;
-        if (o == 0) {
-            pp.srcs.push_back(PlaneSrc{0, off[i], widths[i], heights[i]});
-        } else {
-            pp.srcs.push_back(PlaneSrc{1, turned_bytes, (o & 4) ? heights[i] : widths[i], (o & 4) ? widths[i] : heights[i]});
-            jobs.push_back(KeTurnJob{off[i], turned_bytes, widths[i], heights[i], channels, o});
-            turned_bytes += ((uint64_t)widths[i] * heights[i] + 255) & ~(uint64_t)255;        // every plane starts on a dword
-        }
-        return src_of[{i, o}] = (int64_t)pp.srcs.size() - 1;
-    };
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t ia = pair_a[k], ib = pair_b[k];
-        const bool ok = ia >= 0 && ia < n_images && ib >= 0 && ib < n_images && widths[ia] > 0 && heights[ia] > 0 && widths[ib] > 0 &&
-                        heights[ib] > 0;
-        const int o = orient_b ? orient_b[k] : 0;
-        const bool swap = ok && (o & 4);                                // b as it lies turned
-        if (!classify_pair(pp, k, ok, ok ? widths[ia] : 0, ok ? heights[ia] : 0, ok ? (swap ? heights[ib] : widths[ib]) : 0,
-                           ok ? (swap ? widths[ib] : heights[ib]) : 0, ssim_out, status_out))
-            continue;
-        pp.a[(size_t)k] = source(ia, 0);
-        pp.b[(size_t)k] = source(ib, o);
-    }
-    if (pp.by_size.empty()) return KE_OK;
-    const void *d_px;
-    KE_TRY(ke_to_device(ctx, pixels, (size_t)total_bytes, KE_BUF_PIXELS, &d_px));
-    pp.buf[0] = (const uint8_t *)d_px;
-    ke_time_begin(ctx, KE_T_SSIM);
-    if (!jobs.empty()) {
-        void *d_turned;
-        KE_TRY(ke_reserve(ctx, KE_BUF_TURN_LUMA, (size_t)turned_bytes, &d_turned));
-        KE_TRY(ke_launch_turn_luma(ctx, pp.buf[0], jobs.data(), (int64_t)jobs.size(), (uint8_t *)d_turned));
-        pp.buf[1] = (const uint8_t *)d_turned;
-    }
-    KE_TRY(ssim_over_planes(ctx, pp, ssim_out));
-    ke_time_end(ctx, KE_T_SSIM);
-    return KE_OK;
+    return ssim_pairs_viewed(ctx, pixels, offsets, widths, heights, channels, n_images, pair_a, pair_b, nullptr, nullptr, orient_b, n_pairs,
+                             ssim_out, status_out);
 }
 
-// ke_ssim_pairs on boxes of the images: the luma plane of every distinct (image, box) is cut out first (ke_crop_luma) and is a
-// source of the box's size.  Crop, then fit: the resampler clips its taps to the source it is given, so a box folded into the
-// fit's resample box would let the margin bleed into the crop's edge.
+// ke_ssim_pairs on boxes of the images
 KE_API int ke_ssim_pairs_boxed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
                                int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *box_a,
                                const int32_t *box_b, int64_t n_pairs, double *ssim_out, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    KE_TRY(check_pair_call(ctx, pixels, widths, heights, channels, n_images, pair_a, pair_b, n_pairs, ssim_out,
-                           {offsets, widths, heights, pair_a, pair_b, box_a, box_b, ssim_out, status_out}));
-    if (n_pairs == 0) return KE_OK;
-    auto image_ok = [&](int64_t i) { return i >= 0 && i < n_images && widths[i] > 0 && heights[i] > 0; };
-    // the view of pair k's side: the box, or four zeros for the image as it lies
-    struct View { int32_t x0, y0, x1, y1; };
-    auto view_of = [&](const int32_t *boxes, int64_t k, int64_t i) {
-        if (!boxes) return View{0, 0, 0, 0};
-        const int32_t *b = boxes + 4 * k;
-        if (b[0] == 0 && b[1] == 0 && ((b[2] == 0 && b[3] == 0) || (b[2] == widths[i] && b[3] == heights[i]))) return View{0, 0, 0, 0};
-        return View{b[0], b[1], b[2], b[3]};
-    };
-    auto cut = [](View v) { return v.x1 != 0 || v.y1 != 0 || v.x0 != 0 || v.y0 != 0; };
-    for (int64_t k = 0; k < n_pairs; ++k)
-        for (int side = 0; side < 2; ++side) {
-            const int64_t i = side ? pair_b[k] : pair_a[k];
-            if (!image_ok(i)) continue;                                 // KE_PAIR_BAD_IMAGE below
-            const View v = view_of(side ? box_b : box_a, k, i);
-            if (cut(v) && (v.x0 < 0 || v.y0 < 0 || v.x1 <= v.x0 || v.y1 <= v.y0 || v.x1 > widths[i] || v.y1 > heights[i]))
-                return ke_fail(ctx, KE_EINVAL, "pair %lld: box_%c (%d, %d, %d, %d) is empty or outside image %lld (%dx%d)", (long long)k,
-                               side ? 'b' : 'a', v.x0, v.y0, v.x1, v.y1, (long long)i, widths[i], heights[i]);
-        }
-    KE_HIP(ctx, hipSetDevice(ctx->device));
-    trim_coeff_cache(ctx);
-    std::vector<uint64_t> off;
-    const uint64_t total_bytes = image_offsets(offsets, widths, heights, channels, n_images, off);
-    PlanePairs pp;
-    pp.channels = channels;
-    pp.a.assign((size_t)n_pairs, -1);
-    pp.b.assign((size_t)n_pairs, -1);
-    std::map<std::tuple<int64_t, int32_t, int32_t, int32_t, int32_t>, int64_t> src_of;   // (image, view) -> its source
-    std::vector<KeCropLumaJob> jobs;
-    uint64_t crop_bytes = 0;
-    auto source = [&](int64_t i, View v) {
-        const auto key = std::make_tuple(i, v.x0, v.y0, v.x1, v.y1);
-        auto it = src_of.find(key);
-        if (it != src_of.end()) return it->second;
-        if (!cut(v)) {
-            pp.srcs.push_back(PlaneSrc{0, off[i], widths[i], heights[i]});
-        } else {
-            const int32_t bw = v.x1 - v.x0, bh = v.y1 - v.y0;
-            pp.srcs.push_back(PlaneSrc{1, crop_bytes, bw, bh});
-            jobs.push_back(KeCropLumaJob{off[i], crop_bytes, widths[i], heights[i], channels, v.x0, v.y0, bw, bh});
-            crop_bytes += ((uint64_t)bw * bh + 255) & ~(uint64_t)255;                         // every plane starts on a dword
-        }
-        return src_of[key] = (int64_t)pp.srcs.size() - 1;
-    };
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t ia = pair_a[k], ib = pair_b[k];
-        const bool ok = image_ok(ia) && image_ok(ib);
-        View va{0, 0, 0, 0}, vb{0, 0, 0, 0};
-        int wa = 0, ha = 0, wb = 0, hb = 0;
-        if (ok) {
-            va = view_of(box_a, k, ia);
-            vb = view_of(box_b, k, ib);
-            wa = cut(va) ? va.x1 - va.x0 : widths[ia];
-            ha = cut(va) ? va.y1 - va.y0 : heights[ia];
-            wb = cut(vb) ? vb.x1 - vb.x0 : widths[ib];
-            hb = cut(vb) ? vb.y1 - vb.y0 : heights[ib];
-        }
-        if (!classify_pair(pp, k, ok, wa, ha, wb, hb, ssim_out, status_out)) continue;
-        pp.a[(size_t)k] = source(ia, va);
-        pp.b[(size_t)k] = source(ib, vb);
-    }
-    if (pp.by_size.empty()) return KE_OK;
-    const void *d_px;
-    KE_TRY(ke_to_device(ctx, pixels, (size_t)total_bytes, KE_BUF_PIXELS, &d_px));
-    pp.buf[0] = (const uint8_t *)d_px;
-    ke_time_begin(ctx, KE_T_SSIM);
-    if (!jobs.empty()) {
-        void *d_crops;
-        KE_TRY(ke_reserve(ctx, KE_BUF_TRIM_LUMA, (size_t)crop_bytes, &d_crops));
-        KE_TRY(ke_launch_crop_luma(ctx, pp.buf[0], jobs.data(), (int64_t)jobs.size(), (uint8_t *)d_crops));
-        pp.buf[1] = (const uint8_t *)d_crops;
-    }
-    KE_TRY(ssim_over_planes(ctx, pp, ssim_out));
-    ke_time_end(ctx, KE_T_SSIM);
-    return KE_OK;
+    return ssim_pairs_viewed(ctx, pixels, offsets, widths, heights, channels, n_images, pair_a, pair_b, box_a, box_b, nullptr, n_pairs,
+                             ssim_out, status_out);
 }
 
-// ke_ssim_pairs_boxed with ke_ssim_pairs_turned's orient_b: pair k is box_a of image a against orientation orient_b[k] of box_b
-// of image b -- crop, then turn, then fit.  Every distinct (image, box, orientation) is a plane source; the made ones share one
-// scratch (KE_BUF_VIEW_LUMA) and each kind of view is made by one launch: a box as it lies by ke_crop_luma, a whole picture turned
-// by ke_turn_luma, a box turned by ke_crop_turn_luma.
+// box_a of image a against orientation orient_b[k] of box_b of image b
 KE_API int ke_ssim_pairs_viewed(ke_ctx *ctx, const uint8_t *pixels, const uint64_t *offsets, const int32_t *widths, const int32_t *heights,
                                 int32_t channels, int64_t n_images, const int64_t *pair_a, const int64_t *pair_b, const int32_t *box_a,
                                 const int32_t *box_b, const int32_t *orient_b, int64_t n_pairs, double *ssim_out, int32_t *status_out) {
-    if (!ctx) return KE_EINVAL;
-    KE_TRY(check_pair_call(ctx, pixels, widths, heights, channels, n_images, pair_a, pair_b, n_pairs, ssim_out,
-                           {offsets, widths, heights, pair_a, pair_b, box_a, box_b, orient_b, ssim_out, status_out}));
-    if (n_pairs == 0) return KE_OK;
-    auto image_ok = [&](int64_t i) { return i >= 0 && i < n_images && widths[i] > 0 && heights[i] > 0; };
-    // the view of pair k's side: the box (four zeros for the image as it lies) and the orientation
-    struct View { int32_t x0, y0, x1, y1, o; };
-    auto view_of = [&](const int32_t *boxes, int64_t k, int64_t i, int o) {
-        if (!boxes) return View{0, 0, 0, 0, o};
-        const int32_t *b = boxes + 4 * k;
-        if (b[0] == 0 && b[1] == 0 && ((b[2] == 0 && b[3] == 0) || (b[2] == widths[i] && b[3] == heights[i]))) return View{0, 0, 0, 0, o};
-        return View{b[0], b[1], b[2], b[3], o};
-    };
-    auto cut = [](View v) { return v.x1 != 0 || v.y1 != 0 || v.x0 != 0 || v.y0 != 0; };
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        if (orient_b && (orient_b[k] < 0 || orient_b[k] > 7))
-            return ke_fail(ctx, KE_EINVAL, "pair %lld: orientation %d outside 0..7", (long long)k, orient_b[k]);
-        for (int side = 0; side < 2; ++side) {
-            const int64_t i = side ? pair_b[k] : pair_a[k];
-            if (!image_ok(i)) continue;                                 // KE_PAIR_BAD_IMAGE below
-            const View v = view_of(side ? box_b : box_a, k, i, 0);
-            if (cut(v) && (v.x0 < 0 || v.y0 < 0 || v.x1 <= v.x0 || v.y1 <= v.y0 || v.x1 > widths[i] || v.y1 > heights[i]))
-                return ke_fail(ctx, KE_EINVAL, "pair %lld: box_%c (%d, %d, %d, %d) is empty or outside image %lld (%dx%d)", (long long)k,
-                               side ? 'b' : 'a', v.x0, v.y0, v.x1, v.y1, (long long)i, widths[i], heights[i]);
-        }
-    }
-    KE_HIP(ctx, hipSetDevice(ctx->device));
-    trim_coeff_cache(ctx);
-    std::vector<uint64_t> off;
-    const uint64_t total_bytes = image_offsets(offsets, widths, heights, channels, n_images, off);
-    PlanePairs pp;
-    pp.channels = channels;
-    pp.a.assign((size_t)n_pairs, -1);
-    pp.b.assign((size_t)n_pairs, -1);
-    std::map<std::tuple<int64_t, int32_t, int32_t, int32_t, int32_t, int32_t>, int64_t> src_of;   // (image, view) -> its source
-    std::vector<KeCropLumaJob> crops;
-    std::vector<KeTurnJob> turns;
-    std::vector<KeViewJob> views;
-    uint64_t made_bytes = 0;
-    // size of a view as the fit sees it
-    auto size_of = [&](int64_t i, View v, int *w, int *h) {
-        const int bw = cut(v) ? v.x1 - v.x0 : widths[i], bh = cut(v) ? v.y1 - v.y0 : heights[i];
-        *w = (v.o & 4) ? bh : bw;
-        *h = (v.o & 4) ? bw : bh;
-    };
-    auto source = [&](int64_t i, View v) {
-        const auto key = std::make_tuple(i, v.x0, v.y0, v.x1, v.y1, v.o);
-        auto it = src_of.find(key);
-        if (it != src_of.end()) return it->second;
-        int vw, vh;
-        size_of(i, v, &vw, &vh);
-        if (!cut(v) && v.o == 0) {
-            pp.srcs.push_back(PlaneSrc{0, off[i], widths[i], heights[i]});
-        } else {
-            pp.srcs.push_back(PlaneSrc{1, made_bytes, vw, vh});
-            if (v.o == 0) crops.push_back(KeCropLumaJob{off[i], made_bytes, widths[i], heights[i], channels, v.x0, v.y0, v.x1 - v.x0, v.y1 - v.y0});
-            else if (!cut(v)) turns.push_back(KeTurnJob{off[i], made_bytes, widths[i], heights[i], channels, v.o});
-            else views.push_back(KeViewJob{off[i], made_bytes, widths[i], heights[i], channels, v.o, v.x0, v.y0, v.x1 - v.x0, v.y1 - v.y0});
-            made_bytes += ((uint64_t)vw * vh + 255) & ~(uint64_t)255;                         // every plane starts on a dword
-        }
-        return src_of[key] = (int64_t)pp.srcs.size() - 1;
-    };
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t ia = pair_a[k], ib = pair_b[k];
-        const bool ok = image_ok(ia) && image_ok(ib);
-        View va{0, 0, 0, 0, 0}, vb{0, 0, 0, 0, 0};
-        int wa = 0, ha = 0, wb = 0, hb = 0;
-        if (ok) {
-            va = view_of(box_a, k, ia, 0);
-            vb = view_of(box_b, k, ib, orient_b ? orient_b[k] : 0);
-            size_of(ia, va, &wa, &ha);
-            size_of(ib, vb, &wb, &hb);
-        }
-        if (!classify_pair(pp, k, ok, wa, ha, wb, hb, ssim_out, status_out)) continue;
-        pp.a[(size_t)k] = source(ia, va);
-        pp.b[(size_t)k] = source(ib, vb);
-    }
-    if (pp.by_size.empty()) return KE_OK;
-    const void *d_px;
-    KE_TRY(ke_to_device(ctx, pixels, (size_t)total_bytes, KE_BUF_PIXELS, &d_px));
-    pp.buf[0] = (const uint8_t *)d_px;
-    ke_time_begin(ctx, KE_T_SSIM);
-    if (made_bytes) {
-        void *d_made;
-        KE_TRY(ke_reserve(ctx, KE_BUF_VIEW_LUMA, (size_t)made_bytes, &d_made));
-        KE_TRY(ke_launch_crop_luma(ctx, pp.buf[0], crops.data(), (int64_t)crops.size(), (uint8_t *)d_made));
-        KE_TRY(ke_launch_turn_luma(ctx, pp.buf[0], turns.data(), (int64_t)turns.size(), (uint8_t *)d_made));
-        KE_TRY(ke_launch_crop_turn_luma(ctx, pp.buf[0], views.data(), (int64_t)views.size(), (uint8_t *)d_made));
-        pp.buf[1] = (const uint8_t *)d_made;
-    }
-    KE_TRY(ssim_over_planes(ctx, pp, ssim_out));
-    ke_time_end(ctx, KE_T_SSIM);
-    return KE_OK;
+    return ssim_pairs_viewed(ctx, pixels, offsets, widths, heights, channels, n_images, pair_a, pair_b, box_a, box_b, orient_b, n_pairs,
+                             ssim_out, status_out);
 }
 
 // ---- shipped refine stage: thumbnails, tile aHash, pixel MAE --------------------------------------

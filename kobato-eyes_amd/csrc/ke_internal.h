@@ -14,6 +14,7 @@
 
 #include "../../include/keyes.h"
 #include "ke_coeffs.h"
+#include "ke_view_plan.h"
 
 #define KE_API extern "C" __attribute__((visibility("default")))
 
@@ -45,11 +46,9 @@ enum {
     KE_BUF_COMM_EDGES,   // edge records: [send | world x recv]
     KE_BUF_JPEG_TABLES,  // Huffman tables of a JPEG batch
     KE_BUF_TURN_TILES,   // ke_hash_images_turned: the 32x32 tiles of a call's images, group after group
-    KE_BUF_TURN_LUMA,    // ke_ssim_pairs_turned: the turned luma planes of a call, 1 B/px per distinct (image, orientation)
     KE_BUF_TRIM_BOXES,   // ke_content_boxes: the boxes of a call's images, 16 B each
     KE_BUF_TRIM_CROPS,   // ke_hash_images_trimmed: the packed crops of one chunk of qualifying images
-    KE_BUF_TRIM_LUMA,    // ke_ssim_pairs_boxed: the cropped luma planes of a call, 1 B/px per distinct (image, box)
-    KE_BUF_VIEW_LUMA,    // ke_ssim_pairs_viewed: the luma planes of a call's views, 1 B/px per distinct (image, box, orientation)
+    KE_BUF_VIEW_LUMA,    // the pair calls: the luma planes of a call's made views, 1 B/px per distinct (image, box, orientation)
     KE_BUF_NEAREST_IN,   // ke_hamming_nearest: the host's arrays among [hashes | ids | queries | query_ids]
     KE_BUF_NEAREST_OUT,  // ke_hamming_nearest: the host's arrays among [index | within | distance | count | histogram]
     KE_BUF_COUNT
@@ -167,30 +166,11 @@ int ke_launch_tiles_turned(ke_ctx *ctx, const uint8_t *d_tile32, const int64_t *
 enum { KE_RP_BANDED = 0, KE_RP_CPO, KE_RP_NDWC, KE_RP_LAUNCHES, KE_RP_BANDS, KE_RP_FUNNEL, KE_RP_VMX, KE_RP_VFIRST, KE_RP_COUNT };
 int ke_launch_resize_group(ke_ctx *ctx, const KeHashGroup &g, int ow, int oh, int filter, uint8_t *d_tiles,
                            const float *box = nullptr);
-// the luma plane of orientation `orientation` (0..7, turned.ORIENTATIONS) of each image, rows packed (ke_turn.hip); the
-// job table goes through KE_BUF_META and the stream is drained before the call returns
-struct KeTurnJob {
-    uint64_t src_off, dst_off;   // bytes from d_src / d_dst
-    int32_t w, h, channels, orientation;
-};
-int ke_launch_turn_luma(ke_ctx *ctx, const uint8_t *d_src, const KeTurnJob *jobs, int64_t n, uint8_t *d_dst);
-// the luma plane of box (x0, y0, x0 + bw, y0 + bh) of each image, rows packed (ke_trim.hip); the box lies inside its image, the
-// job table goes through KE_BUF_META and the stream is drained before the call returns
-struct KeCropLumaJob {
-    uint64_t src_off, dst_off;   // bytes from d_src / d_dst
-    int32_t w, h, channels;      // the source image
-    int32_t x0, y0, bw, bh;      // the box
-};
+// the made views of the pair calls (job structs: ke_view_plan.h): the luma plane of a box of each image (ke_trim.hip), and of an
+// orientation of a box of each image (ke_turn.hip; `timer`: the KE_T_* that times the launches, or -1).  The box lies inside its
+// image, the job table goes through KE_BUF_META and the stream is drained before the call returns
 int ke_launch_crop_luma(ke_ctx *ctx, const uint8_t *d_src, const KeCropLumaJob *jobs, int64_t n, uint8_t *d_dst);
-// the luma plane of orientation `orientation` of box (x0, y0, x0 + bw, y0 + bh) of each image, rows packed, bw x bh swapped for
-// orientation & 4 (ke_turn.hip); the box lies inside its image, the job table goes through KE_BUF_META and the stream is drained
-// before the call returns
-struct KeViewJob {
-    uint64_t src_off, dst_off;   // bytes from d_src / d_dst
-    int32_t w, h, channels, orientation;
-    int32_t x0, y0, bw, bh;
-};
-int ke_launch_crop_turn_luma(ke_ctx *ctx, const uint8_t *d_src, const KeViewJob *jobs, int64_t n, uint8_t *d_dst);
+int ke_launch_view_luma(ke_ctx *ctx, const uint8_t *d_src, const KeViewJob *jobs, int64_t n, uint8_t *d_dst, int timer);
 int ke_launch_tile_ahash(ke_ctx *ctx, const uint8_t *d_tiles, int64_t n, int grid, int tile, uint64_t *d_bits);
 int ke_launch_sad_pairs(ke_ctx *ctx, const uint8_t *d_thumbs, int64_t pixels, const int64_t *d_pa, const int64_t *d_pb,
                         int64_t n_pairs, uint64_t *d_out);

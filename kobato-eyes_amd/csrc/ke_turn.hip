@@ -1,14 +1,18 @@
-// ke_turn.hip -- ke_turn_luma: the luma plane of one of the eight orientations of a picture (turned.ORIENTATIONS), in one
-// pass over the pixels.  It serves the SSIM re-check of turned duplicate pairs (ke_ssim_pairs_turned): image a is scored
-// against orientation k of image b, and b's turned luma is all the fit step needs.  Luma is a per-pixel function, so it
-// commutes with the permutation: the plane written here is byte for byte the luma of the turned picture.
+// ke_turn.hip -- the luma plane of a view of a picture: one of the eight orientations (turned.ORIENTATIONS) of a box of it, in one
+// pass over the box's pixels.  ke_crop_turn_luma exports it; ke_turn_luma is the same with the box (0, 0, w, h).  It serves the
+// SSIM re-check of turned pairs and of pairs that are bordered and turned (ke_api.hip, the pair calls): image a is scored against
+// orientation k of a box of image b, and that view's luma is all the fit step needs.  Luma is a per-pixel function, so it commutes
+// with the crop and with the permutation: the plane written here is byte for byte the luma of the cropped and turned picture.
 //
-// One image per blockIdx.y, 64 x 64 tiles of the destination over blockIdx.x (a workgroup strides over the image's tiles),
-// 256 threads.  A tile goes through LDS twice (ke_turn_core.h has the coordinate arithmetic):
+// One view per blockIdx.y, 64 x 64 tiles of the destination over blockIdx.x (a workgroup strides over the view's tiles), 256
+// threads.  The destination is the box's size, swapped for k & 4; a tile's source rectangle lies at the box's origin inside the
+// image (ke_turn_core.h has the turn's coordinate arithmetic, ke_view_core.h the box's).  A tile goes through LDS twice:
 //   A  the tile's source rectangle, source row by source row: a wave takes a row and reads its bytes as aligned dwords --
-//      64 / 192 / 256 contiguous bytes for 1 / 3 / 4 channels -- into `raw`, one row per kRawPitch bytes.  A row starts on
-//      any byte, so the row's first dword is the aligned one below it and `raw` keeps the 0..3 bytes of lead.  Only a dword
-//      that reaches outside the image's own bytes (the first and the last of an image) is put together from byte loads.
+//      64 / 192 / 256 contiguous bytes for 1 / 3 / 4 channels -- into `raw`, one row per kRawPitch bytes.  The rows are the IMAGE's
+//      pitch of w * ch bytes apart, so a row starts on any byte whatever the box's width: the row's first dword is the aligned one
+//      below it and `raw` keeps the 0..3 bytes of lead.  This may read the margin pixels beside the box that share a dword with
+//      it, never a byte outside the image: only a dword that reaches outside the image's own bytes (the first and the last of an
+//      image) is put together from byte loads.
 //   B  a thread per source pixel takes luma from `raw` and writes the byte where the pixel lies in the DESTINATION tile:
 //      `tile`, one destination row per kTilePitch = 68 bytes.  For the transposing orientations the 32 lanes of a half wave
 //      write a column: bytes (68 r + c), banks ((68 r + c) / 4) % 32 = (17 r + c / 4) % 32, all distinct since 17 is odd.
@@ -17,113 +21,20 @@
 //      (banks 17 r + j and 17 r + j + 1 over the 16 lanes of a row: distinct), and the row's first and last <= 3 bytes are byte
 //      stores.
 // No byte-wide global access inside a tile.
-//
-// ke_crop_turn_luma (below) is the same pass over a box of the image: see ke_crop_turn_luma_kernel and ke_view_core.h.
 #include "ke_internal.h"
-#include "ke_turn_core.h"
 #include "ke_view_core.h"
 
 namespace {
-
-struct TurnItem {
-    uint64_t src_off, dst_off;
-    int32_t w, h;            // source size
-    int32_t channels;        // 1, 3 or 4
-    int32_t orientation;     // 0..7
-};
 
 constexpr int kT = KE_TURN_TILE;
 constexpr int kRawPitch = 4 * kT + 4;     // a source row of the tile at 4 channels, and its lead
 constexpr int kTilePitch = kT + 4;        // 68: see B and C above
 
-__global__ __launch_bounds__(256) void ke_turn_luma_kernel(const uint8_t *__restrict__ src, const TurnItem *__restrict__ items, int64_t first,
+__global__ __launch_bounds__(256) void ke_view_luma_kernel(const uint8_t *__restrict__ src, const KeViewJob *__restrict__ items, int64_t first,
                                                            uint8_t *__restrict__ dst) {
     __shared__ __attribute__((aligned(16))) uint8_t raw[kT * kRawPitch];
     __shared__ __attribute__((aligned(16))) uint8_t tile[kT * kTilePitch + 4];
-    const TurnItem it = items[first + blockIdx.y];
-    const int k = it.orientation, w = it.w, h = it.h, ch = it.channels;
-    int dw, dh;
-    ke_turn_dst_size(k, w, h, &dw, &dh);
-    const int ntx = ke_turn_tiles_x(dw), tiles = ntx * ke_turn_tiles_y(dh);
-    const uint8_t *s = src + it.src_off;
-    const uint8_t *s_end = s + (size_t)w * h * ch;
-    uint8_t *d = dst + it.dst_off;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const KeTurnRect dr = ke_turn_tile_dst_rect(dw, dh, t % ntx, t / ntx);
-        const KeTurnRect sr = ke_turn_src_rect(k, dw, dh, dr);
-        // A: source rows -> raw
-        for (int ly = wave; ly < sr.h; ly += 4) {
-            const uint8_t *row = s + ((size_t)(sr.y0 + ly) * w + sr.x0) * ch;
-            const int lead = (int)((uintptr_t)row & 3);
-            const uint8_t *a0 = row - lead;
-            const int ndw = (lead + sr.w * ch + 3) >> 2;
-            uint32_t *out = (uint32_t *)(raw + ly * kRawPitch);
-            for (int j = lane; j < ndw; j += 64) {
-                const uint8_t *p = a0 + 4 * j;
-                uint32_t v;
-                if (p >= s && p + 4 <= s_end) {
-                    v = *(const uint32_t *)p;
-                } else {
-                    v = 0;
-                    for (int b = 0; b < 4; ++b)
-                        if (p + b >= s && p + b < s_end) v |= (uint32_t)p[b] << (8 * b);
-                }
-                out[j] = v;
-            }
-        }
-        __syncthreads();
-        // B: luma, placed where the pixel lies in the destination tile
-        for (int ly = wave; ly < sr.h; ly += 4) {
-            if (lane < sr.w) {
-                const int lead = (int)((uintptr_t)(s + ((size_t)(sr.y0 + ly) * w + sr.x0) * ch) & 3);
-                int x, y;
-                ke_turn_dst_xy(k, dw, dh, sr.x0 + lane, sr.y0 + ly, &x, &y);
-                tile[(y - dr.y0) * kTilePitch + (x - dr.x0)] = (uint8_t)ke_turn_luma_px(raw + ly * kRawPitch + lead + lane * ch, ch);
-            }
-        }
-        __syncthreads();
-        // C: destination rows out of the tile
-        for (int slot = threadIdx.x; slot < dr.h * 16; slot += 256) {
-            const int r = slot >> 4, j = slot & 15;
-            uint8_t *g = d + (size_t)(dr.y0 + r) * dw + dr.x0;
-            const uint8_t *trow = tile + r * kTilePitch;
-            int head = (int)((4 - ((uintptr_t)g & 3)) & 3);
-            if (head > dr.w) head = dr.w;
-            const int nd = (dr.w - head) >> 2, done = head + 4 * nd;
-            if (j < nd) {
-                const uint32_t *q = (const uint32_t *)trow + j + (head ? 1 : 0);
-                // bytes head + 4 j .. + 3 of the row: head = 0 is the dword itself, else the upper bytes of one dword and the lower of the next
-                const uint32_t v = head ? __funnelshift_r(q[-1], q[0], 8 * head) : q[0];
-                *(uint32_t *)(g + head + 4 * j) = v;
-            }
-            if (j == 0)
-                for (int b = 0; b < head; ++b) g[b] = trow[b];
-            if (j == 15)
-                for (int b = done; b < dr.w; ++b) g[b] = trow[b];
-        }
-        // the next tile's A writes `raw`, which nobody reads after the second barrier; its B writes `tile` behind A's barrier
-    }
-}
-
-// ke_crop_turn_luma: ke_turn_luma_kernel on a box of the image (ke_view_core.h).  The tiles, the two trips through LDS, the
-// pitches and the bank arithmetic are the ones above; the destination is the box's size (swapped for k & 4), a tile's source
-// rectangle lies at the box's origin inside the image, and its rows are a pitch of w * ch bytes apart -- the image's, so a row
-// of the rectangle starts on any byte whatever the box's width.  Phase A may read the margin pixels beside the box that share
-// a dword with it, never a byte outside the image.
-struct ViewItem {
-    uint64_t src_off, dst_off;
-    int32_t w, h;            // source image
-    int32_t channels;        // 1, 3 or 4
-    int32_t orientation;     // 0..7
-    int32_t x0, y0, bw, bh;  // the box
-};
-
-__global__ __launch_bounds__(256) void ke_crop_turn_luma_kernel(const uint8_t *__restrict__ src, const ViewItem *__restrict__ items, int64_t first,
-                                                                uint8_t *__restrict__ dst) {
-    __shared__ __attribute__((aligned(16))) uint8_t raw[kT * kRawPitch];
-    __shared__ __attribute__((aligned(16))) uint8_t tile[kT * kTilePitch + 4];
-    const ViewItem it = items[first + blockIdx.y];
+    const KeViewJob it = items[first + blockIdx.y];
     const int k = it.orientation, w = it.w, ch = it.channels;
     const KeViewBox box{it.x0, it.y0, it.bw, it.bh};
     int dw, dh;
@@ -168,7 +79,7 @@ __global__ __launch_bounds__(256) void ke_crop_turn_luma_kernel(const uint8_t *_
             }
         }
         __syncthreads();
-        // C: destination rows out of the tile, as in ke_turn_luma_kernel
+        // C: destination rows out of the tile
         for (int slot = threadIdx.x; slot < dr.h * 16; slot += 256) {
             const int r = slot >> 4, j = slot & 15;
             uint8_t *g = d + (size_t)(dr.y0 + r) * dw + dr.x0;
@@ -178,6 +89,7 @@ __global__ __launch_bounds__(256) void ke_crop_turn_luma_kernel(const uint8_t *_
             const int nd = (dr.w - head) >> 2, done = head + 4 * nd;
             if (j < nd) {
                 const uint32_t *q = (const uint32_t *)trow + j + (head ? 1 : 0);
+                // bytes head + 4 j .. + 3 of the row: head = 0 is the dword itself, else the upper bytes of one dword and the lower of the next
                 const uint32_t v = head ? __funnelshift_r(q[-1], q[0], 8 * head) : q[0];
                 *(uint32_t *)(g + head + 4 * j) = v;
             }
@@ -186,32 +98,32 @@ __global__ __launch_bounds__(256) void ke_crop_turn_luma_kernel(const uint8_t *_
             if (j == 15)
                 for (int b = done; b < dr.w; ++b) g[b] = trow[b];
         }
+        // the next tile's A writes `raw`, which nobody reads after the second barrier; its B writes `tile` behind A's barrier
     }
 }
 
 }  // namespace
 
-int ke_launch_turn_luma(ke_ctx *ctx, const uint8_t *d_src, const KeTurnJob *jobs, int64_t n, uint8_t *d_dst) {
+int ke_launch_view_luma(ke_ctx *ctx, const uint8_t *d_src, const KeViewJob *jobs, int64_t n, uint8_t *d_dst, int timer) {
     if (n == 0) return KE_OK;
-    std::vector<TurnItem> items((size_t)n);
     int64_t most = 1;
     for (int64_t i = 0; i < n; ++i) {
-        const KeTurnJob &j = jobs[i];
-        items[(size_t)i] = TurnItem{j.src_off, j.dst_off, j.w, j.h, j.channels, j.orientation};
         int dw, dh;
-        ke_turn_dst_size(j.orientation, j.w, j.h, &dw, &dh);
+        ke_view_dst_size(jobs[i].orientation, KeViewBox{jobs[i].x0, jobs[i].y0, jobs[i].bw, jobs[i].bh}, &dw, &dh);
         most = std::max<int64_t>(most, (int64_t)ke_turn_tiles_x(dw) * ke_turn_tiles_y(dh));
     }
-    void *d_items;
-    KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)n * sizeof(TurnItem), &d_items));
-    KE_HIP(ctx, hipMemcpyAsync(d_items, items.data(), (size_t)n * sizeof(TurnItem), hipMemcpyHostToDevice, ctx->stream));
+    void *d_items;                                         // the kernel reads the jobs as they are
+    KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)n * sizeof(KeViewJob), &d_items));
+    KE_HIP(ctx, hipMemcpyAsync(d_items, jobs, (size_t)n * sizeof(KeViewJob), hipMemcpyHostToDevice, ctx->stream));
     const unsigned gx = (unsigned)std::min<int64_t>(most, 4096);
+    if (timer >= 0) ke_time_begin(ctx, timer);
     for (int64_t first = 0; first < n; first += 65535) {
         const unsigned gy = (unsigned)std::min<int64_t>(65535, n - first);
-        hipLaunchKernelGGL(ke_turn_luma_kernel, dim3(gx, gy), dim3(256), 0, ctx->stream, d_src, (const TurnItem *)d_items, first, d_dst);
+        hipLaunchKernelGGL(ke_view_luma_kernel, dim3(gx, gy), dim3(256), 0, ctx->stream, d_src, (const KeViewJob *)d_items, first, d_dst);
     }
+    if (timer >= 0) ke_time_end(ctx, timer);
     KE_HIP(ctx, hipGetLastError());
-    KE_HIP(ctx, hipStreamSynchronize(ctx->stream));       // `items` is a host vector
+    KE_HIP(ctx, hipStreamSynchronize(ctx->stream));       // `jobs` is the caller's host array
     return KE_OK;
 }
 
@@ -223,41 +135,15 @@ KE_API int ke_turn_luma(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_off
     if (n == 0) return KE_OK;
     if (!ke_is_device_ptr(src) || !ke_is_device_ptr(dst)) return ke_fail(ctx, KE_EINVAL, "src and dst are device memory");
     KE_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<KeTurnJob> jobs((size_t)n);
+    std::vector<KeViewJob> jobs((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         if (widths[i] <= 0 || heights[i] <= 0 || (channels[i] != 1 && channels[i] != 3 && channels[i] != 4) || orientations[i] < 0 ||
             orientations[i] > 7)
             return ke_fail(ctx, KE_EINVAL, "image %lld: %dx%d, %d channels, orientation %d", (long long)i, widths[i], heights[i], channels[i],
                            orientations[i]);
-        jobs[(size_t)i] = KeTurnJob{src_offsets[i], dst_offsets[i], widths[i], heights[i], channels[i], orientations[i]};
+        jobs[(size_t)i] = KeViewJob{src_offsets[i], dst_offsets[i], widths[i], heights[i], channels[i], orientations[i], 0, 0, widths[i], heights[i]};
     }
-    return ke_launch_turn_luma(ctx, src, jobs.data(), n, dst);
-}
-
-int ke_launch_crop_turn_luma(ke_ctx *ctx, const uint8_t *d_src, const KeViewJob *jobs, int64_t n, uint8_t *d_dst) {
-    if (n == 0) return KE_OK;
-    std::vector<ViewItem> items((size_t)n);
-    int64_t most = 1;
-    for (int64_t i = 0; i < n; ++i) {
-        const KeViewJob &j = jobs[i];
-        items[(size_t)i] = ViewItem{j.src_off, j.dst_off, j.w, j.h, j.channels, j.orientation, j.x0, j.y0, j.bw, j.bh};
-        int dw, dh;
-        ke_view_dst_size(j.orientation, KeViewBox{j.x0, j.y0, j.bw, j.bh}, &dw, &dh);
-        most = std::max<int64_t>(most, (int64_t)ke_turn_tiles_x(dw) * ke_turn_tiles_y(dh));
-    }
-    void *d_items;
-    KE_TRY(ke_reserve(ctx, KE_BUF_META, (size_t)n * sizeof(ViewItem), &d_items));
-    KE_HIP(ctx, hipMemcpyAsync(d_items, items.data(), (size_t)n * sizeof(ViewItem), hipMemcpyHostToDevice, ctx->stream));
-    const unsigned gx = (unsigned)std::min<int64_t>(most, 4096);
-    ke_time_begin(ctx, KE_T_VIEW_LUMA);
-    for (int64_t first = 0; first < n; first += 65535) {
-        const unsigned gy = (unsigned)std::min<int64_t>(65535, n - first);
-        hipLaunchKernelGGL(ke_crop_turn_luma_kernel, dim3(gx, gy), dim3(256), 0, ctx->stream, d_src, (const ViewItem *)d_items, first, d_dst);
-    }
-    ke_time_end(ctx, KE_T_VIEW_LUMA);
-    KE_HIP(ctx, hipGetLastError());
-    KE_HIP(ctx, hipStreamSynchronize(ctx->stream));       // `items` is a host vector
-    return KE_OK;
+    return ke_launch_view_luma(ctx, src, jobs.data(), n, dst, -1);
 }
 
 KE_API int ke_crop_turn_luma(ke_ctx *ctx, const uint8_t *src, const uint64_t *src_offsets, const int32_t *widths, const int32_t *heights,
@@ -279,5 +165,5 @@ KE_API int ke_crop_turn_luma(ke_ctx *ctx, const uint8_t *src, const uint64_t *sr
                            b[1], b[2], b[3], o);
         jobs[(size_t)i] = KeViewJob{src_offsets[i], dst_offsets[i], w, h, ch, o, b[0], b[1], b[2] - b[0], b[3] - b[1]};
     }
-    return ke_launch_crop_turn_luma(ctx, src, jobs.data(), n, dst);
+    return ke_launch_view_luma(ctx, src, jobs.data(), n, dst, KE_T_VIEW_LUMA);
 }

@@ -173,7 +173,10 @@ def _upload(ctx, arrays: dict, placed: dict, buffers: list) -> None:
     ctx.memcpy(dev, flat, len(flat))
 
 
-PLAIN, TURNED, TRIMMED, VIEWED = "plain", "turned", "trimmed", "viewed"     # what a row of _refine_runs carries after its two paths
+PLAIN, TURNED, TRIMMED, VIEWED = "plain", "turned", "trimmed", "viewed"
+# what a mode of _refine_runs uses of a row's (trimmed_a, trimmed_b, orientation): (the flags, the orientation, its own counters)
+_MODES = {PLAIN: (False, False, ()), TURNED: (False, True, ()), TRIMMED: (True, False, ("box_files", "crop_launches")),
+          VIEWED: (True, True, ("box_files", "crop_launches", "turn_launches", "view_launches"))}
 
 
 def _seam_boxes(ctx, pairs: Sequence[tuple], live: list, paths: list, index: dict, placed: dict, count: dict, tolerance: int):
@@ -195,11 +198,10 @@ def _seam_boxes(ctx, pairs: Sequence[tuple], live: list, paths: list, index: dic
 
 def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, count: dict, cfg: RefinementThresholds,
            mode: str = PLAIN, tolerance: int = 48) -> None:
-    """One ``ke_ssim_pairs`` call for the pairs of this run (the library groups them: one fit launch per (source size,
-    common size), one SSIM launch per common size).  TURNED: a pair carries an orientation as its fifth item and the
-    call is ``ke_ssim_pairs_turned``, which scores a against that orientation of b.  TRIMMED: a pair carries two flags, and
-    the call is ``ke_ssim_pairs_boxed`` with the content box, found here, of every flagged side.  VIEWED: two flags and an
-    orientation (seventh item), and the call is ``ke_ssim_pairs_viewed``: a's box against that orientation of b's box."""
+    """One library call for the pairs of this run (the library groups them: one fit launch per (source size, common size), one
+    SSIM launch per common size).  A row is ``(id_a, id_b, path_a, path_b, trimmed_a, trimmed_b, orientation)``.  PLAIN:
+    ``ke_ssim_pairs``.  The other modes: ``ke_ssim_pairs_viewed``, a's view against that orientation of b's view, with the
+    content box, found here, of every flagged side where the mode has boxes, and the orientations where it has them."""
     live = []
     for k in chunk:
         pa, pb = pairs[k][2], pairs[k][3]
@@ -213,19 +215,17 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
     index = {p: i for i, p in enumerate(paths)}
     where = ([placed[p][0] for p in paths], [placed[p][1] for p in paths], [placed[p][2] for p in paths], 3,
              [index[str(pairs[k][2])] for k in live], [index[str(pairs[k][3])] for k in live])
-    zeros = np.zeros((len(live), 4), np.int32)
-    box_a = box_b = zeros
-    if mode == TURNED:
-        scores, status = ctx.ssim_pairs_turned_on_device(*where, [int(pairs[k][4]) for k in live])
-    elif mode == TRIMMED:
+    has_boxes, has_orientations, counters = _MODES[mode]
+    box_a = box_b = None
+    if has_boxes:
         box_a, box_b = _seam_boxes(ctx, pairs, live, paths, index, placed, count, tolerance)
-        scores, status = ctx.ssim_pairs_boxed_on_device(*where, box_a, box_b)
-    elif mode == VIEWED:
-        box_a, box_b = _seam_boxes(ctx, pairs, live, paths, index, placed, count, tolerance)
-        scores, status = ctx.ssim_pairs_viewed_on_device(*where, box_a, box_b, [int(pairs[k][6]) for k in live])
-    else:
+    if mode == PLAIN:
         scores, status = ctx.ssim_pairs_on_device(*where)
-    common, fits, cropped, turned, viewed = set(), set(), False, False, False
+    else:
+        scores, status = ctx.ssim_pairs_viewed_on_device(*where, box_a, box_b, [int(pairs[k][6]) for k in live] if has_orientations else None)
+    if not has_boxes:
+        box_a = box_b = np.zeros((len(live), 4), np.int32)
+    common, fits, made = set(), set(), {"crop_launches": False, "turn_launches": False, "view_launches": False}
     for n, (k, sc, st) in enumerate(zip(live, scores.tolist(), status.tolist())):
         fid_a, fid_b, pa, pb = pairs[k][:4]
         if st != 0:                                            # skimage raises for images smaller than its window
@@ -234,7 +234,7 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
             continue
         out[k] = _decide(fid_a, fid_b, float(sc), [], cfg)
         (_, wa, ha), (_, wb, hb) = placed[str(pa)], placed[str(pb)]
-        o = int(pairs[k][4]) if mode == TURNED else int(pairs[k][6]) if mode == VIEWED else 0
+        o = int(pairs[k][6])
         # a box other than the whole picture (as it lies) is a source of its own, as a turned plane is
         cut_a, cut_b = (bool(b.any()) and tuple(b) != (0, 0, w, h) for b, w, h in ((box_a[n], wa, ha), (box_b[n], wb, hb)))
         if cut_a:
@@ -243,19 +243,17 @@ def _score(ctx, pairs: Sequence[tuple], chunk: range, placed: dict, out: list, c
             wb, hb = int(box_b[n][2] - box_b[n][0]), int(box_b[n][3] - box_b[n][1])
         if o & 4:                                              # crop, then turn
             wb, hb = hb, wb
-        cropped = cropped or cut_a or (cut_b and o == 0)
-        turned = turned or (o != 0 and not cut_b)
-        viewed = viewed or (o != 0 and cut_b)
+        made["crop_launches"] |= cut_a or (cut_b and o == 0)
+        made["turn_launches"] |= o != 0 and not cut_b
+        made["view_launches"] |= o != 0 and cut_b
         size = (min(wa, wb), min(ha, hb))
         common.add(size)
         fits.update({((ha, wa), cut_a, size), ((hb, wb), o != 0 or cut_b, size)})
     count["fit_launches"] += len(fits)
     count["ssim_launches"] += len(common)
-    if mode in (TRIMMED, VIEWED):
-        count["crop_launches"] += int(cropped)
-    if mode == VIEWED:
-        count["turn_launches"] += int(turned)
-        count["view_launches"] += int(viewed)
+    for name in counters:
+        if name in made:
+            count[name] += int(made[name])
 
 
 def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThresholds] = None, device: int = 0,
@@ -284,13 +282,14 @@ def refine_pairs(pairs: Sequence[tuple], *, thresholds: Optional[RefinementThres
 
         return ranks.refine_pairs(pairs, devices, thresholds=thresholds, io_workers=io_workers,
                                   max_decoded_bytes=max_decoded_bytes, stats=stats, max_side=max_side)
-    return _refine_runs(pairs, PLAIN, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, _after_run)
+    rows = [(*p[:4], False, False, 0) for p in pairs]
+    return _refine_runs(rows, PLAIN, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, _after_run)
 
 
 def _refine_runs(pairs: Sequence[tuple], mode: str, thresholds, device: int, io_workers: int, max_decoded_bytes: int,
                  stats: Optional[dict], max_side: int, _after_run=None, tolerance: int = 48) -> list:
     """The run loop of refine_pairs, refine_turned_pairs, refine_trimmed_pairs and refine_turned_trimmed_pairs (``mode``: PLAIN,
-    TURNED, TRIMMED, VIEWED): decode
+    TURNED, TRIMMED, VIEWED; rows ``(id_a, id_b, path_a, path_b, trimmed_a, trimmed_b, orientation)`` whatever the mode): decode
     what a run of pairs needs, once per file and within the budget, score the run with one library call, free, go on."""
     from concurrent.futures import ThreadPoolExecutor
 
@@ -298,10 +297,7 @@ def _refine_runs(pairs: Sequence[tuple], mode: str, thresholds, device: int, io_
     ctx = _native.get_context(device)
     out: list = [None] * len(pairs)
     count = {"decodes": 0, "gpu_decodes": 0, "fit_launches": 0, "ssim_launches": 0, "pairs": len(pairs)}
-    if mode == TRIMMED:
-        count.update(box_files=0, crop_launches=0)
-    if mode == VIEWED:
-        count.update(box_files=0, crop_launches=0, turn_launches=0, view_launches=0)
+    count.update(dict.fromkeys(_MODES[mode][2], 0))
     with ThreadPoolExecutor(max_workers=max(1, io_workers)) as pool:
         start = 0
         while start < len(pairs):
@@ -352,7 +348,8 @@ def refine_turned_pairs(pairs: Sequence[tuple], *, thresholds: Optional[Refineme
     for pair in pairs:
         if not 0 <= int(pair[4]) < 8:
             raise ValueError(f"orientation {pair[4]} outside 0..7")
-    return _refine_runs(pairs, TURNED, thresholds, device, io_workers, max_decoded_bytes, stats, max_side)
+    rows = [(*p[:4], False, False, int(p[4])) for p in pairs]
+    return _refine_runs(rows, TURNED, thresholds, device, io_workers, max_decoded_bytes, stats, max_side)
 
 
 def refine_trimmed_pairs(pairs: Sequence[tuple], *, tolerance: int = 48, thresholds: Optional[RefinementThresholds] = None, device: int = 0,
@@ -378,7 +375,8 @@ def refine_trimmed_pairs(pairs: Sequence[tuple], *, tolerance: int = 48, thresho
     ``ValueError`` before anything is decoded."""
     if not 0 <= int(tolerance) <= 255:
         raise ValueError(f"tolerance {tolerance} outside 0..255")
-    return _refine_runs(pairs, TRIMMED, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, tolerance=int(tolerance))
+    rows = [(*p[:6], 0) for p in pairs]
+    return _refine_runs(rows, TRIMMED, thresholds, device, io_workers, max_decoded_bytes, stats, max_side, tolerance=int(tolerance))
 
 
 def refine_turned_trimmed_pairs(pairs: Sequence[tuple], *, tolerance: int = 48, thresholds: Optional[RefinementThresholds] = None,

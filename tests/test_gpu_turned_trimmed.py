@@ -1,10 +1,11 @@
 """Copies that are both bordered and turned, on the device.
 
 1. ke_crop_turn_luma over one mixed batch == turn(k, O.luma(px)[y0:y1, x0:x1]) byte for byte, guard bytes round every plane
-   untouched; what it refuses.
+   untouched; on whole pictures it is ke_turn_luma; what it refuses.
 2. ke_ssim_pairs_viewed(a, b, box_a, box_b, orient_b) is bit-equal (float64 ==, same status) to ke_ssim_pairs on host-made
    turn(k, crop)s: luma is per pixel, the turn a permutation and every resample plan pinned bit-exact, so there is no tolerance.
-   With no orientation it is ke_ssim_pairs_boxed, with no box ke_ssim_pairs_turned.  Against the oracle's ssim_fit of the views:
+   With no orientation it is ke_ssim_pairs_boxed, with no box ke_ssim_pairs_turned; the four pair calls in any order on one
+   context answer alike.  Against the oracle's ssim_fit of the views:
    1e-5 in the default mode, 1e-6 in the exact one -- the bars of tests/test_gpu_parity.py.
 3. ke_hash_images_turned_trimmed: its columns are ke_hash_images_turned's and ke_hash_images_trimmed's, and the turned hashes of
    the crop are the oracle's, at 1, 3 and 4 channels, host and device pixels, in a ragged batch.
@@ -107,6 +108,47 @@ def test_crop_turn_luma_on_a_mixed_batch(ctx):
     for (i, box, k), p, o in zip(jobs, want, dst_off):
         assert np.array_equal(got[o:o + p.size].reshape(p.shape), p), (sources[i].shape, box, k)
         assert np.all(got[o + p.size:o + p.size + BEHIND] == 0xA5) and np.all(got[o - FRONT:o] == 0xA5), (sources[i].shape, box, k)
+
+
+def test_crop_turn_luma_of_the_whole_picture_is_turn_luma(ctx):
+    """One kernel behind both calls: the box (0, 0, w, h) of every shape of _turned_ssim_cases.KERNEL_SHAPES at 1, 3 and 4
+    channels under every orientation is ke_turn_luma's plane byte for byte, the guard bytes round every plane untouched."""
+    rng = np.random.default_rng(T.SEED + 901)
+    sources = [rng.integers(0, 256, size=(h, w) if ch == 1 else (h, w, ch), dtype=np.uint8) for w, h in TS.KERNEL_SHAPES for ch in (1, 3, 4)]
+    src_off = np.concatenate([[0], np.cumsum([px.size for px in sources])[:-1]]).tolist()      # packed back to back: off the dwords
+    assert {o % 4 for o in src_off} == {0, 1, 2, 3}
+    flat = np.concatenate([px.reshape(-1) for px in sources])
+    jobs = [(i, k) for k in range(8) for i in range(len(sources))]
+    dst_off, at = [], FRONT
+    for i, _ in jobs:
+        dst_off.append(at)
+        at += sources[i].shape[0] * sources[i].shape[1] + BEHIND
+    total = at
+    widths, heights = [sources[i].shape[1] for i, _ in jobs], [sources[i].shape[0] for i, _ in jobs]
+    chans = [1 if sources[i].ndim == 2 else sources[i].shape[2] for i, _ in jobs]
+    where = ([src_off[i] for i, _ in jobs], widths, heights, chans)
+    src, dst = ctx.malloc(flat.nbytes), ctx.malloc(total)
+    got = []
+    try:
+        ctx.memcpy(src, flat, flat.nbytes)
+        for boxed in (False, True):
+            ctx.memcpy(dst, np.full(total, 0xA5, np.uint8), total)
+            if boxed:
+                ctx.crop_turn_luma(src, *where, [(0, 0, w, h) for w, h in zip(widths, heights)], [k for _, k in jobs], dst, dst_off)
+            else:
+                ctx.turn_luma(src, *where, [k for _, k in jobs], dst, dst_off)
+            got.append(np.empty(total, np.uint8))
+            ctx.memcpy(got[-1], dst, total)
+    finally:
+        ctx.free(src)
+        ctx.free(dst)
+    assert np.array_equal(got[0], got[1])
+    lumas = [O.luma(px) for px in sources]
+    assert np.all(got[1][:FRONT] == 0xA5)
+    for (i, k), o in zip(jobs, dst_off):
+        p = np.ascontiguousarray(turned.turn(k, lumas[i]))
+        assert np.array_equal(got[1][o:o + p.size].reshape(p.shape), p), (sources[i].shape, k)
+        assert np.all(got[1][o + p.size:o + p.size + BEHIND] == 0xA5), (sources[i].shape, k)
 
 
 def test_crop_turn_luma_refuses_what_it_cannot_take(ctx):
@@ -224,6 +266,28 @@ def test_without_an_orientation_it_is_the_boxed_call_and_without_a_box_the_turne
     for ba, bb in ((None, None), (zeros, zeros), (size(a), size(b)), (None, size(b)), (zeros, None)):
         got, status = ctx.ssim_pairs_viewed(images, a, b, ba, bb, orient)
         assert got.tolist() == want.tolist() and status.tolist() == want_status.tolist()
+
+
+def test_the_four_pair_calls_share_one_scratch(ctx, pairs):
+    """The made planes of every pair call lie in one scratch buffer of the context.  The turned, boxed, viewed and plain calls one
+    after the other, then the other way round, then a smaller viewed batch twice behind the larger one: every answer is the first
+    one of its kind, float64 == and the same statuses.  The smaller batch is every third row, and its answers are the larger one's
+    for those rows too: all areas here are multiples of four (test_ssim_pairs_viewed_on_views_of_odd_areas says why that matters), so how a call stacks its planes does not show."""
+    images, rows = pairs["images"], pairs["rows"]
+    a, b, box_a, box_b, orient = _columns(rows)
+    calls = {"turned": lambda: ctx.ssim_pairs_turned(images, a, b, orient), "boxed": lambda: ctx.ssim_pairs_boxed(images, a, b, box_a, box_b),
+             "viewed": lambda: ctx.ssim_pairs_viewed(images, a, b, box_a, box_b, orient), "plain": lambda: ctx.ssim_pairs(images, a, b)}
+    first = {}
+    for name in list(calls) + list(calls)[::-1]:
+        got, status = calls[name]()
+        want = first.setdefault(name, (got.tolist(), status.tolist()))
+        assert (got.tolist(), status.tolist()) == want, name
+        assert not status.any() and np.isfinite(got).all(), name
+    assert len({tuple(scores) for scores, _ in first.values()}) == 4                     # four different questions
+    few = rows[::3]
+    for _ in range(2):
+        got, status = ctx.ssim_pairs_viewed(images, *_columns(few))
+        assert got.tolist() == first["viewed"][0][::3] and status.tolist() == first["viewed"][1][::3]
 
 
 def test_ssim_pairs_viewed_against_the_oracle(ctx, pairs):
