@@ -21,6 +21,26 @@ LIB_PATH = os.environ.get("KE_LIBKEYES") or os.path.join(_PKG_DIR, "libkeyes_hip
 KE_OK = 0
 EDGE_DTYPE = np.dtype([("a", "<i8"), ("b", "<i8"), ("h", "<i4"), ("bands", "<i4")])
 
+# The hash calls that stand behind a decode, by mode: (C function, whether it takes ``tolerance``, its outputs as (name, trailing
+# shape, dtype)).  Each is f(ctx, pixels, offsets, widths, heights, channels, n, [tolerance,] *outputs, status); ``has`` comes
+# back as bytes and is handed on as bool.  A further view of a picture is a row here (Context._hash_views_at).
+HASH_CALLS = {
+    "plain": ("ke_hash_images", False, (("phash", (), np.uint64), ("dhash", (), np.uint64))),
+    "turned": ("ke_hash_images_turned", False, (("turned", (8,), np.uint64),)),
+    "trimmed": ("ke_hash_images_trimmed", True, (("phash", (), np.uint64), ("boxes", (4,), np.int32), ("has", (), np.uint8))),
+    "turned_trimmed": ("ke_hash_images_turned_trimmed", True, (("turned", (8,), np.uint64), ("trimmed_turned", (8,), np.uint64),
+                                                               ("boxes", (4,), np.int32), ("has", (), np.uint8))),
+}
+
+
+def hash_outputs(mode: str, n: int, leave: Sequence[str] = ()) -> dict:
+    """{name: zeros[n, ...]} for the outputs of HASH_CALLS[mode] as a caller sees them (``has`` bool; None for a name in
+    ``leave``), then "status": int32[n]."""
+    out = {name: None if name in leave else np.zeros((n,) + shape, bool if name == "has" else dtype)
+           for name, shape, dtype in HASH_CALLS[mode][2]}
+    out["status"] = np.zeros(n, np.int32)
+    return out
+
 # every symbol include/keyes.h declares (tests check the library exports all of them)
 FILTER_LANCZOS, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2   # include/keyes.h KE_FILTER_*
 
@@ -499,19 +519,33 @@ class Context:
             self._check(self._lib.ke_tiles_turned(self._h, _addr(tiles), int(n), _addr(out)), "ke_tiles_turned")
         return out
 
+    def _hash_views_at(self, mode: str, pixels, offsets, widths, heights, channels: int, tolerance: int = 0, *, leave=()) -> dict:
+        """One call of HASH_CALLS[mode] on images that lie in one buffer -- a host array or a device pointer -- at any byte
+        offsets: {output name: array, ..., "status": int32[n]} in the table's order, ``has`` as bool.  ``leave``: the outputs
+        that are not wanted (the library gets a null pointer, the entry is None)."""
+        name, takes_tolerance, outputs = HASH_CALLS[mode]
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        widths, heights = np.ascontiguousarray(widths, np.int32), np.ascontiguousarray(heights, np.int32)
+        n = len(offsets)
+        out = {key: None if key in leave else np.zeros((n,) + shape, dtype) for key, shape, dtype in outputs}
+        out["status"] = np.zeros(n, np.int32)
+        with self._lock:
+            self._check(getattr(self._lib, name)(self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights), int(channels), n,
+                                                 *((int(tolerance),) if takes_tolerance else ()), *(_addr(a) for a in out.values())), name)
+        if out.get("has") is not None:
+            out["has"] = out["has"].astype(bool)
+        return out
+
+    def _hash_views(self, mode: str, images: Sequence[np.ndarray], tolerance: int = 0) -> tuple:
+        """``_hash_views_at`` of a ragged batch of host images sharing one channel count: the outputs, then the status."""
+        if len(images) == 0:
+            return tuple(hash_outputs(mode, 0).values())
+        return tuple(self._hash_views_at(mode, *_pack_images(images), tolerance).values())
+
     def hash_images_turned(self, images: Sequence[np.ndarray]):
         """``hash_images`` with the eight turned pHashes in place of the two hashes: (turned u64[n, 8], status).  Column 0
         is the image's pHash; a failed image has eight zeros."""
-        n = len(images)
-        if n == 0:
-            return np.empty((0, 8), np.uint64), np.empty(0, np.int32)
-        flat, offsets, widths, heights, ch = _pack_images(images)
-        turned = np.zeros((n, 8), np.uint64)
-        status = np.empty(n, np.int32)
-        with self._lock:
-            self._check(self._lib.ke_hash_images_turned(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n,
-                                                        _addr(turned), _addr(status)), "ke_hash_images_turned")
-        return turned, status
+        return self._hash_views("turned", images)
 
     def content_boxes(self, images: Sequence[np.ndarray], tolerance: int):
         """The content boxes (include/keyes.h, ke_content_boxes) of host images sharing one channel count:
@@ -578,42 +612,18 @@ class Context:
     def hash_images_trimmed(self, images: Sequence[np.ndarray], tolerance: int):
         """``hash_images`` with the trimmed pHash (include/keyes.h, ke_hash_images_trimmed): (phash u64[n], boxes int32[n, 4],
         has bool[n], status int32[n]).  An image without a qualifying box has has = False and hash 0; its box is still there."""
-        n = len(images)
-        if n == 0:
-            return np.zeros(0, np.uint64), np.zeros((0, 4), np.int32), np.zeros(0, bool), np.zeros(0, np.int32)
-        flat, offsets, widths, heights, ch = _pack_images(images)
-        ph, boxes = np.zeros(n, np.uint64), np.zeros((n, 4), np.int32)
-        has, status = np.zeros(n, np.uint8), np.zeros(n, np.int32)
-        with self._lock:
-            self._check(self._lib.ke_hash_images_trimmed(self._h, _addr(flat), _addr(offsets), _addr(widths), _addr(heights), ch, n,
-                                                         int(tolerance), _addr(ph), _addr(boxes), _addr(has), _addr(status)),
-                        "ke_hash_images_trimmed")
-        return ph, boxes, has.astype(bool), status
+        return self._hash_views("trimmed", images, tolerance)
 
     def hash_images_turned_trimmed(self, images: Sequence[np.ndarray], tolerance: int):
         """``hash_images_turned`` and ``hash_images_trimmed`` in one call, with the turned pHashes of the crop
         (ke_hash_images_turned_trimmed): (turned u64[n, 8], trimmed_turned u64[n, 8], boxes int32[n, 4], has bool[n], status
         int32[n]).  Column 0 of ``trimmed_turned`` is the trimmed pHash; a row is zeros where the box does not qualify."""
-        n = len(images)
-        if n == 0:
-            return (np.zeros((0, 8), np.uint64), np.zeros((0, 8), np.uint64), np.zeros((0, 4), np.int32), np.zeros(0, bool),
-                    np.zeros(0, np.int32))
-        flat, offsets, widths, heights, ch = _pack_images(images)
-        return self.hash_images_turned_trimmed_at(flat, offsets, widths, heights, ch, tolerance)
+        return self._hash_views("turned_trimmed", images, tolerance)
 
     def hash_images_turned_trimmed_at(self, pixels, offsets, widths, heights, channels: int, tolerance: int):
         """``hash_images_turned_trimmed`` of images that lie in one buffer already -- a host array or a device pointer -- at any
         byte offsets."""
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        widths, heights = np.ascontiguousarray(widths, np.int32), np.ascontiguousarray(heights, np.int32)
-        n = len(offsets)
-        turned, cut = np.zeros((n, 8), np.uint64), np.zeros((n, 8), np.uint64)
-        boxes, has, status = np.zeros((n, 4), np.int32), np.zeros(n, np.uint8), np.zeros(n, np.int32)
-        with self._lock:
-            self._check(self._lib.ke_hash_images_turned_trimmed(self._h, _addr(pixels), _addr(offsets), _addr(widths), _addr(heights),
-                                                                int(channels), n, int(tolerance), _addr(turned), _addr(cut), _addr(boxes),
-                                                                _addr(has), _addr(status)), "ke_hash_images_turned_trimmed")
-        return turned, cut, boxes, has.astype(bool), status
+        return tuple(self._hash_views_at("turned_trimmed", pixels, offsets, widths, heights, channels, tolerance).values())
 
     # -- pinned staging ---------------------------------------------------------------------
     def stage_create(self, bytes_per_buffer: int, max_images: int, n_buffers: int = 2) -> None:
@@ -1010,33 +1020,26 @@ class Context:
         Returns (phash u64[n], dhash u64[n] | None, status int32[n]); status != 0 = not handled here (decode the file with
         Pillow).  The files come as bytes (``blobs``), as ``paths`` the library reads, or as ``ahead = (FilesAhead, lo, hi)``:
         files lo..hi of a batch read beforehand.  ``skip``: a mask of files to leave alone (status 1)."""
-        return self._hash_chain(blobs, want_dhash, kind, paths, ahead, skip, mode="plain")[:3]
+        return tuple(self._hash_chain("plain", blobs, kind, paths, ahead, skip, leave=() if want_dhash else ("dhash",)).values())
 
     def hash_turned(self, blobs, *, kind: str, paths=None):
         """``hash``'s chain with ke_hash_images_turned behind the decode: (turned u64[n, 8], status int32[n]); status != 0 =
         not handled here, eight zeros."""
-        turned, _, st, _ = self._hash_chain(blobs, False, kind, paths, None, None, mode="turned")
-        return turned, st
+        return tuple(self._hash_chain("turned", blobs, kind, paths).values())
 
     def hash_trimmed(self, blobs, *, kind: str, paths=None, tolerance: int = 48):
         """``hash``'s chain with ke_hash_images_trimmed behind the decode: (phash u64[n], boxes int32[n, 4], has bool[n],
         status int32[n]); status != 0 = not handled here, zeros."""
-        ph, _, st, (boxes, has) = self._hash_chain(blobs, False, kind, paths, None, None, mode="trimmed", tolerance=tolerance)
-        return ph, boxes, has, st
+        return tuple(self._hash_chain("trimmed", blobs, kind, paths, tolerance=tolerance).values())
 
     def hash_turned_trimmed(self, blobs, *, kind: str, paths=None, tolerance: int = 48):
         """``hash``'s chain with ke_hash_images_turned_trimmed behind the decode: (turned u64[n, 8], trimmed_turned u64[n, 8],
         boxes int32[n, 4], has bool[n], status int32[n]); status != 0 = not handled here, zeros."""
-        turned, _, st, (boxes, has, cut) = self._hash_chain(blobs, False, kind, paths, None, None, mode="turned_trimmed", tolerance=tolerance)
-        return turned, cut, boxes, has, st
+        return tuple(self._hash_chain("turned_trimmed", blobs, kind, paths, tolerance=tolerance).values())
 
-    def _hash_chain(self, blobs, want_dhash, kind, paths, ahead, skip, *, mode: str, tolerance: int = 0):
-        """(phash, dhash | None, status, extra) of one of the three calls behind the decode: "plain" ke_hash_images, "turned"
-        ke_hash_images_turned (phash is u64[n, 8]), "trimmed" ke_hash_images_trimmed (extra = (boxes, has), else None),
-        "turned_trimmed" ke_hash_images_turned_trimmed (phash is the turned u64[n, 8], extra = (boxes, has, trimmed_turned))."""
-        both = mode == "turned_trimmed"
-        turned, trimmed = mode == "turned", mode == "trimmed" or both
-        shape = (0, 8) if turned or both else (0,)
+    def _hash_chain(self, mode: str, blobs, kind, paths, ahead=None, skip=None, *, tolerance: int = 0, leave=()) -> dict:
+        """Files decoded on the GPU and handed to HASH_CALLS[mode] there, channel count by channel count: ``hash_outputs`` of
+        the mode over all the files, zeros and status != 0 for a file the decoder or the hash call refused."""
         if ahead is not None:                            # where the files come from is settled here, once
             n = ahead[2] - ahead[1]
             take = lambda lo, hi: ahead[0].part(ahead[1] + lo, ahead[1] + hi)
@@ -1047,54 +1050,27 @@ class Context:
             n = len(blobs)
             take = lambda lo, hi: self._packed(blobs[lo:hi])
         if n == 0:
-            return (np.zeros(shape, np.uint64), (np.zeros(0, np.uint64) if want_dhash else None), np.zeros(0, np.int32),
-                    ((np.zeros((0, 4), np.int32), np.zeros(0, bool)) + ((np.zeros((0, 8), np.uint64),) if both else ())) if trimmed else None)
+            return hash_outputs(mode, 0, leave)
         skip = None if skip is None else np.asarray(skip, bool)
 
-        def run(lo: int, hi: int):
-            ph = np.zeros((hi - lo,) + shape[1:], np.uint64)
-            boxes, has = (np.zeros((hi - lo, 4), np.int32), np.zeros(hi - lo, bool)) if trimmed else (None, None)
-            cut = np.zeros((hi - lo, 8), np.uint64) if both else None
-            dh = np.zeros(hi - lo, np.uint64) if want_dhash else None
+        def run(lo: int, hi: int) -> dict:
+            out = hash_outputs(mode, hi - lo, leave)
             dev, out_off, w, h, c, st, _ = self._decode_packed(take(lo, hi), kind, skip=None if skip is None else skip[lo:hi])
             for ch in (1, 3, 4):
                 idx = np.nonzero((st == 0) & (c == ch))[0]
                 if len(idx) == 0:
                     continue
-                p = np.zeros((len(idx),) + shape[1:], np.uint64)
-                d = np.zeros(len(idx), np.uint64) if want_dhash else None
-                status = np.zeros(len(idx), np.int32)
-                offs = np.ascontiguousarray(out_off[idx])
-                ws, hs = np.ascontiguousarray(w[idx]), np.ascontiguousarray(h[idx])
-                if turned:
-                    self._check(self._lib.ke_hash_images_turned(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p),
-                                                                _addr(status)), "ke_hash_images_turned")
-                elif both:
-                    b, t, q = np.zeros((len(idx), 4), np.int32), np.zeros(len(idx), np.uint8), np.zeros((len(idx), 8), np.uint64)
-                    self._check(self._lib.ke_hash_images_turned_trimmed(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx),
-                                                                        int(tolerance), _addr(p), _addr(q), _addr(b), _addr(t), _addr(status)),
-                                "ke_hash_images_turned_trimmed")
-                    boxes[idx], has[idx], cut[idx] = b, t.astype(bool), q
-                elif trimmed:
-                    b, t = np.zeros((len(idx), 4), np.int32), np.zeros(len(idx), np.uint8)
-                    self._check(self._lib.ke_hash_images_trimmed(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), int(tolerance),
-                                                                 _addr(p), _addr(b), _addr(t), _addr(status)), "ke_hash_images_trimmed")
-                    boxes[idx], has[idx] = b, t.astype(bool)
-                else:
-                    self._check(self._lib.ke_hash_images(self._h, dev, _addr(offs), _addr(ws), _addr(hs), ch, len(idx), _addr(p), _addr(d),
-                                                         _addr(status)), "ke_hash_images")
-                ph[idx] = p
-                if want_dhash:
-                    dh[idx] = d
-                st[idx[status != 0]] = 2
-            return ph, dh, st, boxes, has, cut
+                got = self._hash_views_at(mode, dev, out_off[idx], w[idx], h[idx], ch, tolerance, leave=leave)
+                st[idx[got.pop("status") != 0]] = 2
+                for name, values in got.items():
+                    if values is not None:
+                        out[name][idx] = values
+            out["status"] = st
+            return out
 
         with self._lock:                                 # the decode buffer is this call's until the pixels are hashed
             parts = _in_halves(run, 0, n)
-        return (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]) if want_dhash else None,
-                np.concatenate([p[2] for p in parts]),
-                ((np.concatenate([p[3] for p in parts]), np.concatenate([p[4] for p in parts])) +
-                 ((np.concatenate([p[5] for p in parts]),) if both else ())) if trimmed else None)
+        return {name: None if name in leave else np.concatenate([p[name] for p in parts]) for name in parts[0]}
 
     # -- scan -------------------------------------------------------------------------------
     def hamming_scan(self, hashes, n: int, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4,

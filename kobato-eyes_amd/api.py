@@ -189,23 +189,62 @@ def find_similar(library: Iterable, queries: Iterable, *, k: int = 10, max_dista
     return scanner.nearest(files, asked, k, max_distance)
 
 
-def _turned_scan(files: Iterable, *, hamming_threshold, size_ratio, band_bits, band_count, device, ssim_threshold=None):
-    """find_turned_duplicates' work: (clusters, matches, the (id, id) keys of the plain candidate edges).  With
-    ``ssim_threshold`` the matches and the keys are the ones that passed the re-check."""
-    from . import turned as _turned
+def _turned_matches(scanner, candidates, turned, ok) -> list:
+    return scanner.turned_edges(candidates, turned, ok)
+
+
+def _trimmed_matches(scanner, candidates, hashes, boxes, has, ok) -> list:
+    return scanner.trimmed_edges(candidates, hashes, has & ok, boxes)
+
+
+def _turned_trimmed_matches(scanner, candidates, turned, cut, boxes, has, ok) -> list:
+    """The best match per pair of files, by ``view_rank``, over ``trimmed_edges`` on the crops as they lie (orientation 0) and
+    ``turned_trimmed_edges`` (orientations 1..7)."""
+    from .scanner import TransformedMatch, view_rank
+
+    found = [TransformedMatch(m.file_id_a, m.file_id_b, m.trimmed_a, m.trimmed_b, 0, m.hamming, m.box_a, m.box_b)
+             for m in scanner.trimmed_edges(candidates, cut[:, 0], has & ok, boxes)]
+    found += scanner.turned_trimmed_edges(candidates, turned, cut, has & ok, ok, boxes)
+    best: dict = {}
+    for m in found:
+        key = (m.file_id_a, m.file_id_b)
+        rank = view_rank(m.hamming, m.orientation, m.trimmed_a, m.trimmed_b)
+        if key not in best or rank < best[key][0]:
+            best[key] = (rank, m)
+    return [best[key][1] for key in sorted(best)]
+
+
+# The view searches, by mode: (the module and the function that make the signatures -- looked up when called --, whether
+# ``tolerance`` applies, what turns (scanner, candidates, *signatures) into matches, the refine call of the SSIM re-check, the
+# attributes of a match that follow the ids and paths in a row of that call).  A further view is a row here.
+_VIEW_MODES = {
+    "turned": ("turned", "turned_signatures", False, _turned_matches, "refine_turned_pairs", ("orientation",)),
+    "trimmed": ("trimmed", "trimmed_signatures", True, _trimmed_matches, "refine_trimmed_pairs", ("trimmed_a", "trimmed_b")),
+    "turned_trimmed": ("turned_trimmed", "turned_trimmed_signatures", True, _turned_trimmed_matches, "refine_turned_trimmed_pairs",
+                       ("trimmed_a", "trimmed_b", "orientation")),
+}
+
+
+def _view_scan(mode: str, files: Iterable, *, hamming_threshold, size_ratio, band_bits, band_count, device, tolerance=None,
+               ssim_threshold=None) -> tuple:
+    """The work of find_turned_duplicates, find_trimmed_duplicates and find_turned_trimmed_duplicates (``mode``: a key of
+    _VIEW_MODES): (clusters, matches, the (id, id) keys of the plain candidate edges).  With ``ssim_threshold`` the matches and
+    the keys are the ones that passed the re-check.  ``tolerance`` is read by the modes that trim."""
     from .scanner import DuplicateEdge, assemble_clusters
 
+    module, signatures, takes_tolerance, collect, refine_name, tail = _VIEW_MODES[mode]
     candidates = [f for f in _parse_files(files) if f.phash is not None]
     if len(candidates) < 2:
         return [], [], set()
+    keywords = {"tolerance": tolerance} if takes_tolerance else {}
     config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
                                  band_count=band_count)
     scanner = DuplicateScanner(config, device=device)
-    hashes, ok = _turned.turned_signatures([f.path for f in candidates], device=device)
+    made = getattr(importlib.import_module("." + module, __package__), signatures)([f.path for f in candidates], device=device, **keywords)
     plain = scanner.candidate_edges(candidates)
-    matches = scanner.turned_edges(candidates, hashes, ok)
+    matches = collect(scanner, candidates, *made)
     if ssim_threshold is not None and (plain or matches):
-        plain, matches = _turned_ssim_kept(plain, matches, candidates, ssim_threshold, device)
+        plain, matches = _views_ssim_kept(refine_name, tail, plain, matches, candidates, ssim_threshold, device, **keywords)
     edges = list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
     return (assemble_clusters(candidates, edges) if edges else []), matches, set(plain)
 
@@ -231,22 +270,6 @@ def _views_ssim_kept(refine_name: str, tail: tuple, plain: dict, matches: list, 
     return kept_plain, kept_matches
 
 
-def _turned_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, device: int) -> tuple:
-    return _views_ssim_kept("refine_turned_pairs", ("orientation",), plain, matches, candidates, ssim_threshold, device)
-
-
-def _trimmed_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, tolerance: int,
-                       device: int) -> tuple:
-    return _views_ssim_kept("refine_trimmed_pairs", ("trimmed_a", "trimmed_b"), plain, matches, candidates, ssim_threshold, device,
-                            tolerance=tolerance)
-
-
-def _turned_trimmed_ssim_kept(plain: dict, matches: list, candidates: Sequence[DuplicateFile], ssim_threshold: float, tolerance: int,
-                              device: int) -> tuple:
-    return _views_ssim_kept("refine_turned_trimmed_pairs", ("trimmed_a", "trimmed_b", "orientation"), plain, matches, candidates,
-                            ssim_threshold, device, tolerance=tolerance)
-
-
 def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, band_bits: int = 16,
                            band_count: int = 4, device: Optional[int] = None, ssim_threshold: Optional[float] = None) -> tuple:
     """(clusters, matches): near-duplicates including mirrored, flipped and rotated copies.
@@ -266,30 +289,8 @@ def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_
 
     Out of scope here: persisting turned hashes, ``devices=[...]`` (one process, one GPU) and dHash.  A copy that is turned AND has a
     margin round it is ``find_turned_trimmed_duplicates``'."""
-    clusters, matches, _ = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
-                                        band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)
-    return clusters, matches
-
-
-def _trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, band_bits, band_count, device, ssim_threshold=None):
-    """find_trimmed_duplicates' work: (clusters, matches).  With ``ssim_threshold`` the matches, and the plain edges among the
-    clusters' links, are the ones that passed the re-check."""
-    from . import trimmed as _trimmed
-    from .scanner import DuplicateEdge, assemble_clusters
-
-    candidates = [f for f in _parse_files(files) if f.phash is not None]
-    if len(candidates) < 2:
-        return [], []
-    config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
-                                 band_count=band_count)
-    scanner = DuplicateScanner(config, device=device)
-    hashes, boxes, has, ok = _trimmed.trimmed_signatures([f.path for f in candidates], tolerance=tolerance, device=device)
-    plain = scanner.candidate_edges(candidates)
-    matches = scanner.trimmed_edges(candidates, hashes, has & ok, boxes)
-    if ssim_threshold is not None and (plain or matches):
-        plain, matches = _trimmed_ssim_kept(plain, matches, candidates, ssim_threshold, tolerance, device)
-    edges =list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
-    return (assemble_clusters(candidates, edges) if edges else []), matches
+    return _view_scan("turned", files, hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
+                      band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)[:2]
 
 
 def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tolerance: int = 48, size_ratio: Optional[float] = None,
@@ -314,38 +315,8 @@ def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tole
 
     Out of scope here: an MAE re-check on the crop, ``devices=[...]`` (one process, one GPU), persisting trimmed
     hashes, borders of two colours or gradients, and dHash.  Trimmed and turned together is ``find_turned_trimmed_duplicates``'."""
-    return _trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio, band_bits=band_bits,
-                         band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)
-
-
-def _turned_trimmed_scan(files: Iterable, *, hamming_threshold, tolerance, size_ratio, band_bits, band_count, device, ssim_threshold=None):
-    """find_turned_trimmed_duplicates' work: (clusters, matches, the (id, id) keys of the plain candidate edges).  With
-    ``ssim_threshold`` the matches and the keys are the ones that passed the re-check."""
-    from . import turned_trimmed as _views
-    from .scanner import DuplicateEdge, TransformedMatch, assemble_clusters, view_rank
-
-    candidates = [f for f in _parse_files(files) if f.phash is not None]
-    if len(candidates) < 2:
-        return [], [], set()
-    config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
-                                 band_count=band_count)
-    scanner = DuplicateScanner(config, device=device)
-    turned, cut, boxes, has, ok = _views.turned_trimmed_signatures([f.path for f in candidates], tolerance=tolerance, device=device)
-    plain = scanner.candidate_edges(candidates)
-    found = [TransformedMatch(m.file_id_a, m.file_id_b, m.trimmed_a, m.trimmed_b, 0, m.hamming, m.box_a, m.box_b)
-             for m in scanner.trimmed_edges(candidates, cut[:, 0], has & ok, boxes)]
-    found += scanner.turned_trimmed_edges(candidates, turned, cut, has & ok, ok, boxes)
-    best: dict = {}
-    for m in found:
-        key = (m.file_id_a, m.file_id_b)
-        rank = view_rank(m.hamming, m.orientation, m.trimmed_a, m.trimmed_b)
-        if key not in best or rank < best[key][0]:
-            best[key] = (rank, m)
-    matches = [best[key][1] for key in sorted(best)]
-    if ssim_threshold is not None and (plain or matches):
-        plain, matches = _turned_trimmed_ssim_kept(plain, matches, candidates, ssim_threshold, tolerance, device)
-    edges = list(plain.values()) + [DuplicateEdge(m.file_id_a, m.file_id_b, m.hamming) for m in matches]
-    return (assemble_clusters(candidates, edges) if edges else []), matches, set(plain)
+    return _view_scan("trimmed", files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio, band_bits=band_bits,
+                      band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)[:2]
 
 
 def find_turned_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tolerance: int = 48, size_ratio: Optional[float] = None,
@@ -371,10 +342,9 @@ def find_turned_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 
 
     Out of scope here: ``devices=[...]`` (one process, one GPU), persisting any of these hashes, turning side a, dHash, borders
     of two colours or gradients, and an MAE re-check."""
-    clusters, matches, _ = _turned_trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio,
-                                                band_bits=band_bits, band_count=band_count, device=0 if device is None else int(device),
-                                                ssim_threshold=ssim_threshold)
-    return clusters, matches
+    return _view_scan("turned_trimmed", files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio,
+                      band_bits=band_bits, band_count=band_count, device=0 if device is None else int(device),
+                      ssim_threshold=ssim_threshold)[:2]
 
 
 def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None, config: Optional[DuplicateScanConfig] = None,

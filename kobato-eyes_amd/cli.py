@@ -170,6 +170,10 @@ def similar_in_database(db_path: str, *, to: Sequence[str] = (), to_like: Option
             for name, hits in zip(names, found) for rank, hit in enumerate(hits, start=1)]
 
 
+# what a view search of scan_database hands out besides the clusters: mode -> (orientations_out is filled, boxes_out is filled)
+VIEW_COLUMNS = {"turned": (True, False), "trimmed": (False, True), "turned_trimmed": (True, True)}
+
+
 def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, path_like: Optional[str] = None,
                   refine: bool = False, tile_max_bits: int = 32, mae_thr: float = 0.004, device: Optional[int] = None, progress=None,
                   devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None, turned: bool = False,
@@ -222,29 +226,18 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
 
     rows, files = load_files_for_dup(db_path, path_like, added_like, device=device, devices=devices, tick=tick)
     tick("Clustering duplicates", 0, len(files))
-    if turned_trimmed:
-        from .api import _turned_trimmed_scan
+    mode, ssim_threshold = (("turned_trimmed", turned_trimmed_ssim) if turned_trimmed else ("turned", turned_ssim) if turned else
+                            ("trimmed", trimmed_ssim) if trimmed else (None, None))
+    if mode:
+        from .api import _view_scan
 
-        clusters, matches, plain_keys = _turned_trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=trim_tolerance,
-                                                             size_ratio=size_ratio, band_bits=16, band_count=4, device=device,
-                                                             ssim_threshold=turned_trimmed_ssim)
-        if orientations_out is not None:
+        orientations, boxes = VIEW_COLUMNS[mode]
+        clusters, matches, plain_keys = _view_scan(mode, files, hamming_threshold=hamming_threshold, tolerance=trim_tolerance,
+                                                   size_ratio=size_ratio, band_bits=16, band_count=4, device=device,
+                                                   ssim_threshold=ssim_threshold)
+        if orientations and orientations_out is not None:
             orientations_out.update(orientations_to_keeper(clusters, matches, plain_keys))
-        if boxes_out is not None:
-            boxes_out.update(boxes_of_matches(matches))
-    elif turned:
-        from .api import _turned_scan
-
-        clusters, matches, plain_keys = _turned_scan(files, hamming_threshold=hamming_threshold, size_ratio=size_ratio,
-                                                     band_bits=16, band_count=4, device=device, ssim_threshold=turned_ssim)
-        if orientations_out is not None:
-            orientations_out.update(orientations_to_keeper(clusters, matches, plain_keys))
-    elif trimmed:
-        from .api import _trimmed_scan
-
-        clusters, matches = _trimmed_scan(files, hamming_threshold=hamming_threshold, tolerance=trim_tolerance, size_ratio=size_ratio,
-                                          band_bits=16, band_count=4, device=device, ssim_threshold=trimmed_ssim)
-        if boxes_out is not None:
+        if boxes and boxes_out is not None:
             boxes_out.update(boxes_of_matches(matches))
     elif added_like:
         from .api import find_new_duplicates

@@ -212,17 +212,64 @@ class SimilarFile:
     distance: int
 
 
+@dataclass(frozen=True)
+class _ViewTable:
+    """The table of one view scan, one array entry per table entry: ``hashes`` u64[t]; ``row``, the candidate the entry is a
+    view of; ``cut``, whether it is the hash of that candidate's content-box crop; ``k``, the orientation 0..7 it was turned
+    by.  The scan compares the entries before ``first_new`` with those from it on, and with ``cross`` False the latter with
+    each other as well (``Context.hamming_scan``)."""
+
+    hashes: np.ndarray
+    row: np.ndarray
+    cut: np.ndarray
+    k: np.ndarray
+    first_new: int
+    cross: bool
+
+    @classmethod
+    def of(cls, parts: Sequence[tuple], first: int, cross: bool) -> "_ViewTable":
+        """``parts`` laid end to end, the first ``first`` of them before first_new.  A part is (hashes, candidate rows, cut):
+        u64[m], orientation 0 of m candidates, or u64[m, 7], their orientations 1..7, candidate by candidate."""
+        hashes, row, cut, k = [], [], [], []
+        for part, rows, is_cut in parts:
+            per = part.shape[1] if part.ndim == 2 else 1
+            hashes.append(part.reshape(-1))
+            row.append(np.repeat(np.asarray(rows, np.int64), per))
+            cut.append(np.full(part.size, is_cut))
+            k.append(np.tile(np.arange(1, 8), len(rows)) if per == 7 else np.zeros(len(rows), np.int64))
+        return cls(np.concatenate(hashes), np.concatenate(row), np.concatenate(cut), np.concatenate(k),
+                   sum(len(h) for h in hashes[:first]), cross)
+
+    def edge(self, a: int, b: int) -> tuple:
+        """An edge (a, b) of the scan -> (candidate a, trimmed_a, candidate b, trimmed_b, k)."""
+        return int(self.row[a]), bool(self.cut[a]), int(self.row[b]), bool(self.cut[b]), int(self.k[b])
+
+
+def _turned_table(stored, turned, src) -> _ViewTable:
+    """[stored pHash of the n candidates | turned[i, 1:8] of the candidates ``src``, file by file], a cross scan."""
+    return _ViewTable.of([(stored, np.arange(len(stored)), False), (turned[src, 1:8], src, False)], 1, True)
+
+
+def _trimmed_table(stored, trimmed, src) -> _ViewTable:
+    """[stored pHash of the n candidates | trimmed pHash of the candidates ``src``], a scan from first_new: trimmed x trimmed
+    is compared as well."""
+    return _ViewTable.of([(stored, np.arange(len(stored)), False), (trimmed[src], src, True)], 1, False)
+
+
+def _turned_trimmed_table(stored, turned, cut, src_o, src_t) -> _ViewTable:
+    """[stored pHash of the n candidates | cut[i, 0] of the candidates ``src_t``] against [turned[i, 1:8] of the candidates
+    ``src_o`` | cut[i, 1:8] of ``src_t``], a cross scan."""
+    return _ViewTable.of([(stored, np.arange(len(stored)), False), (cut[src_t, 0], src_t, True),
+                          (turned[src_o, 1:8], src_o, False), (cut[src_t, 1:8], src_t, True)], 2, True)
+
+
 def view_edge(a: int, b: int, n: int, trimmed_rows: Sequence[int], turned_rows: Sequence[int]) -> tuple:
     """An edge (a, b) of turned_trimmed_edges' table -> (candidate a, trimmed_a, candidate b, trimmed_b, k): the first part is
     [n stored pHashes | the trimmed pHash of candidates ``trimmed_rows``], the second [seven turned hashes of each of candidates
     ``turned_rows`` | seven turned hashes of the crop of each of ``trimmed_rows``]; a lies in the first part, b in the second."""
-    m = len(trimmed_rows)
-    side_a = (int(trimmed_rows[a - n]), True) if a >= n else (int(a), False)
-    at = b - (n + m)
-    if at < 7 * len(turned_rows):
-        return side_a + (int(turned_rows[at // 7]), False, at % 7 + 1)
-    at -= 7 * len(turned_rows)
-    return side_a + (int(trimmed_rows[at // 7]), True, at % 7 + 1)
+    blank = np.zeros((n, 8), np.uint64)
+    table = _turned_trimmed_table(blank[:, 0], blank, blank, np.asarray(turned_rows, np.int64), np.asarray(trimmed_rows, np.int64))
+    return table.edge(a, b)
 
 
 def ordered_view(id_a: int, trimmed_a: bool, id_b: int, trimmed_b: bool, k: int) -> tuple:
@@ -238,6 +285,16 @@ def ordered_view(id_a: int, trimmed_a: bool, id_b: int, trimmed_b: bool, k: int)
 def view_rank(hamming: int, orientation: int, trimmed_a: bool, trimmed_b: bool) -> tuple:
     """What the one match kept per unordered pair of files is the smallest of."""
     return (int(hamming), int(orientation), bool(trimmed_a), bool(trimmed_b))
+
+
+def _stored_hashes(candidates: Sequence[DuplicateFile]) -> np.ndarray:
+    return np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=len(candidates))
+
+
+def _ids_and_sizes(candidates: Sequence[DuplicateFile]) -> tuple:
+    n = len(candidates)
+    return (np.fromiter((f.file_id for f in candidates), dtype=np.int64, count=n),
+            np.fromiter(((f.size or 0) for f in candidates), dtype=np.int64, count=n))
 
 
 def _safe_positive_int(value: Optional[str]) -> Optional[int]:
@@ -282,24 +339,54 @@ class DuplicateScanner:
         self._funnel: Optional[tuple] = None
 
     # -- candidate edges ---------------------------------------------------------------------
+    def _limits(self) -> tuple:
+        """(size ratio, 0.0 = no size filter; KE_DUP_BUCKET_PAIR_CAP, None = no cap) of every scan of this scanner."""
+        ratio = self._config.size_ratio
+        return (ratio if (ratio is not None and ratio > 0) else 0.0), _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
+
+    def _scan(self, hashes, ids, sizes, **region) -> tuple:
+        """(edges, counters) of ``Context.hamming_scan`` over one table under this scanner's config, limits and shard;
+        ``region``: its first_new / cross."""
+        cfg = self._config
+        ratio, cap = self._limits()
+        return _native.get_context(self._device).hamming_scan(
+            hashes, len(hashes), ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
+            band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
+            part_index=self._part[0], part_count=self._part[1], **region)
+
     def candidate_edges(self, candidates: Sequence[DuplicateFile], first_new: int = 0) -> dict:
         """{(id_lo, id_hi): DuplicateEdge} exactly as the reference's ``edges`` dict ends up.  With ``first_new`` > 0 the
         candidates are [library | added] and only the pairs with a member at position >= first_new are scanned and
         returned (``ke_hamming_scan_from``): the pairs between two library files are not visited."""
-        cfg = self._config
-        n = len(candidates)
-        hashes = np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=n)
-        ids = np.fromiter((f.file_id for f in candidates), dtype=np.int64, count=n)
-        sizes = np.fromiter(((f.size or 0) for f in candidates), dtype=np.int64, count=n)
-        cap = _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
+        hashes, (ids, sizes) = _stored_hashes(candidates), _ids_and_sizes(candidates)
+        ratio, cap = self._limits()
         self._log_bucket_stats(hashes, cap)
-        ratio = cfg.size_ratio if (cfg.size_ratio is not None and cfg.size_ratio > 0) else 0.0
-        ctx = _native.get_context(self._device)
-        raw, counters = ctx.hamming_scan(
-            hashes, n, ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
-            band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
-            part_index=self._part[0], part_count=self._part[1], **({"first_new": int(first_new)} if first_new else {}))
+        raw, counters = self._scan(hashes, ids, sizes, **({"first_new": int(first_new)} if first_new else {}))
         return self._edges_from_raw(candidates, hashes, ids, raw, counters, sizes=sizes, ratio=ratio, cap=cap)
+
+    def _view_edges(self, candidates: Sequence[DuplicateFile], table: _ViewTable, boxes, make) -> list:
+        """The one view scan: ``table``'s entries carry their candidate's id and size -- so the scan's own ``ids[i] != ids[j]``
+        keeps a file from meeting a view of itself --, an edge decodes by lookup in the table, ``ordered_view`` puts the smaller
+        id first, and per unordered pair of ids the match of the smallest ``view_rank`` is kept, the earlier edge at equal rank.
+        Sorted by (id_a, id_b); ``make(id_a, id_b, trimmed_a, trimmed_b, orientation, hamming, box_a, box_b)`` builds a match."""
+        base_ids, base_sizes = _ids_and_sizes(candidates)
+        ids = base_ids[table.row]
+        raw, _ = self._scan(table.hashes, ids, base_sizes[table.row], first_new=table.first_new, cross=table.cross)
+        a, b = raw["a"], raw["b"]
+        best: dict[tuple[int, int], tuple] = {}
+        for id_a, t_a, c_a, id_b, t_b, c_b, k, h in zip(ids[a].tolist(), table.cut[a].tolist(), table.row[a].tolist(), ids[b].tolist(),
+                                                        table.cut[b].tolist(), table.row[b].tolist(), table.k[b].tolist(), raw["h"].tolist()):
+            if id_a > id_b:
+                c_a, c_b = c_b, c_a
+            id_a, t_a, id_b, t_b, k = ordered_view(id_a, t_a, id_b, t_b, k)
+            rank = view_rank(h, k, t_a, t_b)
+            if (id_a, id_b) not in best or rank < best[(id_a, id_b)][0]:
+                best[(id_a, id_b)] = (rank, c_a, c_b)
+
+        def box(c: int, trimmed: bool) -> Optional[tuple]:
+            return tuple(int(v) for v in np.asarray(boxes)[c]) if trimmed and boxes is not None else None
+
+        return [make(id_a, id_b, t_a, t_b, k, h, box(c_a, t_a), box(c_b, t_b)) for (id_a, id_b), ((h, k, t_a, t_b), c_a, c_b) in sorted(best.items())]
 
     def turned_edges(self, candidates: Sequence[DuplicateFile], turned, ok=None) -> list:
         """[TurnedMatch]: the pairs of files of which one looks like a mirrored, flipped or rotated copy of the other.
@@ -310,42 +397,18 @@ class DuplicateScanner:
         with hashes, file by file], a turned entry carrying its source file's id and size -- the scan's own ``ids[i] !=
         ids[j]`` therefore drops a symmetric picture matching itself -- and the scan is a cross scan with first_new = n
         (``ke_hamming_scan_cross``): the 7 n turned entries are not compared with each other.  An edge (a, b) is file a
-        against orientation k = (b - n) % 7 + 1 of the ((b - n) // 7)-th file with hashes.  One match is kept per unordered
-        pair of files: the smallest hamming, then the smallest orientation.  A match found from the file with the larger id
-        has its orientation mapped through turned.INVERSE, so that ``orientation`` always turns b's picture into a's.
-        size_ratio, the band config, KE_DUP_BUCKET_PAIR_CAP and this scanner's part_index / part_count apply as in
-        ``candidate_edges``; the funnel counters are not touched."""
-        from .turned import INVERSE
-
-        cfg = self._config
+        against the orientation and the file that entry b of the table carries (``_ViewTable``).  One match is kept per
+        unordered pair of files: the smallest hamming, then the smallest orientation (``view_rank``).  A match found from the
+        file with the larger id has its orientation mapped through turned.INVERSE (``ordered_view``), so that ``orientation``
+        always turns b's picture into a's.  size_ratio, the band config, KE_DUP_BUCKET_PAIR_CAP and this scanner's part_index /
+        part_count apply as in ``candidate_edges``; the funnel counters are not touched."""
         n = len(candidates)
         turned = np.asarray(turned, dtype=np.uint64).reshape(n, 8)
         src = np.arange(n) if ok is None else np.nonzero(np.asarray(ok, bool))[0]
         if n == 0 or len(src) == 0:
             return []
-        base_h = np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=n)
-        base_ids = np.fromiter((f.file_id for f in candidates), dtype=np.int64, count=n)
-        base_sizes = np.fromiter(((f.size or 0) for f in candidates), dtype=np.int64, count=n)
-        hashes = np.concatenate([base_h, turned[src, 1:8].reshape(-1)])
-        ids = np.concatenate([base_ids, np.repeat(base_ids[src], 7)])
-        sizes = np.concatenate([base_sizes, np.repeat(base_sizes[src], 7)])
-        cap = _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
-        ratio = cfg.size_ratio if (cfg.size_ratio is not None and cfg.size_ratio > 0) else 0.0
-        ctx = _native.get_context(self._device)
-        raw, _ = ctx.hamming_scan(
-            hashes, len(hashes), ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
-            band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
-            part_index=self._part[0], part_count=self._part[1], first_new=n, cross=True)
-        best: dict[tuple[int, int], tuple[int, int]] = {}
-        for a, b, h in zip(raw["a"].tolist(), raw["b"].tolist(), raw["h"].tolist()):
-            k = (b - n) % 7 + 1
-            id_a, id_b = int(base_ids[a]), int(base_ids[src[(b - n) // 7]])
-            if id_a > id_b:                      # found from the other side: what turns a's picture into b's
-                id_a, id_b, k = id_b, id_a, INVERSE[k]
-            found = (int(h), k)
-            if (id_a, id_b) not in best or found < best[(id_a, id_b)]:
-                best[(id_a, id_b)] = found
-        return [TurnedMatch(a, b, k, h) for (a, b), (h, k) in sorted(best.items())]
+        return self._view_edges(candidates, _turned_table(_stored_hashes(candidates), turned, src), None,
+                                lambda a, b, t_a, t_b, k, h, box_a, box_b: TurnedMatch(a, b, k, h))
 
     def trimmed_edges(self, candidates: Sequence[DuplicateFile], hashes, has, boxes=None) -> list:
         """[TrimmedMatch]: the pairs of files of which one looks like the other with a margin round it.
@@ -356,45 +419,15 @@ class DuplicateScanner:
         carrying its file's id and size -- the scan's own ``ids[i] != ids[j]`` therefore drops a file against its own crop --
         and the scan is the scan from first_new = n (``ke_hamming_scan_from``), NOT the cross scan: two copies of a picture
         with different margins meet in trimmed x trimmed.  One match is kept per unordered pair of files: the smallest
-        hamming, then (trimmed_a, trimmed_b) in order.  size_ratio, the band config, KE_DUP_BUCKET_PAIR_CAP and this scanner's
-        part_index / part_count apply as in ``candidate_edges``; the funnel counters are not touched."""
-        cfg = self._config
+        hamming, then (trimmed_a, trimmed_b) in order (``view_rank``).  size_ratio, the band config, KE_DUP_BUCKET_PAIR_CAP and
+        this scanner's part_index / part_count apply as in ``candidate_edges``; the funnel counters are not touched."""
         n = len(candidates)
         hashes = np.asarray(hashes, dtype=np.uint64).reshape(n)
         src = np.nonzero(np.asarray(has, bool).reshape(n))[0]
         if n == 0 or len(src) == 0:
             return []
-        base_h = np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=n)
-        base_ids = np.fromiter((f.file_id for f in candidates), dtype=np.int64, count=n)
-        base_sizes = np.fromiter(((f.size or 0) for f in candidates), dtype=np.int64, count=n)
-        table = np.concatenate([base_h, hashes[src]])
-        ids = np.concatenate([base_ids, base_ids[src]])
-        sizes = np.concatenate([base_sizes, base_sizes[src]])
-        cap = _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
-        ratio = cfg.size_ratio if (cfg.size_ratio is not None and cfg.size_ratio > 0) else 0.0
-        ctx = _native.get_context(self._device)
-        raw, _ = ctx.hamming_scan(
-            table, len(table), ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
-            band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
-            part_index=self._part[0], part_count=self._part[1], first_new=n, cross=False)
-
-        def side(pos: int) -> tuple:           # table position -> (candidate, trimmed)
-            return (int(src[pos - n]), True) if pos >= n else (pos, False)
-
-        best: dict[tuple[int, int], tuple] = {}
-        for a, b, h in zip(raw["a"].tolist(), raw["b"].tolist(), raw["h"].tolist()):
-            (ca, ta), (cb, tb) = side(a), side(b)
-            if base_ids[ca] > base_ids[cb]:
-                ca, ta, cb, tb = cb, tb, ca, ta
-            key = (int(base_ids[ca]), int(base_ids[cb]))
-            found = (int(h), ta, tb, ca, cb)
-            if key not in best or found[:3] < best[key][:3]:
-                best[key] = found
-
-        def box(c: int, trimmed: bool) -> Optional[tuple]:
-            return tuple(int(v) for v in np.asarray(boxes)[c]) if trimmed and boxes is not None else None
-
-        return [TrimmedMatch(a, b, ta, tb, h, box(ca, ta), box(cb, tb)) for (a, b), (h, ta, tb, ca, cb) in sorted(best.items())]
+        return self._view_edges(candidates, _trimmed_table(_stored_hashes(candidates), hashes, src), boxes,
+                                lambda a, b, t_a, t_b, k, h, box_a, box_b: TrimmedMatch(a, b, t_a, t_b, h, box_a, box_b))
 
     def turned_trimmed_edges(self, candidates: Sequence[DuplicateFile], turned, trimmed_turned, has, ok=None, boxes=None) -> list:
         """[TransformedMatch] of orientation 1..7: the pairs of files of which one looks like a turned copy of the other, either
@@ -412,7 +445,6 @@ class DuplicateScanner:
         exchanged and k goes through turned.INVERSE (``ordered_view``), so that ``orientation`` always turns b's (cut) picture
         into a's (cut) picture.  One match is kept per unordered pair of files: the smallest (hamming, orientation, trimmed_a,
         trimmed_b).  Orientation 0 is not in the table: those pairs are ``candidate_edges``' and ``trimmed_edges``'."""
-        cfg = self._config
         n = len(candidates)
         turned = np.asarray(turned, dtype=np.uint64).reshape(n, 8)
         cut = np.asarray(trimmed_turned, dtype=np.uint64).reshape(n, 8)
@@ -420,34 +452,8 @@ class DuplicateScanner:
         src_t = np.nonzero(np.asarray(has, bool).reshape(n))[0]
         if n == 0 or len(src_o) + len(src_t) == 0:
             return []
-        base_h = np.fromiter((f.phash & _MASK64 for f in candidates), dtype=np.uint64, count=n)
-        base_ids = np.fromiter((f.file_id for f in candidates), dtype=np.int64, count=n)
-        base_sizes = np.fromiter(((f.size or 0) for f in candidates), dtype=np.int64, count=n)
-        table = np.concatenate([base_h, cut[src_t, 0], turned[src_o, 1:8].reshape(-1), cut[src_t, 1:8].reshape(-1)])
-        rows = np.concatenate([np.arange(n), src_t, np.repeat(src_o, 7), np.repeat(src_t, 7)])
-        ids, sizes = base_ids[rows], base_sizes[rows]
-        first_new = n + len(src_t)
-        cap = _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
-        ratio = cfg.size_ratio if (cfg.size_ratio is not None and cfg.size_ratio > 0) else 0.0
-        ctx = _native.get_context(self._device)
-        raw, _ = ctx.hamming_scan(
-            table, len(table), ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
-            band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
-            part_index=self._part[0], part_count=self._part[1], first_new=first_new, cross=True)
-        best: dict[tuple[int, int], tuple] = {}
-        for a, b, h in zip(raw["a"].tolist(), raw["b"].tolist(), raw["h"].tolist()):
-            ca, ta, cb, tb, k = view_edge(a, b, n, src_t, src_o)
-            id_a, t_a, id_b, t_b, k = ordered_view(int(base_ids[ca]), ta, int(base_ids[cb]), tb, k)
-            if id_a != int(base_ids[ca]):
-                ca, cb = cb, ca
-            found = view_rank(h, k, t_a, t_b) + (ca, cb)
-            if (id_a, id_b) not in best or found[:4] < best[(id_a, id_b)][:4]:
-                best[(id_a, id_b)] = found
-
-        def box(c: int, trimmed: bool) -> Optional[tuple]:
-            return tuple(int(v) for v in np.asarray(boxes)[c]) if trimmed and boxes is not None else None
-
-        return [TransformedMatch(a, b, ta, tb, k, h, box(ca, ta), box(cb, tb)) for (a, b), (h, k, ta, tb, ca, cb) in sorted(best.items())]
+        return self._view_edges(candidates, _turned_trimmed_table(_stored_hashes(candidates), turned, cut, src_o, src_t), boxes,
+                                TransformedMatch)
 
     # -- the reference's funnel counters (src/dup/scanner.py:258-299) ---------------------------------------------
     def _band_values(self, hashes: np.ndarray, band: int) -> np.ndarray:

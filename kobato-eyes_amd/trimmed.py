@@ -18,10 +18,7 @@ from __future__ import annotations
 
 from typing import Sequence
 
-import numpy as np
-
-from . import _native
-from .formats import Offers
+from ._views import view_signatures
 
 DEFAULT_TOLERANCE = 48
 MIN_SIDE = 8
@@ -35,30 +32,6 @@ def qualifies(width: int, height: int, box) -> bool:
     return (width - bw) * 50 >= width or (height - bh) * 50 >= height
 
 
-def _pillow_trimmed(ctx, paths: Sequence, tolerance: int, out: tuple, rows: Sequence[int]) -> None:
-    """The files the decoders left: ``Image.open`` in this process, then ke_hash_images_trimmed per channel count."""
-    from PIL import Image
-
-    from .phash import image_to_array
-
-    hashes, boxes, has, ok = out
-    by_ch: dict = {}
-    for i in rows:
-        try:
-            with Image.open(paths[i]) as im:
-                arr = image_to_array(im)
-        except Exception:  # noqa: BLE001 - whatever Pillow raises for a file it cannot open: the file is not ok
-            continue
-        if arr.shape[0] > 0 and arr.shape[1] > 0:
-            by_ch.setdefault(1 if arr.ndim == 2 else arr.shape[2], []).append((i, arr))
-    for items in by_ch.values():
-        ph, b, t, status = ctx.hash_images_trimmed([a for _, a in items], tolerance)
-        idx = np.fromiter((i for i, _ in items), np.int64, len(items))
-        good = status == 0
-        hashes[idx[good]], boxes[idx[good]], has[idx[good]] = ph[good], b[good], t[good]
-        ok[idx[good]] = True
-
-
 def trimmed_signatures(paths: Sequence, *, tolerance: int = DEFAULT_TOLERANCE, device: int = 0):
     """(hashes u64[n], boxes int32[n, 4], has bool[n], ok bool[n]) of the files at ``paths``.
 
@@ -70,28 +43,7 @@ def trimmed_signatures(paths: Sequence, *, tolerance: int = DEFAULT_TOLERANCE, d
     cannot open has ok = False and zeros."""
     if not 0 <= int(tolerance) <= 255:
         raise ValueError(f"tolerance {tolerance} outside 0..255")
-    paths = [str(p) for p in paths]
-    n = len(paths)
-    hashes, boxes = np.zeros(n, np.uint64), np.zeros((n, 4), np.int32)
-    has, ok = np.zeros(n, bool), np.zeros(n, bool)
-    if n == 0:
-        return hashes, boxes, has, ok
-    ctx = _native.get_context(device)
-    at = {}
-    for i, p in enumerate(paths):
-        at.setdefault(p, []).append(i)
-    placed: dict = {}
-    offers = Offers("hash", list(at), placed)
-    for kind, mine in offers:
-        ph, b, t, status = ctx.hash_trimmed(None, kind=kind, paths=mine, tolerance=int(tolerance))
-        offers.ran(kind, mine, status)
-        for k, (p, st) in enumerate(zip(mine, status.tolist())):
-            if st == 0:
-                placed[p] = True
-                hashes[at[p]], boxes[at[p]], has[at[p]] = ph[k], b[k], t[k]
-                ok[at[p]] = True
-    _pillow_trimmed(ctx, paths, int(tolerance), (hashes, boxes, has, ok), [i for i in range(n) if not ok[i]])
-    return hashes, boxes, has, ok
+    return view_signatures("trimmed", paths, tolerance, device)
 
 
 __all__ = ["DEFAULT_TOLERANCE", "MIN_SIDE", "qualifies", "trimmed_signatures"]

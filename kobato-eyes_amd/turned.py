@@ -16,8 +16,7 @@ from typing import Sequence
 
 import numpy as np
 
-from . import _native
-from .formats import Offers
+from ._views import view_signatures
 
 # orientation -> what it does to the picture; the second entry is Pillow's name for it (Image.Transpose.<name>), None for 0
 ORIENTATIONS = (
@@ -57,29 +56,6 @@ def _compose_table() -> tuple:
 COMPOSE = _compose_table()
 
 
-def _pillow_turned(ctx, paths: Sequence, turned: np.ndarray, ok: np.ndarray, rows: Sequence[int]) -> None:
-    """The files the decoders left: ``Image.open`` in this process, then ke_hash_images_turned per channel count."""
-    from PIL import Image
-
-    from .phash import image_to_array
-
-    by_ch: dict = {}
-    for i in rows:
-        try:
-            with Image.open(paths[i]) as im:
-                arr = image_to_array(im)
-        except Exception:  # noqa: BLE001 - whatever Pillow raises for a file it cannot open: the file is not ok
-            continue
-        if arr.shape[0] > 0 and arr.shape[1] > 0:
-            by_ch.setdefault(1 if arr.ndim == 2 else arr.shape[2], []).append((i, arr))
-    for items in by_ch.values():
-        t, status = ctx.hash_images_turned([a for _, a in items])
-        idx = np.fromiter((i for i, _ in items), np.int64, len(items))
-        good = status == 0
-        turned[idx[good]] = t[good]
-        ok[idx[good]] = True
-
-
 def turned_signatures(paths: Sequence, *, device: int = 0):
     """(turned u64[n, 8], ok bool[n]) of the files at ``paths``.
 
@@ -88,28 +64,7 @@ def turned_signatures(paths: Sequence, *, device: int = 0):
     to ke_hash_images_turned without the pixels leaving the device.  Whatever comes back with a status other than 0, and
     every file of a suffix no decoder takes, is opened with Pillow in this process and hashed by the same call.  A file
     Pillow cannot open has ok = False and eight zeros."""
-    paths = [str(p) for p in paths]
-    n = len(paths)
-    turned = np.zeros((n, 8), np.uint64)
-    ok = np.zeros(n, bool)
-    if n == 0:
-        return turned, ok
-    ctx = _native.get_context(device)
-    at = {}
-    for i, p in enumerate(paths):
-        at.setdefault(p, []).append(i)
-    placed: dict = {}
-    offers = Offers("hash", list(at), placed)
-    for kind, mine in offers:
-        t, status = ctx.hash_turned(None, kind=kind, paths=mine)
-        offers.ran(kind, mine, status)
-        for p, row, st in zip(mine, t, status.tolist()):
-            if st == 0:
-                placed[p] = True
-                turned[at[p]] = row
-                ok[at[p]] = True
-    _pillow_turned(ctx, paths, turned, ok, [i for i in range(n) if not ok[i]])
-    return turned, ok
+    return view_signatures("turned", paths, device=device)
 
 
 __all__ = ["ORIENTATIONS", "INVERSE", "COMPOSE", "turn", "turned_signatures"]

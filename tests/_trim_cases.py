@@ -7,9 +7,8 @@ import io
 
 import numpy as np
 
+import _scan_standin
 from _turned_cases import picture
-from kobato_eyes_amd._native import EDGE_DTYPE
-from oracle import oracle as O
 
 THRESHOLD = 8
 TOLERANCE = 48
@@ -198,27 +197,9 @@ def write_files(folder) -> list:
 
 
 # ---- the scan of trimmed_edges, by the oracle ----------------------------------------------------------------------------------
-class OracleScanContext:
-    """A stand-in for _native.Context whose hamming_scan is the oracle's banded scan filtered by b >= first_new -- what
-    ke_hamming_scan_from is specified to return.  ``calls`` records the tables it was given."""
+class OracleScanContext(_scan_standin.OracleScanContext):
+    """The shared stand-in, held to the scan from first_new: trimmed_edges must not ask for the cross scan."""
 
-    def __init__(self):
-        self.calls = []
-
-    def hamming_scan(self, hashes, n, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4, size_ratio=0.0,
-                     bucket_pair_cap=0, part_index=0, part_count=1, capacity=None, first_new=None, cross=False):
-        self.calls.append(dict(n=int(n), first_new=first_new, cross=cross, hashes=np.array(hashes), ids=None if ids is None else np.array(ids),
-                               sizes=None if sizes is None else np.array(sizes)))
+    def hamming_scan(self, hashes, n, *, cross=False, **keywords):
         assert not cross
-        first_new = int(first_new or 0)
-        if n < 2:
-            return np.zeros(0, EDGE_DTYPE), np.zeros(4, np.uint64)
-        edges, c = O.scan_banded(hashes, ids=None, sizes=sizes, threshold=threshold, band_bits=band_bits, band_count=band_count,
-                                 size_ratio=size_ratio, bucket_pair_cap=bucket_pair_cap)
-        if ids is not None:
-            edges = edges[ids[edges["a"]] != ids[edges["b"]]]
-        edges = edges[edges["b"] >= first_new]
-        out = np.zeros(len(edges), EDGE_DTYPE)
-        for k in ("a", "b", "h", "bands"):
-            out[k] = edges[k]
-        return out, np.array([0, 0, len(out), int(c[0])], np.uint64)
+        return super().hamming_scan(hashes, n, cross=cross, **keywords)

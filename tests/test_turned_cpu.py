@@ -21,6 +21,7 @@ import pytest
 
 import _scan_from_cases as S
 import _turned_cases as T
+from _scan_standin import OracleScanContext
 from kobato_eyes_amd import _native, api, cli, turned
 from kobato_eyes_amd.scanner import DuplicateFile, DuplicateScanConfig, DuplicateScanner, TurnedMatch
 from oracle import oracle as O
@@ -92,25 +93,13 @@ def test_the_cross_region_arithmetic_holds(tmp_path, flags):
 
 
 # ---- turned_edges and find_turned_duplicates against the oracle's scan ------------------------------------------------------
-class _Context:
-    def __init__(self):
-        self.calls = []
+class _Context(OracleScanContext):
+    """The shared stand-in, with ``calls`` as the (n, first_new, cross) these tests compare."""
 
-    def hamming_scan(self, hashes, n, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4, size_ratio=0.0,
-                     bucket_pair_cap=0, part_index=0, part_count=1, capacity=None, first_new=None, cross=False):
-        self.calls.append((int(n), first_new, cross))
-        first_new = int(first_new or 0)
-        if n < 2:
-            return np.zeros(0, _native.EDGE_DTYPE), np.zeros(4, np.uint64)
-        edges, c = O.scan_banded(hashes, ids=None, sizes=sizes, threshold=threshold, band_bits=band_bits, band_count=band_count,
-                                 size_ratio=size_ratio, bucket_pair_cap=bucket_pair_cap)
-        if ids is not None:
-            edges = edges[ids[edges["a"]] != ids[edges["b"]]]
-        edges = edges[(edges["a"] < first_new) & (edges["b"] >= first_new)] if cross else edges[edges["b"] >= first_new]
-        out = np.zeros(len(edges), _native.EDGE_DTYPE)
-        for k in ("a", "b", "h", "bands"):
-            out[k] = edges[k]
-        return out, np.array([0, 0, len(out), int(c[0])], np.uint64)
+    def hamming_scan(self, hashes, n, **keywords):
+        out = super().hamming_scan(hashes, n, **keywords)
+        self.calls[-1] = (int(n), keywords.get("first_new"), keywords.get("cross", False))
+        return out
 
 
 @pytest.fixture

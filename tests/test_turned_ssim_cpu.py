@@ -88,8 +88,8 @@ def test_threshold_zero_keeps_what_could_be_read(stubs):
 
 
 def test_orientations_to_keeper_works_on_the_survivors(stubs):
-    clusters, matches, plain_keys = api._turned_scan(_files(), hamming_threshold=8, size_ratio=None, band_bits=16, band_count=4, device=0,
-                                                     ssim_threshold=0.9)
+    clusters, matches, plain_keys = api._view_scan("turned", _files(), hamming_threshold=8, size_ratio=None, band_bits=16, band_count=4, device=0,
+                                                   ssim_threshold=0.9)
     assert plain_keys == {(10, 11), (14, 15)}                              # 12-13's plain edge did not pass
     orient = cli.orientations_to_keeper(clusters, matches, plain_keys)
     by_members = {tuple(sorted(e.file.file_id for e in c.files)): c for c in clusters}
@@ -100,7 +100,7 @@ def test_orientations_to_keeper_works_on_the_survivors(stubs):
     want = {f: turned.COMPOSE[k][turned.INVERSE[to_10[keeper]]] for f, k in to_10.items()}
     assert {f: orient.get(f, 0) for f in to_10} == want
     # without the re-check the decoy's link and the unreadable pair would have been walked too
-    clusters0, matches0, keys0 = api._turned_scan(_files(), hamming_threshold=8, size_ratio=None, band_bits=16, band_count=4, device=0)
+    clusters0, matches0, keys0 = api._view_scan("turned", _files(), hamming_threshold=8, size_ratio=None, band_bits=16, band_count=4, device=0)
     assert keys0 == set(PLAIN) and matches0 == MATCHES
 
 
