@@ -837,6 +837,21 @@ int32_t ke_last_scan_path(ke_ctx *ctx);
  * call.  KE_EINVAL for a NULL context or a NULL plan_out. */
 int ke_last_resize_plan(ke_ctx *ctx, int32_t plan_out[8]);
 
+/* ---- for the tests of the SSIM kernels (the scores do not depend on the plan beyond the kernel's own bar): what the last SSIM
+ * launch on this context -- ke_ssim_pairs_uniform, or the last common size of ke_ssim_pairs and of the turned, boxed and viewed
+ * pair calls -- was launched as.  The rules are in csrc/ke_ssim_plan.h.
+ *   [0] kernel: 0 = NaN fill (a side under 7), 1 = exact (fp64 carries), 2 = fast (integer sums)
+ *   [1] pixels per lane (4 or 8)
+ *   [2] 1 = rows read as whole dwords, 0 = through the funnel-shift loader
+ *   [3] column blocks per image
+ *   [4] interior columns per block (250, 248, 506 or 504)
+ *   [5] interior rows per band (exact: 64; fast: 14 .. 126 in steps of 7, by the work in the launch)
+ *   [6] row bands per image
+ *   [7] why [2] is what it is: 0 = aligned, 1 = the width is no multiple of 4, 2 = the base address or the image size is no
+ *       multiple of 4, 3 = blocks of 248 / 504 columns would add a block
+ * [1]..[7] are -1 for the NaN fill; all are -1 before any such call.  KE_EINVAL for a NULL context or a NULL plan_out. */
+int ke_last_ssim_plan(ke_ctx *ctx, int32_t plan_out[8]);
+
 #ifdef __cplusplus
 }
 #endif

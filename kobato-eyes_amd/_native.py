@@ -56,7 +56,7 @@ EXPORTS = (
     "ke_interleave_shards", "ke_host_alloc", "ke_host_free", "ke_host_pack", "ke_host_read_files",
     "ke_normalise_rgb", "ke_thumbnail_rgb", "ke_thumbnail_rgb_box", "ke_reduce_rgb", "ke_jpeg_decode_scaled", "ke_jpeg_last_split", "ke_cluster_labels", "ke_ssim_pairs_uniform", "ke_ssim_pairs", "ke_ssim_pairs_turned", "ke_turn_luma", "ke_ssim_set_mode",
     "ke_resize_luma_uniform", "ke_fit_luma_uniform", "ke_tile_ahash", "ke_sad_pairs", "ke_synth_rgb", "ke_synth_rgb_indexed",
-    "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches", "ke_last_scan_path", "ke_last_resize_plan",
+    "ke_synth_hashes", "ke_last_kernel_ms", "ke_last_decode_sub_batches", "ke_last_scan_path", "ke_last_resize_plan", "ke_last_ssim_plan",
 ) + tuple(f"ke_{kind}_{call}" for kind in KINDS for call in ("probe", "decode", "caveats"))
 
 _lib: Optional[C.CDLL] = None
@@ -198,6 +198,7 @@ def load_library() -> C.CDLL:
         lib.ke_last_scan_path.argtypes = [vp]
         lib.ke_last_scan_path.restype = i32
         lib.ke_last_resize_plan.argtypes = [vp, vp]
+        lib.ke_last_ssim_plan.argtypes = [vp, vp]
         _lib = lib
         return lib
 
@@ -457,6 +458,15 @@ class Context:
         before any call (include/keyes.h: ke_last_resize_plan)."""
         plan = np.empty(8, np.int32)
         self._check(self._lib.ke_last_resize_plan(self._h, _addr(plan)), "ke_last_resize_plan")
+        return tuple(int(v) for v in plan)
+
+    def last_ssim_plan(self) -> tuple:
+        """What the last SSIM launch (ssim_pairs_uniform, or the last common size of the four pair calls) ran as: (kernel: 0 NaN
+        fill, 1 exact, 2 fast; pixels per lane; aligned loader; column blocks; columns per block; rows per band; bands; why the
+        loader: 0 aligned, 1 width, 2 base, 3 blocks); -1 where an entry does not apply and before any call (include/keyes.h:
+        ke_last_ssim_plan)."""
+        plan = np.empty(8, np.int32)
+        self._check(self._lib.ke_last_ssim_plan(self._h, _addr(plan)), "ke_last_ssim_plan")
         return tuple(int(v) for v in plan)
 
     # -- hashing ----------------------------------------------------------------------------

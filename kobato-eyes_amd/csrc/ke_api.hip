@@ -370,6 +370,14 @@ KE_API int ke_last_resize_plan(ke_ctx *ctx, int32_t plan_out[8]) {
     return KE_OK;
 }
 
+static_assert(KE_SP_COUNT == 8, "ke_last_ssim_plan reports eight entries");
+KE_API int ke_last_ssim_plan(ke_ctx *ctx, int32_t plan_out[8]) {
+    if (!ctx) return KE_EINVAL;
+    if (!plan_out) return ke_fail(ctx, KE_EINVAL, "NULL argument");
+    std::memcpy(plan_out, ctx->ssim_plan, sizeof ctx->ssim_plan);
+    return KE_OK;
+}
+
 // ---- hashing -------------------------------------------------------------------------------
 namespace {
 

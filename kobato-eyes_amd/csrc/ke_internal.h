@@ -14,6 +14,7 @@
 
 #include "../../include/keyes.h"
 #include "ke_coeffs.h"
+#include "ke_ssim_plan.h"
 #include "ke_view_plan.h"
 
 #define KE_API extern "C" __attribute__((visibility("default")))
@@ -98,6 +99,7 @@ struct ke_ctx {
     size_t h_meta_bytes = 0;
     int scan_path = -1;              // path of the last ke_hamming_scan: 0 tiles, 1 buckets (ke_last_scan_path)
     int32_t resize_plan[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // of the last group of ke_launch_resize_group (ke_last_resize_plan)
+    int32_t ssim_plan[KE_SP_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1};   // of the last ke_launch_ssim (ke_last_ssim_plan)
     bool ssim_exact = false;         // ke_ssim_set_mode: false = integer-sum kernel (default), true = fp64-carry kernel
     float *margin_cur = nullptr;     // device array the hash kernels of the CURRENT call write tie margins to (slot = hash slot)
     int64_t decode_sub_batches = 0;  // sub-batches the last ke_decode_sub_batches worked its images off in (ke_last_decode_sub_batches)
@@ -181,6 +183,7 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
                    int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
                    unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross = false);
 constexpr int KE_SCAN_STATE_WORDS = 5;   // what ke_hamming_scan reads back: counters [0..3] and the path word
+// ctx->ssim_plan holds the KE_SP_* words of the plan (ke_ssim_plan.h) that the last call launched (ke_last_ssim_plan)
 int ke_launch_ssim(ke_ctx *ctx, const uint8_t *d_images, int w, int h, int channels, const int64_t *d_pa,
                    const int64_t *d_pb, int64_t n_pairs, double *d_out);
 int ke_launch_synth_rgb(ke_ctx *ctx, uint64_t seed, int64_t first, const int64_t *d_indices, int64_t n, int w, int h,

@@ -25,7 +25,7 @@ namespace {
 // (scipy's axis-0 pass), then the horizontal windows are gathered from the two neighbouring lanes with
 // wave shuffles (axis-1 pass), again summed exactly in fp64.  division by 7: see mean7.  x = L/255 is formed arithmetically (exact).
 // ---------------------------------------------------------------------------------------
-constexpr int kBandRows = 64;     // interior rows per wave
+constexpr int kBandRows = kSsimExactBandRows;     // interior rows per wave (64)
 
 struct SsimArgs {
     const uint8_t *images;
@@ -554,51 +554,30 @@ __global__ void ke_fill_nan(double *out, int64_t n) {
 
 int ke_launch_ssim(ke_ctx *ctx, const uint8_t *d_images, int w, int h, int channels, const int64_t *d_pa,
                    const int64_t *d_pb, int64_t n_pairs, double *d_out) {
-    if (w < 7 || h < 7) {  // skimage raises for images smaller than the window
+    // what runs is decided from the shape alone, in ke_ssim_plan.h
+    const KeSsimPlan plan = ke_ssim_plan(w, h, channels, n_pairs, (int)((uintptr_t)d_images % 4), ctx->ssim_exact);
+    const int32_t words[KE_SP_COUNT] = {plan.kernel, plan.px, plan.aligned, plan.col_blocks, plan.block_cols, plan.band_rows, plan.bands, plan.why};
+    if (plan.kernel == KE_SSIM_NAN) {  // skimage raises for images smaller than the window
         hipLaunchKernelGGL(ke_fill_nan, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, ctx->stream, d_out, n_pairs);
         KE_HIP(ctx, hipGetLastError());
+        std::memcpy(ctx->ssim_plan, words, sizeof words);
         return KE_OK;
     }
     if ((int64_t)w * h * channels >= (1LL << 31)) return ke_fail(ctx, KE_EUNSUPPORTED, "image too large for the SSIM kernel");
     SsimArgs a;
     a.images = d_images; a.pa = d_pa; a.pb = d_pb;
     a.w = w; a.h = h;
-    // pixels per lane: the choice that leaves the fewest idle lanes (ties -> 4, which holds 2 waves/SIMD more easily)
-    const int cb4 = (w - 6 + 249) / 250, cb8 = (w - 6 + 505) / 506;
-    const int px = (cb8 * 506 < cb4 * 250) ? 8 : 4;
-    a.col_blocks = px == 8 ? cb8 : cb4;
-    a.block_cols = 64 * px - 6;
-    // aligned loads need dword-aligned quads: width a multiple of 4, image base and size multiples of 4, and every
-    // block starting on a multiple of 4 -- one block, or blocks of 248 / 504 columns when that does not add a block
-    bool al = w % 4 == 0 && (uintptr_t)d_images % 4 == 0 && ((size_t)w * h * channels) % 4 == 0;
-    if (al && a.col_blocks > 1) {
-        const int bca = a.block_cols & ~3;
-        if ((w - 6 + bca - 1) / bca == a.col_blocks) a.block_cols = bca; else al = false;
-    }
-    a.band_rows = kBandRows;
-    // Images of fewer than 4096 windows always take the exact kernel: skimage's float32 intermediates can be off by up to
-    // ~1e-4 in a single window of a bright, nearly flat image (uxx - ux*ux cancels); over thousands of windows that
-    // averages far below 1e-5, in a 7x7 image (one window) it is the whole score.  Such images cost nothing either way.
-    const bool exact = ctx->ssim_exact || (int64_t)(w - 6) * (h - 6) < 4096;
-    if (!exact) {
-        // the fast kernel takes rows seven at a time: bands of 7*G interior rows, G as large as leaves >= ~8 waves per SIMD
-        // of work in the launch (each band re-reads 6 halo rows), at most 18 (126 rows)
-        const int64_t groups_total = (h - 6 + 6) / 7;
-        const int64_t cols = px == 8 ? cb8 : cb4;
-        int64_t G = groups_total * n_pairs * cols / 8192;
-        G = std::max<int64_t>(2, std::min<int64_t>(18, G));
-        const int64_t nb = (groups_total + G - 1) / G;
-        G = (groups_total + nb - 1) / nb;                   // equalise the bands
-        a.band_rows = (int)(7 * G);
-    }
-    a.bands = (h - 6 + a.band_rows - 1) / a.band_rows;
-    a.items_per_pair = a.col_blocks * a.bands;
-    a.n_items = n_pairs * a.items_per_pair;
+    a.col_blocks = plan.col_blocks; a.block_cols = plan.block_cols;
+    a.band_rows = plan.band_rows; a.bands = plan.bands;
+    a.items_per_pair = plan.items_per_pair; a.n_items = plan.n_items;
+    const int px = plan.px;
+    const bool al = plan.aligned != 0, exact = plan.kernel == KE_SSIM_EXACT_KERNEL;
     const int64_t blocks = (a.n_items + 3) / 4;
     if (blocks > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "too many SSIM work items for one launch");
     void *part;
     KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_AUX, (size_t)a.n_items * sizeof(double), &part));
     a.partial = (double *)part;
+    std::memcpy(ctx->ssim_plan, words, sizeof words);
     const dim3 grid((unsigned)blocks), blk(256);
 #define KE_SSIM_LAUNCH(CH, PXV) do { \
         if (exact) { if (al) hipLaunchKernelGGL((ke_ssim_waves<CH, PXV, true>), grid, blk, 0, ctx->stream, a); \

@@ -121,6 +121,50 @@ def test_content_boxes_equal_the_definition_on_the_whole_grid_at_every_alignment
     assert [tuple(b) for b in got.tolist()] == seam_boxes
 
 
+def _long_row_images(tol: int) -> list:
+    """701 x 5 RGB pictures whose corner colour differs from channel to channel, for the rows of over 1024 bytes, where a lane
+    of the box kernel takes a second and a third vector and turns its three patterns round: one picture with every byte within
+    ``tol`` of its own channel's reference (random, the extremes among them), then pictures with a single byte at
+    ref[c] +- tol and at ref[c] +- (tol + 1), for every channel, in a lane's second vector and in its third."""
+    w, h, ref = 701, 5, np.array([10, 120, 240], np.int64)
+    rng = np.random.default_rng(T.SEED + tol)
+    base = np.empty((h, w, 3), np.uint8)
+    base[:] = ref
+    within = np.clip(ref + rng.integers(-tol, tol + 1, size=(h, w, 3)), 0, 255).astype(np.uint8)
+    within[:, ::2] = np.clip(ref + rng.choice([-tol, tol], size=(h, (w + 1) // 2, 3)), 0, 255)
+    within[0, 0] = ref
+    images = [within]
+    for x, y in ((400, 1), (690, 3)):                       # bytes 1200.. and 2070.. of the row
+        assert 1024 <= 3 * x < 2048 or 3 * x >= 2048
+        for c in range(3):
+            for d in (tol, -tol, tol + 1, -tol - 1):
+                if 0 <= ref[c] + d <= 255:
+                    px = base.copy()
+                    px[y, x, c] = ref[c] + d
+                    images.append(px)
+    return images
+
+
+@pytest.mark.parametrize("tol", [0, 1, 15, 48])
+def test_content_boxes_of_rows_over_1024_bytes_keep_each_channel_to_its_own_reference(ctx, tol):
+    """The pattern a lane holds for a dword depends on the channel of the dword's first byte, and for 3 channels it moves on by
+    one with every 64 vectors: a wrong turn compares a byte with another channel's reference, which shows only where the
+    three references differ by more than the tolerance (10, 120, 240)."""
+    pictures = _long_row_images(tol)
+    images = [px for px in pictures for _ in range(16)]
+    aligns = [a for _ in pictures for a in range(16)]
+    want = np.array([T.content_box(px, tol) for px in images], np.int32)
+    # the pictures hold what they were made to hold: no box within the tolerance, one pixel beyond it, in all three channels
+    assert not want[:16].any() and want[16:].any(axis=1).sum() >= 16 * 8 and (~want[16:].any(axis=1)).sum() >= 16 * 8
+    assert {tuple(b) for b in want[want.any(axis=1)].tolist()} == {(400, 1, 401, 2), (690, 3, 691, 4)}
+    flat, offsets = _pack_at(images, aligns)
+    with _Device(ctx, flat) as dev:
+        boxes, status = ctx.content_boxes_at(dev, offsets, [701] * len(images), [5] * len(images), 3, tol)
+    assert not status.any()
+    wrong = np.nonzero((boxes != want).any(axis=1))[0]
+    assert len(wrong) == 0, (tol, [(int(i) // 16, aligns[i], boxes[i].tolist(), want[i].tolist()) for i in wrong[:5]])
+
+
 def test_content_boxes_of_host_pixels_single_pixels_uniform_images_and_nothing(ctx):
     for ch in (1, 3, 4):
         for tol in T.TOLERANCES:
