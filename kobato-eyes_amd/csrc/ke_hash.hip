@@ -13,7 +13,8 @@
 //   * single-pass kernels, one workgroup per image, the whole chain in one launch: the image is
 //     streamed once from HBM (12 or 16 B/lane coalesced loads), luma goes to LDS as signed bytes,
 //     the 22-bit tap weights are split into three signed byte planes; the horizontal taps run on
-//     v_mfma_i32_16x16x64_i8 (exact int32), the (32x smaller) vertical taps on v_dot4_i32_i8.
+//     v_mfma_i32_16x16x64_i8 (exact int32), and so do the (32x smaller) vertical taps behind the row loop
+//     (fused_tail_mx; fused_tail, the same sums on v_dot4_i32_i8, under KE_VTILE_VALU and where LDS is short).
 //     HBM-bound by design: C*W*H bytes in, 8 (16 with dHash) out.
 //       ke_phash_fused_mx    RGB / RGBX rows up to 768 pixels, 32-row tiles, 256 threads
 //       ke_phash_fused_wide  RGB rows of 708..2048 pixels, 16-row tiles, 512 threads
@@ -304,6 +305,8 @@ __device__ __forceinline__ int combine_planes(int d0, int d1, int d2, int bias) 
     return (int)((uint32_t)d0 + ((uint32_t)d1 << 8) + ((uint32_t)d2 << 16) + (uint32_t)bias);
 }
 
+typedef int ke_v4i __attribute__((ext_vector_type(4)));   // one lane's share of a matrix-core operand or result
+
 struct KeFusedArgs {
     const uint8_t *pixels;
     const uint64_t *offsets;
@@ -338,6 +341,13 @@ struct KeFusedArgs {
     int hs_hp, hsd_hp;
     uint64_t *dhash;
     uint8_t *tile98_out;
+    // the tail's vertical taps on the matrix cores (vmx_frag != NULL; fused_tail_mx): KeMxTable::frag of the vertical
+    // 32-output axis, steps per 16-row block (a multiple of 3), first row of the two blocks' windows (multiples of 16);
+    // with a dHash leg the vertical 8-output axis, 4 * vdmx_kq steps from row 0, vdmx_kq (even) per wave
+    const int32_t *vmx_frag;
+    int vmx_ks, vmx_base0, vmx_base1;
+    const int32_t *vdmx_frag;
+    int vdmx_kq;
 };
 
 // UNAL instantiations: a row whose length is not a multiple of 4 ends in a partial quad whose load also takes the first
@@ -445,6 +455,156 @@ __device__ __forceinline__ void fused_tail(const KeFusedArgs &a, uint8_t *Lt, co
     }
 }
 
+// N operand steps of one output tile from step s on: the tap fragments (fr: this lane's slot of step 0, plane 0) ...
+template <int N>
+__device__ __forceinline__ void tail_load(ke_v4i (&fa)[N][3], const ke_v4i *fr, int s) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int p = 0; p < 3; ++p) fa[i][p] = fr[((s + i) * 3 + p) * 64];
+}
+// ... and their products with this lane's 16 rows per step of a transposed column (bp: at the window's first row)
+template <int N>
+__device__ __forceinline__ void tail_mac(ke_v4i (&acc)[3], const ke_v4i (&fa)[N][3], const uint8_t *bp, int s) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const ke_v4i bv = *reinterpret_cast<const ke_v4i *>(__builtin_assume_aligned(bp + 64 * (s + i), 16));
+#pragma unroll
+        for (int p = 0; p < 3; ++p) acc[p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[i][p], bv, acc[p], 0, 0, 0);
+    }
+}
+
+// The same tail with K1' on the matrix cores, as ke_vtile_mx does it for the banded paths: T[yy][col] = sum_y k[yy][y] *
+// HT[col][y] is the product of the tap matrix (A: 16 outputs x 64 rows per step, KeMxTable of the vertical axis) with the
+// transposed columns, which lie in LDS as a B operand does (lane = (column, 16 consecutive rows)).  Wave (mt, nt) makes
+// the 16 x 16 block of T32 at rows 16 mt, columns 16 nt; the same int32 sums as fused_tail's, so every byte behind
+// them is the same.  The dHash axis (8 outputs x 9 columns, its window the whole column) is one block whose steps the
+// four waves share, a.vdmx_kq each; the plane-combined parts meet in X (free behind the row loop) and threads 0..71 add
+// them behind the barrier T32 needs anyway, so the leg costs no barrier of its own.  The fragments come from L2 once per
+// workgroup and nothing before them depends on a load: the first group of both axes and the rounding terms are issued
+// together (tail_prefetch) and one round trip is paid for them, under the barriers that close the row loop (fused_tail paid
+// one per turn of its loops, about 28 for both hashes at 512 rows).
+// HT is free behind that barrier too: its first 72 bytes take T98.  X: 4 KB, 16-byte aligned (DH only).  The pieces:
+
+// What tail_prefetch fetches for fused_tail_mx: the fragments of the first group of steps of both axes (G = 6 steps of this
+// wave's block where it has as many, else 3; 2 of its share of the dHash axis) and the rounding terms.
+struct KeTailRegs {
+    ke_v4i fa[6][3], da[2][3], vbias;
+    int dbias;
+};
+
+// This lane's place in the tail: wave (mt, nt) makes the block of T32 at rows 16 mt, columns 16 nt.
+struct KeTailLane {
+    int lane, wv, mt, nt;
+    __device__ __forceinline__ explicit KeTailLane(int tid) {
+        asm volatile("" : "+v"(tid));     // worked out again where the tail begins, not carried through the row loop
+        lane = tid & 63; wv = __builtin_amdgcn_readfirstlane(tid >> 6); mt = wv >> 1; nt = wv & 1;
+    }
+};
+
+// Issued right behind the last tile's products, in front of the barriers that close the row loop, where the registers that
+// die with the row loop (`dead`: tap operands and pixel loads) hold what is fetched: the round trip to L2 then runs under
+// those barriers.  The other instantiations fetch where the tail begins, three steps at first, and keep their register
+// count and their waves per SIMD (profiles/hash_dispatch_table_tail_resources.txt).
+constexpr bool ke_tail_prefetch_early(bool dh, int dead) { return dead >= (dh ? 124 : 100); }
+
+template <bool DH, int G>
+__device__ __forceinline__ void tail_prefetch(const KeFusedArgs &a, const int tid, KeTailRegs &r) {
+    const KeTailLane l(tid);
+    const int ks = a.vmx_ks;
+    const ke_v4i *fr = reinterpret_cast<const ke_v4i *>(a.vmx_frag) + (size_t)l.mt * ks * 3 * 64 + l.lane;
+    if (DH) {
+        tail_load<2>(r.da, reinterpret_cast<const ke_v4i *>(a.vdmx_frag) + (size_t)l.wv * a.vdmx_kq * 3 * 64 + l.lane, 0);
+        r.dbias = a.vd_bias[min(tid / 9, 7)];       // threads 0..71 finish the dHash tile, row tid / 9
+    }
+    r.vbias = *reinterpret_cast<const ke_v4i *>(a.v_bias + 16 * l.mt + 4 * (l.lane >> 4));
+    if (G == 6 && ks >= 6) {
+        tail_load<6>(r.fa, fr, 0);
+    } else {
+        tail_load<3>(reinterpret_cast<ke_v4i (&)[3][3]>(r.fa), fr, 0);
+    }
+}
+
+template <bool DH, int G>
+__device__ __forceinline__ void fused_tail_mx(const KeFusedArgs &a, const KeTailRegs &r, uint8_t *Lt, uint8_t *HT, const uint8_t *HTd,
+                                              uint8_t *X, const int tid, const int64_t img) {
+    uint8_t *T32 = Lt;
+    double *Td = reinterpret_cast<double *>(Lt + 1024);
+    float *cf = reinterpret_cast<float *>(Lt + 1024 + 2048);
+    uint8_t *T98 = HT;
+    const KeTailLane l(tid);
+    const int lane = l.lane, wv = l.wv, mt = l.mt, nt = l.nt;
+    const int ks = a.vmx_ks, kq = DH ? a.vdmx_kq : 0;
+    const ke_v4i *fr = reinterpret_cast<const ke_v4i *>(a.vmx_frag) + (size_t)mt * ks * 3 * 64 + lane;
+    const ke_v4i *dfr = DH ? reinterpret_cast<const ke_v4i *>(a.vdmx_frag) + (size_t)wv * kq * 3 * 64 + lane : nullptr;
+    const uint8_t *bp = HT + (size_t)(16 * nt + (lane & 15)) * a.hp + (mt ? a.vmx_base1 : a.vmx_base0) + 16 * (lane >> 4);
+    const uint8_t *dbp = HTd + (size_t)min(lane & 15, 8) * a.hpd + 64 * wv * kq + 16 * (lane >> 4);
+    const ke_v4i vbias = r.vbias;
+    ke_v4i acc[3], dacc[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) acc[p] = dacc[p] = ke_v4i{0, 0, 0, 0};
+    int s;
+    if (G == 6 && ks >= 6) {
+        tail_mac<6>(acc, r.fa, bp, 0);
+        s = 6;
+    } else {
+        tail_mac<3>(acc, reinterpret_cast<const ke_v4i (&)[3][3]>(r.fa), bp, 0);
+        s = 3;
+    }
+    for (; s < ks; s += 3) {
+        ke_v4i fa[3][3];
+        tail_load<3>(fa, fr, s);
+        tail_mac<3>(acc, fa, bp, s);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)     // result register i: output row 16 mt + 4 (lane >> 4) + i, column 16 nt + (lane & 15)
+        T32[(16 * mt + 4 * (lane >> 4) + i) * 32 + 16 * nt + (lane & 15)] = (uint8_t)clip8_fixed(combine_planes(acc[0][i], acc[1][i], acc[2][i], vbias[i]));
+    if (DH) {
+        tail_mac<2>(dacc, r.da, dbp, 0);
+        for (int d = 2; d < kq; d += 2) {
+            ke_v4i fa[2][3];
+            tail_load<2>(fa, dfr, d);
+            tail_mac<2>(dacc, fa, dbp, d);
+        }
+        ke_v4i part;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) part[i] = combine_planes(dacc[0][i], dacc[1][i], dacc[2][i], 0);
+        reinterpret_cast<ke_v4i *>(X)[wv * 64 + lane] = part;
+    }
+    __syncthreads();
+    if (a.tile32_out)
+        reinterpret_cast<uint32_t *>(a.tile32_out + (size_t)img * 1024)[tid] = reinterpret_cast<const uint32_t *>(T32)[tid];
+    if (DH && tid < 72) {
+        // output (yy, oc) is result register yy & 3 of lane 16 (yy >> 2) + oc in each wave's part
+        const int yy = tid / 9, oc = tid % 9;
+        const int *xp = reinterpret_cast<const int *>(X) + (16 * (yy >> 2) + oc) * 4 + (yy & 3);
+        const uint32_t sum = (uint32_t)xp[0] + (uint32_t)xp[256] + (uint32_t)xp[512] + (uint32_t)xp[768] + (uint32_t)r.dbias;
+        T98[tid] = (uint8_t)clip8_fixed((int)sum);
+    }
+    // ---- K2: DCT corner, mean, bits (its two barriers also publish T98)
+    const int64_t slot = a.out_idx ? a.out_idx[img] : img;
+    const uint64_t hv = tile32_to_phash(T32, Td, cf, tid, (a.margin && a.phash) ? a.margin + slot : nullptr);
+    if (tid == 0 && a.phash) a.phash[slot] = hv;
+    if (DH) {
+        // ---- K3
+        if (a.tile98_out && tid < 72) a.tile98_out[(size_t)img * 72 + tid] = T98[tid];
+        if (tid < 64) {
+            const int r = tid >> 3, c = tid & 7;
+            const unsigned long long m = __ballot(T98[r * 9 + c + 1] > T98[r * 9 + c]);   // src/sig/phash.py:52
+            if (tid == 0 && a.dhash) a.dhash[slot] = __brevll(m);
+        }
+    }
+}
+
+// The kernel's arguments as fused_tail_mx reads them: from the kernarg segment again, behind the row loop.  Read off the
+// by-value parameter they are all fetched at the kernel's entry and sit in scalar registers through the row loop, which
+// has none to spare (the overflow goes to vector registers, which has none to spare either).
+__device__ __forceinline__ const KeFusedArgs &tail_args() {
+    auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));      // no load through kp moves above this point
+    return *(const KeFusedArgs *)kp;
+}
+
 int upload_dct_tables(ke_ctx *ctx) {
     if (ctx->dct_tables_ready) return KE_OK;
     KE_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_C32), KE_C32, sizeof(KE_C32)));
@@ -478,7 +638,6 @@ int upload_dct_tables(ke_ctx *ctx) {
 // for the loads right after issuing them, an unguarded one would fetch 1/ntiles more bytes from HBM).
 // ---------------------------------------------------------------------------------------
 constexpr int kRTM = kKeTileRowsMx;
-typedef int ke_v4i __attribute__((ext_vector_type(4)));
 
 // dHash leg (DH): the 9-output axis is one more 16-column operand tile whose taps span the whole row,
 // ceil(W/64) steps.  The two waves of a row block take one half of those steps each (KD per wave, columns
@@ -645,6 +804,11 @@ __global__ __launch_bounds__(256, 2) void ke_phash_fused_mx(const KeFusedArgs a)
         __syncthreads();
     }
     hpass(ntiles - 1, Lt + ((ntiles - 1) & 1) * a.lt_half);
+    const KeFusedArgs &ta = tail_args();
+    const bool tail_mx = ta.vmx_frag != nullptr;
+    KeTailRegs tr;
+    constexpr bool EARLY = ke_tail_prefetch_early(DH, 12 * KS + (DH ? 12 * KD : 0) + QPT * C);
+    if (EARLY && tail_mx) tail_prefetch<DH, EARLY ? 6 : 3>(ta, tid, tr);
     __syncthreads();
     if (DH) {
         if (!jt) finish_dhash(ntiles - 1);
@@ -655,7 +819,10 @@ __global__ __launch_bounds__(256, 2) void ke_phash_fused_mx(const KeFusedArgs a)
         if (DH) band_writeout(HTd, a.hpd, 9, h, a.hsd + (size_t)img * 9 * a.hsd_hp + y_begin, a.hsd_hp, tid, 256);
         return;
     }
-    fused_tail<(DH ? 1 : 0)>(a, Lt, HT, HTd, tid, img);
+    if (tail_mx) {
+        if (!EARLY) tail_prefetch<DH, EARLY ? 6 : 3>(ta, tid, tr);
+        fused_tail_mx<DH, EARLY ? 6 : 3>(ta, tr, Lt, HT, HTd, X, tid, img);
+    } else fused_tail<(DH ? 1 : 0)>(a, Lt, HT, HTd, tid, img);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -829,6 +996,11 @@ __global__ __launch_bounds__(512, 1) void ke_phash_fused_wide(const KeFusedArgs 
         __syncthreads();
     }
     hpass(ntiles - 1, Lt + ((ntiles - 1) & 1) * a.lt_half);
+    const KeFusedArgs &ta = tail_args();
+    const bool tail_mx = ta.vmx_frag != nullptr;
+    KeTailRegs tr;
+    constexpr bool EARLY = ke_tail_prefetch_early(DH, 12 * KSH + (DH ? 12 * KDW : 0) + QPT * C);
+    if (EARLY && tail_mx && tid < 256) tail_prefetch<DH, EARLY ? 6 : 3>(ta, tid, tr);
     __syncthreads();
     if (!kh) finish(ntiles - 1);
     if (DH && !wv) dfinish(ntiles - 1);
@@ -840,7 +1012,10 @@ __global__ __launch_bounds__(512, 1) void ke_phash_fused_wide(const KeFusedArgs 
     }
     // the tail is written for 256 threads; the other four waves are done (ended waves leave the barrier count)
     if (tid >= 256) return;
-    fused_tail<(DH ? 1 : 0)>(a, Lt, HT, HTd, tid, img);
+    if (tail_mx) {
+        if (!EARLY) tail_prefetch<DH, EARLY ? 6 : 3>(ta, tid, tr);
+        fused_tail_mx<DH, EARLY ? 6 : 3>(ta, tr, Lt, HT, HTd, X, tid, img);
+    } else fused_tail<(DH ? 1 : 0)>(a, Lt, HT, HTd, tid, img);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1470,7 +1645,7 @@ struct KeBandTarget {
 // fit.  Both families take the same KeFusedArgs; they differ in the tile (32 rows by 256 threads, 16 by 512), in how
 // the operand steps are counted, and in the exchange area behind the columns.
 int launch_fused(ke_ctx *ctx, int r, const KeHashGroup &g, const KeAxisCoeffs *ch, const KeAxisCoeffs *cv, uint64_t *d_phash,
-                 uint8_t *d_tile32, uint64_t *d_dhash, uint8_t *d_tile98, const KeBandTarget *bands) {
+                 uint8_t *d_tile32, uint64_t *d_dhash, uint8_t *d_tile98, const KeBandTarget *bands, const KeHashSwitches &sw) {
     const bool DH = kKeSpRows[r].dh();
     const KeFusedSteps steps = ke_plan_fused_steps(r, g.w);
     if (steps.why) return declined(ctx, steps.why);
@@ -1487,6 +1662,19 @@ int launch_fused(ke_ctx *ctx, int r, const KeHashGroup &g, const KeAxisCoeffs *c
     }
     const KeFusedPlan p = ke_plan_fused(r, g.w, g.h, g.n, steps, *mx, cv->span, mxd, tv, bands ? bands->plan : nullptr);
     if (p.why) return declined(ctx, p.why);
+    // one workgroup per image: the tail's vertical taps on the matrix cores, where its longer columns fit (the tables
+    // are built for the step counts the tail issues in one go)
+    KeFusedTailPlan tail{false, p.hp, p.hpd, p.x_off, p.lds, p.raise_lds_limit, 0, 0};
+    const KeMxTable *vmx = nullptr, *vdmx = nullptr;
+    if (!bands && !sw.vtile_valu) {
+        const KeMxTable *nat = ke_get_mx(ctx, cv), *natd = DH ? ke_get_mx(ctx, cvd) : nullptr;
+        if (!nat || (DH && !natd)) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+        const int want = ke_fused_tail_steps(nat->ks), wantd = DH ? ke_fused_tail_dsteps(natd->ks) : 0;
+        vmx = want == nat->ks ? nat : ke_get_mx(ctx, cv, want);
+        if (DH) vdmx = wantd == natd->ks ? natd : ke_get_mx(ctx, cvd, wantd);
+        if (!vmx || (DH && !vdmx)) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
+        tail = ke_plan_fused_tail(r, p, *vmx, vdmx, sw);
+    }
     KeFusedArgs a;
     std::memset(&a, 0, sizeof a);
     a.pixels = g.pixels; a.offsets = g.offsets; a.stride = g.stride; a.out_idx = g.out_idx; a.h = g.h;
@@ -1498,7 +1686,7 @@ int launch_fused(ke_ctx *ctx, int r, const KeHashGroup &g, const KeAxisCoeffs *c
     a.qw = p.qw; a.qw_inv = p.qw_inv; a.lp = p.lp;
     a.w = g.w; a.row_bytes = p.row_bytes;
     a.lt_half = p.lt_half; a.lt_bytes = 2 * p.lt_half;
-    a.hp = p.hp; a.hpd = p.hpd; a.x_off = p.x_off;
+    a.hp = tail.hp; a.hpd = tail.hpd; a.x_off = tail.x_off;
     a.phash = d_phash; a.tile32_out = d_tile32; a.margin = ctx->margin_cur;
     if (DH) {
         a.mxd_frag = mxd->d_frag;
@@ -1507,9 +1695,13 @@ int launch_fused(ke_ctx *ctx, int r, const KeHashGroup &g, const KeAxisCoeffs *c
         a.ndwcv = tv->ndwc;
         a.dhash = d_dhash; a.tile98_out = d_tile98;
     }
-    if (p.raise_lds_limit)
-        KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kSpKernels[r]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    hipLaunchKernelGGL(kSpKernels[r], dim3((unsigned)p.workgroups), dim3(p.threads), p.lds, ctx->stream, a);
+    if (tail.on_mx) {
+        a.vmx_frag = vmx->d_frag; a.vmx_ks = tail.ks; a.vmx_base0 = vmx->base[0]; a.vmx_base1 = vmx->base[1];
+        if (DH) { a.vdmx_frag = vdmx->d_frag; a.vdmx_kq = tail.kdq; }
+    }
+    if (tail.raise_lds_limit)
+        KE_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kSpKernels[r]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail.lds));
+    hipLaunchKernelGGL(kSpKernels[r], dim3((unsigned)p.workgroups), dim3(p.threads), tail.lds, ctx->stream, a);
     KE_HIP(ctx, hipGetLastError());
     return KE_OK;
 }
@@ -1520,7 +1712,7 @@ int launch_fused(ke_ctx *ctx, int r, const KeHashGroup &g, const KeAxisCoeffs *c
 // transposed columns go to bands->hs / bands->hsd and the caller finishes with ke_vtile.  *did_d: dHash was covered too.
 // Returns KE_EUNSUPPORTED when no single-pass kernel takes the shape (or its LDS needs exceed the CU).
 int dispatch_single_pass(ke_ctx *ctx, const KeHashGroup &g, bool want_d, uint64_t *d_phash, uint8_t *d_t32, uint64_t *d_dhash,
-                         uint8_t *d_t98, const KeBandTarget *bands, bool *did_d) {
+                         uint8_t *d_t98, const KeBandTarget *bands, const KeHashSwitches &sw, bool *did_d) {
     *did_d = false;
     // ragged groups: ke_hash_images checks every offset and sets g.misaligned when one is not a multiple of 4
     const KeSpShape shape{g.w, g.h, g.channels, g.misaligned, (uintptr_t)g.pixels % 4 == 0, g.offsets || g.stride % 4 == 0,
@@ -1533,7 +1725,7 @@ int dispatch_single_pass(ke_ctx *ctx, const KeHashGroup &g, bool want_d, uint64_
     if (!ch || !cv) return ke_fail(ctx, KE_EHIP, "coefficient upload failed");
     for (int k = 0; k < n; ++k) {
         const bool dh = kKeSpRows[rows[k]].dh();
-        const int rc = launch_fused(ctx, rows[k], g, ch, cv, d_phash, d_t32, dh ? d_dhash : nullptr, dh ? d_t98 : nullptr, bands);
+        const int rc = launch_fused(ctx, rows[k], g, ch, cv, d_phash, d_t32, dh ? d_dhash : nullptr, dh ? d_t98 : nullptr, bands, sw);
         if (rc != KE_EUNSUPPORTED) { *did_d = dh && rc == KE_OK; return rc; }
     }
     return KE_EUNSUPPORTED;
@@ -1551,7 +1743,7 @@ int resample_single_pass_banded(ke_ctx *ctx, const KeHashGroup &g, uint8_t *d_t3
     void *hs;
     KE_TRY(ke_reserve(ctx, KE_BUF_TMP, p.scratch_bytes, &hs));
     const KeBandTarget bands{&p, (uint8_t *)hs, cvd ? (uint8_t *)hs + (size_t)g.n * 32 * p.hs_hp : nullptr};
-    KE_TRY(dispatch_single_pass(ctx, g, d_t98 != nullptr, nullptr, nullptr, nullptr, nullptr, &bands, did_d));
+    KE_TRY(dispatch_single_pass(ctx, g, d_t98 != nullptr, nullptr, nullptr, nullptr, nullptr, &bands, sw, did_d));
     KE_TRY(launch_vtile(ctx, bands.hs, p.hs_hp, g.n, 32, 32, cvt, d_t32, sw));
     if (*did_d) KE_TRY(launch_vtile(ctx, bands.hsd, p.hsd_hp, g.n, 9, 8, cvd, d_t98, sw));
     return KE_OK;
@@ -1572,7 +1764,7 @@ int ke_launch_hash_group(ke_ctx *ctx, const KeHashGroup &g, uint64_t *d_phash, u
         // neighbouring size groups' kernels (what follows below uses the context's scratch and stays on the context's stream)
         hipStream_t home = ctx->stream;
         if (fused_stream) ctx->stream = fused_stream;
-        const int rc = dispatch_single_pass(ctx, g, want_d, d_phash, d_tile32_out, d_dhash, d_tile98_out, nullptr, &did_d);
+        const int rc = dispatch_single_pass(ctx, g, want_d, d_phash, d_tile32_out, d_dhash, d_tile98_out, nullptr, sw, &did_d);
         ctx->stream = home;
         if (rc == KE_OK) { p_done = true; d_done = did_d; }
         else if (rc != KE_EUNSUPPORTED) return rc;

@@ -323,6 +323,22 @@ struct KeFusedPlan {
     bool raise_lds_limit;                          // over the 64 KiB a kernel gets without the attribute
 };
 
+// LDS of a single-pass workgroup: two luma tile buffers, the 32 transposed columns (pitch hp), the 9 of the dHash leg (pitch
+// hpd) and the exchange area X behind them: the wide kernel's waves always meet there (12 KB, and 14 KB more for the dHash
+// leg), the narrow kernel's only for its dHash leg (4 KB).  *x_off: where X begins (0 without one).
+inline size_t ke_fused_lds(bool wide, bool DH, int lt_half, int hp, int hpd, int *x_off) {
+    size_t lds = (size_t)2 * lt_half + (size_t)32 * hp;
+    if (!wide) lds = std::max<size_t>(lds, 4096);
+    if (DH) lds += (size_t)9 * hpd;
+    *x_off = 0;
+    if (wide || DH) {
+        lds = (lds + 15) & ~(size_t)15;
+        *x_off = (int)lds;
+        lds += wide ? 2 * 2 * 3 * 1024 + (DH ? 2 * 7 * 1024 : 0) : 4096;
+    }
+    return lds;
+}
+
 // Row r of the table on images of W x h; bands: NULL for one workgroup per image.  mx: operands of the 32-output horizontal
 // axis at KeFusedSteps::ks; vspan: span of the vertical axis to 32 rows.  For a row with a dHash leg, mxd: operands of the
 // 9-output axis at ksd; vd: the vertical axis to 8 rows in 3 chunks.
@@ -347,20 +363,11 @@ inline KeFusedPlan ke_plan_fused(int r, int W, int h, int64_t n, const KeFusedSt
     p.lt_half = (rt * p.lp + overhang + 15) & ~15;
     p.hp = ((std::max(bands ? 0 : vspan, rows_padded) + 7) & ~7) + 8;
     p.hpd = 8;
-    p.lds = (size_t)2 * p.lt_half + (size_t)32 * p.hp;
-    if (!wide) p.lds = std::max<size_t>(p.lds, 4096);
     if (DH) {
         if (mxd->tiles != 1 || mxd->base[0] != 0 || mxd->ks != s.ksd) { p.why = KE_DECLINE_FU_DH_TABLE; return p; }
         p.hpd = ((std::max(bands ? 0 : vd->cspan, rows_padded) + 7) & ~7) + 8;
-        p.lds += (size_t)9 * p.hpd;
     }
-    // the exchange area X behind the columns: the wide kernel's waves always meet there (12 KB, and 14 KB more for the
-    // dHash leg), the narrow kernel's only for its dHash leg (4 KB)
-    if (wide || DH) {
-        p.lds = (p.lds + 15) & ~(size_t)15;
-        p.x_off = (int)p.lds;
-        p.lds += wide ? 2 * 2 * 3 * 1024 + (DH ? 2 * 7 * 1024 : 0) : 4096;
-    }
+    p.lds = ke_fused_lds(wide, DH, p.lt_half, p.hp, p.hpd, &p.x_off);
     // up to 80 KB two workgroups share a CU.  A tall image (its 32 x H transposed columns) would need more and run one
     // per CU; if cutting it into bands brings the columns back under that line, decline: the caller then runs this
     // kernel per band (measured 5.4-6.0 TB/s against 3.9-4.9 for one workgroup per CU)
@@ -370,6 +377,49 @@ inline KeFusedPlan ke_plan_fused(int r, int W, int h, int64_t n, const KeFusedSt
     p.workgroups = n * (bands ? bands->bands : 1);
     if (!ke_fits_one_launch(p.workgroups)) p.why = KE_DECLINE_ONE_LAUNCH;
     return p;
+}
+
+// ---- the tail of the single-pass kernels: the vertical taps on the matrix cores -----------------------------------------
+// One workgroup per image: behind the row loop four waves turn the transposed columns into the 32 x 32 tile, one 16 x 16
+// block each, out of the KeMxTable of the vertical axis; with a dHash leg each wave also takes a quarter of the 8-output
+// axis' operand steps.  The steps are issued in fixed groups, so the tables are built for rounded step counts:
+constexpr int kKeTailStepGroup = 3, kKeTailDStepGroup = 2;
+// ... of the 32-output axis, from the count its table has unpadded (ke_build_mx with min_ks = 0)
+inline int ke_fused_tail_steps(int natural_ks) { return (natural_ks + kKeTailStepGroup - 1) / kKeTailStepGroup * kKeTailStepGroup; }
+// ... of the 8-output axis: four equal parts, each a whole number of groups
+inline int ke_fused_tail_dsteps(int natural_ks) {
+    const int per_wave = ((natural_ks + 3) / 4 + kKeTailDStepGroup - 1) / kKeTailDStepGroup * kKeTailDStepGroup;
+    return 4 * per_wave;
+}
+
+struct KeFusedTailPlan {
+    bool on_mx;              // false: the dot-product tail, and the plan stays as ke_plan_fused made it
+    int hp, hpd, x_off;      // on_mx: these replace the KeFusedPlan's
+    size_t lds;
+    bool raise_lds_limit;
+    int ks, kdq;             // operand steps per 16-row block of the tile; dHash steps per wave
+};
+
+// p: what ke_plan_fused answered for row r without bands.  vmx: the vertical 32-output axis at ke_fused_tail_steps; vdmx
+// (rows with a dHash leg): the vertical 8-output axis at ke_fused_tail_dsteps.  A step reads 64 rows of every column,
+// and the steps of a block run to base + 64 * ks whatever the image's height: rows past it meet zero taps, but the
+// columns are lengthened so that every read stays inside the column area.  The pitch becomes an odd number of 16-byte
+// units: 16-byte reads, and the 16 columns of an operand (and of the row loop's dword stores) in distinct banks.  Where
+// the longer columns would cost the second workgroup of a CU (80 KB each) or pass the kernel's LDS, the shape keeps the
+// dot-product tail; so it does under KE_VTILE_VALU.
+inline KeFusedTailPlan ke_plan_fused_tail(int r, const KeFusedPlan &p, const KeMxTable &vmx, const KeMxTable *vdmx, const KeHashSwitches &sw) {
+    const KeSpRow &row = kKeSpRows[r];
+    const bool wide = row.family == KE_SP_WIDE, DH = row.dh();
+    KeFusedTailPlan t{false, p.hp, p.hpd, p.x_off, p.lds, p.raise_lds_limit, 0, 0};
+    if (sw.vtile_valu || vmx.tiles != 2 || vmx.ks % kKeTailStepGroup) return t;
+    if (DH && (!vdmx || vdmx->tiles != 1 || vdmx->base[0] != 0 || vdmx->ks % (4 * kKeTailDStepGroup))) return t;
+    auto odd16 = [](int bytes) { return (((bytes + 15) / 16) | 1) * 16; };
+    const int hp = odd16(std::max(p.hp, std::max(vmx.base[0], vmx.base[1]) + 64 * vmx.ks));
+    const int hpd = DH ? odd16(std::max(p.hpd, 64 * vdmx->ks)) : p.hpd;
+    int x_off = 0;
+    const size_t lds = ke_fused_lds(wide, DH, p.lt_half, hp, hpd, &x_off);
+    if (lds > 150 * 1024 || (p.lds <= 80 * 1024 && lds > 80 * 1024)) return t;
+    return {true, hp, hpd, x_off, lds, lds > 64 * 1024, vmx.ks, DH ? vdmx->ks / 4 : 0};
 }
 
 // ---- ke_resample_pass: two single-axis passes in Pillow's order -------------------------------------------------------
