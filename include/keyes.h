@@ -561,6 +561,28 @@ int ke_hamming_scan_cross(ke_ctx *ctx, const uint64_t *hashes, const int64_t *id
                           int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
                           int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out);
 
+/* The exact scan: every pair of a region within the threshold, with no band predicate.  The edge set is
+ *   { (a < b) in the region : popcount(x_a ^ x_b) <= threshold, ids[a] != ids[b], size_ok as ke_hamming_scan }
+ * region 0: all pairs, first_new must be 0; region 1: b >= first_new (ke_hamming_scan_from's pairs); region 2:
+ * a < first_new <= b (ke_hamming_scan_cross's pairs).  e.h as in the banded scans.  e.bands is the mask ke_hamming_scan gives
+ * without a pair cap, computed from band_bits / band_count, and 0 for a pair that shares no band: { e : e.bands != 0 } is
+ * exactly the banded call's edge set for the same region and arguments.  There is no bucket_pair_cap: the cap is a property
+ * of buckets.
+ * The call goes straight to the all-pairs tile kernel: no band histogram, no sorted copy, no bucket statistics;
+ * KE_SCAN_MODE is ignored and ke_last_scan_path reports 0.  A shard's tiles are launched in consecutive slices of at most
+ * KE_SCAN_TILES_PER_LAUNCH tiles (read once per process; default and ceiling 8 388 607, what one launch holds), so the
+ * tile limits of the three calls above do not apply here.
+ * counters_out: [0] the region's pairs this shard stands for, counted and checked as above; [1] sum over the edges of the
+ * number of shared bands; [2] edges; [3] 0.
+ * 0 <= threshold <= 64.  At 64 every pair is within the threshold, every 16-column block of every tile takes the kernel's rare
+ * path and every pair goes through the edge cursor: correct, and slow -- the kernel is built for thresholds at which edges are
+ * rare.  first_new outside [0, n], a region outside 0..2 and region 0 with first_new != 0 are KE_EINVAL; the other KE_EINVAL
+ * cases, part_index / part_count, host or device pointers, capacity and *n_edges_out behave as above. */
+int ke_hamming_scan_exact(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
+                          int64_t first_new, int32_t region, int32_t part_index, int32_t part_count, int32_t threshold,
+                          int32_t band_bits, int32_t band_count, double size_ratio, ke_edge *edges_out, int64_t capacity,
+                          int64_t *n_edges_out, uint64_t *counters_out);
+
 /* ---- ranked search.  A capability of this library only (the reference has no such call): the k nearest entries of a table
  * for each of m queries, by Hamming distance alone.  For query q
  *   S_q = { i < n : popcount(hashes[i] ^ queries[q]) <= max_distance,

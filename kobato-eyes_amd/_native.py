@@ -48,7 +48,7 @@ EXPORTS = (
     "ke_abi_version", "ke_create", "ke_create_error", "ke_destroy", "ke_last_error", "ke_set_stream",
     "ke_get_stream", "ke_synchronize", "ke_device_info", "ke_malloc", "ke_free", "ke_memcpy",
     "ke_hash_images", "ke_hash_uniform", "ke_hash_images_ex", "ke_hash_uniform_ex", "ke_luma_tiles_uniform", "ke_hamming_scan",
-    "ke_hamming_scan_from", "ke_hamming_scan_cross", "ke_hamming_nearest", "ke_tiles_turned", "ke_hash_images_turned", "ke_band_pairs_after_size",
+    "ke_hamming_scan_from", "ke_hamming_scan_cross", "ke_hamming_scan_exact", "ke_hamming_nearest", "ke_tiles_turned", "ke_hash_images_turned", "ke_band_pairs_after_size",
     "ke_content_boxes", "ke_crop_pack", "ke_hash_images_trimmed", "ke_crop_luma", "ke_ssim_pairs_boxed",
     "ke_crop_turn_luma", "ke_ssim_pairs_viewed", "ke_hash_images_turned_trimmed",
     "ke_stage_create", "ke_stage_create_shared", "ke_stage_destroy", "ke_stage_acquire", "ke_stage_submit_hash", "ke_stage_wait",
@@ -167,6 +167,7 @@ def load_library() -> C.CDLL:
         lib.ke_hamming_scan_from.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, dbl, i64, vp, i64,
                                              C.POINTER(i64), vp]
         lib.ke_hamming_scan_cross.argtypes = lib.ke_hamming_scan_from.argtypes
+        lib.ke_hamming_scan_exact.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, i32, i32, i32, dbl, vp, i64, vp, vp]
         lib.ke_hamming_nearest.argtypes = [vp, vp, vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]
         lib.ke_tiles_turned.argtypes = [vp, vp, i64, vp]
         lib.ke_hash_images_turned.argtypes = [vp, vp, vp, vp, vp, i32, i64, vp, vp]
@@ -1085,14 +1086,19 @@ class Context:
     # -- scan -------------------------------------------------------------------------------
     def hamming_scan(self, hashes, n: int, *, ids=None, sizes=None, threshold=8, band_bits=16, band_count=4,
                      size_ratio: float = 0.0, bucket_pair_cap: int = 0, part_index=0, part_count=1,
-                     capacity: Optional[int] = None, first_new: Optional[int] = None, cross: bool = False):
+                     capacity: Optional[int] = None, first_new: Optional[int] = None, cross: bool = False, exact: bool = False):
         """Returns (edges[EDGE_DTYPE] on the host, counters u64[4]).  hashes/ids/sizes: host arrays or device ptrs.
         first_new > 0: only the edges whose later position is at least first_new (ke_hamming_scan_from); counters[0] is
         then the region's pair count, [1] and [2] are over those edges, [3] stays the whole table's.
         cross=True (needs first_new): the table is [library | queries] and only the edges a < first_new <= b come back
-        (ke_hamming_scan_cross); counters[0] is first_new * (n - first_new) over the shards."""
+        (ke_hamming_scan_cross); counters[0] is first_new * (n - first_new) over the shards.
+        exact=True (ke_hamming_scan_exact): every pair of the same region -- all pairs, from first_new, or cross -- within the
+        threshold, whether or not it shares a band; ``bands`` is 0 for a pair that shares none, so the edges with bands != 0 are
+        the banded call's.  counters[3] is 0.  A bucket pair cap has no meaning there: ValueError with a non-zero one."""
         if cross and first_new is None:
             raise ValueError("cross=True needs first_new")
+        if exact and int(bucket_pair_cap or 0) != 0:
+            raise ValueError("exact=True takes no bucket_pair_cap: the cap is a property of buckets")
         first_new = int(first_new or 0)
 
         def host(a, dt):
@@ -1105,7 +1111,12 @@ class Context:
         while True:
             edges = np.empty(cap, EDGE_DTYPE)
             with self._lock:
-                if cross:
+                if exact:
+                    self._check(self._lib.ke_hamming_scan_exact(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, first_new,
+                                                                2 if cross else 1 if first_new else 0, part_index, part_count,
+                                                                threshold, band_bits, band_count, float(size_ratio), _addr(edges),
+                                                                cap, C.byref(n_edges), _addr(counters)), "ke_hamming_scan_exact")
+                elif cross:
                     self._check(self._lib.ke_hamming_scan_cross(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, first_new,
                                                                 part_index, part_count, threshold, band_bits, band_count,
                                                                 float(size_ratio), int(bucket_pair_cap), _addr(edges), cap,

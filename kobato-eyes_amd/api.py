@@ -86,7 +86,7 @@ def _ssim_kept(edges: list, candidates: Sequence[DuplicateFile], ssim_threshold:
 def find_duplicates(files: Iterable, *, hamming_threshold: int = 8, ssim_threshold: Optional[float] = None,
                     size_ratio: Optional[float] = None, band_bits: int = 16, band_count: int = 4,
                     scanner_factory: Callable[[DuplicateScanConfig], DuplicateScanner] = DuplicateScanner,
-                    device: Optional[int] = None, devices: Optional[Sequence[int]] = None) -> list:
+                    device: Optional[int] = None, devices: Optional[Sequence[int]] = None, exact: bool = False) -> list:
     """Clusters of near-duplicates.
 
     ``files``: DuplicateFile objects or row mappings (anything ``DuplicateFile.from_row`` takes;
@@ -94,12 +94,14 @@ def find_duplicates(files: Iterable, *, hamming_threshold: int = 8, ssim_thresho
     set, every candidate edge is re-checked with the SSIM kernel on the files' pixels and only
     edges with ``ssim >= ssim_threshold`` survive into the clusters.  ``devices``: the SSIM re-check is spread over one worker
     process per entry (``refine_pairs``); the scan stays in this process, on ``device`` (default ``devices[0]``, else 0).
+    ``exact``: every pair within ``hamming_threshold`` is a candidate edge, whether or not it shares a band
+    (``DuplicateScanConfig.exact``; ``DuplicateScanner`` says what else changes under it).
     """
     if device is None:
         device = int(devices[0]) if devices else 0
     parsed = _parse_files(files)
     config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
-                                 band_count=band_count)
+                                 band_count=band_count, exact=bool(exact))
     scanner = _make_scanner(scanner_factory, config, device)
     if ssim_threshold is None:
         return scanner.build_clusters(parsed)
@@ -117,7 +119,7 @@ def find_new_duplicates(library: Iterable, added: Iterable, *, previous: Optiona
                         hamming_threshold: int = 8, ssim_threshold: Optional[float] = None, size_ratio: Optional[float] = None,
                         band_bits: int = 16, band_count: int = 4,
                         scanner_factory: Callable[[DuplicateScanConfig], DuplicateScanner] = DuplicateScanner,
-                        device: Optional[int] = None, devices: Optional[Sequence[int]] = None) -> list:
+                        device: Optional[int] = None, devices: Optional[Sequence[int]] = None, exact: bool = False) -> list:
     """The clusters that contain at least one file of ``added``, from a scan of only the pairs that touch an added file:
     the pairs between two ``library`` files, which an earlier run judged, are neither scanned nor re-checked.
 
@@ -129,12 +131,13 @@ def find_new_duplicates(library: Iterable, added: Iterable, *, previous: Optiona
     should come from a run with the same ``ssim_threshold``.  Without ``previous`` the clusters are assembled from the
     new edges alone: a link between two library files is then absent, so two library files appear together only when an
     added file (or a chain of them) connects them, and a library member's best_hamming is taken over its new edges only.
+    ``exact``: as for ``find_duplicates``; ``previous`` should then come from an exact run as well.
     """
     if device is None:
         device = int(devices[0]) if devices else 0
     old, new = _parse_files(library), _parse_files(added)
     config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
-                                 band_count=band_count)
+                                 band_count=band_count, exact=bool(exact))
     scanner = _make_scanner(scanner_factory, config, device)
     from .scanner import assemble_clusters
 
@@ -175,7 +178,7 @@ def find_similar(library: Iterable, queries: Iterable, *, k: int = 10, max_dista
     """For every query the ``k`` library files most like it, best first: one list of ``SimilarFile(file, distance)`` per
     query, ordered by the Hamming distance of the pHashes, ties by the file's place in ``library``
     (``DuplicateScanner.nearest``).  A ranked, threshold-free answer: no band predicate, no size filter -- it finds the
-    pairs 4..8 bits apart that share no 16-bit band, which ``find_duplicates`` never links.
+    pairs 4..8 bits apart that share no 16-bit band, which ``find_duplicates`` links only with ``exact=True``.
 
     ``library``: as ``files`` of ``find_duplicates``.  An item of ``queries`` is a DuplicateFile, a row mapping, or a ``str`` /
     ``Path`` / PIL image; the last three are hashed here through ``compute_signature``, one at a time -- meant for a handful of
@@ -226,10 +229,11 @@ _VIEW_MODES = {
 
 
 def _view_scan(mode: str, files: Iterable, *, hamming_threshold, size_ratio, band_bits, band_count, device, tolerance=None,
-               ssim_threshold=None) -> tuple:
+               ssim_threshold=None, exact=False) -> tuple:
     """The work of find_turned_duplicates, find_trimmed_duplicates and find_turned_trimmed_duplicates (``mode``: a key of
     _VIEW_MODES): (clusters, matches, the (id, id) keys of the plain candidate edges).  With ``ssim_threshold`` the matches and
-    the keys are the ones that passed the re-check.  ``tolerance`` is read by the modes that trim."""
+    the keys are the ones that passed the re-check.  ``tolerance`` is read by the modes that trim.  ``exact``: the plain scan and
+    the view scan both take every pair within the threshold (``DuplicateScanConfig.exact``)."""
     from .scanner import DuplicateEdge, assemble_clusters
 
     module, signatures, takes_tolerance, collect, refine_name, tail = _VIEW_MODES[mode]
@@ -238,7 +242,7 @@ def _view_scan(mode: str, files: Iterable, *, hamming_threshold, size_ratio, ban
         return [], [], set()
     keywords = {"tolerance": tolerance} if takes_tolerance else {}
     config = DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
-                                 band_count=band_count)
+                                 band_count=band_count, exact=bool(exact))
     scanner = DuplicateScanner(config, device=device)
     made = getattr(importlib.import_module("." + module, __package__), signatures)([f.path for f in candidates], device=device, **keywords)
     plain = scanner.candidate_edges(candidates)
@@ -271,7 +275,8 @@ def _views_ssim_kept(refine_name: str, tail: tuple, plain: dict, matches: list, 
 
 
 def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_ratio: Optional[float] = None, band_bits: int = 16,
-                           band_count: int = 4, device: Optional[int] = None, ssim_threshold: Optional[float] = None) -> tuple:
+                           band_count: int = 4, device: Optional[int] = None, ssim_threshold: Optional[float] = None,
+                           exact: bool = False) -> tuple:
     """(clusters, matches): near-duplicates including mirrored, flipped and rotated copies.
 
     ``files``: as for ``find_duplicates``, each with a readable ``path``: the files are read and the pHashes of their
@@ -285,17 +290,18 @@ def find_turned_duplicates(files: Iterable, *, hamming_threshold: int = 8, size_
     file a against its orientation of file b, turned on the device (``refine.refine_turned_pairs``, one call for all).
     Only edges with ``ssim >= ssim_threshold`` reach the clusters, and ``matches`` holds the surviving matches, each with
     its ``ssim``.  A pair that is both a plain edge and a match stays linked if either passes; a pair with an unreadable
-    file is dropped.  Unset: no pixels are compared and ``ssim`` is None.
+    file is dropped.  Unset: no pixels are compared and ``ssim`` is None.  ``exact``: as for ``find_duplicates``, for the plain
+    edges and the matches alike -- a turned copy 6 bits away with a flipped bit in every band is then a match.
 
     Out of scope here: persisting turned hashes, ``devices=[...]`` (one process, one GPU) and dHash.  A copy that is turned AND has a
     margin round it is ``find_turned_trimmed_duplicates``'."""
     return _view_scan("turned", files, hamming_threshold=hamming_threshold, size_ratio=size_ratio, band_bits=band_bits,
-                      band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)[:2]
+                      band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold, exact=exact)[:2]
 
 
 def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tolerance: int = 48, size_ratio: Optional[float] = None,
                             band_bits: int = 16, band_count: int = 4, device: Optional[int] = None,
-                            ssim_threshold: Optional[float] = None) -> tuple:
+                            ssim_threshold: Optional[float] = None, exact: bool = False) -> tuple:
     """(clusters, matches): near-duplicates including copies with a margin round them -- letterboxed, pillarboxed, framed,
     on a white page, on a larger canvas.
 
@@ -312,16 +318,17 @@ def find_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tole
     there (``refine.refine_trimmed_pairs``, one call for all).  Only edges with ``ssim >= ssim_threshold`` reach the clusters,
     and ``matches`` holds the surviving matches, each with its ``ssim``.  A pair that is both a plain edge and a match stays
     linked if either passes; a pair with an unreadable file is dropped.  Unset: no pixels are compared and ``ssim`` is None.
+    ``exact``: as for ``find_duplicates``, for the plain edges and the matches alike.
 
     Out of scope here: an MAE re-check on the crop, ``devices=[...]`` (one process, one GPU), persisting trimmed
     hashes, borders of two colours or gradients, and dHash.  Trimmed and turned together is ``find_turned_trimmed_duplicates``'."""
     return _view_scan("trimmed", files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio, band_bits=band_bits,
-                      band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold)[:2]
+                      band_count=band_count, device=0 if device is None else int(device), ssim_threshold=ssim_threshold, exact=exact)[:2]
 
 
 def find_turned_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 8, tolerance: int = 48, size_ratio: Optional[float] = None,
                                    band_bits: int = 16, band_count: int = 4, device: Optional[int] = None,
-                                   ssim_threshold: Optional[float] = None) -> tuple:
+                                   ssim_threshold: Optional[float] = None, exact: bool = False) -> tuple:
     """(clusters, matches): near-duplicates including copies that were given a margin, turned, or both -- a scan laid on the
     glass sideways with a white margin, a letterboxed frame that was mirrored, a framed repost rotated a quarter turn.
 
@@ -338,13 +345,14 @@ def find_turned_trimmed_duplicates(files: Iterable, *, hamming_threshold: int = 
     ``refine.refine_turned_trimmed_pairs`` call: a's view against b's, cut (to the box found at that seam) and turned on the
     device.  Only edges with ``ssim >= ssim_threshold`` reach the clusters, and ``matches`` holds the surviving matches, each
     with its ``ssim``.  A pair that is both a plain edge and a match stays linked if either passes; a pair with an unreadable
-    file is dropped.  Unset: no pixels are compared and ``ssim`` is None.
+    file is dropped.  Unset: no pixels are compared and ``ssim`` is None.  ``exact``: as for ``find_duplicates``, for the plain
+    edges and the matches alike.
 
     Out of scope here: ``devices=[...]`` (one process, one GPU), persisting any of these hashes, turning side a, dHash, borders
     of two colours or gradients, and an MAE re-check."""
     return _view_scan("turned_trimmed", files, hamming_threshold=hamming_threshold, tolerance=tolerance, size_ratio=size_ratio,
                       band_bits=band_bits, band_count=band_count, device=0 if device is None else int(device),
-                      ssim_threshold=ssim_threshold)[:2]
+                      ssim_threshold=ssim_threshold, exact=exact)[:2]
 
 
 def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None, config: Optional[DuplicateScanConfig] = None,
@@ -353,7 +361,8 @@ def run_duplicate_scan(rows: Sequence[Mapping], *, db_path: Optional[str] = None
                        devices: Optional[Sequence[int]] = None) -> list:
     """Headless ``DuplicateScanRunnable.run``: stage names and order as the reference emits them.  ``devices``: the missing
     signatures are computed by one worker process per entry (``fast_fill_missing_signatures``); the scan and the clusters stay
-    in this process, on ``device`` (default ``devices[0]``, else 0)."""
+    in this process, on ``device`` (default ``devices[0]``, else 0).  An exact scan is asked for through ``config``
+    (``DuplicateScanConfig(exact=True)``)."""
     if device is None:
         device = int(devices[0]) if devices else 0
     def tick(stage, done, total):

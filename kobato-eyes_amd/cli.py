@@ -5,6 +5,7 @@
                                             [--devices 0,1,2] [--turned [--turned-ssim 0.9]]
                                             [--trimmed [--trim-tolerance 48] [--trimmed-ssim 0.9]]
                                             [--turned-trimmed [--trim-tolerance 48] [--turned-trimmed-ssim 0.9]]
+                                            [--exact]
     python -m kobato_eyes_amd.cli similar --db kobato.db (--to PATH ... | --to-like '%/incoming/%') [--like '%/photos/%']
                                           [--k 10] [--max-distance N] [--csv out.csv] [--device 0]
 
@@ -179,7 +180,7 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
                   devices: Optional[Sequence[int]] = None, added_like: Optional[str] = None, turned: bool = False,
                   orientations_out: Optional[dict] = None, turned_ssim: Optional[float] = None, trimmed: bool = False,
                   trim_tolerance: int = 48, boxes_out: Optional[dict] = None, trimmed_ssim: Optional[float] = None,
-                  turned_trimmed: bool = False, turned_trimmed_ssim: Optional[float] = None) -> list:
+                  turned_trimmed: bool = False, turned_trimmed_ssim: Optional[float] = None, exact: bool = False) -> list:
     """``devices``: the missing signatures are computed by one worker process per entry; the scan and the tile-aHash / MAE
     refine stay in this process, on ``device`` (default ``devices[0]``, else 0).  ``added_like``: the files of the
     selection whose path matches this LIKE pattern are the added set, the rest the library; only the pairs that touch an
@@ -198,7 +199,8 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
     its own -- copies that were given a margin, turned, or both are linked (``find_turned_trimmed_duplicates`` with
     ``trim_tolerance``; not together with ``turned``, ``trimmed``, ``added_like`` or ``refine``); ``orientations_out`` and
     ``boxes_out`` receive what they receive in those two modes.  ``turned_trimmed_ssim`` (only with ``turned_trimmed``): its
-    ``ssim_threshold``."""
+    ``ssim_threshold``.  ``exact``: in whichever mode, every pair within ``hamming_threshold`` links, whether or not it shares a
+    16-bit band (``DuplicateScanConfig.exact``)."""
     if turned_trimmed_ssim is not None and not turned_trimmed:
         raise ValueError("--turned-trimmed-ssim needs --turned-trimmed")
     if turned_trimmed and (turned or trimmed or added_like or refine):
@@ -234,7 +236,7 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
         orientations, boxes = VIEW_COLUMNS[mode]
         clusters, matches, plain_keys = _view_scan(mode, files, hamming_threshold=hamming_threshold, tolerance=trim_tolerance,
                                                    size_ratio=size_ratio, band_bits=16, band_count=4, device=device,
-                                                   ssim_threshold=ssim_threshold)
+                                                   ssim_threshold=ssim_threshold, exact=exact)
         if orientations and orientations_out is not None:
             orientations_out.update(orientations_to_keeper(clusters, matches, plain_keys))
         if boxes and boxes_out is not None:
@@ -244,9 +246,9 @@ def scan_database(db_path: str, *, hamming_threshold: int = 8, size_ratio: Optio
 
         added_ids = {r["file_id"] for r in rows if r["added"]}
         clusters = find_new_duplicates([f for f in files if f.file_id not in added_ids], [f for f in files if f.file_id in added_ids],
-                                       hamming_threshold=hamming_threshold, size_ratio=size_ratio, device=device)
+                                       hamming_threshold=hamming_threshold, size_ratio=size_ratio, device=device, exact=exact)
     else:
-        clusters = DuplicateScanner(DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio),
+        clusters = DuplicateScanner(DuplicateScanConfig(hamming_threshold=hamming_threshold, size_ratio=size_ratio, exact=bool(exact)),
                                     device=device).build_clusters(files)
     if refine and clusters:
         clusters = refine_by_tilehash_parallel(clusters, max_bits=tile_max_bits, device=device,
@@ -287,6 +289,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     sp.add_argument("--turned-trimmed-ssim", type=float, default=None,
                     help="with --turned-trimmed: re-check every candidate edge and match with SSIM on the pixels (cut and turned on the "
                          "device) and link only those at or above this score, e.g. 0.9")
+    sp.add_argument("--exact", action="store_true",
+                    help="link every pair within --hamming bits, whether or not it shares a 16-bit band (without it a pair links "
+                         "only when one of the four bands is equal, so --hamming above about 8 finds nothing more); combines with "
+                         "every mode above")
     sp.add_argument("--refine", action="store_true", help="run the tile-aHash + pixel-MAE refine pipeline on the clusters")
     sp.add_argument("--tile-max-bits", type=int, default=32)
     sp.add_argument("--mae-thr", type=float, default=0.004)
@@ -330,7 +336,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                              devices=args.devices, added_like=args.added_like, turned=args.turned, orientations_out=orientations,
                              turned_ssim=args.turned_ssim, trimmed=args.trimmed, trim_tolerance=args.trim_tolerance, boxes_out=boxes,
                              trimmed_ssim=args.trimmed_ssim, turned_trimmed=args.turned_trimmed,
-                             turned_trimmed_ssim=args.turned_trimmed_ssim)
+                             turned_trimmed_ssim=args.turned_trimmed_ssim, exact=args.exact)
     if args.csv:
         export_duplicate_clusters_csv(clusters, args.csv, orientations, boxes)
     members = sum(len(c.files) for c in clusters)

@@ -841,11 +841,13 @@ KE_API int ke_stage_submit_hash(ke_ctx *ctx, int32_t slot, const uint64_t *offse
 }
 
 // ---- scan ------------------------------------------------------------------------------------
-// ke_hamming_scan (first_new = 0), ke_hamming_scan_from and ke_hamming_scan_cross: one body, the region is ke_launch_scan's business
+// ke_hamming_scan (first_new = 0), ke_hamming_scan_from, ke_hamming_scan_cross and ke_hamming_scan_exact: one body, the region
+// and what exact changes are ke_launch_scan's business
 static int hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n, int64_t first_new,
                         int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
                         int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
-                        int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out, bool cross = false) {
+                        int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out, bool cross = false,
+                        bool exact = false) {
     if (!ctx) return KE_EINVAL;
     if (n < 0 || (n > 0 && !hashes)) return ke_fail(ctx, KE_EINVAL, "hashes is NULL");
     if (first_new < 0 || first_new > n) return ke_fail(ctx, KE_EINVAL, "first_new %lld outside [0, %lld]", (long long)first_new, (long long)n);
@@ -892,7 +894,7 @@ static int hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids,
     unsigned long long *d_cnt = nullptr, pairs = 0;
     KE_TRY(ke_launch_scan(ctx, (const uint64_t *)d_h, (const int64_t *)d_ids, (const int64_t *)d_sizes, n, part_index,
                           part_count, threshold, band_bits, band_count, size_ratio, bucket_pair_cap, d_edges, capacity,
-                          &d_cnt, &pairs, counters_out != nullptr, first_new, cross));
+                          &d_cnt, &pairs, counters_out != nullptr, first_new, cross, exact));
     unsigned long long h_cnt[KE_SCAN_STATE_WORDS];
     KE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, ctx->stream));
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -934,6 +936,17 @@ KE_API int ke_hamming_scan_cross(ke_ctx *ctx, const uint64_t *hashes, const int6
                                  int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
     return hamming_scan(ctx, hashes, ids, sizes, n, first_new, part_index, part_count, threshold, band_bits, band_count, size_ratio,
                         bucket_pair_cap, edges_out, capacity, n_edges_out, counters_out, true);
+}
+
+KE_API int ke_hamming_scan_exact(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
+                                 int64_t first_new, int32_t region, int32_t part_index, int32_t part_count, int32_t threshold,
+                                 int32_t band_bits, int32_t band_count, double size_ratio, ke_edge *edges_out, int64_t capacity,
+                                 int64_t *n_edges_out, uint64_t *counters_out) {
+    if (!ctx) return KE_EINVAL;
+    if (region < 0 || region > 2) return ke_fail(ctx, KE_EINVAL, "region %d is not 0 (all pairs), 1 (from first_new) or 2 (cross)", region);
+    if (region == 0 && first_new != 0) return ke_fail(ctx, KE_EINVAL, "region 0 (all pairs) needs first_new = 0");
+    return hamming_scan(ctx, hashes, ids, sizes, n, first_new, part_index, part_count, threshold, band_bits, band_count, size_ratio,
+                        0, edges_out, capacity, n_edges_out, counters_out, region == 2, true);
 }
 
 KE_API int ke_band_pairs_after_size(ke_ctx *ctx, const uint64_t *hashes, const int64_t *sizes, int64_t n, int32_t band_bits,

@@ -181,7 +181,8 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
 int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
                    int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
                    int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
-                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross = false);
+                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross = false,
+                   bool exact = false);   // exact: ke_hamming_scan_exact, the tile kernel alone, in slices (ke_scan.hip)
 constexpr int KE_SCAN_STATE_WORDS = 5;   // what ke_hamming_scan reads back: counters [0..3] and the path word
 // ctx->ssim_plan holds the KE_SP_* words of the plan (ke_ssim_plan.h) that the last call launched (ke_last_ssim_plan)
 int ke_launch_ssim(ke_ctx *ctx, const uint8_t *d_images, int w, int h, int channels, const int64_t *d_pa,

@@ -58,6 +58,7 @@ struct ScanArgs {
     int64_t capacity;
     unsigned long long *counters;  // [0] pairs, [1] sum of shared bands, [2] edges, [3] bucket pairs, [4] path (kPathWord)
     int xcd_remap;
+    int exact;              // ke_hamming_scan_exact: a pair that shares no band is an edge as well, with bands = 0
 };
 
 // counters[kPathWord]: 0 = the all-pairs tile kernel does the scan, 1 = the bucket kernels do.  Zeroed with the counters,
@@ -68,9 +69,9 @@ constexpr int kPathWord = 4, kLongestWord = 5;
 __device__ __forceinline__ int popc64(uint32_t lo, uint32_t hi) { return __popc(lo) + __popc(hi); }
 
 // Full predicate for one pair that already passed popcount <= threshold: true when the pair is an edge, with its bands
-// mask and the number of bands it shares.  only_band >= 0 (bucket path, which meets a pair once per band it shares): true
-// only when that band is the lowest one counted here, so that the pair appears once.  The index is kept beside the mask
-// because bands >= 31 share the mask's bit 31.
+// mask and the number of bands it shares (both 0 for an edge that only an exact scan keeps).  only_band >= 0 (bucket path,
+// which meets a pair once per band it shares): true only when that band is the lowest one counted here, so that the pair
+// appears once.  The index is kept beside the mask because bands >= 31 share the mask's bit 31.
 __device__ bool pair_is_edge(const ScanArgs &a, int64_t gi, int64_t gj, uint64_t x, uint64_t y, int only_band, int *bands_out,
                              int *shared_out) {
     if (gi >= gj || gj >= a.n) return false;
@@ -97,7 +98,7 @@ __device__ bool pair_is_edge(const ScanArgs &a, int64_t gi, int64_t gj, uint64_t
         if (first < 0) first = b;
         ++shared;
     }
-    if (!shared) return false;
+    if (!shared && !a.exact) return false;
     if (only_band >= 0 && first != only_band) return false;
     *bands_out = bands; *shared_out = shared;
     return true;
@@ -661,10 +662,13 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
 int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
                    int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
                    int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
-                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross) {
+                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross, bool exact) {
     // first_new > 0: only the pairs i < j with j >= first_new (ke_hamming_scan_from), through kernels of their own;
     // first_new == 0 launches what it always did.  cross: only the pairs i < first_new <= j (ke_hamming_scan_cross), again
     // through kernels of its own, for every first_new in [0, n] (0 and n: an empty region, no tile kernel).
+    // exact (ke_hamming_scan_exact): every pair of the region within the threshold, whether or not it shares a band.  The
+    // tile kernel is the only path: no histogram, no sorted copy, no statistics, KE_SCAN_MODE is not looked at, the path word
+    // and counters[3] stay 0; and the tiles go out in slices of at most KE_SCAN_TILES_PER_LAUNCH (below).
     const bool from = cross || first_new > 0;
     const KeScanRegion region = cross ? ke_cross_region(n, first_new) : ke_scan_region(n, first_new);
     ScanArgs a;
@@ -678,7 +682,9 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
     a.threshold = threshold; a.band_bits = band_bits; a.band_count = band_count;
     a.size_ratio = size_ratio;
     a.hist = nullptr; a.blen = nullptr;
-    a.cap = bucket_pair_cap > 0 ? (unsigned long long)bucket_pair_cap : 0ull;
+    a.cap = (!exact && bucket_pair_cap > 0) ? (unsigned long long)bucket_pair_cap : 0ull;
+    a.exact = exact ? 1 : 0;
+    if (exact) want_bucket_pairs = false;
     a.edges = d_edges; a.capacity = capacity;
     // pairs of the region this shard stands for (host, O(row blocks); first_new = 0: the pairs i < j < n)
     const unsigned long long pairs = cross ? ke_cross_shard_pairs(region, part_index, part_count)
@@ -692,7 +698,7 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
     }();
     const bool table = band_bits <= 24;
     const size_t bins = table ? (size_t)band_count << band_bits : 0;
-    bool bucket_path = table && bins <= kBucketMaxBins && n <= 0xffffffffLL && forced != 1 && (forced == 2 || n >= kBucketMinN);
+    bool bucket_path = !exact && table && bins <= kBucketMaxBins && n <= 0xffffffffLL && forced != 1 && (forced == 2 || n >= kBucketMinN);
     // [sorted hashes | per-bin offsets | sorted positions]; a table too large for it is scanned by the tile kernel
     void *srt = nullptr;
     const size_t slots = (size_t)band_count * (size_t)n;
@@ -703,7 +709,7 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
     }
     uint64_t *sorted_hash = (uint64_t *)srt;
     uint32_t *offsets = (uint32_t *)(sorted_hash + slots), *sorted_pos = offsets + bins;
-    const bool need_hist = table && (bucket_path || bucket_pair_cap > 0 || want_bucket_pairs);
+    const bool need_hist = table && (bucket_path || a.cap > 0 || want_bucket_pairs);
     // One allocation, one memset: [counters, path, longest bucket | block sums | histogram]
     const size_t hist_at = kStateBytes + kBlockSumBytes;
     const size_t state_bytes = (hist_at + (need_hist ? bins * sizeof(uint32_t) : 0) + 15) & ~(size_t)15;
@@ -756,7 +762,7 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
             hipLaunchKernelGGL(ke_hist_pairs, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins, a.cap, state + 3);
             KE_HIP(ctx, hipGetLastError());
         }
-    } else if (bucket_pair_cap > 0 || want_bucket_pairs) {
+    } else if (a.cap > 0 || want_bucket_pairs) {
         if (n > 0xffffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "bands wider than 24 bits need n < 2^32");
         // sort (band value, position) per band; scratch: keys in/out, positions in/out, per-hash lengths, cub temp storage
         size_t temp_bytes = 0;
@@ -784,25 +790,45 @@ int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, 
     if (my_tiles > 0) {
         hipLaunchKernelGGL(ke_scan_expand, dim3((unsigned)((n_pad * 4 + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, n_pad,
                            (ke_v4i *)exp, (const unsigned long long *)(state + kPathWord));
-        if (my_tiles > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
-        // A launch holds fewer than 2^32 threads; beyond that only a part of the grid runs and the call ends at the caller's
-        // pair count check with a count that is short (so it does for the two older scans, from about 4 million hashes on).
-        // The cross scan says so here where the tile kernel is its only path.
-        if (cross && !bucket_path && my_tiles > 0xffffffffLL / kThreads)
-            return ke_fail(ctx, KE_EUNSUPPORTED, "%lld tiles of %d threads do not fit one launch", (long long)my_tiles, kThreads);
         static const int xcd = [] { const char *e = std::getenv("KE_SCAN_XCD"); return e ? std::atoi(e) : 0; }();
-        a.xcd_remap = xcd;
-        // with the remap the grid is padded to a multiple of 8 so that every slot exists on some workgroup
-        const int64_t grid = xcd ? (my_tiles + 7) / 8 * 8 : my_tiles;
-        // one workgroup per tile on either kernel: splitting a thin region's tiles over 2 or 4 workgroups was measured and
-        // did not pay
-        if (cross)
-            hipLaunchKernelGGL(ke_scan_tiles_cross, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
-        else if (from)
-            hipLaunchKernelGGL(ke_scan_tiles_from, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
-        else
-            hipLaunchKernelGGL(ke_scan_tiles, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a);
-        KE_HIP(ctx, hipGetLastError());
+        // A launch holds fewer than 2^32 threads: kMaxLaunchTiles tiles.
+        constexpr int64_t kMaxLaunchTiles = 0xffffffffLL / kThreads;
+        // An exact scan launches its tiles in consecutive slices of the shard's enumeration, at most KE_SCAN_TILES_PER_LAUNCH
+        // (read once; default and ceiling: what one launch holds) to a launch: slot s of a slice that starts at slot s0 is
+        // tile part_index + (s0 + s) * part_count, so only first_tile moves.  The tiles count their pairs into counters[0]
+        // as ever, and the caller's closed-form check covers all slices together.
+        static const int64_t per_launch = [] {
+            const char *e = std::getenv("KE_SCAN_TILES_PER_LAUNCH");
+            const long long v = e ? std::atoll(e) : 0;
+            return (int64_t)(v > 0 && v < kMaxLaunchTiles ? v : kMaxLaunchTiles);
+        }();
+        if (!exact) {
+            if (my_tiles > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
+            // Beyond kMaxLaunchTiles only a part of the grid runs and the call ends at the caller's pair count check with a
+            // count that is short (so it does for the two older scans, from about 4 million hashes on).  The cross scan says
+            // so here where the tile kernel is its only path.
+            if (cross && !bucket_path && my_tiles > kMaxLaunchTiles)
+                return ke_fail(ctx, KE_EUNSUPPORTED, "%lld tiles of %d threads do not fit one launch", (long long)my_tiles, kThreads);
+        }
+        const int64_t slice = exact ? per_launch : my_tiles;
+        for (int64_t s0 = 0; s0 < my_tiles; s0 += slice) {
+            const int64_t count = std::min(slice, my_tiles - s0);
+            a.first_tile = (int64_t)part_index + s0 * (int64_t)part_count;
+            // With the remap the grid is padded to a multiple of 8 so that every slot exists on some workgroup; the padding
+            // slots name tiles past the slice, which only the end of the enumeration turns away: a slice that is followed by
+            // another is remapped only when it needs no padding.
+            a.xcd_remap = (xcd && (s0 + count == my_tiles || count % 8 == 0)) ? xcd : 0;
+            const int64_t grid = a.xcd_remap ? (count + 7) / 8 * 8 : count;
+            // one workgroup per tile on either kernel: splitting a thin region's tiles over 2 or 4 workgroups was measured and
+            // did not pay
+            if (cross)
+                hipLaunchKernelGGL(ke_scan_tiles_cross, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
+            else if (from)
+                hipLaunchKernelGGL(ke_scan_tiles_from, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
+            else
+                hipLaunchKernelGGL(ke_scan_tiles, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a);
+            KE_HIP(ctx, hipGetLastError());
+        }
     }
     ke_time_end(ctx, KE_T_SCAN);
     return KE_OK;

@@ -125,13 +125,16 @@ class DuplicateCluster:
 
 @dataclass(frozen=True)
 class DuplicateScanConfig:
-    """Thresholds of the scan; validation as src/dup/scanner.py:147-166."""
+    """Thresholds of the scan; validation as src/dup/scanner.py:147-166.  ``exact`` (this project's, the last field so that
+    the reference's positional constructor keeps working): every pair within ``hamming_threshold`` is an edge, whether or not
+    it shares a band (``DuplicateScanner``'s docstring)."""
 
     hamming_threshold: int = 8
     size_ratio: Optional[float] = None
     band_bits: int = 16
     band_count: int = 4
     cosine_threshold: Optional[float] = None
+    exact: bool = False
 
     def __post_init__(self) -> None:
         if self.band_bits <= 0:
@@ -328,7 +331,23 @@ def _cosine(left: DuplicateFile, right: DuplicateFile) -> Optional[float]:
 
 
 class DuplicateScanner:
-    """GPU-backed replacement of the reference scanner (same constructor, same method)."""
+    """GPU-backed replacement of the reference scanner (same constructor, same method).
+
+    With ``config.exact`` every scan of this scanner -- ``candidate_edges`` and through it ``build_clusters`` and
+    ``extend_clusters``, and the three view scans -- goes through ``ke_hamming_scan_exact``: an edge is every pair of the
+    region within ``hamming_threshold`` whose ids differ and whose sizes pass ``size_ratio``; the band config only fills an
+    edge's ``bands`` mask and decides nothing.  Under it
+      * KE_DUP_BUCKET_PAIR_CAP is ignored (one INFO line says so; ``extend_clusters`` does not refuse it either): the cap is
+        a property of buckets, and no bucket is walked;
+      * the bucket statistics line is not logged;
+      * with a file id that occurs twice, the edge kept per pair of ids is the one with the smallest (a, b): the reference's
+        first-writer-wins order is an order of buckets, and a pair that shares none has no place in it;
+      * ``last_counters`` counts pairs, not bucket pairs: ``pair_total`` is the region's pairs whose ids differ, worked out
+        on the host from the id multiplicities (all shards together, as before); ``after_size`` is ``pair_total`` when no
+        size ratio is set and None otherwise (nothing counts the pairs that pass the size filter alone; the log line prints
+        n/a); ``after_ham`` is the device's edge count; ``after_cosine`` the edges that pass the cosine filter, one per pair
+        where the banded funnel counts one per shared band -- so that it still equals ``after_ham`` when no cosine threshold
+        is set; ``edges`` as ever."""
 
     def __init__(self, config: DuplicateScanConfig, *, device: int = 0, part_index: int = 0, part_count: int = 1) -> None:
         assert config.band_bits * config.band_count <= 64, "band config too large"
@@ -337,18 +356,28 @@ class DuplicateScanner:
         self._part = (part_index, part_count)
         self._counters: Optional[dict] = None
         self._funnel: Optional[tuple] = None
+        self._cap_noted = False
 
     # -- candidate edges ---------------------------------------------------------------------
     def _limits(self) -> tuple:
-        """(size ratio, 0.0 = no size filter; KE_DUP_BUCKET_PAIR_CAP, None = no cap) of every scan of this scanner."""
+        """(size ratio, 0.0 = no size filter; KE_DUP_BUCKET_PAIR_CAP, None = no cap -- always None under ``exact``) of every
+        scan of this scanner."""
         ratio = self._config.size_ratio
-        return (ratio if (ratio is not None and ratio > 0) else 0.0), _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
+        cap = _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP"))
+        if cap is not None and self._config.exact:
+            if not self._cap_noted:
+                logger.info("dup: exact scan, KE_DUP_BUCKET_PAIR_CAP=%d is ignored (no bucket is walked)", cap)
+                self._cap_noted = True
+            cap = None
+        return (ratio if (ratio is not None and ratio > 0) else 0.0), cap
 
     def _scan(self, hashes, ids, sizes, **region) -> tuple:
         """(edges, counters) of ``Context.hamming_scan`` over one table under this scanner's config, limits and shard;
         ``region``: its first_new / cross."""
         cfg = self._config
         ratio, cap = self._limits()
+        if cfg.exact:
+            region = dict(region, exact=True)
         return _native.get_context(self._device).hamming_scan(
             hashes, len(hashes), ids=ids, sizes=sizes if ratio > 0 else None, threshold=cfg.hamming_threshold,
             band_bits=cfg.band_bits, band_count=cfg.band_count, size_ratio=ratio, bucket_pair_cap=cap or 0,
@@ -360,9 +389,10 @@ class DuplicateScanner:
         returned (``ke_hamming_scan_from``): the pairs between two library files are not visited."""
         hashes, (ids, sizes) = _stored_hashes(candidates), _ids_and_sizes(candidates)
         ratio, cap = self._limits()
-        self._log_bucket_stats(hashes, cap)
+        if not self._config.exact:
+            self._log_bucket_stats(hashes, cap)
         raw, counters = self._scan(hashes, ids, sizes, **({"first_new": int(first_new)} if first_new else {}))
-        return self._edges_from_raw(candidates, hashes, ids, raw, counters, sizes=sizes, ratio=ratio, cap=cap)
+        return self._edges_from_raw(candidates, hashes, ids, raw, counters, sizes=sizes, ratio=ratio, cap=cap, first_new=int(first_new))
 
     def _view_edges(self, candidates: Sequence[DuplicateFile], table: _ViewTable, boxes, make) -> list:
         """The one view scan: ``table``'s entries carry their candidate's id and size -- so the scan's own ``ids[i] != ids[j]``
@@ -489,7 +519,7 @@ class DuplicateScanner:
                         sized += _size_ok(int(sizes[i]), int(sizes[j]), ratio)
         return total, sized
 
-    def _edges_from_raw(self, candidates, hashes, ids, raw, counters, *, sizes=None, ratio=0.0, cap=None) -> dict:
+    def _edges_from_raw(self, candidates, hashes, ids, raw, counters, *, sizes=None, ratio=0.0, cap=None, first_new=0) -> dict:
         cfg = self._config
         order = np.lexsort((raw["b"], raw["a"]))
         raw = raw[order]
@@ -500,7 +530,7 @@ class DuplicateScanner:
                 cos = _cosine(candidates[a], candidates[b])
                 if cos is not None and cos < cfg.cosine_threshold:
                     continue
-            after_cos += bin(bands & 0xFFFFFFFF).count("1")
+            after_cos += 1 if cfg.exact else bin(bands & 0xFFFFFFFF).count("1")
             ia, ib = int(ids[a]), int(ids[b])
             keyed.setdefault((ia, ib) if ia < ib else (ib, ia), []).append((a, b, h, bands))
         edges: dict[tuple[int, int], DuplicateEdge] = {}
@@ -523,19 +553,34 @@ class DuplicateScanner:
             return best if best is not None else 0
 
         for key, hits in keyed.items():
-            if len(hits) > 1:  # duplicate file ids: the first writer wins (src/dup/scanner.py:287-290)
+            if len(hits) > 1 and cfg.exact:  # duplicate file ids under exact: no bucket order to go by, the smallest (a, b)
+                hits.sort(key=lambda t: (t[0], t[1]))
+            elif len(hits) > 1:  # duplicate file ids: the first writer wins (src/dup/scanner.py:287-290)
                 hits.sort(key=lambda t: (bucket_rank(t[0], t[3]), t[0], t[1]))
             a, b, h, _ = hits[0]
             edges[key] = DuplicateEdge(int(ids[a]), int(ids[b]), int(h))
         # The reference's funnel figures (src/dup/scanner.py:292-299) are a log line, not part of the result: they are worked
         # out when somebody looks -- the logger at INFO, or a reader of ``last_counters`` -- and cost nothing otherwise.
         self._counters = None
-        self._funnel = (hashes, ids, sizes, ratio, cap, [int(c) for c in counters], after_cos, len(edges))
+        self._funnel = (hashes, ids, sizes, ratio, cap, [int(c) for c in counters], after_cos, len(edges), first_new)
         if logger.isEnabledFor(logging.INFO):
             c = self.last_counters
-            logger.info("dup: pairs total=%d -> size=%d -> ham=%d -> cosine=%d -> edges=%d", c["pair_total"], c["after_size"],
-                        c["after_ham"], c["after_cosine"], c["edges"])
+            logger.info("dup: pairs total=%d -> size=%s -> ham=%d -> cosine=%d -> edges=%d", c["pair_total"],
+                        "n/a" if c["after_size"] is None else c["after_size"], c["after_ham"], c["after_cosine"], c["edges"])
         return edges
+
+    @staticmethod
+    def _region_pairs_of_differing_ids(ids: np.ndarray, first_new: int) -> int:
+        """Pairs i < j with j >= first_new and ids[i] != ids[j]: the region's pairs less, per id, the pairs among its
+        occurrences that lie in the region."""
+        n, f = len(ids), int(first_new)
+        total = n * (n - 1) // 2 - f * (f - 1) // 2
+        uniq, inverse, counts = np.unique(ids, return_inverse=True, return_counts=True)
+        if (counts > 1).any():
+            old = np.bincount(inverse[:f], minlength=len(uniq)).astype(object)
+            counts = counts.astype(object)
+            total -= int((counts * (counts - 1) // 2 - old * (old - 1) // 2).sum())
+        return total
 
     @property
     def last_counters(self) -> Optional[dict]:
@@ -544,9 +589,17 @@ class DuplicateScanner:
         table's figures for these two (they do not depend on the tiles it was dealt), its own share for the rest.
         After ``candidate_edges(..., first_new)`` the same split holds for the region: ``pairs_evaluated``, ``after_ham``,
         ``after_cosine`` and ``edges`` are taken over the pairs with a member at position >= first_new, ``pair_total`` and
-        ``after_size`` remain the whole table's (bucket sizes are a property of the table, not of the region)."""
+        ``after_size`` remain the whole table's (bucket sizes are a property of the table, not of the region).
+        Under ``config.exact`` the keys count pairs of the region instead (the class docstring)."""
         if self._counters is None and self._funnel is not None:
-            hashes, ids, sizes, ratio, cap, counters, after_cos, n_edges = self._funnel
+            hashes, ids, sizes, ratio, cap, counters, after_cos, n_edges, first_new = self._funnel
+            if self._config.exact:
+                pair_total = self._region_pairs_of_differing_ids(ids, first_new)
+                self._counters = {"pairs_evaluated": counters[0], "pair_total": pair_total,
+                                  "after_size": pair_total if not (ratio > 0 and sizes is not None) else None,
+                                  "after_ham": counters[2], "after_cosine": after_cos, "edges": n_edges}
+                self._funnel = None
+                return self._counters
             same_total, same_sized = self._same_id_bucket_pairs(hashes, ids, sizes if sizes is not None else np.zeros(len(ids), np.int64),
                                                                 ratio, cap)
             pair_total = counters[3] - same_total
@@ -612,12 +665,12 @@ class DuplicateScanner:
         pairs that touch an added file.  Connectivity among library files comes from ``previous``' memberships, an old
         member's best_hamming is the minimum of its previous value and its new edges.
 
-        ValueError where that equality cannot hold: with KE_DUP_BUCKET_PAIR_CAP set (buckets grow with the table, so an
+        ValueError where that equality cannot hold: with KE_DUP_BUCKET_PAIR_CAP set and not ``config.exact`` (buckets grow with the table, so an
         edge between two library files can vanish under the cap and ``previous`` would keep it), with a file id that
         occurs twice across library + added (the first-writer-wins rule between equal ids needs the pairs this scan leaves
         out), and when ``previous`` names a file that is not in ``library``."""
         cfg = self._config
-        if _safe_positive_int(os.environ.get("KE_DUP_BUCKET_PAIR_CAP")) is not None:
+        if self._limits()[1] is not None:
             raise ValueError("extend_clusters: KE_DUP_BUCKET_PAIR_CAP is set; under a bucket pair cap edges between library "
                              "files can disappear as the table grows, so previous clusters cannot be extended")
         old = [f for f in library if f.phash is not None]
