@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The scan from first_new (ke_hamming_scan_from) beside the full scan (ke_hamming_scan) of the same table, in the same
+"""The scan from first_new (ke_hamming_scan_from) beside the full scan (ke_hamming_scan) and the cross scan
+(ke_hamming_scan_cross, same first_new) of the same table, in the same
 process, alternating: HIP-event times of everything each call launches (ke_last_kernel_ms), on device-resident tables of
 ke_synth_hashes.  One JSON line per row, appended to --out as well (profiles/r13_scan_from.jsonl is the record).
 
@@ -109,18 +110,23 @@ for n in args.n:
         continue
     for m in sorted(set(args.m or [1_000, 10_000, n // 10, n // 2])):
         f = n - m
-        ms_from, ms_full = [], []
-        for k in range(args.warmup + args.reps):                      # alternating, so that both see the same neighbours
+        ms_from, ms_full, ms_cross = [], [], []
+        for k in range(args.warmup + args.reps):                      # alternating, so that all see the same neighbours
             full_edges, full_counters = ctx.hamming_scan(d, n, threshold=8, capacity=cap)
             ms_full.append(ctx.last_kernel_ms(1))
             full_path = ctx.last_scan_path()
+            cross_edges, _ = ctx.hamming_scan(d, n, threshold=8, capacity=cap, first_new=f, cross=True)
+            ms_cross.append(ctx.last_kernel_ms(1))
+            cross_path = ctx.last_scan_path()
             edges, counters = ctx.hamming_scan(d, n, threshold=8, capacity=cap, first_new=f)
             ms_from.append(ctx.last_kernel_ms(1))
             cap = max(cap, len(full_edges))
         assert len(edges) == int((full_edges["b"] >= f).sum()), "the region's edges are not the full scan's with b >= first_new"
+        assert len(cross_edges) == int(((full_edges["a"] < f) & (full_edges["b"] >= f)).sum()), "the cross edges are not the full scan's with a < first_new <= b"
         fr, fu = stats(ms_from[args.warmup:]), stats(ms_full[args.warmup:])
-        emit({"case": "scan_from", "n": n, "m": m, "first_new": f, "mode": os.environ.get("KE_SCAN_MODE", "auto"),
-              "path": ctx.last_scan_path(), "full_path": full_path, "region_pairs": int(counters[0]),
+        emit({"case": "scan_from", "tag": args.tag, "n": n, "m": m, "first_new": f, "mode": os.environ.get("KE_SCAN_MODE", "auto"),
+              "path": ctx.last_scan_path(), "full_path": full_path, "cross_path": cross_path, "cross_edges": int(len(cross_edges)),
+              "cross_ms": stats(ms_cross[args.warmup:]), "region_pairs": int(counters[0]),
               "tiles": region_tiles(n, f), "full_tiles": region_tiles(n, 0), "edges": int(len(edges)), "full_edges": int(len(full_edges)),
               "bucket_pairs": int(counters[3]), "from_ms": fr, "full_ms": fu, "full_over_from": fu["median"] / fr["median"], "gpus": 1})
     ctx.free(d)

@@ -1108,29 +1108,19 @@ class Context:
         cap = int(capacity) if capacity else max(1 << 16, 2 * int(n))
         counters = np.zeros(4, np.uint64)
         n_edges = C.c_int64(0)
+        # the four calls differ in what stands between n and the shard, and in whether they take a cap
+        region = 2 if cross else 1 if first_new else 0
+        if exact:
+            name, after_n, pair_cap = "ke_hamming_scan_exact", (first_new, region), ()
+        else:
+            name, after_n = (("ke_hamming_scan", ()), ("ke_hamming_scan_from", (first_new,)), ("ke_hamming_scan_cross", (first_new,)))[region]
+            pair_cap = (int(bucket_pair_cap),)
         while True:
             edges = np.empty(cap, EDGE_DTYPE)
             with self._lock:
-                if exact:
-                    self._check(self._lib.ke_hamming_scan_exact(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, first_new,
-                                                                2 if cross else 1 if first_new else 0, part_index, part_count,
-                                                                threshold, band_bits, band_count, float(size_ratio), _addr(edges),
-                                                                cap, C.byref(n_edges), _addr(counters)), "ke_hamming_scan_exact")
-                elif cross:
-                    self._check(self._lib.ke_hamming_scan_cross(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, first_new,
-                                                                part_index, part_count, threshold, band_bits, band_count,
-                                                                float(size_ratio), int(bucket_pair_cap), _addr(edges), cap,
-                                                                C.byref(n_edges), _addr(counters)), "ke_hamming_scan_cross")
-                elif first_new:
-                    self._check(self._lib.ke_hamming_scan_from(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, int(first_new),
-                                                               part_index, part_count, threshold, band_bits, band_count,
-                                                               float(size_ratio), int(bucket_pair_cap), _addr(edges), cap,
-                                                               C.byref(n_edges), _addr(counters)), "ke_hamming_scan_from")
-                else:
-                    self._check(self._lib.ke_hamming_scan(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, part_index,
-                                                          part_count, threshold, band_bits, band_count, float(size_ratio),
-                                                          int(bucket_pair_cap), _addr(edges), cap, C.byref(n_edges),
-                                                          _addr(counters)), "ke_hamming_scan")
+                self._check(getattr(self._lib, name)(self._h, _addr(hashes), _addr(ids), _addr(sizes), n, *after_n, part_index,
+                                                     part_count, threshold, band_bits, band_count, float(size_ratio), *pair_cap,
+                                                     _addr(edges), cap, C.byref(n_edges), _addr(counters)), name)
             if n_edges.value <= cap:
                 return edges[: n_edges.value], counters
             cap = int(n_edges.value)  # overflow protocol: retry with the reported size

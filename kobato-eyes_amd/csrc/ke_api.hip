@@ -841,60 +841,54 @@ KE_API int ke_stage_submit_hash(ke_ctx *ctx, int32_t slot, const uint64_t *offse
 }
 
 // ---- scan ------------------------------------------------------------------------------------
-// ke_hamming_scan (first_new = 0), ke_hamming_scan_from, ke_hamming_scan_cross and ke_hamming_scan_exact: one body, the region
-// and what exact changes are ke_launch_scan's business
-static int hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n, int64_t first_new,
-                        int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
-                        int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
-                        int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out, bool cross = false,
-                        bool exact = false) {
+// The host arrays among a scan's inputs go to the device through one buffer, slot 0 hashes, 1 ids, 2 sizes of n x 8 B each; a
+// device pointer and NULL stay what they are.  ids: nullable for a call that has none.
+static int stage_scan_inputs(ke_ctx *ctx, int64_t n, const uint64_t **hashes, const int64_t **ids, const int64_t **sizes) {
+    const void *in[3] = {*hashes, ids ? *ids : nullptr, *sizes};
+    void *base = nullptr;
+    for (int slot = 0; slot < 3; ++slot) {
+        if (!in[slot] || ke_is_device_ptr(in[slot])) continue;
+        if (!base) KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_IN, (size_t)n * 24, &base));
+        void *d = (uint8_t *)base + slot * (size_t)n * 8;
+        KE_HIP(ctx, hipMemcpyAsync(d, in[slot], (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        in[slot] = d;
+    }
+    *hashes = (const uint64_t *)in[0]; *sizes = (const int64_t *)in[2];
+    if (ids) *ids = (const int64_t *)in[1];
+    return KE_OK;
+}
+
+// ke_hamming_scan, ke_hamming_scan_from, ke_hamming_scan_cross and ke_hamming_scan_exact: one body, the region and what exact
+// changes are ke_launch_scan's business.  rq holds the caller's pointers.
+static int hamming_scan(ke_ctx *ctx, KeScanRequest rq, int64_t *n_edges_out, uint64_t *counters_out) {
     if (!ctx) return KE_EINVAL;
-    if (n < 0 || (n > 0 && !hashes)) return ke_fail(ctx, KE_EINVAL, "hashes is NULL");
-    if (first_new < 0 || first_new > n) return ke_fail(ctx, KE_EINVAL, "first_new %lld outside [0, %lld]", (long long)first_new, (long long)n);
+    const int64_t n = rq.n;
+    if (n < 0 || (n > 0 && !rq.hashes)) return ke_fail(ctx, KE_EINVAL, "hashes is NULL");
+    if (rq.first_new < 0 || rq.first_new > n) return ke_fail(ctx, KE_EINVAL, "first_new %lld outside [0, %lld]", (long long)rq.first_new, (long long)n);
     if (!n_edges_out) return ke_fail(ctx, KE_EINVAL, "n_edges_out is NULL");
     // DuplicateScanConfig.__post_init__ / DuplicateScanner.__init__ (src/dup/scanner.py:155-166, 208)
-    if (band_bits <= 0) return ke_fail(ctx, KE_EINVAL, "band_bits must be positive");
-    if (band_count <= 0) return ke_fail(ctx, KE_EINVAL, "band_count must be positive");
-    if ((int64_t)band_bits * band_count > 64) return ke_fail(ctx, KE_EINVAL, "band config too large");
-    if (threshold < 0 || threshold > 64) return ke_fail(ctx, KE_EINVAL, "hamming_threshold must be in [0, 64]");
-    if (part_count <= 0 || part_index < 0 || part_index >= part_count)
-        return ke_fail(ctx, KE_EINVAL, "bad shard %d/%d", part_index, part_count);
-    if (capacity < 0 || (capacity > 0 && !edges_out)) return ke_fail(ctx, KE_EINVAL, "edges_out is NULL");
+    if (rq.band_bits <= 0) return ke_fail(ctx, KE_EINVAL, "band_bits must be positive");
+    if (rq.band_count <= 0) return ke_fail(ctx, KE_EINVAL, "band_count must be positive");
+    if ((int64_t)rq.band_bits * rq.band_count > 64) return ke_fail(ctx, KE_EINVAL, "band config too large");
+    if (rq.threshold < 0 || rq.threshold > 64) return ke_fail(ctx, KE_EINVAL, "hamming_threshold must be in [0, 64]");
+    if (rq.part_count <= 0 || rq.part_index < 0 || rq.part_index >= rq.part_count)
+        return ke_fail(ctx, KE_EINVAL, "bad shard %d/%d", rq.part_index, rq.part_count);
+    if (rq.capacity < 0 || (rq.capacity > 0 && !rq.edges)) return ke_fail(ctx, KE_EINVAL, "edges_out is NULL");
     *n_edges_out = 0;
     if (counters_out) std::memset(counters_out, 0, 4 * sizeof(uint64_t));
     if (n < 2) return KE_OK;
     KE_HIP(ctx, hipSetDevice(ctx->device));
-    const void *d_h, *d_ids, *d_sizes;
-    // three inputs share one staging buffer when they come from the host
-    const bool any_host = !ke_is_device_ptr(hashes) || (ids && !ke_is_device_ptr(ids)) || (sizes && !ke_is_device_ptr(sizes));
-    if (any_host) {
-        void *base;
-        KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_IN, (size_t)n * 24, &base));
-        auto stage = [&](const void *src, size_t slot, const void **dst) -> int {
-            if (!src) { *dst = nullptr; return KE_OK; }
-            if (ke_is_device_ptr(src)) { *dst = src; return KE_OK; }
-            void *d = (uint8_t *)base + slot * (size_t)n * 8;
-            KE_HIP(ctx, hipMemcpyAsync(d, src, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-            *dst = d;
-            return KE_OK;
-        };
-        KE_TRY(stage(hashes, 0, &d_h));
-        KE_TRY(stage(ids, 1, &d_ids));
-        KE_TRY(stage(sizes, 2, &d_sizes));
-    } else {
-        d_h = hashes; d_ids = ids; d_sizes = sizes;
+    KE_TRY(stage_scan_inputs(ctx, n, &rq.hashes, &rq.ids, &rq.sizes));
+    ke_edge *edges_out = rq.edges;
+    const bool edges_dev = rq.capacity > 0 && ke_is_device_ptr(edges_out);
+    if (rq.capacity > 0 && !edges_dev) {
+        void *tmp;
+        KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_EDGES, (size_t)rq.capacity * sizeof(ke_edge), &tmp));
+        rq.edges = (ke_edge *)tmp;
     }
-    const bool edges_dev = capacity > 0 && ke_is_device_ptr(edges_out);
-    ke_edge *d_edges = edges_out;
-    void *tmp;
-    if (capacity > 0 && !edges_dev) {
-        KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_EDGES, (size_t)capacity * sizeof(ke_edge), &tmp));
-        d_edges = (ke_edge *)tmp;
-    }
+    rq.want_bucket_pairs = counters_out != nullptr;
     unsigned long long *d_cnt = nullptr, pairs = 0;
-    KE_TRY(ke_launch_scan(ctx, (const uint64_t *)d_h, (const int64_t *)d_ids, (const int64_t *)d_sizes, n, part_index,
-                          part_count, threshold, band_bits, band_count, size_ratio, bucket_pair_cap, d_edges, capacity,
-                          &d_cnt, &pairs, counters_out != nullptr, first_new, cross, exact));
+    KE_TRY(ke_launch_scan(ctx, rq, &d_cnt, &pairs));
     unsigned long long h_cnt[KE_SCAN_STATE_WORDS];
     KE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, ctx->stream));
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -904,10 +898,10 @@ static int hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids,
         return ke_fail(ctx, KE_EHIP, "scan evaluated %llu pairs, expected %llu", h_cnt[0], pairs);
     if (counters_out)
         for (int k = 0; k < 4; ++k) counters_out[k] = h_cnt[k];
-    if (capacity > 0 && !edges_dev) {
-        const int64_t m = std::min<int64_t>(capacity, (int64_t)h_cnt[2]);
+    if (rq.capacity > 0 && !edges_dev) {
+        const int64_t m = std::min<int64_t>(rq.capacity, (int64_t)h_cnt[2]);
         if (m > 0) {
-            KE_HIP(ctx, hipMemcpyAsync(edges_out, d_edges, (size_t)m * sizeof(ke_edge), hipMemcpyDeviceToHost, ctx->stream));
+            KE_HIP(ctx, hipMemcpyAsync(edges_out, rq.edges, (size_t)m * sizeof(ke_edge), hipMemcpyDeviceToHost, ctx->stream));
             KE_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
     }
@@ -918,24 +912,41 @@ KE_API int ke_hamming_scan(ke_ctx *ctx, const uint64_t *hashes, const int64_t *i
                            int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
                            int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
                            int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
-    return hamming_scan(ctx, hashes, ids, sizes, n, 0, part_index, part_count, threshold, band_bits, band_count, size_ratio,
-                        bucket_pair_cap, edges_out, capacity, n_edges_out, counters_out);
+    KeScanRequest rq;
+    rq.hashes = hashes; rq.ids = ids; rq.sizes = sizes; rq.n = n;
+    rq.part_index = part_index; rq.part_count = part_count;
+    rq.threshold = threshold; rq.band_bits = band_bits; rq.band_count = band_count;
+    rq.size_ratio = size_ratio; rq.bucket_pair_cap = bucket_pair_cap;
+    rq.edges = edges_out; rq.capacity = capacity;
+    return hamming_scan(ctx, rq, n_edges_out, counters_out);
 }
 
 KE_API int ke_hamming_scan_from(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
                                 int64_t first_new, int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
                                 int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
                                 int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
-    return hamming_scan(ctx, hashes, ids, sizes, n, first_new, part_index, part_count, threshold, band_bits, band_count, size_ratio,
-                        bucket_pair_cap, edges_out, capacity, n_edges_out, counters_out);
+    KeScanRequest rq;
+    rq.hashes = hashes; rq.ids = ids; rq.sizes = sizes; rq.n = n;
+    rq.first_new = first_new; rq.kind = KE_SCAN_FROM;
+    rq.part_index = part_index; rq.part_count = part_count;
+    rq.threshold = threshold; rq.band_bits = band_bits; rq.band_count = band_count;
+    rq.size_ratio = size_ratio; rq.bucket_pair_cap = bucket_pair_cap;
+    rq.edges = edges_out; rq.capacity = capacity;
+    return hamming_scan(ctx, rq, n_edges_out, counters_out);
 }
 
 KE_API int ke_hamming_scan_cross(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
                                  int64_t first_new, int32_t part_index, int32_t part_count, int32_t threshold, int32_t band_bits,
                                  int32_t band_count, double size_ratio, int64_t bucket_pair_cap, ke_edge *edges_out,
                                  int64_t capacity, int64_t *n_edges_out, uint64_t *counters_out) {
-    return hamming_scan(ctx, hashes, ids, sizes, n, first_new, part_index, part_count, threshold, band_bits, band_count, size_ratio,
-                        bucket_pair_cap, edges_out, capacity, n_edges_out, counters_out, true);
+    KeScanRequest rq;
+    rq.hashes = hashes; rq.ids = ids; rq.sizes = sizes; rq.n = n;
+    rq.first_new = first_new; rq.kind = KE_SCAN_CROSS;
+    rq.part_index = part_index; rq.part_count = part_count;
+    rq.threshold = threshold; rq.band_bits = band_bits; rq.band_count = band_count;
+    rq.size_ratio = size_ratio; rq.bucket_pair_cap = bucket_pair_cap;
+    rq.edges = edges_out; rq.capacity = capacity;
+    return hamming_scan(ctx, rq, n_edges_out, counters_out);
 }
 
 KE_API int ke_hamming_scan_exact(ke_ctx *ctx, const uint64_t *hashes, const int64_t *ids, const int64_t *sizes, int64_t n,
@@ -945,8 +956,14 @@ KE_API int ke_hamming_scan_exact(ke_ctx *ctx, const uint64_t *hashes, const int6
     if (!ctx) return KE_EINVAL;
     if (region < 0 || region > 2) return ke_fail(ctx, KE_EINVAL, "region %d is not 0 (all pairs), 1 (from first_new) or 2 (cross)", region);
     if (region == 0 && first_new != 0) return ke_fail(ctx, KE_EINVAL, "region 0 (all pairs) needs first_new = 0");
-    return hamming_scan(ctx, hashes, ids, sizes, n, first_new, part_index, part_count, threshold, band_bits, band_count, size_ratio,
-                        0, edges_out, capacity, n_edges_out, counters_out, region == 2, true);
+    KeScanRequest rq;
+    rq.hashes = hashes; rq.ids = ids; rq.sizes = sizes; rq.n = n;
+    rq.first_new = first_new; rq.kind = (KeScanKind)region; rq.exact = true;
+    rq.part_index = part_index; rq.part_count = part_count;
+    rq.threshold = threshold; rq.band_bits = band_bits; rq.band_count = band_count;
+    rq.size_ratio = size_ratio;
+    rq.edges = edges_out; rq.capacity = capacity;
+    return hamming_scan(ctx, rq, n_edges_out, counters_out);
 }
 
 KE_API int ke_band_pairs_after_size(ke_ctx *ctx, const uint64_t *hashes, const int64_t *sizes, int64_t n, int32_t band_bits,
@@ -959,26 +976,12 @@ KE_API int ke_band_pairs_after_size(ke_ctx *ctx, const uint64_t *hashes, const i
     *count_out = 0;
     if (n < 2) return KE_OK;
     KE_HIP(ctx, hipSetDevice(ctx->device));
-    const void *d_h = hashes, *d_s = sizes;
-    if (!ke_is_device_ptr(hashes) || !ke_is_device_ptr(sizes)) {
-        void *base;
-        KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_IN, (size_t)n * 24, &base));
-        if (!ke_is_device_ptr(hashes)) {
-            KE_HIP(ctx, hipMemcpyAsync(base, hashes, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-            d_h = base;
-        }
-        if (!ke_is_device_ptr(sizes)) {
-            void *d = (uint8_t *)base + (size_t)n * 16;
-            KE_HIP(ctx, hipMemcpyAsync(d, sizes, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-            d_s = d;
-        }
-    }
+    KE_TRY(stage_scan_inputs(ctx, n, &hashes, nullptr, &sizes));
     void *tmp;
     KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_CNT, 4 * sizeof(unsigned long long), &tmp));
     unsigned long long *d_cnt = (unsigned long long *)tmp;
     KE_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), ctx->stream));
-    KE_TRY(ke_launch_band_pairs_after_size(ctx, (const uint64_t *)d_h, (const int64_t *)d_s, n, band_bits, band_count, size_ratio,
-                                           bucket_pair_cap, d_cnt));
+    KE_TRY(ke_launch_band_pairs_after_size(ctx, hashes, sizes, n, band_bits, band_count, size_ratio, bucket_pair_cap, d_cnt));
     unsigned long long h = 0;
     KE_HIP(ctx, hipMemcpyAsync(&h, d_cnt, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     KE_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -14,6 +14,7 @@
 
 #include "../../include/keyes.h"
 #include "ke_coeffs.h"
+#include "ke_scan_plan.h"
 #include "ke_ssim_plan.h"
 #include "ke_view_plan.h"
 
@@ -178,11 +179,23 @@ int ke_launch_sad_pairs(ke_ctx *ctx, const uint8_t *d_thumbs, int64_t pixels, co
                         int64_t n_pairs, uint64_t *d_out);
 int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_sizes, int64_t n, int band_bits,
                                     int band_count, double ratio, int64_t bucket_pair_cap, unsigned long long *d_out);
-int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
-                   int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
-                   int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
-                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross = false,
-                   bool exact = false);   // exact: ke_hamming_scan_exact, the tile kernel alone, in slices (ke_scan.hip)
+// One pair scan.  The four ke_hamming_scan* calls fill it with their caller's pointers (host or device), ke_launch_scan gets it
+// with device pointers; what is launched for it: ke_scan_plan.h
+struct KeScanRequest {
+    const uint64_t *hashes = nullptr;
+    const int64_t *ids = nullptr, *sizes = nullptr;   // nullable
+    int64_t n = 0, first_new = 0;
+    KeScanKind kind = KE_SCAN_ALL;
+    int part_index = 0, part_count = 1;
+    int threshold = 0, band_bits = 0, band_count = 0;
+    double size_ratio = 0.0;
+    int64_t bucket_pair_cap = 0;
+    bool exact = false;               // ke_hamming_scan_exact: pairs that share no band are edges as well
+    ke_edge *edges = nullptr;
+    int64_t capacity = 0;
+    bool want_bucket_pairs = false;   // counters[3] is wanted
+};
+int ke_launch_scan(ke_ctx *ctx, const KeScanRequest &rq, unsigned long long **d_counters_out, unsigned long long *pairs_evaluated);
 constexpr int KE_SCAN_STATE_WORDS = 5;   // what ke_hamming_scan reads back: counters [0..3] and the path word
 // ctx->ssim_plan holds the KE_SP_* words of the plan (ke_ssim_plan.h) that the last call launched (ke_last_ssim_plan)
 int ke_launch_ssim(ke_ctx *ctx, const uint8_t *d_images, int w, int h, int channels, const int64_t *d_pa,

@@ -22,11 +22,10 @@
 #include <hipcub/hipcub.hpp>
 
 #include "ke_internal.h"
-#include "ke_scan_region.h"
 
 namespace {
 
-constexpr int kThreads = 512;               // 8 waves
+constexpr int kThreads = kScanThreads;      // 8 waves
 constexpr int kRT = 8;                      // 16-hash row tiles per wave
 constexpr int kTile = 8 * kRT * 16;         // 1024 rows per workgroup ...
 constexpr int kCols = 1024;                 // ... against 1024 columns
@@ -57,7 +56,6 @@ struct ScanArgs {
     ke_edge *edges;
     int64_t capacity;
     unsigned long long *counters;  // [0] pairs, [1] sum of shared bands, [2] edges, [3] bucket pairs, [4] path (kPathWord)
-    int xcd_remap;
     int exact;              // ke_hamming_scan_exact: a pair that shares no band is an edge as well, with bands = 0
 };
 
@@ -144,48 +142,31 @@ __global__ __launch_bounds__(256) void ke_scan_expand(const uint64_t *__restrict
     out[e] = v;
 }
 
-// The tile kernel's body.  kFrom = false is ke_scan_tiles, the whole triangle; kFrom = true is ke_scan_tiles_from, a scan
+// The tile kernel's body.  kMode = KE_SCAN_ALL is ke_scan_tiles, the whole triangle; kFrom is ke_scan_tiles_from, a scan
 // from first_new: the tile comes from the enumeration of the trapezoid of tiles that hold a pair with j >= first_new
 // (region, ke_scan_region.h) and the columns below first_new are left out -- whole chunks and 16-column blocks by where
 // the loops start (wave-uniform), the lanes of the block first_new lies in at the rare path.  Every kFrom branch is
 // compile-time, region is not read without it.
-// kMode = kScanCross is ke_scan_tiles_cross, the pairs i < first_new <= j of a table [library | queries]: the region is the
+// kMode = KE_SCAN_CROSS is ke_scan_tiles_cross, the pairs i < first_new <= j of a table [library | queries]: the region is the
 // rectangle of row blocks that hold a row below first_new against the chunks from first_new's on (ke_cross_region), the
 // columns are cut as for kFrom, and the rows at or beyond first_new are left out -- a wave whose 128 rows all lie there
 // walks no block but still meets the others at every barrier of the chunk loop, a single such row is dropped per lane at
 // the rare path.  Every kCross branch is compile-time too.
-constexpr int kScanAll = 0, kScanFrom = 1, kScanCross = 2;
-template <int kMode>
+template <KeScanKind kMode>
 __device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRegion region) {
-    constexpr bool kCross = kMode == kScanCross, kFrom = kMode != kScanAll;   // kFrom: the columns start at first_new
+    constexpr bool kCross = kMode == KE_SCAN_CROSS, kFrom = kMode != KE_SCAN_ALL;   // kFrom: the columns start at first_new
     __shared__ ke_v4i s_b[2][kChunk / 16 * 64];      // two chunks of 16 operand tiles
     if (a.counters[kPathWord]) return;               // the bucket kernels do this call's scan
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // workgroup b runs on XCD b mod 8 (round-robin dispatch), each XCD has its own L2: XCD x takes the x-th eighth of this
-    // launch's tiles, consecutive tiles (which share their row operands) on one L2 instead of on eight.  KE_SCAN_XCD=0: off.
-    int64_t slot = blockIdx.x;
-    if (a.xcd_remap) {
-        const int64_t per = ((int64_t)gridDim.x + 7) / 8;
-        slot = (int64_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        if (slot >= (int64_t)gridDim.x) return;
-    }
-    const int64_t t = a.first_tile + slot * a.tile_step;
+    const int64_t t = a.first_tile + (int64_t)blockIdx.x * a.tile_step;
     if (t >= a.n_tiles) return;
-    // Tiles of the upper triangle, row-major: row block rb owns column chunks kCPR*rb .. ncc-1, so
-    // offset(rb) = rb*ncc - kCPR*rb*(rb-1)/2.  Invert with a float estimate and an exact fix-up.
     int64_t rb, cc;
     if constexpr (kCross) {
         ke_cross_tile(region, t, &rb, &cc);
     } else if constexpr (kFrom) {
         ke_region_tile(region, t, &rb, &cc);         // the same inversion behind the region's rectangle (ke_scan_region.h)
     } else {
-        const double hc = 0.5 * kCPR, bq = (double)a.ncc + hc;
-        rb = (int64_t)floor((bq - sqrt(fmax(bq * bq - 4.0 * hc * (double)t, 0.0))) / (2.0 * hc));
-        if (rb < 0) rb = 0;
-        if (rb >= a.nb) rb = a.nb - 1;
-        while (rb > 0 && rb * a.ncc - kCPR * rb * (rb - 1) / 2 > t) --rb;
-        while (rb + 1 < a.nb && (rb + 1) * a.ncc - kCPR * (rb + 1) * rb / 2 <= t) ++rb;
-        cc = kCPR * rb + (t - (rb * a.ncc - kCPR * rb * (rb - 1) / 2));
+        ke_tri_tile(t, a.nb, a.ncc, &rb, &cc);       // the whole triangle, row-major
     }
     const int64_t row0 = rb * kTile, col0 = cc * kCols;
     const int64_t wrow0 = row0 + (int64_t)wv * (kRT * 16);          // this wave's 128 rows
@@ -292,14 +273,16 @@ __device__ __forceinline__ void scan_tiles_body(const ScanArgs a, const KeScanRe
     }
 }
 
-__global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a) { scan_tiles_body<kScanAll>(a, KeScanRegion{}); }
+__global__ __launch_bounds__(kThreads) void ke_scan_tiles(const ScanArgs a, const KeScanRegion region) {
+    scan_tiles_body<KE_SCAN_ALL>(a, region);
+}
 
 __global__ __launch_bounds__(kThreads) void ke_scan_tiles_from(const ScanArgs a, const KeScanRegion region) {
-    scan_tiles_body<kScanFrom>(a, region);
+    scan_tiles_body<KE_SCAN_FROM>(a, region);
 }
 
 __global__ __launch_bounds__(kThreads) void ke_scan_tiles_cross(const ScanArgs a, const KeScanRegion region) {
-    scan_tiles_body<kScanCross>(a, region);
+    scan_tiles_body<KE_SCAN_CROSS>(a, region);
 }
 
 __global__ void ke_band_hist(const uint64_t *__restrict__ hashes, int64_t n, int band_bits, int band_count,
@@ -331,22 +314,20 @@ __global__ void ke_hist_pairs(const uint32_t *__restrict__ hist, size_t bins, un
 // consider_pair drops every pair that shares no band, so an edge exists only inside a bucket of some band -- the
 // reference's own candidate generation (src/dup/scanner.py:227-290).  The positions are counting-sorted by band value per
 // band (histogram -> exclusive offsets -> scatter of (hash, position)), then one thread per slot of a sorted run compares
-// its hash with the later members of its bucket.  Tables up to kBucketMaxBins bins: one 1024-bin block per workgroup of the two histogram
+// its hash with the later members of its bucket.  Tables up to kScanBucketMaxBins bins: one 1024-bin block per workgroup of the two histogram
 // passes, at most 256 block sums, so a workgroup of ke_bucket_offsets adds its predecessors' sums with one value per thread.
 constexpr int kBinsPerBlock = 1024;
-constexpr size_t kBucketMaxBins = (size_t)1 << 18;
-constexpr size_t kStateBytes = 128;                                 // counters [0..3], path, longest bucket, padding
-constexpr size_t kBlockSumBytes = kBucketMaxBins / kBinsPerBlock * sizeof(uint32_t);
-// The rule between the paths (set from the sweep recorded there): buckets when the table has at least
-// kBucketMinN hashes (below, both paths cost about their launches), the walked bucket pairs are at most 1/kBucketRatio of all
-// pairs and no walked bucket is longer than kBucketLongest (one thread walks the rest of its bucket), else tiles.
+// The rule between the paths (ke_scan_plan.h plans with it, DESIGN section 5 has the sweeps it was set from): buckets when the
+// table has at least kBucketMinN hashes, the walked bucket pairs are at most 1/kBucketRatio of all pairs (1/kBucketRatioFrom of
+// the region's for a scan from first_new or a cross scan) and no walked bucket is longer than kBucketLongest (one thread walks
+// the rest of its bucket; checked on the device, ke_bucket_offsets), else tiles.  The host's three are stated here as well, where
+// the tables of the GPU tests read them, and held to the plan's.
 constexpr unsigned long long kBucketRatio = 6000, kBucketLongest = 260;
 constexpr int64_t kBucketMinN = 50000;
-// The same rule for a scan from first_new, with the region's pairs in place of all pairs and a ratio of its own: the bucket
-// kernels walk every bucket of the table however thin the region is, so their time does not shrink with it, while the
-// tile kernel's does.  Between the rows of the record (tiles ahead at region pairs / bucket pairs = 33 and
-// 312, level at 325, buckets ahead from 2 978) the ratio sits at the geometric middle.
 constexpr unsigned long long kBucketRatioFrom = 1000;
+static_assert(kBucketRatio == kScanBucketRatio && kBucketMinN == kScanBucketMinN && kBucketRatioFrom == kScanBucketRatioFrom,
+              "ke_scan_plan.h plans with these");
+static_assert(kScanBucketMaxBins / kBinsPerBlock * sizeof(uint32_t) == kScanBlockSumBytes, "ke_scan_plan.h sizes the block sums");
 
 __device__ __forceinline__ unsigned long long block_sum_256(unsigned long long v, unsigned long long *s4) {
     for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
@@ -450,8 +431,8 @@ __global__ void ke_bucket_scatter(const uint64_t *__restrict__ hashes, int64_t n
 constexpr int kPairSlots = 1024, kPairStage = 256;
 
 // kFrom (ke_bucket_pairs_from): a pair is kept only when its later position is at least first_new; its shard stays
-// (lo + hi) mod part_count.  kScanCross (ke_bucket_pairs_cross): only when lo < first_new <= hi as well.
-template <int kMode>
+// (lo + hi) mod part_count.  KE_SCAN_CROSS (ke_bucket_pairs_cross): only when lo < first_new <= hi as well.
+template <KeScanKind kMode>
 __device__ __forceinline__ void bucket_pairs_body(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
                                                   const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
                                                   int64_t first_new) {
@@ -483,8 +464,8 @@ __device__ __forceinline__ void bucket_pairs_body(const ScanArgs a, const uint64
             const int64_t pj = pos[k];
             const int64_t lo = pi < pj ? pi : pj, hi = pi < pj ? pj : pi;
             if (hi >= a.n || (lo + hi) % part_count != part_index) continue;
-            if constexpr (kMode != kScanAll) { if (hi < first_new) continue; }
-            if constexpr (kMode == kScanCross) { if (lo >= first_new) continue; }
+            if constexpr (kMode != KE_SCAN_ALL) { if (hi < first_new) continue; }
+            if constexpr (kMode == KE_SCAN_CROSS) { if (lo >= first_new) continue; }
             const uint64_t xl = pi < pj ? x : y, xh = pi < pj ? y : x;
             int bands, shared;
             if (!pair_is_edge(a, lo, hi, xl, xh, b, &bands, &shared)) continue;
@@ -512,20 +493,21 @@ __device__ __forceinline__ void bucket_pairs_body(const ScanArgs a, const uint64
 }
 
 __global__ __launch_bounds__(256) void ke_bucket_pairs(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
-                                                        const uint32_t *__restrict__ sorted_pos, int part_index, int part_count) {
-    bucket_pairs_body<kScanAll>(a, sorted_hash, sorted_pos, part_index, part_count, 0);
+                                                        const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
+                                                        int64_t first_new) {
+    bucket_pairs_body<KE_SCAN_ALL>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
 }
 
 __global__ __launch_bounds__(256) void ke_bucket_pairs_from(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
                                                              const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
                                                              int64_t first_new) {
-    bucket_pairs_body<kScanFrom>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
+    bucket_pairs_body<KE_SCAN_FROM>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
 }
 
 __global__ __launch_bounds__(256) void ke_bucket_pairs_cross(const ScanArgs a, const uint64_t *__restrict__ sorted_hash,
                                                               const uint32_t *__restrict__ sorted_pos, int part_index, int part_count,
                                                               int64_t first_new) {
-    bucket_pairs_body<kScanCross>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
+    bucket_pairs_body<KE_SCAN_CROSS>(a, sorted_hash, sorted_pos, part_index, part_count, first_new);
 }
 
 // Wide bands (2^band_bits bins do not fit a table): the band values are sorted together with their positions and the
@@ -659,176 +641,134 @@ int ke_launch_band_pairs_after_size(ke_ctx *ctx, const uint64_t *d_hashes, const
     return KE_OK;
 }
 
-int ke_launch_scan(ke_ctx *ctx, const uint64_t *d_hashes, const int64_t *d_ids, const int64_t *d_sizes, int64_t n,
-                   int part_index, int part_count, int threshold, int band_bits, int band_count, double size_ratio,
-                   int64_t bucket_pair_cap, ke_edge *d_edges, int64_t capacity, unsigned long long **d_counters_out,
-                   unsigned long long *pairs_evaluated, bool want_bucket_pairs, int64_t first_new, bool cross, bool exact) {
-    // first_new > 0: only the pairs i < j with j >= first_new (ke_hamming_scan_from), through kernels of their own;
-    // first_new == 0 launches what it always did.  cross: only the pairs i < first_new <= j (ke_hamming_scan_cross), again
-    // through kernels of its own, for every first_new in [0, n] (0 and n: an empty region, no tile kernel).
-    // exact (ke_hamming_scan_exact): every pair of the region within the threshold, whether or not it shares a band.  The
-    // tile kernel is the only path: no histogram, no sorted copy, no statistics, KE_SCAN_MODE is not looked at, the path word
-    // and counters[3] stay 0; and the tiles go out in slices of at most KE_SCAN_TILES_PER_LAUNCH (below).
-    const bool from = cross || first_new > 0;
-    const KeScanRegion region = cross ? ke_cross_region(n, first_new) : ke_scan_region(n, first_new);
-    ScanArgs a;
-    a.hashes = d_hashes; a.ids = d_ids; a.sizes = (size_ratio > 0.0) ? d_sizes : nullptr;
-    a.n = n;
-    a.nb = (int)((n + kTile - 1) / kTile);
-    a.ncc = (int)((n + kCols - 1) / kCols);
-    a.n_tiles = from ? region.n_tiles : (int64_t)a.nb * a.ncc - (int64_t)kCPR * a.nb * (a.nb - 1) / 2;
-    a.first_tile = part_index;
-    a.tile_step = part_count;
-    a.threshold = threshold; a.band_bits = band_bits; a.band_count = band_count;
-    a.size_ratio = size_ratio;
-    a.hist = nullptr; a.blen = nullptr;
-    a.cap = (!exact && bucket_pair_cap > 0) ? (unsigned long long)bucket_pair_cap : 0ull;
-    a.exact = exact ? 1 : 0;
-    if (exact) want_bucket_pairs = false;
-    a.edges = d_edges; a.capacity = capacity;
-    // pairs of the region this shard stands for (host, O(row blocks); first_new = 0: the pairs i < j < n)
-    const unsigned long long pairs = cross ? ke_cross_shard_pairs(region, part_index, part_count)
-                                           : ke_region_shard_pairs(region, part_index, part_count);
-    *pairs_evaluated = pairs;
-    // KE_SCAN_MODE=auto|tiles|buckets, read once: auto lets the device choose per call; the other two force a path
-    // (buckets still means tiles where the bucket path is not built).  Must be the same on every rank of a sharded scan.
-    static const int forced = [] {
-        const char *e = std::getenv("KE_SCAN_MODE");
-        return !e ? 0 : !std::strcmp(e, "tiles") ? 1 : !std::strcmp(e, "buckets") ? 2 : 0;
+// Plan, reserve, launch: what runs and how large its buffers are is ke_scan_plan.h's business.  KE_SCAN_MODE=auto|tiles|buckets
+// (auto lets the device choose per call, the other two force a path; buckets still means tiles where the plan has no bucket
+// path; must be the same on every rank of a sharded scan) and KE_SCAN_TILES_PER_LAUNCH are read once per process.
+int ke_launch_scan(ke_ctx *ctx, const KeScanRequest &rq, unsigned long long **d_counters_out, unsigned long long *pairs_evaluated) {
+    static const KeScanKnobs knobs = [] {
+        const char *mode = std::getenv("KE_SCAN_MODE"), *per = std::getenv("KE_SCAN_TILES_PER_LAUNCH");
+        KeScanKnobs k;
+        k.forced = !mode ? KE_SCAN_AUTO : !std::strcmp(mode, "tiles") ? KE_SCAN_FORCE_TILES : !std::strcmp(mode, "buckets") ? KE_SCAN_FORCE_BUCKETS : KE_SCAN_AUTO;
+        k.tiles_per_launch = per ? std::atoll(per) : 0;
+        return k;
     }();
-    const bool table = band_bits <= 24;
-    const size_t bins = table ? (size_t)band_count << band_bits : 0;
-    bool bucket_path = !exact && table && bins <= kBucketMaxBins && n <= 0xffffffffLL && forced != 1 && (forced == 2 || n >= kBucketMinN);
+    // by KeScanKind; KE_SCAN_ALL launches what a scan always did: its kernels read neither the region nor first_new
+    static constexpr void (*tile_kernels[])(ScanArgs, KeScanRegion) = {ke_scan_tiles, ke_scan_tiles_from, ke_scan_tiles_cross};
+    static constexpr void (*pair_kernels[])(ScanArgs, const uint64_t *, const uint32_t *, int, int, int64_t) = {
+        ke_bucket_pairs, ke_bucket_pairs_from, ke_bucket_pairs_cross};
+    const int64_t n = rq.n;
+    KeScanShape shape;
+    shape.n = n; shape.first_new = rq.first_new; shape.kind = rq.kind;
+    shape.part_index = rq.part_index; shape.part_count = rq.part_count;
+    shape.band_bits = rq.band_bits; shape.band_count = rq.band_count;
+    shape.bucket_pair_cap = rq.bucket_pair_cap;
+    shape.exact = rq.exact; shape.want_bucket_pairs = rq.want_bucket_pairs;
+    KeScanPlan p = ke_scan_plan(shape, knobs);
     // [sorted hashes | per-bin offsets | sorted positions]; a table too large for it is scanned by the tile kernel
     void *srt = nullptr;
-    const size_t slots = (size_t)band_count * (size_t)n;
-    if (bucket_path && ke_reserve(ctx, KE_BUF_SCAN_SORT, slots * 12 + bins * sizeof(uint32_t), &srt) != KE_OK) {
+    if (p.buckets && ke_reserve(ctx, KE_BUF_SCAN_SORT, p.sort_bytes, &srt) != KE_OK) {
         (void)hipGetLastError();
         ctx->err.clear();                          // not a failure of this call: the tile kernel needs no such buffer
-        bucket_path = false;
+        shape.buckets_allowed = false;
+        p = ke_scan_plan(shape, knobs);
     }
+    switch (p.refusal) {
+    case KE_SCAN_WIDE_NEEDS_32_BITS: return ke_fail(ctx, KE_EUNSUPPORTED, "bands wider than 24 bits need n < 2^32");
+    case KE_SCAN_TOO_MANY_TILES: return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
+    case KE_SCAN_CROSS_OVER_ONE_LAUNCH:
+        return ke_fail(ctx, KE_EUNSUPPORTED, "%lld tiles of %d threads do not fit one launch", (long long)p.my_tiles, kThreads);
+    }
+    *pairs_evaluated = p.pairs;
+    ScanArgs a;
+    a.hashes = rq.hashes; a.ids = rq.ids; a.sizes = (rq.size_ratio > 0.0) ? rq.sizes : nullptr;
+    a.n = n;
+    a.nb = (int)p.region.nb;
+    a.ncc = (int)p.region.ncc;
+    a.n_tiles = p.n_tiles;
+    a.first_tile = rq.part_index;
+    a.tile_step = rq.part_count;
+    a.threshold = rq.threshold; a.band_bits = rq.band_bits; a.band_count = rq.band_count;
+    a.size_ratio = rq.size_ratio;
+    a.hist = nullptr; a.blen = nullptr;
+    a.cap = p.cap;
+    a.exact = rq.exact ? 1 : 0;
+    a.edges = rq.edges; a.capacity = rq.capacity;
+    const size_t slots = (size_t)rq.band_count * (size_t)n;
     uint64_t *sorted_hash = (uint64_t *)srt;
-    uint32_t *offsets = (uint32_t *)(sorted_hash + slots), *sorted_pos = offsets + bins;
-    const bool need_hist = table && (bucket_path || a.cap > 0 || want_bucket_pairs);
+    uint32_t *offsets = (uint32_t *)(sorted_hash + slots), *sorted_pos = offsets + p.bins;
     // One allocation, one memset: [counters, path, longest bucket | block sums | histogram]
-    const size_t hist_at = kStateBytes + kBlockSumBytes;
-    const size_t state_bytes = (hist_at + (need_hist ? bins * sizeof(uint32_t) : 0) + 15) & ~(size_t)15;
     void *st;
-    KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_CNT, state_bytes, &st));
+    KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_CNT, p.state_bytes, &st));
     unsigned long long *state = (unsigned long long *)st;
-    uint32_t *block_sums = (uint32_t *)((uint8_t *)st + kStateBytes), *hist = (uint32_t *)((uint8_t *)st + hist_at);
+    uint32_t *block_sums = (uint32_t *)((uint8_t *)st + kScanStateBytes), *hist = (uint32_t *)((uint8_t *)st + p.hist_at);
     a.counters = state;
     *d_counters_out = state;
-    const int64_t my_tiles = a.n_tiles > part_index ? (a.n_tiles - part_index + part_count - 1) / part_count : 0;
-    const int64_t n_pad = (int64_t)a.nb * kTile;     // the kernel reads whole tiles: operands beyond n are zero
     void *exp;
-    KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_EXP, (size_t)n_pad * 64, &exp));
+    KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_EXP, p.exp_bytes, &exp));
     a.expanded = (const ke_v4i *)exp;
     ke_time_begin(ctx, KE_T_SCAN);
-    KE_HIP(ctx, hipMemsetAsync(st, 0, state_bytes, ctx->stream));
+    KE_HIP(ctx, hipMemsetAsync(st, 0, p.state_bytes, ctx->stream));
+    const dim3 per_hash((unsigned)((n + 255) / 256)), blk(256);
     // Bucket sizes per band: needed by the bucket path and the pair cap, and they give the reference's "pairs total"
     // counter (counters[3]).
-    if (need_hist) {
-        hipLaunchKernelGGL(ke_band_hist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, band_bits,
-                           band_count, hist);
+    if (p.need_hist) {
+        hipLaunchKernelGGL(ke_band_hist, per_hash, blk, 0, ctx->stream, rq.hashes, n, rq.band_bits, rq.band_count, hist);
         KE_HIP(ctx, hipGetLastError());
         a.hist = hist;
-        if (bucket_path) {
-            const unsigned blocks = (unsigned)((bins + kBinsPerBlock - 1) / kBinsPerBlock);
-            // the rule's yardstick is what the tile kernel would have to visit: the region's pairs
-            const unsigned long long all_pairs =
-                cross ? (unsigned long long)first_new * (unsigned long long)(n - first_new)
-                      : (unsigned long long)n * (unsigned long long)(n - 1) / 2 -
-                            (unsigned long long)first_new * (unsigned long long)(first_new > 0 ? first_new - 1 : 0) / 2;
-            hipLaunchKernelGGL(ke_bucket_stats, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins, a.cap, block_sums,
-                               state);
-            hipLaunchKernelGGL(ke_bucket_offsets, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins,
-                               (const uint32_t *)block_sums, offsets, state, forced, all_pairs / (from ? kBucketRatioFrom : kBucketRatio), pairs);
-            hipLaunchKernelGGL(ke_bucket_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, band_bits,
-                               band_count, offsets, sorted_hash, sorted_pos, (const unsigned long long *)state);
-            const dim3 pair_grid((unsigned)((n + kPairSlots - 1) / kPairSlots), (unsigned)band_count);
-            if (cross)
-                hipLaunchKernelGGL(ke_bucket_pairs_cross, pair_grid, dim3(256), 0, ctx->stream, a, (const uint64_t *)sorted_hash,
-                                   (const uint32_t *)sorted_pos, part_index, part_count, first_new);
-            else if (from)
-                hipLaunchKernelGGL(ke_bucket_pairs_from, pair_grid, dim3(256), 0, ctx->stream, a, (const uint64_t *)sorted_hash,
-                                   (const uint32_t *)sorted_pos, part_index, part_count, first_new);
-            else
-                hipLaunchKernelGGL(ke_bucket_pairs, pair_grid, dim3(256), 0, ctx->stream, a,
-                                   (const uint64_t *)sorted_hash, (const uint32_t *)sorted_pos, part_index, part_count);
-            KE_HIP(ctx, hipGetLastError());
-        } else if (want_bucket_pairs) {
-            const unsigned blocks = (unsigned)std::min<size_t>((bins + 1023) / 1024, 256);
-            hipLaunchKernelGGL(ke_hist_pairs, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t *)hist, bins, a.cap, state + 3);
-            KE_HIP(ctx, hipGetLastError());
-        }
-    } else if (a.cap > 0 || want_bucket_pairs) {
-        if (n > 0xffffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "bands wider than 24 bits need n < 2^32");
+    }
+    if (p.buckets) {
+        const dim3 blocks((unsigned)((p.bins + kBinsPerBlock - 1) / kBinsPerBlock));
+        hipLaunchKernelGGL(ke_bucket_stats, blocks, blk, 0, ctx->stream, (const uint32_t *)hist, p.bins, a.cap, block_sums, state);
+        hipLaunchKernelGGL(ke_bucket_offsets, blocks, blk, 0, ctx->stream, (const uint32_t *)hist, p.bins, (const uint32_t *)block_sums,
+                           offsets, state, knobs.forced, (unsigned long long)p.bucket_threshold, (unsigned long long)p.pairs);
+        hipLaunchKernelGGL(ke_bucket_scatter, per_hash, blk, 0, ctx->stream, rq.hashes, n, rq.band_bits, rq.band_count, offsets,
+                           sorted_hash, sorted_pos, (const unsigned long long *)state);
+        hipLaunchKernelGGL(pair_kernels[p.kind], dim3((unsigned)((n + kPairSlots - 1) / kPairSlots), (unsigned)rq.band_count), blk, 0,
+                           ctx->stream, a, (const uint64_t *)sorted_hash, (const uint32_t *)sorted_pos, rq.part_index, rq.part_count,
+                           rq.first_new);
+        KE_HIP(ctx, hipGetLastError());
+    }
+    if (p.hist_pairs) {
+        const unsigned blocks = (unsigned)std::min<size_t>((p.bins + 1023) / 1024, 256);
+        hipLaunchKernelGGL(ke_hist_pairs, dim3(blocks), blk, 0, ctx->stream, (const uint32_t *)hist, p.bins, a.cap, state + 3);
+        KE_HIP(ctx, hipGetLastError());
+    }
+    if (p.wide_sort) {
         // sort (band value, position) per band; scratch: keys in/out, positions in/out, per-hash lengths, cub temp storage
         size_t temp_bytes = 0;
         KE_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr,
-                                                       (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, 0, band_bits, ctx->stream));
+                                                       (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, 0, rq.band_bits, ctx->stream));
         const size_t kb = ((size_t)n * 8 + 255) & ~(size_t)255, pb = ((size_t)n * 4 + 255) & ~(size_t)255;
         void *scratch, *lens;
         KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_AUX, 2 * kb + 2 * pb + temp_bytes + 256, &scratch));
-        KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_HIST, (size_t)band_count * n * sizeof(uint32_t), &lens));
+        KE_TRY(ke_reserve(ctx, KE_BUF_SCAN_HIST, (size_t)rq.band_count * n * sizeof(uint32_t), &lens));
         uint8_t *sp = (uint8_t *)scratch;
         uint64_t *k_in = (uint64_t *)sp, *k_out = (uint64_t *)(sp + kb);
         uint32_t *p_in = (uint32_t *)(sp + 2 * kb), *p_out = (uint32_t *)(sp + 2 * kb + pb);
         void *temp = sp + 2 * kb + 2 * pb;
-        const uint64_t mask = band_bits >= 64 ? ~0ull : ((1ull << band_bits) - 1ull);
-        const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
-        for (int b = 0; b < band_count; ++b) {
-            hipLaunchKernelGGL(ke_band_keys, grid, blk, 0, ctx->stream, d_hashes, n, b * band_bits, mask, k_in, p_in);
-            KE_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, k_in, k_out, p_in, p_out, (int)n, 0, band_bits, ctx->stream));
-            hipLaunchKernelGGL(ke_run_lengths, grid, blk, 0, ctx->stream, k_out, p_out, n, a.cap, (uint32_t *)lens + (size_t)b * n,
+        const uint64_t mask = rq.band_bits >= 64 ? ~0ull : ((1ull << rq.band_bits) - 1ull);
+        for (int b = 0; b < rq.band_count; ++b) {
+            hipLaunchKernelGGL(ke_band_keys, per_hash, blk, 0, ctx->stream, rq.hashes, n, b * rq.band_bits, mask, k_in, p_in);
+            KE_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, k_in, k_out, p_in, p_out, (int)n, 0, rq.band_bits, ctx->stream));
+            hipLaunchKernelGGL(ke_run_lengths, per_hash, blk, 0, ctx->stream, k_out, p_out, n, a.cap, (uint32_t *)lens + (size_t)b * n,
                                state + 3);
             KE_HIP(ctx, hipGetLastError());
         }
         a.blen = (const uint32_t *)lens;
     }
-    if (my_tiles > 0) {
-        hipLaunchKernelGGL(ke_scan_expand, dim3((unsigned)((n_pad * 4 + 255) / 256)), dim3(256), 0, ctx->stream, d_hashes, n, n_pad,
+    if (p.n_slices > 0) {
+        const int64_t n_pad = p.region.nb * kTile;
+        hipLaunchKernelGGL(ke_scan_expand, dim3((unsigned)((n_pad * 4 + 255) / 256)), blk, 0, ctx->stream, rq.hashes, n, n_pad,
                            (ke_v4i *)exp, (const unsigned long long *)(state + kPathWord));
-        static const int xcd = [] { const char *e = std::getenv("KE_SCAN_XCD"); return e ? std::atoi(e) : 0; }();
-        // A launch holds fewer than 2^32 threads: kMaxLaunchTiles tiles.
-        constexpr int64_t kMaxLaunchTiles = 0xffffffffLL / kThreads;
-        // An exact scan launches its tiles in consecutive slices of the shard's enumeration, at most KE_SCAN_TILES_PER_LAUNCH
-        // (read once; default and ceiling: what one launch holds) to a launch: slot s of a slice that starts at slot s0 is
-        // tile part_index + (s0 + s) * part_count, so only first_tile moves.  The tiles count their pairs into counters[0]
-        // as ever, and the caller's closed-form check covers all slices together.
-        static const int64_t per_launch = [] {
-            const char *e = std::getenv("KE_SCAN_TILES_PER_LAUNCH");
-            const long long v = e ? std::atoll(e) : 0;
-            return (int64_t)(v > 0 && v < kMaxLaunchTiles ? v : kMaxLaunchTiles);
-        }();
-        if (!exact) {
-            if (my_tiles > 0x7fffffffLL) return ke_fail(ctx, KE_EUNSUPPORTED, "too many tiles for one launch");
-            // Beyond kMaxLaunchTiles only a part of the grid runs and the call ends at the caller's pair count check with a
-            // count that is short (so it does for the two older scans, from about 4 million hashes on).  The cross scan says
-            // so here where the tile kernel is its only path.
-            if (cross && !bucket_path && my_tiles > kMaxLaunchTiles)
-                return ke_fail(ctx, KE_EUNSUPPORTED, "%lld tiles of %d threads do not fit one launch", (long long)my_tiles, kThreads);
-        }
-        const int64_t slice = exact ? per_launch : my_tiles;
-        for (int64_t s0 = 0; s0 < my_tiles; s0 += slice) {
-            const int64_t count = std::min(slice, my_tiles - s0);
-            a.first_tile = (int64_t)part_index + s0 * (int64_t)part_count;
-            // With the remap the grid is padded to a multiple of 8 so that every slot exists on some workgroup; the padding
-            // slots name tiles past the slice, which only the end of the enumeration turns away: a slice that is followed by
-            // another is remapped only when it needs no padding.
-            a.xcd_remap = (xcd && (s0 + count == my_tiles || count % 8 == 0)) ? xcd : 0;
-            const int64_t grid = a.xcd_remap ? (count + 7) / 8 * 8 : count;
-            // one workgroup per tile on either kernel: splitting a thin region's tiles over 2 or 4 workgroups was measured and
-            // did not pay
-            if (cross)
-                hipLaunchKernelGGL(ke_scan_tiles_cross, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
-            else if (from)
-                hipLaunchKernelGGL(ke_scan_tiles_from, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a, region);
-            else
-                hipLaunchKernelGGL(ke_scan_tiles, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, a);
-            KE_HIP(ctx, hipGetLastError());
-        }
+    }
+    // one workgroup per tile: splitting a thin region's tiles over 2 or 4 workgroups was measured and did not pay (DESIGN
+    // section 5).  Only first_tile moves from slice to slice; the tiles count their pairs into counters[0] as ever, and the
+    // caller's closed-form check covers all slices together.
+    for (int64_t i = 0; i < p.n_slices; ++i) {
+        const KeScanSlice slice = ke_scan_slice(p, i);
+        a.first_tile = slice.first_tile;
+        hipLaunchKernelGGL(tile_kernels[p.kind], dim3((unsigned)slice.count), dim3(kThreads), 0, ctx->stream, a, p.region);
+        KE_HIP(ctx, hipGetLastError());
     }
     ke_time_end(ctx, KE_T_SCAN);
     return KE_OK;
